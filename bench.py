@@ -11,8 +11,13 @@ Scaling: weak — each GPU evaluates its own 1M-hypothesis batch of the same pro
 one RANSAC call over N x 1M hypotheses), one 16-byte all-reduce per step.
 
 Printed JSON carries the live roofline of the dominant kernel (mcv_h_verify_pk, HIP events on its
-launch stream; algorithmic bytes = 16 B x N correspondences per hypothesis) and the oracle's CPU
-throughput on a bounded sample of the same workload (rank 0, N = 1 only).
+launch stream; algorithmic bytes = 16 B x N correspondences per hypothesis). A plain run does no more
+than that: set up, warm up, time the steps, print the line. `--full` adds the legs that take runs of
+their own: the oracle's CPU throughput on a bounded sample of the same workload (rank 0, N = 1
+only), the secondary fast_minimal figure of the H / F lines and the essential workload's model count.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32 / float64; rank 0). The inputs are seeded, so two builds can be compared array for array.
 """
 from __future__ import annotations
 
@@ -138,14 +143,20 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--hyps", type=int, default=HYPS_PER_GPU, help="hypotheses per GPU per step")
     ap.add_argument("--n", type=int, default=N_CORR)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline, the secondary "
+                         "fast_minimal leg of the H / F lines, the essential workload's model count")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample time (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--hamming-form", default="gemm", choices=["gemm", "popcount"],
                     help="Hamming kernel: fp4 GEMM on the matrix cores (default) or the XOR / popcount sweep")
     ap.add_argument("--pnp-kind", default="EPNP", choices=["Iterative", "EPNP", "P3P", "DLS", "UPNP", "AP3P"],
                     help="pnp workload: the reference's solverKind (EPNP = its own testPnp, Program.fs:27-32)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary fast_minimal leg of the H / F lines (profiling runs: one solver per process)")
+                    help="with --full: skip the secondary fast_minimal leg of the H / F lines (profiling runs: "
+                         "one solver per process)")
     ap.add_argument("--fast-minimal", action="store_true",
                     help="opt-in elimination minimal solver for H / 8-point F (default: OpenCV's cv::eigen runKernel)")
     ap.add_argument("--fused", action="store_true",
@@ -154,6 +165,28 @@ def parse():
                     choices=["homography", "fundamental", "essential", "pnp", "hamming", "l2", "scaled"],
                     help="homography = the headline (BASELINE config[2]); the others are config[1], [3], [4]")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one <name>.npy per array the last timed step handed back. Integer and mask
+    outputs are widened to float64 / float32 (exact at these sizes); all of them together stay far
+    below DUMP_MAX_BYTES at every workload's shape, which is checked, not sampled around."""
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype in (np.float32, np.uint8, np.bool_)
+                                          else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte bound")
+    for name, a in conv.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def cpu_baseline(src, dst, target_s: float):
@@ -251,6 +284,9 @@ def bench_matcher(args):
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"idx": idx.cpu().numpy(), "dist": dist_t.cpu().numpy(),
+                                         "idx2": idx2.cpu().numpy(), "dist2": dist2.cpu().numpy()})
     if rank == 0:
         avg_ms = kms.value / max(launches, 1)
         if ham:
@@ -320,7 +356,7 @@ def bench_matcher(args):
                      "config": {"workload": args.workload, "queries": nq, "train": nt,
                                 "parallelism": f"query-sharded dp{world}"},
                      "cpu_baseline": None})
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, str(ROOT / "tests"))
             import _oracle as O
             threads = cpu_threads()
@@ -518,6 +554,10 @@ def bench_ransac(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"model": result["H"], "mask": mask.cpu().numpy(),
+                                         "best": np.array([result["count"], result["idx"],
+                                                           result["final_count"]], dtype=np.float64)})
     if rank == 0:
         value = total * args.steps / el
         avg_ms = kms.value / max(launches, 1)
@@ -599,11 +639,11 @@ def bench_ransac(args):
                                                 "SIMD cycles per 64 (model, correspondence) at 2.4 GHz"}},
                 "result": {"best_count": result["count"], "best_hyp": result["idx"]},
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = (cpu_baseline_f if fund else cpu_baseline)(src, dst, args.cpu_seconds)
         else:
             line["cpu_baseline"] = None
-        if world == 1 and not args.fast_minimal and not args.no_secondary:
+        if world == 1 and args.full and not args.fast_minimal and not args.no_secondary:
             # the same step with the opt-in elimination minimal solver (a secondary figure, not `value`)
             cfg_default = cfg
             cfg = opencv.RansacParams(threshold=THR, confidence=0.995, max_iters=total,
@@ -688,7 +728,7 @@ def bench_essential(args, world, rank, dev):
         if slot < 0:
             raise RuntimeError("no model found")
         fc, E = plan.finalize(pts, n, cfg, slot, mask)
-        result.update(count=cnt, slot=slot, final_count=fc)
+        result.update(count=cnt, slot=slot, final_count=fc, E=E)
 
     for _ in range(args.warmup):
         step()
@@ -712,15 +752,23 @@ def bench_essential(args, world, rank, dev):
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    # models per verify launch (the sweep runs over the dense model list): count them once, untimed
-    slots = torch.zeros(hyps * NL.E_SLOTS, dtype=torch.int32, device=dev)
-    plan.evaluate(pts, n, cfg, rank * hyps, hyps, key, slots)
-    models = int((slots >= 0).sum().item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"model": result["E"], "mask": mask.cpu().numpy(),
+                                         "best": np.array([result["count"], result["slot"],
+                                                           result["final_count"]], dtype=np.float64)})
+    # models per verify launch (the sweep runs over the dense model list): counted once, untimed, in a
+    # run of its own (--full); the roofline is priced per model, so a plain run carries none
+    models = None
+    if args.full:
+        slots = torch.zeros(hyps * NL.E_SLOTS, dtype=torch.int32, device=dev)
+        plan.evaluate(pts, n, cfg, rank * hyps, hyps, key, slots)
+        models = int((slots >= 0).sum().item())
     if rank == 0:
         v_ms = vms.value / max(vl, 1)
         g_ms = gms.value / max(gl, 1)
-        alg_bytes = 16.0 * n * models            # each model reads all N float4 correspondences
-        e_tf = SAMPSON_FLOPS_PER_EVAL * n * models / (v_ms * 1e-3) / 1e12
+        alg_bytes = 16.0 * n * (models or 0)     # each model reads all N float4 correspondences
+        e_evals = n * (models or 0) / (v_ms * 1e-3)
+        e_tf = SAMPSON_FLOPS_PER_EVAL * e_evals / 1e12
         line = {
             "metric": "RANSAC hypotheses/sec, findEssentialMat 5-pt (cvRecoverPose path) @100k corrs",
             "value": total * args.steps / el, "unit": "hypotheses/s", "n_gpus": world, "steps": args.steps,
@@ -743,16 +791,18 @@ def bench_essential(args, world, rank, dev):
                                   "certified packed-fp32 prefilter, fp64 only for undecided lanes",
                          "hbm": {"effective_GBps": alg_bytes / (v_ms * 1e-3) / 1e9,
                                  "algorithmic_bytes_per_launch": alg_bytes, "peak": HBM_PEAK_GBPS},
-                         "issue": measured_issue("mcv_e_verify", f"{n}x{hyps}", n * models / (v_ms * 1e-3)) or
-                                  {"achieved": n * models / (v_ms * 1e-3), "peak": issue_peak(SPK_CYC_PER_WAVE_EVAL),
+                         "issue": measured_issue("mcv_e_verify", f"{n}x{hyps}", e_evals) or
+                                  {"achieved": e_evals, "peak": issue_peak(SPK_CYC_PER_WAVE_EVAL),
                                    "unit": "evaluations/s",
-                                   "frac": n * models / (v_ms * 1e-3) / issue_peak(SPK_CYC_PER_WAVE_EVAL),
+                                   "frac": e_evals / issue_peak(SPK_CYC_PER_WAVE_EVAL),
                                    "model": f"certified packed-fp32 Sampson prefilter: {SPK_CYC_PER_WAVE_EVAL} SIMD "
                                             "cycles per 64 (model, correspondence) at 2.4 GHz"}},
             "result": {"best_count": result["count"], "best_slot": result["slot"],
                        "final_count": result["final_count"]},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if models is None:
+            line["roofline"] = None
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, str(ROOT / "tests"))
             import _oracle as O
             line["cpu_baseline"] = cpu_baseline_e(O.pack_e(a, b, E_FOCAL, E_PP), args.cpu_seconds)
@@ -855,6 +905,11 @@ def bench_pnp(args, world, rank, dev):
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"model": np.array(result["pose"], dtype=np.float64),
+                                         "mask": mask.cpu().numpy(),
+                                         "best": np.array([result["count"], result["idx"],
+                                                           result["final_count"]], dtype=np.float64)})
     if rank == 0:
         v_ms = vms.value / max(vl, 1)
         p_bytes = 20.0 * n * hyps                # PnpPoint {X, Y, Z, u, v} f32 per (hypothesis, correspondence)
@@ -896,7 +951,7 @@ def bench_pnp(args, world, rank, dev):
                        "final_count": result["final_count"], "true_inliers": int(inl.sum())},
         }
         line["cpu_baseline"] = (cpu_baseline_p(img, W, K, d, args.cpu_seconds, kind)
-                                if world == 1 and not args.no_cpu_baseline else None)
+                                if world == 1 and args.full and not args.no_cpu_baseline else None)
         print(json.dumps(line), flush=True)
     plan.close()
 
@@ -957,6 +1012,9 @@ def bench_scaled(args):
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"best": np.array([res["candidates"], res["cost"], res["scale"]],
+                                                          dtype=np.float64)})
     if rank == 0:
         avg_ms = kms.value / max(launches, 1)
         cands = 2 * n
@@ -979,7 +1037,7 @@ def bench_scaled(args):
                                   "counted as one", "terms_per_launch": terms},
             "result": {"evaluated_candidates": res["candidates"], "cost": res["cost"], "scale": res["scale"]},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, str(ROOT / "tests"))
             import _oracle as O_
             threads = cpu_threads()

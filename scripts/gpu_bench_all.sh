@@ -11,10 +11,10 @@ step() {   # name timeout cmd...
     if [ $rc -gt 1 ]; then exit $rc; fi
 }
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
-step bench_homography 300 python bench.py --steps 10 --warmup 3 --cpu-seconds 8
-step bench_fundamental 300 python bench.py --workload fundamental --steps 5 --warmup 1 --cpu-seconds 8
-step bench_hamming 300 python bench.py --workload hamming --steps 20 --warmup 3
-step bench_l2 300 python bench.py --workload l2 --steps 5 --warmup 2
-step bench_essential 300 python bench.py --workload essential --steps 5 --warmup 2 --cpu-seconds 8
-step bench_pnp 300 python bench.py --workload pnp --steps 5 --warmup 2 --cpu-seconds 8
-step bench_scaled 300 python bench.py --workload scaled --steps 5 --warmup 2 --cpu-seconds 8
+step bench_homography 300 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 8
+step bench_fundamental 300 python bench.py --full --workload fundamental --steps 5 --warmup 1 --cpu-seconds 8
+step bench_hamming 300 python bench.py --full --workload hamming --steps 20 --warmup 3
+step bench_l2 300 python bench.py --full --workload l2 --steps 5 --warmup 2
+step bench_essential 300 python bench.py --full --workload essential --steps 5 --warmup 2 --cpu-seconds 8
+step bench_pnp 300 python bench.py --full --workload pnp --steps 5 --warmup 2 --cpu-seconds 8
+step bench_scaled 300 python bench.py --full --workload scaled --steps 5 --warmup 2 --cpu-seconds 8

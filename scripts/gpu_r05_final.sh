@@ -10,17 +10,17 @@ step pytest_gpu 1000 python -u -m pytest tests -m gpu -x -q -rA --timeout 300 --
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [[ $PARTS == *b* ]]; then
-step bench_homography 300 python bench.py --steps 10 --warmup 3 --cpu-seconds 8
-step bench_homography_fused 300 python bench.py --steps 10 --warmup 3 --fused --no-cpu-baseline
+step bench_homography 300 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 8
+step bench_homography_fused 300 python bench.py --full --steps 10 --warmup 3 --fused --no-cpu-baseline
 step bench_homography_fast 300 python bench.py --steps 10 --warmup 3 --fast-minimal --no-cpu-baseline
-step bench_fundamental 300 python bench.py --workload fundamental --steps 5 --warmup 1 --cpu-seconds 8
-step bench_hamming 300 python bench.py --workload hamming --steps 50 --warmup 5
-step bench_l2 300 python bench.py --workload l2 --steps 10 --warmup 2
-step bench_essential 300 python bench.py --workload essential --steps 5 --warmup 2 --cpu-seconds 8
-step bench_pnp 300 python bench.py --workload pnp --steps 5 --warmup 2 --cpu-seconds 8
+step bench_fundamental 300 python bench.py --full --workload fundamental --steps 5 --warmup 1 --cpu-seconds 8
+step bench_hamming 300 python bench.py --full --workload hamming --steps 50 --warmup 5
+step bench_l2 300 python bench.py --full --workload l2 --steps 10 --warmup 2
+step bench_essential 300 python bench.py --full --workload essential --steps 5 --warmup 2 --cpu-seconds 8
+step bench_pnp 300 python bench.py --full --workload pnp --steps 5 --warmup 2 --cpu-seconds 8
 step bench_pnp_ap3p 300 python bench.py --workload pnp --pnp-kind AP3P --steps 5 --warmup 2 --no-cpu-baseline
 step bench_essential_fast 300 python bench.py --workload essential --steps 5 --warmup 2 --no-cpu-baseline --fast-minimal
-step bench_scaled 300 python bench.py --workload scaled --steps 5 --warmup 2 --cpu-seconds 8
+step bench_scaled 300 python bench.py --full --workload scaled --steps 5 --warmup 2 --cpu-seconds 8
 for w in fundamental l2; do
     MCV_DIST_BACKEND=gloo step selflaunch_$w 300 python bench.py --workload $w --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline
 done

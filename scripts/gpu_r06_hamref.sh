@@ -3,7 +3,7 @@
 # timings, rocprofv3 kernel stats and the PMC passes for the Hamming workload.
 source scripts/gpu_step.sh
 step pytest_gpu_match 600 python -u -m pytest tests/test_gpu_matchers.py tests/test_gpu_matcher_shards.py tests/test_gpu_pipeline.py -m gpu -x -q -rA --timeout 300 --timeout-method thread
-step bench_hamming 300 python bench.py --workload hamming --steps 50 --warmup 5
+step bench_hamming 300 python bench.py --full --workload hamming --steps 50 --warmup 5
 step ham_sizes 300 python -u scripts/exp/ham_size_timing.py
 cd /tmp && export TMPDIR=/tmp
 step prof_hamming 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_hamming" -o run -- \

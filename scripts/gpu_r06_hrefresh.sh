@@ -4,8 +4,8 @@
 source scripts/gpu_step.sh
 step pytest_gpu 1000 python -u -m pytest tests -m gpu -x -q -rA --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_homography 300 python bench.py --steps 10 --warmup 3 --cpu-seconds 8
-step bench_homography_fused 300 python bench.py --steps 10 --warmup 3 --fused --no-cpu-baseline
+step bench_homography 300 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 8
+step bench_homography_fused 300 python bench.py --full --steps 10 --warmup 3 --fused --no-cpu-baseline
 step bench_homography_fast 300 python bench.py --steps 10 --warmup 3 --fast-minimal --no-cpu-baseline
 cd /tmp && export TMPDIR=/tmp
 step prof_homography 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_homography" -o run -- \

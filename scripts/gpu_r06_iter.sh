@@ -12,11 +12,11 @@ case $st in
   t_f) step t_f 900 $PT tests/test_gpu_fundamental.py ;;
   t_pnp) step t_pnp 900 $PT tests/test_gpu_pnp.py ;;
   t_all) step t_all 1100 $PT tests ;;
-  b_ham) step b_ham 300 python bench.py --workload hamming --steps 200 --warmup 10 ;;
-  b_l2) step b_l2 300 python bench.py --workload l2 --steps 20 --warmup 3 ;;
-  b_h) step b_h 300 python bench.py --steps 20 --warmup 3 --cpu-seconds 8 ;;
+  b_ham) step b_ham 300 python bench.py --full --workload hamming --steps 200 --warmup 10 ;;
+  b_l2) step b_l2 300 python bench.py --full --workload l2 --steps 20 --warmup 3 ;;
+  b_h) step b_h 300 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 8 ;;
   b_e) step b_e 300 python bench.py --workload essential --steps 5 --warmup 2 --no-cpu-baseline ;;
-  b_f) step b_f 300 python bench.py --workload fundamental --steps 5 --warmup 1 --no-cpu-baseline ;;
+  b_f) step b_f 300 python bench.py --full --workload fundamental --steps 5 --warmup 1 --no-cpu-baseline ;;
   b_pnp) step b_pnp 300 python bench.py --workload pnp --steps 5 --warmup 2 --no-cpu-baseline ;;
   rank_share) step rank_share 600 python scripts/exp/rank_share_timing.py ;;
   p_*) w=${st#p_}; (cd /tmp && export TMPDIR=/tmp && step prof_$w 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_$w" -o run -- python3 "$R/bench.py" --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-secondary) || exit 1 ;;
