@@ -145,6 +145,15 @@ MCV_API mcvBool cvDetectArucoMarkers(char* data, int width, int height, int chan
 
 /* method codes (OpenCV numbering) */
 #define MCV_METHOD_LSQ     0   /* all points, no RANSAC (OpenCV method 0) */
+#define MCV_METHOD_LMEDS   4   /* cv::LMEDS, least median of squares (cvFindHomography / cvFindFundamentalMat
+                                  only): no inlier threshold. RANSACUpdateNumIters(confidence, 0.45, m,
+                                  maxIters) hypotheses (maxIters with MCV_FLAG_FIXED_ITERS), each model's
+                                  median error (rank N / 2 of its N fp32 errors), the first smallest median
+                                  wins; inliers: err <= (float)sigma^2, sigma = max(2.5 * 1.4826 *
+                                  (1 + 5 / (N - m)) * sqrt(median), 0.001). Errors are ordered by their fp32
+                                  bit patterns as OpenCV's nth_element over the reinterpreted ints does; the
+                                  one difference: every NaN sorts after +inf here (an x86 build's negative
+                                  NaNs sort first). N == m takes the direct solve, as for RANSAC. */
 #define MCV_METHOD_RANSAC  8   /* cv::RANSAC */
 
 /* flags */
@@ -156,8 +165,9 @@ MCV_API mcvBool cvDetectArucoMarkers(char* data, int width, int height, int chan
 #define MCV_FLAG_SEVEN_POINT  8   /* fundamental only: OpenCV FM_RANSAC's minimal solver (run7Point: 7-point
                                      samples, up to 3 models each, model slots 3h .. 3h+2 in the device
                                      API) instead of the 8-point default; with errorKind EPIPOLAR it is
-                                     cv::findFundamentalMat(FM_RANSAC). Needs N >= 15 (OpenCV switches to
-                                     LMeDS below that, not provided) or N == 7 (one solve, first model). */
+                                     cv::findFundamentalMat(FM_RANSAC). With MCV_METHOD_RANSAC it needs N >= 15
+                                     (OpenCV switches to LMeDS below that: use MCV_METHOD_LMEDS, which takes
+                                     7-point samples at any N >= 7) or N == 7 (one solve, first model). */
 #define MCV_FLAG_CV_SAMPLER   32  /* OpenCV's own sample stream instead of the counter-based Philox one:
                                      cv::RNG((uint64)-1) per call, getSubset's duplicate rejection and
                                      checkSubset, 10000 attempts (RANSACPointSetRegistrator::run), generated
@@ -182,12 +192,15 @@ MCV_API mcvBool cvDetectArucoMarkers(char* data, int width, int height, int chan
 #define MCV_FERR_EPIPOLAR  1   /* OpenCV FM_RANSAC: max of the two squared point-to-epipolar-line distances */
 
 typedef struct {
-    double threshold;     /* max reprojection / epipolar distance of an inlier (point units) */
-    double confidence;    /* RANSAC confidence in (0,1) */
+    double threshold;     /* max reprojection / epipolar distance of an inlier (point units); not read by
+                             MCV_METHOD_LMEDS, which derives its own */
+    double confidence;    /* RANSAC / LMedS confidence in (0,1) */
     int    maxIters;      /* hypothesis budget */
-    int    method;        /* MCV_METHOD_* */
+    int    method;        /* MCV_METHOD_* (LMEDS: homography and fundamental only) */
     uint64_t seed;        /* counter-based sampler key: hypothesis i depends only on (seed, i) */
-    int    deviceCount;   /* 0/1: one GPU; >1 shard hypotheses over that many local GPUs */
+    int    deviceCount;   /* 0/1: one GPU; >1 shard hypotheses over that many local GPUs (MCV_METHOD_LMEDS
+                             always runs on the calling device: its budget is at most maxIters, and results
+                             are defined as those of one device) */
     int    flags;         /* MCV_FLAG_* */
     int    errorKind;     /* MCV_FERR_* (fundamental only) */
     int    pnpKind;       /* PnP only: the reference's solverKind (0 ITERATIVE, 1 EPNP, 2 P3P, 3 DLS, 4 UPNP,
@@ -196,14 +209,17 @@ typedef struct {
 } RansacConfig;           /* 48 bytes */
 
 /* findHomography. src/dst: N AoS fp64 points (converted to fp32 like OpenCV's convertTo(CV_32F)).
- * H: out, row-major, H[8] == 1. mask: caller-allocated uint8[N] (RANSAC inliers of the best
- * hypothesis; all 1 for METHOD_LSQ / N == 4). Returns the inlier count (>= 4), 0 on failure. */
+ * H: out, row-major, H[8] == 1. mask: caller-allocated uint8[N] (RANSAC / LMedS inliers of the best
+ * hypothesis; all 1 for METHOD_LSQ / N == 4). Returns the inlier count (>= 4), 0 on failure.
+ * cfg->method: MCV_METHOD_LSQ, MCV_METHOD_RANSAC or MCV_METHOD_LMEDS (refit + 10 LM iterations on the
+ * inliers unless MCV_FLAG_NO_REFINE, for both robust methods). */
 MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, const int N, const RansacConfig* cfg,
                              mcvM33d* H, uint8_t* mask);
 
 /* findFundamentalMat, 8-point minimal sets. a/b: N AoS fp64 points. F: out, scaled so that F[8] = 1 when
  * |F[8]| > FLT_EPSILON (run8Point's normalisation), otherwise as solved.
- * mask: caller-allocated uint8[N]. Returns inlier count (>= 8), 0 on failure. */
+ * mask: caller-allocated uint8[N]. Returns inlier count (>= 8; >= 7 with MCV_FLAG_SEVEN_POINT), 0 on failure.
+ * cfg->method: MCV_METHOD_LSQ, MCV_METHOD_RANSAC or MCV_METHOD_LMEDS (F as solved by the winning sample). */
 MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, const int N, const RansacConfig* cfg,
                                  mcvM33d* F, uint8_t* mask);
 
@@ -432,6 +448,15 @@ MCV_API long long mcvTestDivF64(int mode, unsigned long long seed, long long cou
  * sweep, 3 = op-by-op through the certified division-free sweep (the default path). */
 MCV_API int mcvTestHomographySweep(const float* pts4, int N, const float* models8, int nModels, float thr2, int fused,
                                    int* counts);
+/* Device self-test: the LMedS rank kernel (lmeds.hip) on caller-supplied models: values[k] = the error
+ * of rank `rank` (0-based, ascending; NaN last) of model k over pts4 (N float4 correspondences), NaN
+ * when that element is a NaN. model MCV_MODEL_HOMOGRAPHY: 8 floats per model, errKind 0 = op-by-op,
+ * 1 = fused error; MCV_MODEL_FUNDAMENTAL: 9 doubles per model, errKind = errorKind * 2 + unfused (0..3).
+ * Returns 1, 0 on failure. mcvHostErrorRank: the host twin (the same three radix passes, sequentially). */
+MCV_API int mcvTestErrorRank(int model, const float* pts4, int N, const void* models, int nModels, int errKind,
+                             int rank, float* values);
+MCV_API int mcvHostErrorRank(int model, const float* pts4, int N, const void* models, int nModels, int errKind,
+                             int rank, float* values);
 /* Host twins of the essential path: hypothesis (double4 normalised points; E90 = 10 x 9; the reference's
  * solver, as the default GPU path) and the raw five-point solves (x1[5], y1[5], x2[5], y2[5] packed in
  * p20): mcvHostFivePoint = the opt-in replacement solver, mcvHostFivePointRef = the reference's.

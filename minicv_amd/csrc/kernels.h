@@ -194,6 +194,13 @@ void pnp_reduce_lm(const void* d_pts, int N, const uint8_t* d_mask, const double
 void pnp_reduce_vvs(const void* d_pts, int N, const uint8_t* d_mask, const double* cam8, const double* R9,
                     const double* t3, double* d_part, double* d_out, hipStream_t s);
 
+// ---- LMedS (lmeds.hip): d_keys[slot] = the order key (rank_select.h) of the rank-`rank` error (0-based,
+// ascending) of slot's model over the N correspondences; model = MCV_MODEL_HOMOGRAPHY (HModelF slots,
+// errKind = fused 0 / 1) or MCV_MODEL_FUNDAMENTAL (FModelD slots, errKind = f_error's kinds). d_status
+// (may be NULL: every slot has a model): slots with a negative status get the NaN class.
+void launch_error_rank(int model, const float* d_pts4, int N, const void* d_models, const int* d_status, int nSlots,
+                       int errKind, int rank, uint32_t* d_keys, hipStream_t s);
+
 // ---- shared (ransac_h.hip)
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,
                  uint64_t* d_out, hipStream_t s);

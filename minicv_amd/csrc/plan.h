@@ -92,6 +92,8 @@ struct Plan {
     PinnedBuf<uint8_t> h_one;
     PinnedBuf<int> h_i;
     PinnedBuf<uint64_t> h_keys;   // per-shard best key + first failure (fixed-iteration searches)
+    DevBuf<uint32_t> med;         // LMedS: each model slot's median order key (lmeds.hip)
+    PinnedBuf<uint32_t> h_med;
 
     void reserve(int n, int64_t hyps);
     hipStream_t own_stream();
@@ -161,6 +163,11 @@ bool fused_error(const RansacConfig& cfg);
 RansacConfig config_or_default(const RansacConfig* cfg);
 int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, hipStream_t s,
                       const float* h_pts4 = nullptr);
+// LMedS (method 4) on device-resident H / F points: RANSACUpdateNumIters(confidence, 0.45, m, maxIters)
+// hypotheses in one chunk, each slot's median error (lmeds.hip), first minimum wins. Returns the winning
+// slot and its inlier threshold sigma (cfg.threshold is not read); fails when there is no model.
+int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, hipStream_t s, const float* h_pts4,
+                     double* sigma);
 int finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
              uint8_t* d_mask, hipStream_t s);
 void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,

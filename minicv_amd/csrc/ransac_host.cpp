@@ -14,6 +14,7 @@
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "plan.h"
+#include "rank_select.h"
 
 #include <cmath>
 #include <cfloat>
@@ -597,6 +598,73 @@ int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
     return st.bestIndex;
 }
 
+// LMedS (LMeDSPointSetRegistrator::run restated): the whole budget is one chunk (it
+// never exceeds maxIters and does not adapt), the medians come back as 4 B per model slot beside the
+// statuses, and the scan below is OpenCV's loop: stop at the first sampler failure, first minimum wins.
+int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, hipStream_t s, const float* h_pts4,
+                     double* sigma) {
+    const int m = model_points_cfg(P.model, cfg);
+    const int slots = model_slots_cfg(P.model, cfg);
+    const bool fixed = (cfg.flags & MCV_FLAG_FIXED_ITERS) != 0;
+    const int64_t niters = fixed ? cfg.maxIters : ransac_update_num_iters(cfg.confidence, 0.45, m, cfg.maxIters);
+    if (niters <= 0) fail("LMedS: no hypotheses to evaluate (maxIters=%d)", cfg.maxIters);
+    if (niters > kChunkMax) fail("LMedS: %lld hypotheses exceed the one-chunk budget %lld", (long long)niters, (long long)kChunkMax);
+    if (N <= m) fail("LMedS: needs more than %d correspondences (N=%d)", m, N);
+    const int cnt = (int)niters;
+    const int nSlots = cnt * slots;
+    P.reserve(N, (int64_t)cnt * (slots / model_slots(P.model)));
+    if (cv_sampler(cfg)) cv_table_prepare(P, d_pts, h_pts4, N, cfg, niters, s);
+    const Sampler smp = P.sampler(cfg);
+    int errKind = 0;
+    if (P.model == MCV_MODEL_HOMOGRAPHY) {
+        errKind = fused_error(cfg) ? 1 : 0;
+        if (!fast_minimal(cfg)) P.hgen.ensure(h_gen_scratch_bytes(cnt));
+        launch_h_generate(d_pts, N, smp, 0, cnt, P.models.p, P.h64.p, P.counts.p, s, fast_minimal(cfg),
+                          fast_minimal(cfg) ? nullptr : P.hgen.p);
+        mark_chunk(P, 0, cnt, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
+    } else if (f_seven(P.model, cfg)) {
+        errKind = f_error_kind(cfg);
+        P.last.clear();
+        launch_f7_generate(d_pts, N, smp, 0, cnt, P.models.p, P.counts.p, s);
+    } else {
+        errKind = f_error_kind(cfg);
+        launch_f_generate(d_pts, N, smp, 0, cnt, P.models.p, P.counts.p, s, fast_minimal(cfg));
+        mark_chunk(P, 0, cnt, smp, d_pts, N, fast_minimal(cfg) ? 11 : 10, s);
+    }
+    P.med.ensure((size_t)nSlots);
+    P.h_med.ensure((size_t)nSlots);
+    {
+        ProfScope ps("lmeds_select", s);
+        launch_error_rank(P.model, d_pts, N, P.models.p, P.counts.p, nSlots, errKind, N / 2, P.med.p, s);
+    }
+    MCV_HIP(hipGetLastError());
+    MCV_HIP(hipMemcpyAsync(P.h_counts.p, P.counts.p, (size_t)nSlots * sizeof(int), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipMemcpyAsync(P.h_med.p, P.med.p, (size_t)nSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipStreamSynchronize(s));
+    int64_t best = -1;
+    uint32_t bestKey = 0;
+    for (int h = 0; h < cnt; ++h) {
+        const int* c = P.h_counts.p + (size_t)h * slots;
+        if (c[0] == kStatusNoSample) {
+            if (h == 0) fail("LMedS: the sampler found no valid subset");
+            break;
+        }
+        for (int k = 0; k < slots; ++k) {
+            if (c[k] < 0) continue;
+            const uint32_t key = P.h_med.p[(size_t)h * slots + k];
+            if (best < 0 || key < bestKey) {
+                best = (int64_t)h * slots + k;
+                bestKey = key;
+            }
+        }
+    }
+    if (best < 0) fail("LMedS: no hypothesis gave a model");
+    if (bestKey == kRankKeyNaN) fail("LMedS: the best median error is NaN");
+    const double med = (double)rank_value(bestKey);
+    *sigma = std::max(2.5 * 1.4826 * (1 + 5.0 / (N - m)) * std::sqrt(med), 0.001);
+    return best;
+}
+
 void require_device() {
     int n = 0;
     const hipError_t e = hipGetDeviceCount(&n);
@@ -630,9 +698,9 @@ extern "C" MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, co
         if (N < 4) fail("cvFindHomography: need at least 4 correspondences (N=%d)", N);
         const RansacConfig cfg = config_or_default(cfgp);
         check_flags(cfg, "cvFindHomography");
-        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ)
+        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
             fail("cvFindHomography: unsupported method %d", cfg.method);
-        if (cfg.method == MCV_METHOD_RANSAC && !(cfg.confidence > 0 && cfg.confidence < 1))
+        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
             fail("cvFindHomography: confidence must be in (0,1)");
         require_device();
         Plan& P = thread_plan(MCV_MODEL_HOMOGRAPHY);
@@ -646,6 +714,16 @@ extern "C" MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, co
             if (N > 4) h_lm_refine(P, P.pts.p, N, nullptr, s, Hm, 10);
             if (mask) std::memset(mask, 1, (size_t)N);
             count = N;
+        } else if (cfg.method == MCV_METHOD_LMEDS) {
+            // the winner's mask comes from the existing finalize with LMedS' own threshold
+            RansacConfig fin = cfg;
+            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+            count = h_finalize(P, P.pts.p, N, fin, best, Hm, P.mask.p, s);
+            if (count < 4) fail("cvFindHomography: LMedS model has %d inliers (< 4)", count);
+            if (mask) {
+                MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
+                MCV_HIP(hipStreamSynchronize(s));
+            }
         } else {
             const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
             if (best < 0) fail("cvFindHomography: RANSAC found no model with >= 4 inliers");
@@ -716,6 +794,9 @@ extern "C" MCV_API int mcvRansacEvaluate(mcvRansacPlan* plan, const void* d_pts4
         if (hypBegin < 0 || (hypBegin + hypCount) * model_slots_cfg(P->model, *cfg) > 0xFFFFFFFFll)
             fail("mcvRansacEvaluate: hypothesis (slot) index beyond 2^32");
         check_flags(*cfg, "mcvRansacEvaluate");
+        if (cfg->method == MCV_METHOD_LMEDS)
+            fail("mcvRansacEvaluate: LMedS (method 4) has no device-level form; use cvFindHomography / "
+                 "cvFindFundamentalMat");
         if (cv_sampler(*cfg) && cv_table_stale(*P, d_pts4, N, *cfg, hypBegin, hypBegin + hypCount, (hipStream_t)stream))
             // a search starts at hypothesis 0, and a table drawn for other points is never reused: the
             // stream is rebuilt from the current points
@@ -783,12 +864,13 @@ extern "C" MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, co
         check_flags(cfg, "cvFindFundamentalMat");
         const bool seven = (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0;
         if (seven && cfg.method == MCV_METHOD_RANSAC && N != 7 && N < 15)
-            fail("cvFindFundamentalMat: 7-point FM_RANSAC needs N >= 15 (OpenCV uses LMeDS below that; N=%d)", N);
+            fail("cvFindFundamentalMat: 7-point FM_RANSAC needs N >= 15 (OpenCV uses LMeDS below that: use method 4; "
+                 "N=%d)", N);
         if (!seven && N < 8) fail("cvFindFundamentalMat: need at least 8 correspondences (N=%d)", N);
         if (seven && N < 7) fail("cvFindFundamentalMat: need at least 7 correspondences (N=%d)", N);
-        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ)
+        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
             fail("cvFindFundamentalMat: unsupported method %d", cfg.method);
-        if (cfg.method == MCV_METHOD_RANSAC && !(cfg.confidence > 0 && cfg.confidence < 1))
+        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
             fail("cvFindFundamentalMat: confidence must be in (0,1)");
         require_device();
         Plan& P = thread_plan(MCV_MODEL_FUNDAMENTAL);
@@ -809,10 +891,20 @@ extern "C" MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, co
             for (int k = 0; k < 9; ++k) Fm[k] = one.F[k];
             if (mask) std::memset(mask, 1, (size_t)N);
             count = N;
-        } else if (cfg.method == MCV_METHOD_LSQ || N == 8) {
+        } else if (cfg.method == MCV_METHOD_LSQ || (N == 8 && !(seven && cfg.method == MCV_METHOD_LMEDS))) {
             count = f_fit_all(P, P.pts.p, N, s, Fm);
             if (count <= 0) fail("cvFindFundamentalMat: degenerate point set");
             if (mask) std::memset(mask, 1, (size_t)N);
+        } else if (cfg.method == MCV_METHOD_LMEDS) {
+            // 8-point, or 7-point at any N > 7 (the range below 15 is where OpenCV itself runs LMedS)
+            RansacConfig fin = cfg;
+            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+            count = f_finalize(P, P.pts.p, N, fin, best, Fm, P.mask.p, s);
+            if (count < (seven ? 7 : 8)) fail("cvFindFundamentalMat: LMedS model has %d inliers (< %d)", count, seven ? 7 : 8);
+            if (mask) {
+                MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
+                MCV_HIP(hipStreamSynchronize(s));
+            }
         } else {
             const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
             if (best < 0) fail("cvFindFundamentalMat: RANSAC found no model with >= %d inliers", seven ? 7 : 8);

@@ -6,6 +6,7 @@
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
+#include "plan.h"
 
 namespace mcv {
 
@@ -185,6 +186,9 @@ extern "C" MCV_API int mcvTestHomographySweep(const float* pts4, int N, const fl
             launch_h_verify_packed(p.p, pairs.p, N, m.p, c.p, nModels, thr2, bb.p, 0);
             MCV_HIP(hipDeviceSynchronize());
         } else {
+            // timed under mcvProfileEnable as "h_verify_scalar": the per-evaluation baseline of the LMedS
+            // rank kernel (scripts/lmeds_bench.py)
+            ProfScope ps("h_verify_scalar", 0);
             launch_h_verify(p.p, N, m.p, c.p, nModels, thr2, fused != 0, bb.p, 0);
         }
         MCV_HIP(hipGetLastError());

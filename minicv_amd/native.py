@@ -68,6 +68,7 @@ class ReplayState(C.Structure):
 
 METHOD_LSQ = 0
 METHOD_RANSAC = 8
+METHOD_LMEDS = 4    # cv::LMEDS (findHomography / findFundamentalMat)
 FLAG_FIXED_ITERS = 1
 FLAG_NO_REFINE = 2
 FLAG_FUSED_ERROR = 64   # bit 4 is retired (rejected by the library)
@@ -173,6 +174,8 @@ SIGNATURES = {
     "mcvTestRcpExhaustive": (C.c_longlong, [_I, _P]),
     "mcvTestDivF64": (C.c_longlong, [_I, C.c_ulonglong, C.c_longlong, _P]),
     "mcvTestHomographySweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
+    "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
+    "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostScaledCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
 }
 

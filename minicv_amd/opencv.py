@@ -49,7 +49,9 @@ def _v2d(a) -> np.ndarray:
 
 
 def findHomography(src, dst, params: RansacParams | None = None):
-    """-> (inlierCount, H (3x3 float64), mask (bool[N])). Raises NativeError on failure."""
+    """-> (inlierCount, H (3x3 float64), mask (bool[N])). Raises NativeError on failure.
+    params.method: N.METHOD_RANSAC (default), N.METHOD_LSQ, or N.METHOD_LMEDS (cv::LMEDS: no threshold,
+    the smallest median error wins)."""
     params = params or RansacParams()
     a, b = _v2d(src), _v2d(dst)
     n = a.shape[0]
@@ -66,6 +68,7 @@ def findHomography(src, dst, params: RansacParams | None = None):
 
 def findFundamentalMat(a, b, params: RansacParams | None = None):
     """8-point RANSAC (default), or OpenCV FM_RANSAC with params.seven_point (+ error_kind EPIPOLAR).
+    params.method = N.METHOD_LMEDS: cv::LMEDS (no threshold); with seven_point it runs at any N >= 7.
     -> (inlierCount, F (3x3 float64), mask (bool[N]))."""
     params = params or RansacParams(threshold=3.0, confidence=0.99)
     pa, pb = _v2d(a), _v2d(b)

@@ -10,7 +10,7 @@ from pathlib import Path
 import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from minicv_amd import camera as CM, opencv, synthetic as S  # noqa: E402
+from minicv_amd import camera as CM, native as N, opencv, synthetic as S  # noqa: E402
 
 
 def timed(fn, reps=20, warm=3):
@@ -29,6 +29,9 @@ def main():
     for n in (500, 5000):
         src, dst, _ = S.homography_problem(n, 1)
         out.append(("cvFindHomography", n, timed(lambda: opencv.findHomography(src, dst))))
+        if n == 500:
+            lmeds = opencv.RansacParams(method=N.METHOD_LMEDS)
+            out.append(("cvFindHomography(LMEDS)", n, timed(lambda: opencv.findHomography(src, dst, lmeds))))
         a, b, *_ = S.essential_problem(n, seed=2)
         cfg = opencv.recoverPoseConfig(800.0, (640.0, 360.0), 0.999, 1.0)
         out.append(("cvRecoverPose", n, timed(lambda: opencv.recoverPose(cfg, a, b))))
