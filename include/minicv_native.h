@@ -540,6 +540,17 @@ MCV_API int mcvTestFingerprint(const void* d_buf, size_t bytes, uint64_t* d_out)
  * (default and maximum 192; a cfg3 LtL takes 110-157); a hypothesis needing more is solved again by
  * the one-pass kernel. Lowering the cap sends lanes down that path (tests). Returns the previous cap. */
 MCV_API int mcvTestEigLogCap(int cap);
+/* The homography sweep's self-pruning stages (key-only evaluations: mcvRansacEvaluate with d_counts ==
+ * NULL, fixed-iteration cvFindHomography). mode 0: automatic (large calls only), 1: staged whatever
+ * the call's size (it still switches itself off without a candidate, on a sampler failure, or when
+ * the first boundary is too late to pay), 2: never; any other mode leaves the setting. Returns the
+ * previous mode, -1 on error. stats (may be NULL; 16 values), for the calling thread's last
+ * homography evaluate, read after its stream was synchronised: [0] 0 = the stages pruned, 1 = no
+ * candidate, 2 = sampler failure in the chunk, 3 = first boundary too late, 4 = forced off (mode 2),
+ * 5 = the call did not qualify, -1 = no evaluate yet; [1] B, the candidate's full count; [2] the
+ * number of stages; [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
+ * [10..15] the slots alive entering each stage. Not thread-safe: tests only. */
+MCV_API int mcvTestHStaging(int mode, long long* stats);
 MCV_API void mcvHostPhilox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                            uint32_t* out4);
 /* Host twin of CameraPose.findScaled: the same candidates and costs as cvFindScaledPoseCosts,

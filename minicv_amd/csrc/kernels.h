@@ -40,6 +40,32 @@ void launch_h_verify_packed(const float* d_pts4, const void* d_pairs, int N, con
 // d_bb = launch_abs_bound4 of the float4 points.
 void launch_h_verify_certified(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                                int hypCount, float thr2, const double* d_bb, hipStream_t s);
+// The certified sweep in self-pruning stages, for callers that consume only the best key (the counts
+// of pruned slots stay partial). d_ctl: kHStageCtlInts ints (layout in ransac_h.hip, read back by
+// mcvTestHStaging); d_list: 2 x hypCount ints; d_pkey / d_pfail: launch_best's partials.
+static const int kHStageCtlInts = 32;
+static const int kCtlB = 0;        // the candidate's full count: a lower bound of the winning count
+static const int kCtlReason = 1;   // 0 = pruning engaged, else kHStage* (why everything runs to the end)
+static const int kCtlStages = 2;   // stages in use (2 + the later stages)
+static const int kCtlBound = 4;    // kHStageMax + 1 boundaries, in pairs
+static const int kCtlAlive = 12;   // slots alive entering each stage
+static const int kCtlKey = 24;     // the candidate's packed key and the first failure (2 x 64 bit)
+static const int kHStageMax = 6;          // stages: the prefix, the run to the first boundary, <= 4 later ones
+static const int kHStagePrefixDiv = 16;   // stage 0 sweeps ~N / 16 points
+static const int kHStageSlackDiv = 64;    // first boundary at N - B + N / 64 points
+static const int kHStageLater = 2;        // stages after the first boundary
+static const int kHStageLatest256 = 192;  // latest first boundary that still prunes: 192 / 256 of the pairs
+// the automatic rule: calls with fewer (hypothesis, correspondence) evaluations or fewer
+// correspondences than these run unstaged (below them the extra launches cost more
+// than the pruning saves)
+static const int64_t kHStageMinEvals = (int64_t)1 << 31;
+static const int kHStageMinN = 4096;
+// why a staged evaluation pruned nothing (control block / mcvTestHStaging stats[0]; 0 = it pruned)
+enum { kHStageNoCandidate = 1, kHStageSamplerFailure = 2, kHStageLate = 3, kHStageForcedOff = 4,
+       kHStageNotApplicable = 5 };
+void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
+                            int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
+                            uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s);
 void launch_h_mask(const float* d_pts4, int N, const float* hf8, float thr2, bool fused, uint8_t* d_mask,
                    int* d_count, hipStream_t s);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);

@@ -66,6 +66,9 @@ struct Plan {
     DevBuf<double> h64;       // homography: each hypothesis' fp64 model (finalize takes the winner's)
     DevBuf<uint8_t> hgen;     // homography: the split eigen generate's scratch (rotation log of one piece)
     DevBuf<float> pairs;      // paired point layout of the packed sweeps (homography 8, PnP 12 floats per 2)
+    DevBuf<int> hstageList;   // homography staged sweep: the two survivor lists (2 x hypCount slots)
+    DevBuf<int> hstageCtl;    // homography staged sweep: the control block (kHStageCtlInts)
+    int hstageLast = -1;      // last homography evaluate: 0 staged (the control block tells), else kHStage*
     DevBuf<uint8_t> one;      // single-hypothesis output record
     DevBuf<double> ptsd;      // essential: double4 normalised correspondences
     DevBuf<double> raw;       // essential: uploaded V2d pairs (a then b)
@@ -170,8 +173,10 @@ int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg
                      double* sigma);
 int finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
              uint8_t* d_mask, hipStream_t s);
+// needCounts: the caller reads d_counts (every slot's full count). false: only d_key is consumed, and
+// the homography sweep may run in self-pruning stages that leave partial counts in pruned slots.
 void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                    int* d_counts, uint64_t* d_key, hipStream_t s);
+                    int* d_counts, uint64_t* d_key, hipStream_t s, bool needCounts = true);
 
 // fundamental-matrix family (ransac_f.hip / ransac_f_host.cpp)
 int f_error_kind(const RansacConfig& cfg);

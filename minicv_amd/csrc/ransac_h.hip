@@ -736,11 +736,26 @@ __device__ __noinline__ uint32_t h_cert_resolve(const HPair* __restrict__ pairs,
 // nComplete = N / 2 pairs hold two correspondences; pair nComplete (odd N) holds one.
 static constexpr int kCertEvents = 256;   // per wave
 
-template <int K, int NP>
+// Control block of the staged sweep (ints; device memory, kHStageCtlInts of them). Stage s sweeps the
+// pairs [bound[s], bound[s + 1]): stage 0 is the prefix that finds the candidate, stage 1 runs every
+// slot up to the first boundary, stages 2.. run the survivor lists.
+// Indices: kCtl* in kernels.h.
+
+struct HStageArgs {
+    const int* ctl;    // control block
+    const int* list;   // survivor slots of this stage (nullptr: every slot, in order)
+    int stage;
+};
+
+// STAGED: the wave sweeps only the pair range of its stage (read from the control block), takes its
+// models through the survivor list and adds to the slots' counts; everything else (the certified
+// arithmetic, the per-model offsets, the LDS offsets and events, the overflow fallback) is the one
+// body. Stage ranges start trip-aligned, so only the stage that ends at nPairs meets the tail trip.
+template <int K, int NP, bool STAGED>
 __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict__ pairs, int nPairs, int nComplete,
                                                          const HModelF* __restrict__ models, int* __restrict__ counts,
                                                          int hypCount, float thr2, HCertSlopes slopes,
-                                                         const double* __restrict__ bb) {
+                                                         const double* __restrict__ bb, HStageArgs sa) {
     static_assert(K <= 8, "model mask in 8 bits");
     __shared__ uint32_t events[4][kCertEvents];
     __shared__ f2 offsets[4][K];
@@ -748,10 +763,22 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
     const int wib = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
     const int h0 = wave * K;
+    int pBeg = 0, pEnd = nPairs;
+    if constexpr (STAGED) {
+        pBeg = sa.ctl[kCtlBound + sa.stage];
+        pEnd = sa.ctl[kCtlBound + sa.stage + 1];
+        if (pBeg >= pEnd) return;
+        if (sa.list) hypCount = sa.ctl[kCtlAlive + sa.stage];
+    }
     if (h0 >= hypCount) return;
 
     f2 hp[K][4], hc[K], cb[K];
     bool valid[K];
+    int slot[STAGED ? K : 1];   // STAGED: the slots of the wave's entries (wave-uniform, kept for the write-back)
+    auto slot_of = [&](int k) -> int {
+        if constexpr (STAGED) return slot[k];
+        else return h0 + k < hypCount ? h0 + k : hypCount - 1;
+    };
     bool fast = true;
     double b4[4];
 #pragma unroll
@@ -759,8 +786,12 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int hk = h0 + k;
-        valid[k] = (hk < hypCount) && (counts[hk] >= 0);
-        const f2* mp = (const f2*)&models[hk < hypCount ? hk : hypCount - 1];
+        if constexpr (STAGED) {
+            const int e = hk < hypCount ? hk : hypCount - 1;
+            slot[k] = sa.list ? sa.list[e] : e;
+        }
+        valid[k] = (hk < hypCount) && (counts[STAGED ? slot_of(k) : hk] >= 0);
+        const f2* mp = (const f2*)&models[slot_of(k)];
 #pragma unroll
         for (int j = 0; j < 4; ++j) hp[k][j] = mp[j];
         hc[k] = f2{hp[k][1].x, hp[k][2].y};
@@ -784,10 +815,11 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
     constexpr int TRIP = 64 * NP;
     if (fast) {
         const int nFull = nComplete / TRIP * TRIP;
+        const int fullEnd = STAGED ? (pEnd < nFull ? pEnd : nFull) : nFull;
         uint64_t all[NP];
 #pragma unroll
         for (int j = 0; j < NP; ++j) all[j] = ~0ull;
-        for (int base = 0; base < nFull; base += TRIP) {
+        for (int base = pBeg; base < fullEnd; base += TRIP) {
             HPair q[NP];
 #pragma unroll
             for (int j = 0; j < NP; ++j) q[j] = pairs[base + 64 * j + lane];
@@ -795,7 +827,8 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
             if (__builtin_expect(und != 0, 0))
                 h_cert_fix_regs<K, NP, false>(und, hp, hc, slopes.a, cb, q, all, all, thr2, one, cnt);
         }
-        for (int base = nFull; base < nPairs; base += TRIP) {
+        // the tail: pairs [nFull, nPairs), part of the stage that ends at nPairs (pBeg <= nFull there)
+        for (int base = STAGED ? (pBeg > nFull ? pBeg : nFull) : nFull; base < pEnd; base += TRIP) {
             HPair q[NP];
             uint64_t vx[NP], vy[NP];
 #pragma unroll
@@ -821,8 +854,7 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     if (!(ev & (1u << k))) continue;
-                    const int hk = h0 + k < hypCount ? h0 + k : hypCount - 1;
-                    cnt[k] += h_cert_resolve<NP>(pairs, nPairs, nComplete, base, models, hk, slopes.a,
+                    cnt[k] += h_cert_resolve<NP>(pairs, nPairs, nComplete, base, models, slot_of(k), slopes.a,
                                                  offsets[wib][k], thr2);
                 }
             }
@@ -830,9 +862,105 @@ __global__ __launch_bounds__(256) void mcv_h_verify_cert(const HPair* __restrict
     }
     if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (valid[k]) counts[h0 + k] = fast ? (int)cnt[k] : kStatusRedo;
+        for (int k = 0; k < K; ++k) {
+            if (!valid[k]) continue;
+            if constexpr (STAGED)
+                counts[slot[k]] = fast ? counts[slot[k]] + (int)cnt[k] : kStatusRedo;
+            else
+                counts[h0 + k] = fast ? (int)cnt[k] : kStatusRedo;
+        }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Staged sweep: the small kernels between the stages (launch_h_verify_staged).
+// ------------------------------------------------------------------------------------------
+__global__ void mcv_h_stage_init(int* __restrict__ ctl, int pa, int hypCount) {
+    const int i = threadIdx.x;
+    if (i >= kHStageCtlInts) return;
+    int v = 0;
+    if (i == kCtlBound + 1) v = pa;
+    if (i == kCtlAlive || i == kCtlAlive + 1) v = hypCount;
+    ctl[i] = v;
+}
+
+// The candidate (best partial count of stage 0) counted over all N correspondences with the exact
+// op-by-op error: ctl[kCtlB] (zeroed by mcv_h_stage_init). No candidate (key 0): B stays 0.
+__global__ __launch_bounds__(256) void mcv_h_stage_count(const float4* __restrict__ pts, int N,
+                                                         const HModelF* __restrict__ models, int64_t hypBegin,
+                                                         float thr2, int* __restrict__ ctl) {
+    const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
+    if (key == 0) return;
+    const int64_t hyp = (int64_t)(0xFFFFFFFFull - (key & 0xFFFFFFFFull));
+    const HModelF m = models[hyp - hypBegin];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool in = false;
+    if (i < N) {
+        const float4 q = pts[i];
+        in = h_error(m.h, q.x, q.y, q.z, q.w) <= thr2;
+    }
+    const uint64_t b = __ballot(in);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(ctl + kCtlB, (int)__popcll(b));
+}
+
+// One thread: the stage boundaries from B. The first boundary is the first point count at which a
+// slot can fall below the bound (N - B) plus the slack, rounded up to a trip; the later stages split
+// the rest evenly. Pruning switches itself off (stage 1 runs every slot to the end) without a
+// candidate, with a sampler failure in the chunk (the host then reads every count) and when the first
+// boundary lies beyond latest/256 of the pairs.
+__global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int later, int slackPts, int latest256) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int nPairs = (N + 1) / 2;
+    const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
+    const int64_t fail = *(const int64_t*)(ctl + kCtlKey + 2);
+    const int pa = ctl[kCtlBound + 1];
+    int reason = 0;
+    int p1 = nPairs;
+    if (key == 0) reason = kHStageNoCandidate;
+    else if (fail != INT64_MAX) reason = kHStageSamplerFailure;
+    else {
+        const int64_t pts = (int64_t)N - ctl[kCtlB] + slackPts;
+        const int64_t pr = ((pts + 1) / 2 + trip - 1) / trip * trip;
+        p1 = pr < pa ? pa : (pr > nPairs ? nPairs : (int)pr);
+        if ((int64_t)p1 * 256 > (int64_t)nPairs * latest256) reason = kHStageLate;
+    }
+    if (reason) p1 = nPairs;
+    ctl[kCtlReason] = reason;
+    ctl[kCtlStages] = 2 + later;
+    ctl[kCtlBound + 2] = p1;
+    const int trips = (nPairs - p1) / trip;   // whole trips left after the first boundary
+    for (int s = 1; s <= later; ++s) {
+        int b = s == later ? nPairs : p1 + (int)((int64_t)trips * s / later) * trip;
+        ctl[kCtlBound + 2 + s] = b;
+    }
+}
+
+// Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
+// whose count can still reach B, count + (N - processed) >= B. Inclusive, so ties survive; a status
+// (count < 0: no model, no sample, the exact-recount mark) never enters a list. Any order: ballot
+// and one atomic per wave.
+__global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict__ counts, int hypCount, int N,
+                                                           int* __restrict__ ctl, int stage,
+                                                           const int* __restrict__ src, int* __restrict__ dst) {
+    if (ctl[kCtlReason] != 0) return;
+    const int n = src ? ctl[kCtlAlive + stage - 1] : hypCount;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int done2 = 2 * ctl[kCtlBound + stage];
+    const int left = N - (done2 < N ? done2 : N);
+    bool keep = false;
+    int slot = 0;
+    if (i < n) {
+        slot = src ? src[i] : i;
+        const int c = counts[slot];
+        keep = c >= 0 && c + left >= ctl[kCtlB];
+    }
+    const uint64_t b = __ballot(keep);
+    if (b == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(ctl + kCtlAlive + stage, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
 }
 
 // Bounding box of the source points: bbox[0] = max |x|, bbox[1] = max |y| (one block; the
@@ -1186,19 +1314,71 @@ static void launch_h_verify_cert_k(const void* d_pairs, int N, const void* d_mod
                                    float thr2, const double* d_bb, hipStream_t s) {
     const int waves = (hypCount + K - 1) / K;
     const int blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL((mcv_h_verify_cert<K, NP>), dim3(blocks), dim3(256), 0, s, (const HPair*)d_pairs, (N + 1) / 2,
-                       N / 2, (const HModelF*)d_models, d_counts, hypCount, thr2, h_cert_slopes_host(thr2), d_bb);
+    hipLaunchKernelGGL((mcv_h_verify_cert<K, NP, false>), dim3(blocks), dim3(256), 0, s, (const HPair*)d_pairs,
+                       (N + 1) / 2, N / 2, (const HModelF*)d_models, d_counts, hypCount, thr2,
+                       h_cert_slopes_host(thr2), d_bb, HStageArgs{nullptr, nullptr, 0});
 }
 
 // Certified sweep of the op-by-op error + the exact recount of the slots it marks kStatusRedo.
 // <6, 1>: screened against <4, 2>, <4, 1>, <5, 1>, <3, 2>, <8, 2> and t = 2^-12 / 2^-11 / 2^-10
 // (28.8 ms vs 29.6-33 ms at cfg3; scripts/gpu_r02_cert.sh); re-screened in round 5 (same box: 29.9-30.0 ms
 // against 30.7-30.9 / 30.4-30.5 / 31.0-31.1 ms for <4, 1> / <5, 1> / <4, 2>; scripts/gpu_r05_am.sh).
+static constexpr int kCertK = 6, kCertNP = 1;
 void launch_h_verify_certified(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                                int hypCount, float thr2, const double* d_bb, hipStream_t s) {
-    launch_h_verify_cert_k<6, 1>(d_pairs, N, d_models, d_counts, hypCount, thr2, d_bb, s);
+    launch_h_verify_cert_k<kCertK, kCertNP>(d_pairs, N, d_models, d_counts, hypCount, thr2, d_bb, s);
     launch_h_verify_kp<kVerifyHypPerWave, kVerifyPtsPerLane>(d_pts4, N, d_models, d_counts, hypCount, thr2, false,
                                                              nullptr, s, 1);
+}
+
+// The certified sweep in stages that prune themselves (the caller consumes only the best key): stage 0
+// sweeps a prefix, its best partial count names a candidate, the candidate's full count B bounds the
+// winning count from below, and from the first boundary on only the slots that can still reach B go on
+// (kernels above; the exactness argument is at the caller's staging decision). Everything is enqueued
+// on s: the boundaries and the live counts stay on the device, the grids are sized for every slot and
+// the waves beyond the live count exit at once.
+// d_ctl: kHStageCtlInts ints; d_list: 2 x hypCount ints (the survivor lists, ping-pong).
+void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
+                            int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
+                            uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s) {
+    constexpr int K = kCertK, NP = kCertNP, TRIP = 64 * NP;
+    const int nPairs = (N + 1) / 2, nComplete = N / 2;
+    const int nFull = nComplete / TRIP * TRIP;
+    // stage 0: ~N / kHStagePrefixDiv points, a whole number of trips (at least one where N has one)
+    int pa = (N / kHStagePrefixDiv / 2 + TRIP / 2) / TRIP * TRIP;
+    if (pa < TRIP) pa = TRIP;
+    if (pa > nFull) pa = nFull;
+    const int waves = (hypCount + K - 1) / K;
+    const int blocks = (waves + 3) / 4;
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    auto stage = [&](int st, const int* list) {
+        hipLaunchKernelGGL((mcv_h_verify_cert<K, NP, true>), dim3(blocks), dim3(256), 0, s, (const HPair*)d_pairs,
+                           nPairs, nComplete, (const HModelF*)d_models, d_counts, hypCount, thr2, slopes, d_bb,
+                           HStageArgs{d_ctl, list, st});
+    };
+    auto recount = [&]() {   // the slots marked kStatusRedo, over all N, by the exact scalar sweep
+        launch_h_verify_kp<kVerifyHypPerWave, kVerifyPtsPerLane>(d_pts4, N, d_models, d_counts, hypCount, thr2, false,
+                                                                 nullptr, s, 1);
+    };
+    hipLaunchKernelGGL(mcv_h_stage_init, dim3(1), dim3(64), 0, s, d_ctl, pa, hypCount);
+    stage(0, nullptr);
+    // candidate: the best partial count before any sampler failure (minimum count 0: any model will do)
+    launch_best(d_counts, hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
+    hipLaunchKernelGGL(mcv_h_stage_count, dim3((N + 255) / 256), dim3(256), 0, s, (const float4*)d_pts4, N,
+                       (const HModelF*)d_models, hypBegin, thr2, d_ctl);
+    hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, TRIP, kHStageLater,
+                       N / kHStageSlackDiv, kHStageLatest256);
+    stage(1, nullptr);
+    int* lists[2] = {d_list, d_list + hypCount};
+    for (int st = 2; st < 2 + kHStageLater; ++st) {
+        // the first compaction sees the recount marks (count < 0) before the recount overwrites them
+        hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_counts, hypCount, N,
+                           d_ctl, st, st == 2 ? (const int*)nullptr : (const int*)lists[(st - 1) & 1], lists[st & 1]);
+        if (st == 2) recount();
+        stage(st, lists[st & 1]);
+    }
+    // a wave of a later stage that left the fast path (event overflow in the tail) marked its slots too
+    recount();
 }
 
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,

@@ -97,6 +97,11 @@ namespace mcv {
 // ------------------------------------------------------------------------------------------
 // Plan
 // ------------------------------------------------------------------------------------------
+// mcvTestHStaging: 0 automatic, 1 staging regardless of the call's size, 2 never (tests only)
+static int g_hstage_mode = 0;
+// the plan of the calling thread's last homography evaluate (mcvTestHStaging reads its control block)
+static thread_local Plan* t_hstage_plan = nullptr;
+
 void Plan::reserve(int n, int64_t hyps) {
     if (n > maxN) maxN = n;
     if (hyps > maxHyps) maxHyps = hyps;
@@ -146,6 +151,7 @@ hipStream_t Plan::own_stream() {
 }
 
 Plan::~Plan() {
+    if (t_hstage_plan == this) t_hstage_plan = nullptr;
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -324,7 +330,7 @@ void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipS
 
 // Evaluate one chunk of hypotheses on the device (generate + verify [+ best key]).
 void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                    int* d_counts, uint64_t* d_key, hipStream_t s) {
+                    int* d_counts, uint64_t* d_key, hipStream_t s, bool needCounts) {
     if (P.model == MCV_MODEL_ESSENTIAL) {
         e_evaluate_chunk(P, (const double*)d_ptsv, N, cfg, hypBegin, hypCount, d_counts, s);
         if (d_key)
@@ -362,8 +368,31 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
         }
         // the winner's models can come straight from this chunk's buffers (h_finalize)
         mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
+        // Staging decision. The certified sweep may run in self-pruning stages only where nobody reads
+        // the per-hypothesis counts: the caller gets the key alone. The key stays exact. B is the full
+        // count of one hypothesis with a model before any sampler failure (the candidate), so B <= the
+        // winning count. A slot is dropped only when count-so-far + points-left < B: its full count is
+        // below B, and so is the partial count it keeps (partial <= full). The candidate and every slot
+        // that reaches the winning count are never dropped (the test is inclusive, so ties stay) and end
+        // with full counts. The unchanged reduction below therefore packs, for each dropped slot, a key
+        // below the candidate's whether it sees the partial or the full count (both < B; both map to key
+        // 0 when B itself is below the minimum count), and the true key for every other slot: the same
+        // maximum, the same lowest-index tie-break, the same minimum-count rule. Adaptive replay, LMedS,
+        // callers that pass d_counts, the fused error and the other models keep the single full sweep.
+        const bool stageable = !fused && d_key != nullptr && !needCounts;
+        const bool staged = stageable && g_hstage_mode != 2 &&
+                            (g_hstage_mode == 1 || (N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals));
+        P.hstageLast = staged ? 0 : (stageable && g_hstage_mode == 2 ? kHStageForcedOff : kHStageNotApplicable);
+        t_hstage_plan = &P;
+        if (staged) {
+            P.hstageCtl.ensure(kHStageCtlInts);
+            P.hstageList.ensure(2 * (size_t)hypCount);
+        }
         ProfScope ps("h_verify", s);
-        if (!fused) {
+        if (staged) {
+            launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
+                                   P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s);
+        } else if (!fused) {
             // default: OpenCV's op-by-op error, certified division-free packed sweep
             launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s);
         } else {
@@ -550,7 +579,9 @@ int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
                 MCV_HIP(hipSetDevice(x.dev));
                 x.P->reserve(N, ck * slotScale);
             }
-            evaluate_chunk(*x.P, x.pts, N, cfg, begin + off, ck, x.P->counts.p, fixed ? x.P->key.p : nullptr, x.s);
+            // fixed: only the key is read (the counts only after a sampler failure, which unstages the chunk)
+            evaluate_chunk(*x.P, x.pts, N, cfg, begin + off, ck, x.P->counts.p, fixed ? x.P->key.p : nullptr, x.s,
+                           !fixed);
             if (fixed)
                 MCV_HIP(hipMemcpyAsync(P.h_keys.p + 2 * k, x.P->key.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                        x.s));
@@ -803,8 +834,35 @@ extern "C" MCV_API int mcvRansacEvaluate(mcvRansacPlan* plan, const void* d_pts4
             cv_table_prepare(*P, d_pts4, nullptr, N, *cfg, std::max<int64_t>(hypBegin + hypCount, cfg->maxIters),
                              (hipStream_t)stream);
         evaluate_chunk(*P, d_pts4, N, *cfg, hypBegin, (int)hypCount, d_counts ? d_counts : P->counts.p, d_key,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, d_counts != nullptr);
         return 1;
+    })
+}
+
+// Test hook (declared in minicv_native.h). stats[16]: [0] -1 no homography evaluate on this thread yet,
+// 0 the stages pruned, else why not (kHStage*); [1] B; [2] stages; [3..9] stage boundaries in points;
+// [10..15] slots alive entering each stage. Call after synchronising the evaluate's stream.
+extern "C" MCV_API int mcvTestHStaging(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hstage_mode;
+        if (mode >= 0 && mode <= 2) g_hstage_mode = mode;
+        if (stats) {
+            for (int i = 0; i < 16; ++i) stats[i] = 0;
+            const Plan* P = t_hstage_plan;
+            stats[0] = P ? P->hstageLast : -1;
+            if (P && P->hstageLast == 0) {
+                int ctl[kHStageCtlInts];
+                MCV_HIP(hipMemcpy(ctl, P->hstageCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+                const int N = P->last.N;
+                stats[0] = ctl[kCtlReason];
+                stats[1] = ctl[kCtlB];
+                stats[2] = ctl[kCtlStages];
+                for (int i = 0; i <= kHStageMax; ++i)
+                    stats[3 + i] = std::min<long long>(2LL * ctl[kCtlBound + i], N);
+                for (int i = 0; i < kHStageMax; ++i) stats[10 + i] = ctl[kCtlAlive + i];
+            }
+        }
+        return prev;
     })
 }
 
