@@ -260,6 +260,21 @@ MCV_API int cvMatchAndFindModel(const DetectorResult* a, const DetectorResult* b
                                 const RansacConfig* rcfg, mcvM33d* M, int* pairs, uint8_t* mask, int maxPairs,
                                 int* matchCount);
 
+/* The same two calls with the descriptor norm chosen by the caller (OpenCV's NormTypes numbering).
+ * cvMatchFeatures / cvMatchAndFindModel are the MCV_NORM_AUTO forms. uint8 descriptors under
+ * MCV_NORM_L2 (byte SIFT: cv::SIFT::create(..., CV_8U), the reference's default descriptor type) take
+ * the exact int8 matcher of cvMatchL2U8, in both directions when crossCheck is set; dist is then the
+ * L2 distance, and every output equals that of the float32 call on the same values. uint8 + AUTO or
+ * HAMMING: Hamming. float32 + AUTO or L2: L2. float32 + HAMMING, or any other norm: failure. */
+#define MCV_NORM_AUTO    0   /* by element type: u8 -> Hamming, f32 -> L2 (cvMatchFeatures' rule) */
+#define MCV_NORM_L2      4   /* OpenCV numbering */
+#define MCV_NORM_HAMMING 6
+MCV_API int cvMatchFeaturesNorm(const DetectorResult* a, const DetectorResult* b, const MatchConfig* cfg, int norm,
+                                int* pairs, float* dist, int maxPairs);
+MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const DetectorResult* b, const MatchConfig* mcfg,
+                                    int norm, const RansacConfig* rcfg, mcvM33d* M, int* pairs, uint8_t* mask,
+                                    int maxPairs, int* matchCount);
+
 /* Brute-force Hamming matcher (BFMatcher NORM_HAMMING, knn k = 2). q: [nq][bytesPerDesc],
  * t: [nt][bytesPerDesc] row-major bytes; bytesPerDesc in [1, 64]; nt < 2^22.
  * Outputs per query: best train index / distance and second best (idx2/dist2 may be NULL;
@@ -272,7 +287,15 @@ MCV_API int cvMatchHamming(const uint8_t* q, const int nq, const uint8_t* t, con
 MCV_API int cvMatchL2(const float* q, const int nq, const float* t, const int nt, const int dim,
                       int* idx, float* dist, int* idx2, float* dist2);
 
-/* Multi-GPU forms of the two matchers (query blocks Nq / D per GPU, train set
+/* Brute-force L2 matcher (BFMatcher NORM_L2, knn k = 2) on uint8 descriptors [n][dim] (byte SIFT),
+ * exact on the int8 matrix cores: d^2 = sum (q_k - t_k)^2 as an integer, order (d^2, train index)
+ * (ties -> lowest train index), dist = (float)sqrt((double)d^2). Every output equals cvMatchL2's on the
+ * same bytes converted to float32 (idx2 / dist2 = -1 / +inf when nt < 2; idx = -1, dist = +inf when
+ * nt == 0). dim in [1, 512]; nq, nt <= 2^24. Returns nq, or -1 on failure. */
+MCV_API int cvMatchL2U8(const uint8_t* q, const int nq, const uint8_t* t, const int nt, const int dim,
+                        int* idx, float* dist, int* idx2, float* dist2);
+
+/* Multi-GPU forms of the matchers (query blocks Nq / D per GPU, train set
  * replicated), for a host that calls one synchronous export from one process like the reference's
  * P/Invoke layer (OpenCV.fs:339-382). The queries are split into deviceCount contiguous blocks (the
  * first nq % deviceCount one query longer), block k runs on visible device (current + k) mod count,
@@ -284,6 +307,8 @@ MCV_API int cvMatchHammingMulti(const uint8_t* q, const int nq, const uint8_t* t
                                 int* dist2);
 MCV_API int cvMatchL2Multi(const float* q, const int nq, const float* t, const int nt, const int dim,
                            const int deviceCount, int* idx, float* dist, int* idx2, float* dist2);
+MCV_API int cvMatchL2U8Multi(const uint8_t* q, const int nq, const uint8_t* t, const int nt, const int dim,
+                             const int deviceCount, int* idx, float* dist, int* idx2, float* dist2);
 
 /* Diagnostics of the exact L2 re-rank: queries the calling thread's last L2 match sent to the exact
  * full scan (near-ties the GEMM form cannot separate); synchronises that match's stream. */
@@ -412,6 +437,9 @@ MCV_API int mcvMatchHammingDeviceForm(const uint8_t* d_q, int nq, const uint8_t*
                                       int* d_idx, int* d_dist, int* d_idx2, int* d_dist2, int form, void* stream);
 MCV_API int mcvMatchL2Device(const float* d_q, int nq, const float* d_t, int nt, int dim,
                              int* d_idx, float* d_dist, int* d_idx2, float* d_dist2, void* stream);
+/* cvMatchL2U8 on device arrays (three launches, no host round trip). */
+MCV_API int mcvMatchL2U8Device(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim,
+                               int* d_idx, float* d_dist, int* d_idx2, float* d_dist2, void* stream);
 
 /* Device-level CameraPose.findScaled: d_world V3d[N], d_obs V2d[N] on the device. Synchronises
  * `stream`; same outputs and return value as cvFindScaledPose. */

@@ -242,7 +242,7 @@ void launch_match_compact(const int* d_idx, const int* d_di1, const int* d_di2, 
                           const uint8_t* d_kpA, const uint8_t* d_kpB, int kpStride, uint8_t* d_keep, int* d_cnt,
                           int* d_off, int* d_pairs, float* d_dist, float* d_pts4, hipStream_t s);
 
-// ---- matchers (match_hamming.hip, match_l2.hip)
+// ---- matchers (match_hamming.hip, match_l2.hip, match_l2u8.hip)
 static constexpr int kHammingFormGemm = 0, kHammingFormPopcount = 1;
 int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytesPerDesc, int* d_idx,
                          int* d_dist, int* d_idx2, int* d_dist2, hipStream_t s, int form = kHammingFormGemm);
@@ -250,6 +250,12 @@ int launch_match_l2(const float* d_q, int nq, const float* d_t, int nt, int dim,
                     int* d_idx2, float* d_dist2, hipStream_t s);
 int l2_last_exact_scans();
 int l2_last_gemm_form();
+// uint8 descriptors under L2 on the int8 matrix cores (match_l2u8.hip): exact, the outputs of
+// launch_match_l2 on the same bytes as fp32. check_match_l2u8 throws on a dim / nq / nt outside the
+// kernel's range (no device needed).
+void check_match_l2u8(const char* who, int nq, int nt, int dim);
+int launch_match_l2u8(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim, int* d_idx, float* d_dist,
+                      int* d_idx2, float* d_dist2, hipStream_t s);
 
 // ---- CameraPose.findScaled (scaled_pose.hip)
 struct ScaledSetup;

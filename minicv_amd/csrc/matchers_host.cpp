@@ -169,13 +169,42 @@ extern "C" MCV_API int cvMatchL2(const float* q, const int nq, const float* t, c
     return cvMatchL2Multi(q, nq, t, nt, dim, 1, idx, dist, idx2, dist2);
 }
 
+extern "C" MCV_API int cvMatchL2U8Multi(const uint8_t* q, const int nq, const uint8_t* t, const int nt, const int dim,
+                                        const int deviceCount, int* idx, float* dist, int* idx2, float* dist2) {
+    MCV_GUARD(-1, {
+        if (nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist)) || (nt > 0 && !t))
+            fail("cvMatchL2U8: bad argument");
+        check_match_l2u8("cvMatchL2U8", nq, nt, dim);
+        return match_sharded<float>("cvMatchL2U8", q, nq, t, nt, (size_t)dim, deviceCount, idx, dist, idx2, dist2,
+                                    [&](const uint8_t* dq, int c, const uint8_t* dt, int* i1, float* d1, int* i2,
+                                        float* d2, hipStream_t s) {
+                                        launch_match_l2u8(dq, c, dt, nt, dim, i1, d1, i2, d2, s);
+                                    });
+    })
+}
+
+extern "C" MCV_API int cvMatchL2U8(const uint8_t* q, const int nq, const uint8_t* t, const int nt, const int dim,
+                                   int* idx, float* dist, int* idx2, float* dist2) {
+    return cvMatchL2U8Multi(q, nq, t, nt, dim, 1, idx, dist, idx2, dist2);
+}
+
+extern "C" MCV_API int mcvMatchL2U8Device(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim, int* d_idx,
+                                          float* d_dist, int* d_idx2, float* d_dist2, void* stream) {
+    MCV_GUARD(-1, {
+        if (nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_idx || !d_dist)) || (nt > 0 && !d_t))
+            fail("mcvMatchL2U8Device: bad argument");
+        check_match_l2u8("mcvMatchL2U8Device", nq, nt, dim);
+        return launch_match_l2u8(d_q, nq, d_t, nt, dim, d_idx, d_dist, d_idx2, d_dist2, (hipStream_t)stream);
+    })
+}
+
 extern "C" MCV_API int mcvMatchHammingDeviceForm(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                                                  int bytesPerDesc, int* d_idx, int* d_dist, int* d_idx2, int* d_dist2,
                                                  int form, void* stream) {
     MCV_GUARD(-1, {
         if (nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_idx || !d_dist))) fail("mcvMatchHammingDevice: bad argument");
         if (form != kHammingFormGemm && form != kHammingFormPopcount)
-            fail("mcvMatchHammingDeviceForm: form %d is neither 0 (int8 GEMM) nor 1 (popcount)", form);
+            fail("mcvMatchHammingDeviceForm: form %d is neither 0 (fp4 GEMM) nor 1 (popcount)", form);
         return launch_match_hamming(d_q, nq, d_t, nt, bytesPerDesc, d_idx, d_dist, d_idx2, d_dist2,
                                     (hipStream_t)stream, form);
     })

@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "plan.h"
 
+#include <algorithm>
 #include <climits>
 #include <cstring>
 
@@ -34,12 +35,21 @@ void check_result(const DetectorResult* r, const char* who, const char* which) {
         fail("%s: %s DescriptorEntries %d not a multiple of PointCount %d", who, which, r->DescriptorEntries,
              r->PointCount);
 }
+
+// The norm argument of the *Norm exports against the descriptor element type: AUTO follows the
+// element type (uint8 -> Hamming, float32 -> L2), L2 serves both, Hamming only bytes.
+void check_norm(int norm, bool u8, const char* who) {
+    if (norm != MCV_NORM_AUTO && norm != MCV_NORM_L2 && norm != MCV_NORM_HAMMING)
+        fail("%s: norm %d is none of MCV_NORM_AUTO (0), MCV_NORM_L2 (4), MCV_NORM_HAMMING (6)", who, norm);
+    if (!u8 && norm == MCV_NORM_HAMMING) fail("%s: MCV_NORM_HAMMING needs uint8 descriptors, got float32", who);
+}
 }  // namespace
 
 // Match a -> b on the GPU and compact the surviving pairs in query order. Device outputs:
 // w.pairs (2 per match), w.dist, pts4 (float4 per match, written to d_pts4). Returns the count.
-static int match_compact(const DetectorResult* a, const DetectorResult* b, const MatchConfig& cfg, PipeWork& w,
-                         float* d_pts4_or_null, Plan* P, hipStream_t s, const char* who) {
+// norm: MCV_NORM_*; uint8 rows go to the Hamming kernel unless it is MCV_NORM_L2 (the int8 L2 kernel).
+static int match_compact(const DetectorResult* a, const DetectorResult* b, const MatchConfig& cfg, int norm,
+                         PipeWork& w, float* d_pts4_or_null, Plan* P, hipStream_t s, const char* who) {
     check_result(a, who, "a");
     check_result(b, who, "b");
     const int na = a->PointCount, nb = b->PointCount;
@@ -48,11 +58,14 @@ static int match_compact(const DetectorResult* a, const DetectorResult* b, const
         fail("%s: descriptor element types differ (%d vs %d)", who, a->DescriptorElementType, b->DescriptorElementType);
     const int dim = a->DescriptorEntries / na;
     if (b->DescriptorEntries / nb != dim) fail("%s: descriptor widths differ", who);
-    const bool ham = a->DescriptorElementType == kElemU8;
-    if (!ham && a->DescriptorElementType != kElemF32)
+    const bool u8 = a->DescriptorElementType == kElemU8;
+    if (!u8 && a->DescriptorElementType != kElemF32)
         fail("%s: descriptor element type %d unsupported (0 = uint8 Hamming, 5 = float32 L2)", who,
              a->DescriptorElementType);
-    const size_t esz = ham ? 1 : 4;
+    check_norm(norm, u8, who);
+    const bool ham = u8 && norm != MCV_NORM_L2;   // uint8 rows: Hamming unless L2 is asked for
+    if (u8 && !ham) check_match_l2u8(who, std::max(na, nb), std::max(na, nb), dim);
+    const size_t esz = u8 ? 1 : 4;
     w.da.ensure((size_t)a->DescriptorEntries * esz);
     w.db.ensure((size_t)b->DescriptorEntries * esz);
     w.kpa.ensure((size_t)na * sizeof(KeyPoint2d));
@@ -75,6 +88,14 @@ static int match_compact(const DetectorResult* a, const DetectorResult* b, const
         if (cfg.crossCheck) {
             w.idxBack.ensure(nb); w.diBack.ensure(nb);
             launch_match_hamming(w.db.p, nb, w.da.p, na, dim, w.idxBack.p, w.diBack.p, nullptr, nullptr, s);
+            idxBack = w.idxBack.p;
+        }
+    } else if (u8) {
+        w.df1.ensure(na); w.df2.ensure(na);
+        launch_match_l2u8(w.da.p, na, w.db.p, nb, dim, w.idx.p, w.df1.p, nullptr, w.df2.p, s);
+        if (cfg.crossCheck) {
+            w.idxBack.ensure(nb); w.dfBack.ensure(nb);
+            launch_match_l2u8(w.db.p, nb, w.da.p, na, dim, w.idxBack.p, w.dfBack.p, nullptr, nullptr, s);
             idxBack = w.idxBack.p;
         }
     } else {
@@ -107,16 +128,23 @@ static int match_compact(const DetectorResult* a, const DetectorResult* b, const
 
 using namespace mcv;
 
-extern "C" MCV_API int cvMatchFeatures(const DetectorResult* a, const DetectorResult* b, const MatchConfig* cfgp,
-                                       int* pairs, float* dist, int maxPairs) {
+// The norm check that needs no device: an unknown norm, or Hamming on float32 rows, fails before
+// require_device() (match_compact repeats it with the other argument checks).
+static void precheck_norm(const DetectorResult* a, int norm, const char* who) {
+    check_norm(norm, !a || a->DescriptorElementType != kElemF32, who);
+}
+
+extern "C" MCV_API int cvMatchFeaturesNorm(const DetectorResult* a, const DetectorResult* b, const MatchConfig* cfgp,
+                                           int norm, int* pairs, float* dist, int maxPairs) {
     MCV_GUARD(-1, {
         if (!pairs) fail("cvMatchFeatures: pairs is NULL");
+        precheck_norm(a, norm, "cvMatchFeatures");
         MatchConfig cfg = cfgp ? *cfgp : MatchConfig{0.8f, 0, 0.f, MCV_MODEL_HOMOGRAPHY};
         require_device();
         Plan& P = thread_plan(MCV_MODEL_HOMOGRAPHY);
         hipStream_t s = P.own_stream();
         PipeWork& w = pipe_work();
-        const int n = match_compact(a, b, cfg, w, nullptr, &P, s, "cvMatchFeatures");
+        const int n = match_compact(a, b, cfg, norm, w, nullptr, &P, s, "cvMatchFeatures");
         if (n > maxPairs) fail("cvMatchFeatures: %d matches exceed maxPairs %d", n, maxPairs);
         if (n > 0) {
             MCV_HIP(hipMemcpyAsync(pairs, w.pairs.p, (size_t)2 * n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -127,12 +155,18 @@ extern "C" MCV_API int cvMatchFeatures(const DetectorResult* a, const DetectorRe
     })
 }
 
-extern "C" MCV_API int cvMatchAndFindModel(const DetectorResult* a, const DetectorResult* b, const MatchConfig* mcfgp,
-                                           const RansacConfig* rcfgp, mcvM33d* M, int* pairs, uint8_t* mask,
-                                           int maxPairs, int* matchCount) {
+extern "C" MCV_API int cvMatchFeatures(const DetectorResult* a, const DetectorResult* b, const MatchConfig* cfgp,
+                                       int* pairs, float* dist, int maxPairs) {
+    return cvMatchFeaturesNorm(a, b, cfgp, MCV_NORM_AUTO, pairs, dist, maxPairs);
+}
+
+extern "C" MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const DetectorResult* b,
+                                               const MatchConfig* mcfgp, int norm, const RansacConfig* rcfgp,
+                                               mcvM33d* M, int* pairs, uint8_t* mask, int maxPairs, int* matchCount) {
     MCV_GUARD(0, {
         if (matchCount) *matchCount = 0;
         if (!M || !pairs || !mask) fail("cvMatchAndFindModel: null argument");
+        precheck_norm(a, norm, "cvMatchAndFindModel");
         const MatchConfig mcfg = mcfgp ? *mcfgp : MatchConfig{0.8f, 0, 0.f, MCV_MODEL_HOMOGRAPHY};
         if (mcfg.model != MCV_MODEL_HOMOGRAPHY && mcfg.model != MCV_MODEL_FUNDAMENTAL)
             fail("cvMatchAndFindModel: model %d unsupported (homography or fundamental)", mcfg.model);
@@ -145,7 +179,7 @@ extern "C" MCV_API int cvMatchAndFindModel(const DetectorResult* a, const Detect
         Plan& P = thread_plan(mcfg.model);
         hipStream_t s = P.own_stream();
         PipeWork& w = pipe_work();
-        const int n = match_compact(a, b, mcfg, w, nullptr, &P, s, "cvMatchAndFindModel");
+        const int n = match_compact(a, b, mcfg, norm, w, nullptr, &P, s, "cvMatchAndFindModel");
         if (n > maxPairs) fail("cvMatchAndFindModel: %d matches exceed maxPairs %d", n, maxPairs);
         if (matchCount) *matchCount = n;
         if (n > 0) MCV_HIP(hipMemcpyAsync(pairs, w.pairs.p, (size_t)2 * n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -165,4 +199,10 @@ extern "C" MCV_API int cvMatchAndFindModel(const DetectorResult* a, const Detect
         for (int k = 0; k < 9; ++k) M->M[k] = model9[k];
         return count;
     })
+}
+
+extern "C" MCV_API int cvMatchAndFindModel(const DetectorResult* a, const DetectorResult* b, const MatchConfig* mcfgp,
+                                           const RansacConfig* rcfgp, mcvM33d* M, int* pairs, uint8_t* mask,
+                                           int maxPairs, int* matchCount) {
+    return cvMatchAndFindModelNorm(a, b, mcfgp, MCV_NORM_AUTO, rcfgp, M, pairs, mask, maxPairs, matchCount);
 }

@@ -95,6 +95,16 @@ def match_l2(q, t, idx, dist, idx2=None, dist2=None, stream=None) -> None:
     N.check(r == q.shape[0], "mcvMatchL2Device")
 
 
+def match_l2_u8(q, t, idx, dist, idx2=None, dist2=None, stream=None) -> None:
+    """uint8 descriptors under L2 (byte SIFT), exact on the int8 matrix cores: q, t uint8 [n][dim], dim <= 512;
+    idx / idx2 int32, dist / dist2 float32. The outputs of match_l2 on the same bytes as float32."""
+    r = N.lib().mcvMatchL2U8Device(q.data_ptr(), q.shape[0], t.data_ptr(), t.shape[0], q.shape[1],
+                                   idx.data_ptr(), dist.data_ptr(),
+                                   idx2.data_ptr() if idx2 is not None else None,
+                                   dist2.data_ptr() if dist2 is not None else None, _stream_handle(stream))
+    N.check(r == q.shape[0], "mcvMatchL2U8Device")
+
+
 def pack_essential_tensor(a: np.ndarray, b: np.ndarray, focal: float, pp, device, stream=None):
     """(N,2)+(N,2) fp64 pixels -> device float64 [N,4] normalised (x - pp) / focal, computed on the GPU
     (mcvPackEssential; synchronises the stream)."""

@@ -82,6 +82,9 @@ MODEL_FUNDAMENTAL = 1
 MODEL_ESSENTIAL = 2
 MODEL_PNP = 3
 E_SLOTS = 10
+NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
+NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
+NORM_HAMMING = 6
 
 _P = C.c_void_p
 _I = C.c_int
@@ -113,10 +116,14 @@ SIGNATURES = {
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "cvMatchFeaturesNorm": (_I, [_P, _P, _P, _I, _P, _P, _I]),
+    "cvMatchAndFindModelNorm": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
     "cvMatchHamming": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cvMatchL2": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cvMatchHammingMulti": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cvMatchL2Multi": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "cvMatchL2U8": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "cvMatchL2U8Multi": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cvFindScaledPose": (_I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvFindScaledPoseCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "mcvGetLastError": (C.c_char_p, []),
@@ -141,6 +148,7 @@ SIGNATURES = {
     "mcvMatchHammingDevice": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mcvMatchHammingDeviceForm": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
     "mcvMatchL2Device": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mcvMatchL2U8Device": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mcvFindScaledPoseDevice": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcvProfileEnable": (None, [_I]),
     "mcvProfileReset": (None, []),

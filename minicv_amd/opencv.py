@@ -120,6 +120,27 @@ def matchL2(q, t, deviceCount: int = 1):
     return idx[:nq], d[:nq], idx2[:nq], d2[:nq]
 
 
+def matchL2U8(q, t, deviceCount: int = 1):
+    """BFMatcher(NORM_L2).knnMatch(k=2) on uint8 descriptors (byte SIFT). q, t: uint8 [n][dim], dim <= 512.
+    -> (idx, dist, idx2, dist2), exact: the outputs of matchL2 on the same bytes as float32.
+    deviceCount > 1: cvMatchL2U8Multi (query blocks over the visible GPUs, same answer)."""
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    t = np.ascontiguousarray(t, dtype=np.uint8)
+    if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
+        raise ValueError("descriptor arrays must be [n][dim] with equal widths")
+    nq, nt, dim = q.shape[0], t.shape[0], q.shape[1]
+    idx, idx2 = np.empty(max(nq, 1), np.int32), np.empty(max(nq, 1), np.int32)
+    d, d2 = np.empty(max(nq, 1), np.float32), np.empty(max(nq, 1), np.float32)
+    if deviceCount == 1:
+        r = N.lib().cvMatchL2U8(q.ctypes.data, nq, t.ctypes.data, nt, dim, idx.ctypes.data, d.ctypes.data,
+                                idx2.ctypes.data, d2.ctypes.data)
+    else:
+        r = N.lib().cvMatchL2U8Multi(q.ctypes.data, nq, t.ctypes.data, nt, dim, int(deviceCount), idx.ctypes.data,
+                                     d.ctypes.data, idx2.ctypes.data, d2.ctypes.data)
+    N.check(r == nq, "cvMatchL2U8")
+    return idx[:nq], d[:nq], idx2[:nq], d2[:nq]
+
+
 def recoverPoseConfig(focal: float = 1.0, pp=(0.0, 0.0), probability: float = 0.999,
                       threshold: float = 0.005) -> N.RecoverPoseConfig:
     """RecoverPoseConfig (OpenCV.fs:16-36); defaults = RecoverPoseConfig.Default (:33-34)."""
@@ -306,14 +327,16 @@ def solveAp3p(img, world, K):
 # ---- device-resident match -> RANSAC hand-off ------------------------------
 class Features:
     """A DetectorResult (MiniCVNative.h:23-29) built from keypoint coordinates and descriptors, as
-    cvDetectFeatures returns it: KeyPoint2d[N] + row-major descriptors (uint8 -> Hamming,
-    float32 -> L2). Keeps the backing arrays alive while the struct is in use."""
+    cvDetectFeatures returns it: KeyPoint2d[N] + row-major descriptors, uint8 or float32. The matching
+    calls pick the norm from the element type (uint8 -> Hamming, float32 -> L2) unless told otherwise:
+    byte SIFT descriptors are uint8 and must be matched with norm=N.NORM_L2. Keeps the backing arrays
+    alive while the struct is in use."""
 
     def __init__(self, points, descriptors):
         pts = np.asarray(points, dtype=np.float64)
         d = np.ascontiguousarray(descriptors)
         if d.dtype not in (np.uint8, np.float32):
-            raise ValueError("descriptors must be uint8 (Hamming) or float32 (L2)")
+            raise ValueError("descriptors must be uint8 (Hamming, or L2 with norm=NORM_L2) or float32 (L2)")
         n = pts.shape[0]
         self._kp = (N.KeyPoint2d * max(n, 1))()
         for i in range(n):
@@ -328,21 +351,24 @@ def _mcfg(ratio, cross_check, max_distance, model):
 
 
 def matchFeatures(a: Features, b: Features, ratio: float = 0.8, cross_check: bool = False,
-                  max_distance: float = 0.0):
-    """cvMatchFeatures -> (pairs int32 [k][2] (index in a, index in b), dist float32 [k])."""
+                  max_distance: float = 0.0, norm: int = N.NORM_AUTO):
+    """cvMatchFeaturesNorm -> (pairs int32 [k][2] (index in a, index in b), dist float32 [k]).
+    norm: N.NORM_AUTO (uint8 -> Hamming, float32 -> L2), N.NORM_L2 (uint8 rows too: byte SIFT) or
+    N.NORM_HAMMING (uint8 only)."""
     n = a.struct.PointCount
     pairs = np.zeros((max(n, 1), 2), dtype=np.int32)
     dist = np.zeros(max(n, 1), dtype=np.float32)
     cfg = _mcfg(ratio, cross_check, max_distance, N.MODEL_HOMOGRAPHY)
-    k = N.lib().cvMatchFeatures(N.C.addressof(a.struct), N.C.addressof(b.struct), N.C.addressof(cfg),
-                                pairs.ctypes.data, dist.ctypes.data, max(n, 1))
+    k = N.lib().cvMatchFeaturesNorm(N.C.addressof(a.struct), N.C.addressof(b.struct), N.C.addressof(cfg), int(norm),
+                                    pairs.ctypes.data, dist.ctypes.data, max(n, 1))
     N.check(k >= 0, "cvMatchFeatures")
     return pairs[:k].copy(), dist[:k].copy()
 
 
 def matchAndFindModel(a: Features, b: Features, model: int = N.MODEL_HOMOGRAPHY, ratio: float = 0.8,
-                      cross_check: bool = False, max_distance: float = 0.0, params: RansacParams | None = None):
-    """cvMatchAndFindModel -> (inliers, M 3x3, pairs [k][2], mask bool[k])."""
+                      cross_check: bool = False, max_distance: float = 0.0, params: RansacParams | None = None,
+                      norm: int = N.NORM_AUTO):
+    """cvMatchAndFindModelNorm -> (inliers, M 3x3, pairs [k][2], mask bool[k]). norm: as matchFeatures."""
     n = a.struct.PointCount
     pairs = np.zeros((max(n, 1), 2), dtype=np.int32)
     mask = np.zeros(max(n, 1), dtype=np.uint8)
@@ -350,9 +376,9 @@ def matchAndFindModel(a: Features, b: Features, model: int = N.MODEL_HOMOGRAPHY,
     mc = N.C.c_int(0)
     cfg = _mcfg(ratio, cross_check, max_distance, model)
     rc = (params or (RansacParams() if model == N.MODEL_HOMOGRAPHY else RansacParams(confidence=0.99))).to_c()
-    cnt = N.lib().cvMatchAndFindModel(N.C.addressof(a.struct), N.C.addressof(b.struct), N.C.addressof(cfg),
-                                      N.C.addressof(rc), N.C.addressof(M), pairs.ctypes.data, mask.ctypes.data,
-                                      max(n, 1), N.C.addressof(mc))
+    cnt = N.lib().cvMatchAndFindModelNorm(N.C.addressof(a.struct), N.C.addressof(b.struct), N.C.addressof(cfg),
+                                          int(norm), N.C.addressof(rc), N.C.addressof(M), pairs.ctypes.data,
+                                          mask.ctypes.data, max(n, 1), N.C.addressof(mc))
     N.check(cnt > 0, "cvMatchAndFindModel")
     k = mc.value
     return cnt, np.array(M.M[:]).reshape(3, 3), pairs[:k].copy(), mask[:k] != 0

@@ -73,6 +73,31 @@ def l2_problem(nq: int, nt: int, dim: int = 128, seed: int = 5, noise: float = 2
     return q, t, planted
 
 
+def sift_u8_problem(nq: int, nt: int, dim: int = 128, seed: int = 12, noise: float = 2.0, random_frac: float = 0.1,
+                    dup_frac: float = 0.05):
+    """Byte SIFT descriptors (cv::SIFT with CV_8U): non-negative SIFT-like rows, L2-normalised, x512,
+    clipped to 255, rounded to uint8. Queries = planted train rows + N(0, noise), rounded and clipped;
+    a fraction pure random. A fraction of the train rows are exact copies of earlier rows and a
+    fraction of the queries exact copies of their planted row, so exact ties occur (planted then names
+    one of the tied rows). -> q (nq, dim) u8, t (nt, dim) u8, planted (nq,) int (-1 for random queries)"""
+    rng = np.random.default_rng(seed)
+    t = np.rint(sift_like(nt, dim, rng)).astype(np.uint8)
+    ndup = int(nt * dup_frac) if nt > 1 else 0
+    if ndup:
+        dst = rng.choice(np.arange(1, nt), size=ndup, replace=False)
+        t[dst] = t[rng.integers(0, dst)]        # a copy of an earlier row
+    planted = rng.integers(0, max(nt, 1), size=nq)
+    if nt == 0:
+        return np.rint(sift_like(nq, dim, rng)).astype(np.uint8), t, np.full(nq, -1)
+    q = np.clip(np.rint(t[planted].astype(np.float64) + rng.normal(0, noise, size=(nq, dim))), 0, 255).astype(np.uint8)
+    same = rng.random(nq) < dup_frac
+    q[same] = t[planted[same]]
+    rnd = rng.random(nq) < random_frac
+    q[rnd] = np.rint(sift_like(int(rnd.sum()), dim, rng)).astype(np.uint8)
+    planted[rnd] = -1
+    return q, t, planted
+
+
 def look_at(eye, target, up):
     """World->camera rotation/translation of a lookAt camera (camera looks down -z)."""
     eye, target, up = map(lambda v: np.asarray(v, dtype=np.float64), (eye, target, up))
@@ -172,11 +197,14 @@ H_PIX = np.array([[1.05, 0.02, 15.0], [-0.03, 0.98, -10.0], [1e-5, 2e-5, 1.0]])
 def feature_pair_problem(na: int, nb: int, seed: int = 9, kind: str = "hamming", match_frac: float = 0.6,
                          sigma: float = 0.5, H: np.ndarray = H_PIX, size=(640.0, 480.0)):
     """Two 'images' of keypoints + descriptors: a fraction of a's keypoints reappear in b at
-    H(a) + N(0, sigma) px with a perturbed copy of their descriptor (binary: bit flips; SIFT-like:
-    additive noise); the rest of b is random. -> (pts_a, desc_a, pts_b, desc_b, planted)"""
+    H(a) + N(0, sigma) px with a perturbed copy of their descriptor (kind "hamming": bit flips; "l2"
+    (fp32 SIFT-like) and "sift_u8" (byte SIFT): additive noise); the rest of b is random.
+    -> (pts_a, desc_a, pts_b, desc_b, planted)"""
     rng = np.random.default_rng(seed)
     if kind == "hamming":
         da, db, planted = hamming_problem(na, nb, seed=seed, random_frac=1.0 - match_frac)
+    elif kind == "sift_u8":
+        da, db, planted = sift_u8_problem(na, nb, seed=seed, random_frac=1.0 - match_frac)
     else:
         da, db, planted = l2_problem(na, nb, seed=seed, random_frac=1.0 - match_frac)
     pa = rng.uniform([0, 0], size, size=(na, 2))
