@@ -196,7 +196,7 @@ typedef struct {
                              MCV_METHOD_LMEDS, which derives its own */
     double confidence;    /* RANSAC / LMedS confidence in (0,1) */
     int    maxIters;      /* hypothesis budget */
-    int    method;        /* MCV_METHOD_* (LMEDS: homography and fundamental only) */
+    int    method;        /* MCV_METHOD_* (LMEDS: homography, fundamental, affine and similarity only) */
     uint64_t seed;        /* counter-based sampler key: hypothesis i depends only on (seed, i) */
     int    deviceCount;   /* 0/1: one GPU; >1 shard hypotheses over that many local GPUs (MCV_METHOD_LMEDS
                              always runs on the calling device: its budget is at most maxIters, and results
@@ -223,6 +223,19 @@ MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, const int N, 
 MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, const int N, const RansacConfig* cfg,
                                  mcvM33d* F, uint8_t* mask);
 
+/* estimateAffine2D (6-DoF, 3-point samples) and estimateAffinePartial2D (4-DoF similarity, 2-point
+ * samples): from/to N AoS fp64 points (converted to fp32). A6: out, the 2x3 matrix row-major (the
+ * similarity as [a -b tx; b a ty]). mask: caller-allocated uint8[N], may be NULL. cfg->method:
+ * MCV_METHOD_RANSAC or MCV_METHOD_LMEDS; the winner is refined on its inliers by 10 Levenberg-Marquardt
+ * iterations (no refit first) when it has more inliers than the sample size, unless MCV_FLAG_NO_REFINE.
+ * N equal to the sample size: one solve on all points, mask all 1. cfg NULL: RANSAC, threshold 3,
+ * maxIters 2000, confidence 0.99, OpenCV's sample stream. Error (fp32): a = F0 x + F1 y + F2 - X,
+ * b = F3 x + F4 y + F5 - Y, a a + b b <= (float)threshold^2. Returns the inlier count, 0 on failure. */
+MCV_API int cvEstimateAffine2D(const mcvV2d* from, const mcvV2d* to, const int N, const RansacConfig* cfg,
+                               double* A6, uint8_t* mask);
+MCV_API int cvEstimateAffinePartial2D(const mcvV2d* from, const mcvV2d* to, const int N, const RansacConfig* cfg,
+                                      double* A6, uint8_t* mask);
+
 /* findEssentialMat (OpenCV focal/pp overload): a/b pixel points, normalised (x - pp) / focal in
  * fp64; five-point minimal sets (<= 10 models per hypothesis), Sampson error, inlier iff
  * err <= (float)(threshold / focal)^2. cfg NULL: threshold 1, confidence 0.999, maxIters 1000,
@@ -245,7 +258,8 @@ typedef struct {
     float ratio;
     int   crossCheck;
     float maxDistance;
-    int   model;        /* MCV_MODEL_HOMOGRAPHY or MCV_MODEL_FUNDAMENTAL (cvMatchAndFindModel) */
+    int   model;        /* MCV_MODEL_HOMOGRAPHY, MCV_MODEL_FUNDAMENTAL, MCV_MODEL_AFFINE or
+                           MCV_MODEL_SIMILARITY (cvMatchAndFindModel) */
 } MatchConfig;          /* 16 bytes */
 
 /* Matches only: pairs[2k] = index in a, pairs[2k+1] = index in b (ascending in a), dist[k]
@@ -253,8 +267,9 @@ typedef struct {
  * (maxPairs >= a->PointCount is always enough). */
 MCV_API int cvMatchFeatures(const DetectorResult* a, const DetectorResult* b, const MatchConfig* cfg, int* pairs,
                             float* dist, int maxPairs);
-/* Matches + RANSAC on the matched keypoints (cvFindHomography / cvFindFundamentalMat semantics,
- * cfg->method RANSAC) without leaving the GPU. M: model; pairs as above; mask[k]: inlier flag of
+/* Matches + RANSAC on the matched keypoints (cvFindHomography / cvFindFundamentalMat /
+ * cvEstimateAffine2D / cvEstimateAffinePartial2D semantics, cfg->method RANSAC) without leaving the GPU.
+ * M: model (affine family: the 2x3 matrix, third row 0 0 1); pairs as above; mask[k]: inlier flag of
  * match k; *matchCount: number of matches written. Returns the inlier count, 0 on failure. */
 MCV_API int cvMatchAndFindModel(const DetectorResult* a, const DetectorResult* b, const MatchConfig* mcfg,
                                 const RansacConfig* rcfg, mcvM33d* M, int* pairs, uint8_t* mask, int maxPairs,
@@ -374,6 +389,9 @@ typedef struct mcvRansacPlan_ mcvRansacPlan;
                                       picks the minimal solver; finalize writes model9 = {rvec[3],
                                       tvec[3], 0, 0, 0}, the inlier solve of cfg->pnpKind unless
                                       MCV_FLAG_NO_REFINE */
+#define MCV_MODEL_AFFINE       4   /* estimateAffine2D: float4 points, 3-point samples; finalize writes
+                                      model9 = the 2x3 matrix followed by 0 0 1 */
+#define MCV_MODEL_SIMILARITY   5   /* estimateAffinePartial2D: 2-point samples, model9 as for AFFINE */
 
 /* Workspace for problems up to maxN correspondences and maxHyps hypotheses per evaluate call. */
 MCV_API mcvRansacPlan* mcvRansacPlanCreate(int model, int maxN, int64_t maxHyps);
@@ -448,7 +466,7 @@ MCV_API int mcvFindScaledPoseDevice(const mcvCamera* srcCam, const mcvV3d* d_wor
                                     double* outScale, void* stream);
 
 /* Opt-in kernel timing: HIP events recorded around the inlier-sweep launches on their stream.
- * mcvProfileRead returns the number of launches of `kernel` ("h_verify", "f_verify") and their
+ * mcvProfileRead returns the number of launches of `kernel` ("h_verify", "f_verify", "a_verify") and their
  * summed duration in ms (synchronises the recorded events). */
 MCV_API void mcvProfileEnable(int on);
 MCV_API void mcvProfileReset(void);
@@ -460,8 +478,20 @@ MCV_API int  mcvProfileRead(const char* kernel, double* total_ms);
  * oracle bit for bit without a GPU. Never on a product path.
  * ---------------------------------------------------------------------------------------- */
 #define MCV_HOST_FAST_MINIMAL 0x100   /* or-ed into mcvHostHypothesis' model: the elimination solver */
+/* model MCV_MODEL_AFFINE / MCV_MODEL_SIMILARITY: model9 / modelf9 hold the 6 values of the 2x3 matrix
+ * (the rest untouched), sampleIdx 3 / 2 indices. */
 MCV_API int mcvHostHypothesis(int model, const float* pts4, int N, uint64_t seed, int64_t hyp,
                               double* model9, float* modelf9, int* sampleIdx);
+/* Device self-test: the packed affine inlier sweep (mcv_a_verify_pk) on caller-supplied fp32 models
+ * (6 floats each) over host float4 points; fused: 0 = op-by-op error, 1 = fused. counts[k] = inliers of
+ * model k. Timed under mcvProfileEnable as "a_verify". Returns 1, 0 on failure. */
+MCV_API int mcvTestAffineSweep(const float* pts4, int N, const float* models6, int nModels, float thr2, int fused,
+                               int* counts);
+/* Host twin of the affine-family refine: the LM solver of the product on the masked correspondences
+ * (mask NULL: all) with sequential sums (point order) instead of the device's block order. model =
+ * MCV_MODEL_AFFINE or MCV_MODEL_SIMILARITY; A6: in the start (2x3), out the refined matrix. Returns the
+ * number of correspondences used, -1 on failure. */
+MCV_API int mcvHostAffineRefine(int model, const float* pts4, int N, const uint8_t* mask, double* A6);
 /* Device self-test: number of 32-bit patterns w where a reciprocal differs from 1.f/w (mode 0 =
  * rcp_exact; 1 = rcp_newton everywhere; 2 = rcp_newton + v_div_fixup; 3 = rcp_newton on its domain
  * |w| in [2^-126, 2^126) only; 4 = raw v_rcp_f32; 5 = rcp_exact_bounded on |w| < 2^126 and NaN). */
@@ -479,7 +509,8 @@ MCV_API int mcvTestHomographySweep(const float* pts4, int N, const float* models
 /* Device self-test: the LMedS rank kernel (lmeds.hip) on caller-supplied models: values[k] = the error
  * of rank `rank` (0-based, ascending; NaN last) of model k over pts4 (N float4 correspondences), NaN
  * when that element is a NaN. model MCV_MODEL_HOMOGRAPHY: 8 floats per model, errKind 0 = op-by-op,
- * 1 = fused error; MCV_MODEL_FUNDAMENTAL: 9 doubles per model, errKind = errorKind * 2 + unfused (0..3).
+ * 1 = fused error; MCV_MODEL_FUNDAMENTAL: 9 doubles per model, errKind = errorKind * 2 + unfused (0..3);
+ * MCV_MODEL_AFFINE / MCV_MODEL_SIMILARITY: 6 floats per model, errKind 0 = op-by-op, 1 = fused.
  * Returns 1, 0 on failure. mcvHostErrorRank: the host twin (the same three radix passes, sequentially). */
 MCV_API int mcvTestErrorRank(int model, const float* pts4, int N, const void* models, int nModels, int errKind,
                              int rank, float* values);
@@ -550,8 +581,8 @@ MCV_API int mcvHostSqpnp(const double* img, const double* world, int N, const do
 MCV_API void mcvHostRodrigues(const double* r, double* R, double* dR27);
 MCV_API void mcvHostRodriguesInv(const double* R, double* r);
 /* OpenCV's sample stream (MCV_FLAG_CV_SAMPLER) on the host: rows [0, rows) of m indices each for the
- * model family (homography / fundamental: pts4 = the float4 points their checkSubset reads; essential /
- * PnP: no check, pts4 may be NULL). Rows from the first failed getSubset on are -1. Returns the number
+ * model family (homography / fundamental / affine: pts4 = the float4 points their checkSubset reads;
+ * essential / PnP / similarity: no check, pts4 may be NULL; m in 2, 3, 4, 5, 7, 8). Rows from the first failed getSubset on are -1. Returns the number
  * of accepted rows, -1 on bad arguments. */
 MCV_API int64_t mcvCvSubsets(int model, int m, const float* pts4, int N, int64_t rows, int* out);
 /* glibc_math.h's restatements over arrays: fn 0 cbrt(a), 1 hypot(a, b), 2 the real part of clog(a + i b),

@@ -7,17 +7,19 @@
 // getSubset(m1, m2, ms1, ms2, rng, 10000): up to 10000 attempts, each drawing modelPoints indices
 // with rng.uniform(0, count), an index equal to an earlier one of the same attempt drawn again, then
 // the callback's checkSubset on the gathered subset (homography: collinearity of either point set
-// + the orientation consistency of the 4 triangles; fundamental: collinearity; essential / PnP:
-// none). No draw depends on a model or an inlier count, so the whole stream is a function of the
-// point set alone: it is generated here, sequentially, before the GPU evaluates the hypotheses
-// (microseconds for the reference's maxIters <= a few thousand), and the generate kernels read
-// row h instead of the Philox stream (mcv_common.h SubsetSrc). The checks are the same host-compiled
-// functions the kernels run (hyp_homography.h, hyp_fundamental.h), on the same float4 points.
+// + the orientation consistency of the 4 triangles; fundamental and affine: collinearity; essential,
+// PnP and the 2-point similarity: none). No draw depends on a model or an inlier count, so the whole
+// stream is a function of the point set alone: it is generated here, sequentially, before the GPU
+// evaluates the hypotheses (microseconds for the reference's maxIters <= a few thousand), and the
+// generate kernels read row h instead of the Philox stream (mcv_common.h SubsetSrc). The checks are the
+// same host-compiled functions the kernels run (hyp_homography.h, hyp_fundamental.h, hyp_affine.h), on
+// the same float4 points.
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "hyp_fundamental.h"
+#include "hyp_affine.h"
 #include "plan.h"
 #include "kernels.h"
 
@@ -34,8 +36,10 @@ void check_flags(const RansacConfig& cfg, const char* who) {
              "now the default and the FMA-contracted one is MCV_FLAG_FUSED_ERROR = 64)", who);
 }
 
-// Subset check of the model family: 1 homography, 2 fundamental (7- or 8-point), 0 none.
+// Subset check of the model family: 1 homography, 2 fundamental (7- or 8-point), 3 affine (collinearity
+// of the 3 points in either set; the similarity's 2-point check is vacuous), 0 none.
 static int check_kind(int model) {
+    if (model == MCV_MODEL_AFFINE) return 3;
     return model == MCV_MODEL_HOMOGRAPHY ? 1 : (model == MCV_MODEL_FUNDAMENTAL ? 2 : 0);
 }
 
@@ -51,6 +55,7 @@ static bool subset_ok(int check, const float* pts4, const int* idx) {
         if constexpr (M == 4) return h_check_subset(x1, y1, x2, y2);
         return false;
     }
+    if (check == 3) return a_check_subset<M>(x1, y1, x2, y2);
     return !(have_collinear_last<M>(x1, y1) || have_collinear_last<M>(x2, y2));
 }
 
@@ -83,6 +88,8 @@ static int64_t cv_subsets(int check, const float* pts4, int N, int64_t rows, int
 
 static int64_t cv_subsets_m(int m, int check, const float* pts4, int N, int64_t rows, int* out) {
     switch (m) {
+        case 2: return cv_subsets<2>(check, pts4, N, rows, out);
+        case 3: return cv_subsets<3>(check, pts4, N, rows, out);
         case 4: return cv_subsets<4>(check, pts4, N, rows, out);
         case 5: return cv_subsets<5>(check, pts4, N, rows, out);
         case 7: return cv_subsets<7>(check, pts4, N, rows, out);
@@ -154,9 +161,10 @@ using namespace mcv;
 extern "C" MCV_API int64_t mcvCvSubsets(int model, int m, const float* pts4, int N, int64_t rows, int* out) {
     MCV_GUARD(-1, {
         if (!out || rows < 0 || N < m || m < 1) fail("mcvCvSubsets: bad argument");
-        const int check = model == MCV_MODEL_HOMOGRAPHY ? 1 : (model == MCV_MODEL_FUNDAMENTAL ? 2 : 0);
-        if (check && !pts4) fail("mcvCvSubsets: the homography / fundamental checks need pts4");
+        const int check = check_kind(model);
+        if (check && !pts4) fail("mcvCvSubsets: the homography / fundamental / affine checks need pts4");
         if (check == 1 && m != 4) fail("mcvCvSubsets: homography samples have 4 points");
+        if (check == 3 && m != 3) fail("mcvCvSubsets: affine samples have 3 points");
         return cv_subsets_m(m, check, pts4, N, rows, out);
     })
 }

@@ -77,6 +77,30 @@ void h_reduce_ltl(const float* d_pts4, int N, const uint8_t* d_mask, const doubl
 void h_reduce_lm(const float* d_pts4, int N, const uint8_t* d_mask, const double* h8, bool wantJ, double* d_part,
                  double* d_out, hipStream_t s);
 
+// ---- affine / similarity (ransac_a.hip); m = 3 (affine) or 2 (similarity) point samples, lx = 6 / 4
+// refine parameters; both store AModelF (6 floats) per hypothesis
+static const int kVerifyAHypPerWave = 8;     // hypotheses per wave of the packed sweep
+static const int kVerifyAPairsPerLane = 2;   // HPair loads per lane per trip
+struct AOneOut {
+    double A[6];
+    float af[6];
+    int status;
+    int idx[3];
+};
+void launch_a_generate(int m, const float* d_pts4, int N, Sampler smp, int64_t hypBegin, int hypCount, void* d_models,
+                       double* d_a64, int* d_counts, hipStream_t s);
+// direct: the first m correspondences as they are (the N == m call), no sampler, no subset check
+void launch_a_one(int m, const float* d_pts4, int N, Sampler smp, int64_t hyp, AOneOut* d_out, hipStream_t s,
+                  bool direct = false);
+// d_pairs = launch_h_pair of the float4 points. The counts are final (nothing divides: no recount).
+void launch_a_verify(const void* d_pairs, int N, const void* d_models, int* d_counts, int hypCount, float thr2,
+                     bool fused, hipStream_t s);
+void launch_a_mask_one(const float* d_pts4, int N, const AOneOut* d_one, float thr2, bool fused, uint8_t* d_mask,
+                       int* d_count, hipStream_t s);
+// d_out = {JtJ upper triangle, Jtr, |r|^2} of the refine callback at h[lx]: 28 (lx 6) or 15 (lx 4) sums
+void a_reduce_lm(int lx, const float* d_pts4, int N, const uint8_t* d_mask, const double* h, double* d_part,
+                 double* d_out, hipStream_t s);
+
 // ---- fundamental (ransac_f.hip)
 static const int kVerifyFHypPerWave = 4;
 static const int kVerifyFPtsPerLane = 2;
@@ -222,7 +246,8 @@ void pnp_reduce_vvs(const void* d_pts, int N, const uint8_t* d_mask, const doubl
 
 // ---- LMedS (lmeds.hip): d_keys[slot] = the order key (rank_select.h) of the rank-`rank` error (0-based,
 // ascending) of slot's model over the N correspondences; model = MCV_MODEL_HOMOGRAPHY (HModelF slots,
-// errKind = fused 0 / 1) or MCV_MODEL_FUNDAMENTAL (FModelD slots, errKind = f_error's kinds). d_status
+// errKind = fused 0 / 1), MCV_MODEL_FUNDAMENTAL (FModelD slots, errKind = f_error's kinds) or
+// MCV_MODEL_AFFINE / MCV_MODEL_SIMILARITY (AModelF slots, errKind = fused 0 / 1). d_status
 // (may be NULL: every slot has a model): slots with a negative status get the NaN class.
 void launch_error_rank(int model, const float* d_pts4, int N, const void* d_models, const int* d_status, int nSlots,
                        int errKind, int rank, uint32_t* d_keys, hipStream_t s);

@@ -16,6 +16,7 @@
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "hyp_fundamental.h"
+#include "hyp_affine.h"
 #include "rank_select.h"
 #include "kernels.h"
 #include "plan.h"
@@ -30,7 +31,8 @@ static const int kRankPeel = 4;
 static const int kRankThreads = 256;
 
 // Error of one correspondence under a slot's model. MODEL 0: homography (HModelF; KIND 0 op-by-op,
-// 1 fused); MODEL 1: fundamental (FModelD; KIND = f_error's kinds 0..3).
+// 1 fused); MODEL 1: fundamental (FModelD; KIND = f_error's kinds 0..3); MODEL 4: affine and
+// similarity alike (AModelF, the same 6-float model; KIND 0 op-by-op, 1 fused).
 template <int MODEL>
 struct RankModel;
 template <>
@@ -55,6 +57,19 @@ struct RankModel<MCV_MODEL_FUNDAMENTAL> {
     template <int KIND>
     MCV_HD float error(float x1, float y1, float x2, float y2) const {
         return f_error(KIND, f, x1, y1, x2, y2);
+    }
+};
+
+template <>
+struct RankModel<MCV_MODEL_AFFINE> {
+    typedef AModelF Stored;
+    float f[6];
+    MCV_HD void load(const Stored& m) {
+        for (int j = 0; j < 6; ++j) f[j] = m.a[j];
+    }
+    template <int KIND>
+    MCV_HD float error(float x, float y, float X, float Y) const {
+        return KIND ? a_error_fused(f, x, y, X, Y) : a_error(f, x, y, X, Y);
     }
 };
 
@@ -146,6 +161,11 @@ void launch_error_rank(int model, const float* d_pts4, int N, const void* d_mode
         else launch_error_rank_k<MCV_MODEL_HOMOGRAPHY, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
         return;
     }
+    if (affine_family(model)) {
+        if (errKind) launch_error_rank_k<MCV_MODEL_AFFINE, 1>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
+        else launch_error_rank_k<MCV_MODEL_AFFINE, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
+        return;
+    }
     if (model != MCV_MODEL_FUNDAMENTAL) fail("error rank: model %d has no rank kernel", model);
     switch (errKind) {
         case 0: launch_error_rank_k<MCV_MODEL_FUNDAMENTAL, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s); break;
@@ -159,9 +179,10 @@ void launch_error_rank(int model, const float* d_pts4, int N, const void* d_mode
 static void check_rank_args(const char* who, int model, const float* pts4, int N, const void* models, int nModels,
                             int errKind, int rank, const float* values) {
     if (!pts4 || !models || !values) fail("%s: null argument", who);
-    if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL) fail("%s: model %d has no rank kernel", who, model);
+    if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
+        fail("%s: model %d has no rank kernel", who, model);
     if (N <= 0 || nModels <= 0 || rank < 0 || rank >= N) fail("%s: bad sizes (N=%d, models=%d, rank=%d)", who, N, nModels, rank);
-    if (errKind < 0 || errKind > (model == MCV_MODEL_HOMOGRAPHY ? 1 : 3)) fail("%s: unknown error kind %d", who, errKind);
+    if (errKind < 0 || errKind > (model == MCV_MODEL_FUNDAMENTAL ? 3 : 1)) fail("%s: unknown error kind %d", who, errKind);
 }
 
 template <int MODEL, int KIND>
@@ -190,7 +211,8 @@ extern "C" MCV_API int mcvTestErrorRank(int model, const float* pts4, int N, con
     MCV_GUARD(0, {
         check_rank_args("mcvTestErrorRank", model, pts4, N, models, nModels, errKind, rank, values);
         require_device();
-        const size_t mb = model == MCV_MODEL_HOMOGRAPHY ? sizeof(HModelF) : sizeof(FModelD);
+        const size_t mb = model == MCV_MODEL_HOMOGRAPHY ? sizeof(HModelF)
+                                                        : (affine_family(model) ? sizeof(AModelF) : sizeof(FModelD));
         DevBuf<float> p;
         DevBuf<uint8_t> m;
         DevBuf<uint32_t> k;
@@ -219,6 +241,9 @@ extern "C" MCV_API int mcvHostErrorRank(int model, const float* pts4, int N, con
         if (model == MCV_MODEL_HOMOGRAPHY) {
             if (errKind) host_error_rank<MCV_MODEL_HOMOGRAPHY, 1>(pts4, N, models, nModels, rank, values);
             else host_error_rank<MCV_MODEL_HOMOGRAPHY, 0>(pts4, N, models, nModels, rank, values);
+        } else if (affine_family(model)) {
+            if (errKind) host_error_rank<MCV_MODEL_AFFINE, 1>(pts4, N, models, nModels, rank, values);
+            else host_error_rank<MCV_MODEL_AFFINE, 0>(pts4, N, models, nModels, rank, values);
         } else {
             switch (errKind) {
                 case 0: host_error_rank<MCV_MODEL_FUNDAMENTAL, 0>(pts4, N, models, nModels, rank, values); break;

@@ -168,10 +168,11 @@ extern "C" MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const De
         if (!M || !pairs || !mask) fail("cvMatchAndFindModel: null argument");
         precheck_norm(a, norm, "cvMatchAndFindModel");
         const MatchConfig mcfg = mcfgp ? *mcfgp : MatchConfig{0.8f, 0, 0.f, MCV_MODEL_HOMOGRAPHY};
-        if (mcfg.model != MCV_MODEL_HOMOGRAPHY && mcfg.model != MCV_MODEL_FUNDAMENTAL)
-            fail("cvMatchAndFindModel: model %d unsupported (homography or fundamental)", mcfg.model);
+        if (mcfg.model != MCV_MODEL_HOMOGRAPHY && mcfg.model != MCV_MODEL_FUNDAMENTAL && !affine_family(mcfg.model))
+            fail("cvMatchAndFindModel: model %d unsupported (homography, fundamental, affine or similarity)",
+                 mcfg.model);
         RansacConfig rcfg = config_or_default(rcfgp);
-        if (!rcfgp && mcfg.model == MCV_MODEL_FUNDAMENTAL) rcfg.confidence = 0.99;
+        if (!rcfgp && mcfg.model != MCV_MODEL_HOMOGRAPHY) rcfg.confidence = 0.99;
         if (rcfg.method != MCV_METHOD_RANSAC) fail("cvMatchAndFindModel: only RANSAC (method 8)");
         check_flags(rcfg, "cvMatchAndFindModel");
         if (!(rcfg.confidence > 0 && rcfg.confidence < 1)) fail("cvMatchAndFindModel: confidence must be in (0,1)");

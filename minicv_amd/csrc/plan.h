@@ -63,7 +63,8 @@ struct Plan {
     DevBuf<int> count;
     DevBuf<float> bbox;       // max |x|, max |y| of the source points (fused fast-path bound)
     DevBuf<double> bb4;       // F / E: max |x1|, |y1|, |x2|, |y2| (packed-fp32 Sampson prefilter bound)
-    DevBuf<double> h64;       // homography: each hypothesis' fp64 model (finalize takes the winner's)
+    DevBuf<double> h64;       // homography: each hypothesis' fp64 model (finalize takes the winner's);
+                              // affine / similarity: the generate's fp64 models (6 per hypothesis)
     DevBuf<uint8_t> hgen;     // homography: the split eigen generate's scratch (rotation log of one piece)
     DevBuf<float> pairs;      // paired point layout of the packed sweeps (homography 8, PnP 12 floats per 2)
     DevBuf<int> hstageList;   // homography staged sweep: the two survivor lists (2 x hypCount slots)
@@ -166,7 +167,7 @@ bool fused_error(const RansacConfig& cfg);
 RansacConfig config_or_default(const RansacConfig* cfg);
 int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, hipStream_t s,
                       const float* h_pts4 = nullptr);
-// LMedS (method 4) on device-resident H / F points: RANSACUpdateNumIters(confidence, 0.45, m, maxIters)
+// LMedS (method 4) on device-resident H / F / affine-family points: RANSACUpdateNumIters(confidence, 0.45, m, maxIters)
 // hypotheses in one chunk, each slot's median error (lmeds.hip), first minimum wins. Returns the winning
 // slot and its inlier threshold sigma (cfg.threshold is not read); fails when there is no model.
 int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, hipStream_t s, const float* h_pts4,
@@ -185,6 +186,13 @@ int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
 int f_fit_all(Plan& P, const float* d_pts, int N, hipStream_t s, double* F);
 int f_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* F9, float* Ff9, int* sampleIdx,
                       bool fast);
+
+// affine / similarity family (ransac_a.hip / ransac_a_host.cpp)
+inline bool affine_family(int model) { return model == MCV_MODEL_AFFINE || model == MCV_MODEL_SIMILARITY; }
+void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s);
+int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+               uint8_t* d_mask, hipStream_t s);
 
 // PnP family (ransac_pnp.hip / pnp_host.cpp)
 void p_evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,

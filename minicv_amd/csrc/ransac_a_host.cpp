@@ -1,0 +1,215 @@
+// ransac_a_host.cpp — host side of the 2-D affine family: cvEstimateAffine2D (MCV_MODEL_AFFINE, 3-point
+// samples, 6 refine parameters) and cvEstimateAffinePartial2D (MCV_MODEL_SIMILARITY, 2-point samples, 4
+// refine parameters). Mirrors cv::estimateAffine2D / cv::estimateAffinePartial2D of OpenCV 4.x
+// [ext: calib3d/src/ptsetreg.cpp, levmarq.cpp — absent here, DESIGN.md §3 / §7d]:
+//   pack V2d -> float4  ->  RANSAC (ransac_search) or LMedS (lmeds_search) over the shared framework  ->
+//   finalize: the winner's re-solve and mask, then LMSolver(refine callback, 10) on the inliers when
+//   there are more of them than the sample size (no runKernel refit first)  ->  the 2x3 matrix, mask.
+#include "minicv_native.h"
+#include "mcv_runtime.h"
+#include "kernels.h"
+#include "mcv_common.h"
+#include "hyp_affine.h"
+#include "lm_solver.h"
+#include "plan.h"
+
+#include <cstring>
+#include <vector>
+
+namespace mcv {
+
+void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s) {
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    P.pairs.ensure((size_t)(N + 1) / 2 * 8);
+    launch_h_pair(d_pts, N, P.pairs.p, s);
+    P.last.clear();   // the winner is re-solved from its sample (a closed form: nothing to cache)
+    {
+        ProfScope pg("a_generate", s);
+        launch_a_generate(model_points(P.model), d_pts, N, P.sampler(cfg), hypBegin, hypCount, P.models.p, P.h64.p,
+                          d_counts, s);
+    }
+    ProfScope ps("a_verify", s);
+    launch_a_verify(P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, fused_error(cfg), s);
+}
+
+// 2x3 matrix <-> refine parameters (similarity: a, b, tx, ty of [a -b tx; b a ty]).
+static void a_to_params(int lx, const double* A, double* h) {
+    if (lx == 6) for (int i = 0; i < 6; ++i) h[i] = A[i];
+    else { h[0] = A[0]; h[1] = A[3]; h[2] = A[2]; h[3] = A[5]; }
+}
+static void a_from_params(int lx, const double* h, double* A) {
+    if (lx == 6) for (int i = 0; i < 6; ++i) A[i] = h[i];
+    else { A[0] = h[0]; A[1] = -h[1]; A[2] = h[2]; A[3] = h[1]; A[4] = h[0]; A[5] = h[3]; }
+}
+
+// LMSolver::create(Affine2DRefineCallback / AffinePartial2DRefineCallback, 10)->run: the sums over the
+// inliers on the GPU (reduce.h's block order), the solver on the host (lm_solver.h).
+template <int LX>
+static void a_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* A) {
+    double h[LX];
+    a_to_params(LX, A, h);
+    auto compute = [&](const double* x, double* Aout, double* vout) -> double {
+        double buf[a_lm_values(LX)];
+        reduce_to_host(P, s, a_lm_values(LX), buf,
+                       [&](double* part, double* red) { a_reduce_lm(LX, d_pts, N, d_mask, x, part, red, s); });
+        return lm_unpack_sums<LX>(buf, Aout, vout);
+    };
+    lm_solver_run<LX>(compute, h, 10);
+    a_from_params(LX, h, A);
+}
+
+// The same refine with sequential sums on the host (mcvHostAffineRefine).
+template <int LX>
+static int a_lm_refine_host(const float* pts4, int N, const uint8_t* mask, double* A) {
+    double h[LX];
+    a_to_params(LX, A, h);
+    int used = 0;
+    for (int i = 0; i < N; ++i) used += (!mask || mask[i]) ? 1 : 0;
+    auto compute = [&](const double* x, double* Aout, double* vout) -> double {
+        double buf[a_lm_values(LX)];
+        for (int k = 0; k < a_lm_values(LX); ++k) buf[k] = 0;
+        for (int i = 0; i < N; ++i) {
+            if (mask && !mask[i]) continue;
+            const float* q = pts4 + 4 * (size_t)i;
+            a_lm_terms<LX>(x, (double)q[0], (double)q[1], (double)q[2], (double)q[3], buf);
+        }
+        return lm_unpack_sums<LX>(buf, Aout, vout);
+    };
+    lm_solver_run<LX>(compute, h, 10);
+    a_from_params(LX, h, A);
+    return used;
+}
+
+// Winner -> mask (+ LM). direct: the N == m solve on all points. Returns the inlier count. Synchronises s.
+static int a_finalize_impl(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+                           uint8_t* d_mask, hipStream_t s, bool direct) {
+    const int m = model_points(P.model);
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    AOneOut* d_one = (AOneOut*)P.one.p;
+    launch_a_one(m, d_pts, N, P.sampler(cfg), hyp, d_one, s, direct);
+    int count = N;
+    if (!direct) {
+        MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
+        launch_a_mask_one(d_pts, N, d_one, thr2, fused_error(cfg), d_mask, P.count.p, s);
+        MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    MCV_HIP(hipGetLastError());
+    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(AOneOut), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipStreamSynchronize(s));
+    AOneOut one;
+    std::memcpy(&one, P.h_one.p, sizeof(AOneOut));
+    if (one.status != 1) {
+        if (direct) fail("degenerate point set (no finite model from the %d correspondences)", m);
+        fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
+    }
+    if (!direct) count = P.h_i.p[0];
+    double A[6];
+    for (int k = 0; k < 6; ++k) A[k] = one.A[k];
+    if (!direct && !(cfg.flags & MCV_FLAG_NO_REFINE) && count > m) {
+        if (m == 3) a_lm_refine<6>(P, d_pts, N, d_mask, s, A);
+        else a_lm_refine<4>(P, d_pts, N, d_mask, s, A);
+    }
+    for (int k = 0; k < 6; ++k) model9[k] = A[k];
+    model9[6] = 0; model9[7] = 0; model9[8] = 1;
+    return count;
+}
+
+int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+               uint8_t* d_mask, hipStream_t s) {
+    return a_finalize_impl(P, d_pts, N, cfg, hyp, model9, d_mask, s, false);
+}
+
+static int estimate_affine(int model, const char* who, const mcvV2d* from, const mcvV2d* to, int N,
+                           const RansacConfig* cfgp, double* A6, uint8_t* mask) {
+    if (!from || !to || !A6 || N < 0) fail("%s: null argument or negative N", who);
+    if (mask) std::memset(mask, 0, (size_t)N);
+    const int m = model_points(model);
+    if (N < m) fail("%s: need at least %d correspondences (N=%d)", who, m, N);
+    RansacConfig cfg = config_or_default(cfgp);
+    if (!cfgp) cfg.confidence = 0.99;
+    check_flags(cfg, who);
+    if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LMEDS) fail("%s: unsupported method %d", who, cfg.method);
+    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);
+    require_device();
+    Plan& P = thread_plan(model);
+    hipStream_t s = P.own_stream();
+    P.reserve(N, 1);
+    pack_points(P, from, to, N, P.pts.p, s);
+    double model9[9];
+    int count = 0;
+    if (N == m) {
+        count = a_finalize_impl(P, P.pts.p, N, cfg, 0, model9, P.mask.p, s, true);
+        if (mask) std::memset(mask, 1, (size_t)N);
+    } else {
+        RansacConfig fin = cfg;
+        int64_t best;
+        if (cfg.method == MCV_METHOD_LMEDS) {
+            best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+        } else {
+            best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
+            if (best < 0) fail("%s: RANSAC found no model with >= %d inliers", who, m);
+        }
+        count = a_finalize(P, P.pts.p, N, fin, best, model9, P.mask.p, s);
+        if (cfg.method == MCV_METHOD_LMEDS && count < m) fail("%s: LMedS model has %d inliers (< %d)", who, count, m);
+        if (mask) {
+            MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
+            MCV_HIP(hipStreamSynchronize(s));
+        }
+    }
+    for (int k = 0; k < 6; ++k) A6[k] = model9[k];
+    return count;
+}
+
+}  // namespace mcv
+
+using namespace mcv;
+
+extern "C" MCV_API int cvEstimateAffine2D(const mcvV2d* from, const mcvV2d* to, const int N, const RansacConfig* cfg,
+                                          double* A6, uint8_t* mask) {
+    MCV_GUARD(0, { return estimate_affine(MCV_MODEL_AFFINE, "cvEstimateAffine2D", from, to, N, cfg, A6, mask); })
+}
+
+extern "C" MCV_API int cvEstimateAffinePartial2D(const mcvV2d* from, const mcvV2d* to, const int N,
+                                                 const RansacConfig* cfg, double* A6, uint8_t* mask) {
+    MCV_GUARD(0, {
+        return estimate_affine(MCV_MODEL_SIMILARITY, "cvEstimateAffinePartial2D", from, to, N, cfg, A6, mask);
+    })
+}
+
+extern "C" MCV_API int mcvTestAffineSweep(const float* pts4, int N, const float* models6, int nModels, float thr2,
+                                          int fused, int* counts) {
+    MCV_GUARD(0, {
+        if (!pts4 || !models6 || !counts) fail("mcvTestAffineSweep: null argument");
+        if (N <= 0 || nModels <= 0) fail("mcvTestAffineSweep: bad sizes (N=%d, models=%d)", N, nModels);
+        require_device();
+        DevBuf<float> p, m, pairs;
+        DevBuf<int> c;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 6);
+        pairs.ensure((size_t)(N + 1) / 2 * 8);
+        c.ensure((size_t)nModels);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models6, (size_t)nModels * 24, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(c.p, 0, (size_t)nModels * 4));
+        launch_h_pair(p.p, N, pairs.p, 0);
+        {
+            ProfScope ps("a_verify", 0);
+            launch_a_verify(pairs.p, N, m.p, c.p, nModels, thr2, fused != 0, 0);
+        }
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipMemcpy(counts, c.p, (size_t)nModels * 4, hipMemcpyDeviceToHost));
+        return 1;
+    })
+}
+
+extern "C" MCV_API int mcvHostAffineRefine(int model, const float* pts4, int N, const uint8_t* mask, double* A6) {
+    MCV_GUARD(-1, {
+        if (!pts4 || !A6 || N <= 0) fail("mcvHostAffineRefine: bad argument");
+        if (!affine_family(model)) fail("mcvHostAffineRefine: model %d is not affine / similarity", model);
+        return model == MCV_MODEL_AFFINE ? a_lm_refine_host<6>(pts4, N, mask, A6)
+                                         : a_lm_refine_host<4>(pts4, N, mask, A6);
+    })
+}

@@ -19,6 +19,7 @@
 #include <cmath>
 #include "mcv_common.h"
 #include "hyp_homography.h"
+#include "pk_pair.h"
 #include "reduce.h"
 #include "kernels.h"
 #include "minicv_native.h"
@@ -372,12 +373,8 @@ __global__ __launch_bounds__(256) void mcv_h_verify(const float4* __restrict__ p
 // with {0, 0, NaN, NaN}, whose error is NaN (never an inlier) and whose w is 1 (never "bad").
 // Model coefficients stay in SGPRs and are broadcast to both halves with op_sel / op_sel_hi.
 // Every operation rounds exactly like h_denominator_fused / rcp_newton / h_error_fused_ww.
+// (f2, HPair and the packed helpers pk_fma / lo / hi: pk_pair.h, shared with ransac_a.hip.)
 // ------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-struct HPair {
-    f2 x, y, mx, my;
-};
-
 __global__ __launch_bounds__(256) void mcv_h_pair(const float4* __restrict__ pts, int N, HPair* __restrict__ out) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= (N + 1) / 2) return;
@@ -391,14 +388,6 @@ __global__ __launch_bounds__(256) void mcv_h_pair(const float4* __restrict__ pts
     o.my = f2{a.w, b.w};
     out[p] = o;
 }
-
-// Packed FMA through the compiler (llvm.fma.v2f32 -> v_pk_fma_f32): it folds a splat of an SGPR
-// coefficient into op_sel / op_sel_hi and inserts the wait states between dependent packed ops
-// (hand-written asm would not get them: the hazard recognizer does not see into inline asm).
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-// Broadcast one half of a coefficient pair: a shuffle the backend folds into op_sel / op_sel_hi.
-__device__ __forceinline__ f2 lo(f2 v) { return __builtin_shufflevector(v, v, 0, 0); }
-__device__ __forceinline__ f2 hi(f2 v) { return __builtin_shufflevector(v, v, 1, 1); }
 
 // One trip: NP pairs per lane against the wave's K hypotheses.
 template <int K, int NP, bool PRED>

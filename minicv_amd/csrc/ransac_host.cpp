@@ -13,8 +13,10 @@
 #include "linalg.h"
 #include "mcv_common.h"
 #include "hyp_homography.h"
+#include "hyp_affine.h"
 #include "plan.h"
 #include "rank_select.h"
+#include "lm_solver.h"
 
 #include <cmath>
 #include <cfloat>
@@ -117,6 +119,7 @@ void Plan::reserve(int n, int64_t hyps) {
     }
     models.ensure((size_t)maxHyps * model_bytes(model));
     if (model == MCV_MODEL_HOMOGRAPHY) h64.ensure((size_t)maxHyps * 9);
+    if (affine_family(model)) h64.ensure((size_t)maxHyps * 6);
     counts.ensure((size_t)maxHyps * slots);
     pkey.ensure(512);
     pfail.ensure(512);
@@ -137,6 +140,7 @@ void Plan::reserve(int n, int64_t hyps) {
 
 size_t model_bytes(int model) {
     if (model == MCV_MODEL_PNP) return 96;
+    if (affine_family(model)) return 24;
     return model == MCV_MODEL_ESSENTIAL ? 72 * kEModelSlots : (model == MCV_MODEL_FUNDAMENTAL ? 80 : 32);
 }
 int model_slots(int model) { return model == MCV_MODEL_ESSENTIAL ? kEModelSlots : 1; }
@@ -256,76 +260,12 @@ bool h_refit(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStrea
 // (Marquardt-Nielsen lambda control, eigen-based solve). The O(N) JtJ / Jtr / |r|^2 sums run on
 // the GPU; the 8x8 algebra runs here.
 void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H, int maxIters) {
-    const int lx = 8;
-    const double epsx = FLT_EPSILON, epsf = FLT_EPSILON;
-    double x[8], xd[8], d[8], v[8], A[64], Ap[64], D[8], temp_d[8];
-    for (int i = 0; i < 8; ++i) x[i] = H[i];
-    auto compute = [&](const double* h, bool wantJ, double* Aout, double* vout) -> double {
+    auto compute = [&](const double* h, double* Aout, double* vout) -> double {
         double buf[45];
-        if (wantJ) {
-            reduce_to_host(P, s, 45, buf, [&](double* part, double* red) { h_reduce_lm(d_pts, N, d_mask, h, true, part, red, s); });
-            int o = 0;
-            for (int j = 0; j < 8; ++j)
-                for (int k = j; k < 8; ++k) { Aout[j * 8 + k] = buf[o]; Aout[k * 8 + j] = buf[o]; ++o; }
-            for (int j = 0; j < 8; ++j) vout[j] = buf[36 + j];
-            return buf[44];
-        }
-        reduce_to_host(P, s, 1, buf, [&](double* part, double* red) { h_reduce_lm(d_pts, N, d_mask, h, false, part, red, s); });
-        return buf[0];
+        reduce_to_host(P, s, 45, buf, [&](double* part, double* red) { h_reduce_lm(d_pts, N, d_mask, h, true, part, red, s); });
+        return lm_unpack_sums<8>(buf, Aout, vout);
     };
-    double S = compute(x, true, A, v);
-    for (int i = 0; i < lx; ++i) D[i] = A[i * lx + i];
-    const double Rlo = 0.25, Rhi = 0.75;
-    double lambda = 1, lc = 0.75;
-    int iter = 0;
-    for (;;) {
-        for (int i = 0; i < lx * lx; ++i) Ap[i] = A[i];
-        for (int i = 0; i < lx; ++i) Ap[i * lx + i] += lambda * D[i];
-        eig_solve(Ap, lx, v, d);
-        for (int i = 0; i < lx; ++i) xd[i] = x[i] - d[i];
-        // JtJ / Jtr at xd ride along with its cost (one synchronisation per step): on acceptance they
-        // are exactly what LMSolverImpl's re-evaluation at the new x returns (same sums, same order;
-        // the cost is summed identically by OpLM and OpLMErr)
-        double Ad[64], vd[8];
-        const double Sd = compute(xd, true, Ad, vd);
-        for (int i = 0; i < lx; ++i) {   // temp_d = -A d + 2 v
-            double acc = 0;
-            for (int k = 0; k < lx; ++k) acc += A[i * lx + k] * d[k];
-            temp_d[i] = -acc + 2 * v[i];
-        }
-        double dS = 0;
-        for (int i = 0; i < lx; ++i) dS += d[i] * temp_d[i];
-        const double R = (S - Sd) / (std::fabs(dS) > DBL_EPSILON ? dS : 1);
-        if (R > Rhi) {
-            lambda *= 0.5;
-            if (lambda < lc) lambda = 0;
-        } else if (R < Rlo) {
-            double t = 0;
-            for (int i = 0; i < lx; ++i) t += d[i] * v[i];
-            double nu = (Sd - S) / (std::fabs(t) > DBL_EPSILON ? t : 1) + 2;
-            nu = std::min(std::max(nu, 2.), 10.);
-            if (lambda == 0) {
-                eig_invert(A, lx, Ap);
-                double maxval = DBL_EPSILON;
-                for (int i = 0; i < lx; ++i) maxval = std::max(maxval, std::fabs(Ap[i * lx + i]));
-                lambda = lc = 1. / maxval;
-                nu *= 0.5;
-            }
-            lambda *= nu;
-        }
-        if (Sd < S) {
-            S = Sd;
-            for (int i = 0; i < lx; ++i) x[i] = xd[i];
-            std::memcpy(A, Ad, sizeof(Ad));
-            std::memcpy(v, vd, sizeof(vd));
-        }
-        ++iter;
-        double dn = 0;
-        for (int i = 0; i < lx; ++i) dn = std::max(dn, std::fabs(d[i]));
-        const bool proceed = iter < maxIters && dn >= epsx && S >= epsf * epsf;
-        if (!proceed) break;
-    }
-    for (int i = 0; i < 8; ++i) H[i] = x[i];
+    lm_solver_run<8>(compute, H, maxIters);   // H[0..7]; H[8] stays
 }
 
 // Evaluate one chunk of hypotheses on the device (generate + verify [+ best key]).
@@ -347,6 +287,12 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
         return;
     }
     const float* d_pts = (const float*)d_ptsv;
+    if (affine_family(P.model)) {
+        a_evaluate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+        if (d_key) launch_best(d_counts, hypCount, hypBegin, model_points(P.model), P.pkey.p, P.pfail.p, d_key, s);
+        MCV_HIP(hipGetLastError());
+        return;
+    }
     const double t = effective_threshold(cfg);
     const float thr2 = (float)(t * t);
     if (P.model == MCV_MODEL_HOMOGRAPHY) {
@@ -429,7 +375,11 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
     MCV_HIP(hipGetLastError());
 }
 
-int model_points(int model) { return model == MCV_MODEL_FUNDAMENTAL ? 8 : (model == MCV_MODEL_ESSENTIAL ? 5 : 4); }
+int model_points(int model) {
+    if (model == MCV_MODEL_AFFINE) return 3;
+    if (model == MCV_MODEL_SIMILARITY) return 2;
+    return model == MCV_MODEL_FUNDAMENTAL ? 8 : (model == MCV_MODEL_ESSENTIAL ? 5 : 4);
+}
 // (homography and PnP with the AP3P kernel: 4)
 int model_points_cfg(int model, const RansacConfig& cfg) {
     if (f_seven(model, cfg)) return 7;
@@ -489,6 +439,7 @@ int finalize(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_
     if (P.model == MCV_MODEL_PNP) return p_finalize(P, d_ptsv, N, cfg, hyp, model9, d_mask, s);
     const float* d_pts = (const float*)d_ptsv;
     if (P.model == MCV_MODEL_HOMOGRAPHY) return h_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
+    if (affine_family(P.model)) return a_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
     return f_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
 }
 
@@ -653,6 +604,10 @@ int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg
         launch_h_generate(d_pts, N, smp, 0, cnt, P.models.p, P.h64.p, P.counts.p, s, fast_minimal(cfg),
                           fast_minimal(cfg) ? nullptr : P.hgen.p);
         mark_chunk(P, 0, cnt, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
+    } else if (affine_family(P.model)) {
+        errKind = fused_error(cfg) ? 1 : 0;
+        P.last.clear();
+        launch_a_generate(m, d_pts, N, smp, 0, cnt, P.models.p, P.h64.p, P.counts.p, s);
     } else if (f_seven(P.model, cfg)) {
         errKind = f_error_kind(cfg);
         P.last.clear();
@@ -771,7 +726,7 @@ extern "C" MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, co
 
 extern "C" MCV_API mcvRansacPlan* mcvRansacPlanCreate(int model, int maxN, int64_t maxHyps) {
     MCV_GUARD(nullptr, {
-        if (model < MCV_MODEL_HOMOGRAPHY || model > MCV_MODEL_PNP)
+        if (model < MCV_MODEL_HOMOGRAPHY || model > MCV_MODEL_SIMILARITY)
             fail("unknown model %d", model);
         require_device();
         std::unique_ptr<Plan> p(new Plan());
@@ -827,7 +782,7 @@ extern "C" MCV_API int mcvRansacEvaluate(mcvRansacPlan* plan, const void* d_pts4
         check_flags(*cfg, "mcvRansacEvaluate");
         if (cfg->method == MCV_METHOD_LMEDS)
             fail("mcvRansacEvaluate: LMedS (method 4) has no device-level form; use cvFindHomography / "
-                 "cvFindFundamentalMat");
+                 "cvFindFundamentalMat / cvEstimateAffine2D / cvEstimateAffinePartial2D");
         if (cv_sampler(*cfg) && cv_table_stale(*P, d_pts4, N, *cfg, hypBegin, hypBegin + hypCount, (hipStream_t)stream))
             // a search starts at hypothesis 0, and a table drawn for other points is never reused: the
             // stream is rebuilt from the current points
@@ -898,6 +853,20 @@ extern "C" MCV_API int mcvHostHypothesis(int model, const float* pts4, int N, ui
                                         fast);
             for (int k = 0; k < 8; ++k) modelf9[k] = mf.h[k];
             modelf9[8] = 1.f;
+            return st;
+        }
+        if (affine_family(model)) {
+            const int m = model_points(model);
+            if (N < m) fail("N < %d", m);
+            AModelF mf;
+            double A[6];
+            for (int k = 0; k < 6; ++k) { A[k] = 0; mf.a[k] = 0; }
+            int idx[3] = {-1, -1, -1};
+            const Sampler smp{seed, nullptr};
+            const int st = m == 3 ? a_hypothesis<3>(pts4, N, smp, (uint64_t)hyp, A, &mf, idx)
+                                  : a_hypothesis<2>(pts4, N, smp, (uint64_t)hyp, A, &mf, idx);
+            for (int k = 0; k < 6; ++k) { model9[k] = A[k]; modelf9[k] = mf.a[k]; }
+            if (sampleIdx) for (int k = 0; k < m; ++k) sampleIdx[k] = idx[k];
             return st;
         }
         return f_host_hypothesis(pts4, N, seed, hyp, model9, modelf9, sampleIdx, fast);

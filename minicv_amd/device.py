@@ -20,7 +20,9 @@ def _stream_handle(stream=None) -> int:
 
 
 class RansacPlan:
-    """Workspace for one RANSAC problem family on the current device."""
+    """Workspace for one RANSAC problem family on the current device. model: N.MODEL_HOMOGRAPHY,
+    MODEL_FUNDAMENTAL, MODEL_ESSENTIAL, MODEL_PNP, MODEL_AFFINE or MODEL_SIMILARITY (the last two take the
+    float4 points of pack_points_tensor; finalize returns their 2x3 matrix with the third row 0 0 1)."""
 
     def __init__(self, model: int, max_n: int, max_hyps: int):
         self.model = model

@@ -81,6 +81,9 @@ MODEL_HOMOGRAPHY = 0
 MODEL_FUNDAMENTAL = 1
 MODEL_ESSENTIAL = 2
 MODEL_PNP = 3
+MODEL_AFFINE = 4        # estimateAffine2D: 3-point samples, 2x3 model
+MODEL_SIMILARITY = 5    # estimateAffinePartial2D: 2-point samples, [a -b tx; b a ty]
+A_SWEEP_K = 8           # hypotheses per wave of the packed affine sweep (kernels.h kVerifyAHypPerWave)
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
 NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
@@ -113,6 +116,8 @@ SIGNATURES = {
     "cvFindHomography": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvFindFundamentalMat": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvFindEssentialMat": (_I, [_P, _P, _I, _D, V2d, _P, _P, _P]),
+    "cvEstimateAffine2D": (_I, [_P, _P, _I, _P, _P, _P]),
+    "cvEstimateAffinePartial2D": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -185,6 +190,8 @@ SIGNATURES = {
     "mcvTestHomographySweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
+    "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
+    "mcvHostAffineRefine": (_I, [_I, _P, _I, _P, _P]),
     "mcvHostScaledCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
 }
 

@@ -82,6 +82,33 @@ def findFundamentalMat(a, b, params: RansacParams | None = None):
     return cnt, np.array(F.M[:], dtype=np.float64).reshape(3, 3), ms[:n] != 0
 
 
+def _estimate_affine(fn, name, from_, to, params):
+    params = params or RansacParams(threshold=3.0, confidence=0.99, cv_sampler=True)
+    a, b = _v2d(from_), _v2d(to)
+    n = a.shape[0]
+    if b.shape[0] != n:
+        raise ValueError("from/to length mismatch")
+    A = np.zeros(6, dtype=np.float64)
+    ms = np.zeros(max(n, 1), dtype=np.uint8)
+    cfg = params.to_c()
+    cnt = fn(a.ctypes.data, b.ctypes.data, n, N.C.addressof(cfg), A.ctypes.data, ms.ctypes.data)
+    N.check(cnt > 0, name)
+    return A.reshape(2, 3), ms[:n] != 0, cnt
+
+
+def estimateAffine2D(from_, to, params: RansacParams | None = None):
+    """cv::estimateAffine2D (6 DoF, 3-point samples) -> (A (2x3 float64), mask (bool[N]), inlierCount).
+    params.method: N.METHOD_RANSAC (default) or N.METHOD_LMEDS; params None: OpenCV's defaults (threshold 3,
+    maxIters 2000, confidence 0.99, its own sample stream, refine on). Raises NativeError on failure."""
+    return _estimate_affine(N.lib().cvEstimateAffine2D, "cvEstimateAffine2D", from_, to, params)
+
+
+def estimateAffinePartial2D(from_, to, params: RansacParams | None = None):
+    """cv::estimateAffinePartial2D (4-DoF similarity [a -b tx; b a ty], 2-point samples)
+    -> (A (2x3 float64), mask (bool[N]), inlierCount). Parameters as estimateAffine2D."""
+    return _estimate_affine(N.lib().cvEstimateAffinePartial2D, "cvEstimateAffinePartial2D", from_, to, params)
+
+
 def matchHamming(q, t, deviceCount: int = 1):
     """BFMatcher(NORM_HAMMING).knnMatch(k=2). q, t: uint8 [n][bytes]. -> (idx, dist, idx2, dist2).
     deviceCount > 1: cvMatchHammingMulti (query blocks over the visible GPUs, same answer)."""
@@ -368,7 +395,9 @@ def matchFeatures(a: Features, b: Features, ratio: float = 0.8, cross_check: boo
 def matchAndFindModel(a: Features, b: Features, model: int = N.MODEL_HOMOGRAPHY, ratio: float = 0.8,
                       cross_check: bool = False, max_distance: float = 0.0, params: RansacParams | None = None,
                       norm: int = N.NORM_AUTO):
-    """cvMatchAndFindModelNorm -> (inliers, M 3x3, pairs [k][2], mask bool[k]). norm: as matchFeatures."""
+    """cvMatchAndFindModelNorm -> (inliers, M 3x3, pairs [k][2], mask bool[k]). norm: as matchFeatures.
+    model: N.MODEL_HOMOGRAPHY, N.MODEL_FUNDAMENTAL, N.MODEL_AFFINE or N.MODEL_SIMILARITY (the last two
+    return the 2x3 matrix with the third row 0 0 1)."""
     n = a.struct.PointCount
     pairs = np.zeros((max(n, 1), 2), dtype=np.int32)
     mask = np.zeros(max(n, 1), dtype=np.uint8)

@@ -241,3 +241,23 @@ def scaled_problem(n: int, seed: int = 10, outlier_frac: float = 0.3, sigma: flo
     out = rng.random(n) < outlier_frac
     obs[out] = rng.uniform(-1, 1, size=(int(out.sum()), 2))
     return src, pose, world, obs, ~out
+
+
+# estimateAffine2D / estimateAffinePartial2D scenes (pixel-like coordinates, threshold in pixels).
+A_TRUE = np.array([[0.92, -0.31, 14.5], [0.27, 1.08, -22.25]])
+_S_ANG, _S_SCALE = 0.35, 1.3
+S_TRUE = np.array([[_S_SCALE * np.cos(_S_ANG), -_S_SCALE * np.sin(_S_ANG), 31.0],
+                   [_S_SCALE * np.sin(_S_ANG), _S_SCALE * np.cos(_S_ANG), -12.5]])
+
+
+def affine_problem(n: int, seed: int, outlier_frac: float = 0.5, sigma: float = 0.5, similarity: bool = False,
+                   extent: float = 640.0):
+    """-> src (n,2) f64, dst (n,2) f64, is_inlier (n,) bool, A_true (2x3). src ~ U[0, extent]^2,
+    dst = A_true [src; 1] + N(0, sigma) for the inliers, U[-extent, 2 extent]^2 for the outlier share."""
+    rng = np.random.default_rng(seed)
+    A = S_TRUE if similarity else A_TRUE
+    src = rng.uniform(0, extent, size=(n, 2))
+    dst = src @ A[:, :2].T + A[:, 2] + rng.normal(0, sigma, size=(n, 2))
+    out = rng.random(n) < outlier_frac
+    dst[out] = rng.uniform(-extent, 2 * extent, size=(int(out.sum()), 2))
+    return src, dst, ~out, A.copy()
