@@ -236,6 +236,26 @@ MCV_API int cvEstimateAffine2D(const mcvV2d* from, const mcvV2d* to, const int N
 MCV_API int cvEstimateAffinePartial2D(const mcvV2d* from, const mcvV2d* to, const int N, const RansacConfig* cfg,
                                       double* A6, uint8_t* mask);
 
+/* B independent RANSAC problems of one model family in one call. Problem p owns correspondences
+ * [offsets[p], offsets[p+1]) of a / b (offsets: B + 1 ints, offsets[0] == 0, non-decreasing).
+ * model: 0 homography, 1 fundamental (8-point), 4 affine, 5 similarity (the MCV_MODEL_* values of section 4).
+ * models[p]: the 3x3 model (affine family: the 2x3 matrix, then 0 0 1, as cvMatchAndFindModel writes it).
+ * mask: uint8[offsets[B]], may be NULL. counts[p]: inlier count of problem p, 0 when it has no model.
+ * Every problem returns exactly what the model's single export (cvFindHomography, cvFindFundamentalMat,
+ * cvEstimateAffine2D, cvEstimateAffinePartial2D) returns for the same slice and cfg: the same count, mask
+ * bytes and nine doubles, refined models included; a NULL cfg means that export's own defaults. A problem
+ * on which the single call would return 0 gets count 0, a zero model and a zero mask slice, the others
+ * are untouched, and mcvGetLastError() names the first failed problem's index and its message.
+ * The kernel launches and stream synchronisations of a call do not grow with B (problems with exactly
+ * the sample size take the single export's direct solve, one by one).
+ * cfg: method MCV_METHOD_RANSAC; flags any of MCV_FLAG_CV_SAMPLER (one stream per problem), MCV_FLAG_FIXED_ITERS,
+ * MCV_FLAG_NO_REFINE; both errorKinds for F; every problem uses cfg->seed. LSQ, LMedS, MCV_FLAG_FUSED_ERROR,
+ * MCV_FLAG_FAST_MINIMAL, MCV_FLAG_SEVEN_POINT, deviceCount > 1, the retired bit 4 and other models fail the
+ * whole call; every argument check runs before the device is touched.
+ * Returns the number of problems with a model (0 for B == 0), -1 on a bad argument or a device failure. */
+MCV_API int cvFindModelBatch(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
+                             const RansacConfig* cfg, mcvM33d* models, uint8_t* mask, int* counts);
+
 /* findEssentialMat (OpenCV focal/pp overload): a/b pixel points, normalised (x - pp) / focal in
  * fp64; five-point minimal sets (<= 10 models per hypothesis), Sampson error, inlier iff
  * err <= (float)(threshold / focal)^2. cfg NULL: threshold 1, confidence 0.999, maxIters 1000,
@@ -610,6 +630,31 @@ MCV_API int mcvTestEigLogCap(int cap);
  * number of stages; [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
  * [10..15] the slots alive entering each stage. Not thread-safe: tests only. */
 MCV_API int mcvTestHStaging(int mode, long long* stats);
+/* cvFindModelBatch's index arithmetic, as the export itself computes it (no device). Problems with more
+ * than m (the sample size) correspondences run on the device and are numbered in order (d = 0, 1, ...).
+ * desc4[4 p ..]: point offset (= offsets[p]: float4 points, no padding), N, slot offset (d * per, 64-bit;
+ * -1 for a problem not on the device), sampler row offset (d * max(maxIters, 1); -1 likewise).
+ * info4: device problems D, per = hypotheses per problem per round = clamp(cap / D, 1, max(maxIters, 1)),
+ * rounds = ceil(max(maxIters, 1) / per), slots of a full round D * per. cap <= 0: the export's own cap
+ * (2^21 slots). Returns D, -1 on a bad argument. */
+MCV_API int mcvHostBatchLayout(const int* offsets, int B, int m, int maxIters, long long cap, long long* desc4,
+                               long long* info4);
+/* The slot cap of cvFindModelBatch's rounds (cap <= 0: back to the default). Returns the previous cap.
+ * Not thread-safe: tests only. */
+MCV_API long long mcvTestBatchCap(long long cap);
+/* The calling thread's last cvFindModelBatch: stats16[0] kernel launches, [1] stream synchronisations,
+ * [2] hypothesis rounds, [3] Levenberg-Marquardt rounds, [4] problems routed through the single export,
+ * [5] B (the launches and synchronisations of routed problems are the single export's and not counted),
+ * [6] host microseconds spent converting the points to float4, [7] host microseconds spent drawing
+ * OpenCV's sample tables (MCV_FLAG_CV_SAMPLER; 0 with the Philox sampler). Returns 1. */
+MCV_API int mcvTestBatchStats(long long* stats16);
+/* Device self-test: the batched inlier sweep (mcv_batch_sweep) on caller-supplied models. pts4: the
+ * segmented float4 points, problem p owning [offsets[p], offsets[p+1]); its models are
+ * [modelOffsets[p], modelOffsets[p+1]) of `models` (homography: 8 floats each, affine / similarity: 6
+ * floats, fundamental: 9 doubles). errKind: fundamental 0..3 (errorKind * 2 + unfused), else 0 (op-by-op).
+ * counts[k] = inliers of model k over its problem's points. Returns 1, 0 on failure. */
+MCV_API int mcvTestBatchSweep(int model, const float* pts4, const int* offsets, int B, const void* models,
+                              const int* modelOffsets, float thr2, int errKind, int* counts);
 MCV_API void mcvHostPhilox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                            uint32_t* out4);
 /* Host twin of CameraPose.findScaled: the same candidates and costs as cvFindScaledPoseCosts,

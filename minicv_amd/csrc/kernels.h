@@ -252,6 +252,48 @@ void pnp_reduce_vvs(const void* d_pts, int N, const uint8_t* d_mask, const doubl
 void launch_error_rank(int model, const float* d_pts4, int N, const void* d_models, const int* d_status, int nSlots,
                        int errKind, int rank, uint32_t* d_keys, hipStream_t s);
 
+// ---- batched 2-D model RANSAC (ransac_batch.hip): B problems of one family per launch. All problems'
+// float4 points sit in one segmented buffer; the tables below name each problem's share of it.
+static const int kBatchTile = 1024;          // points staged in LDS per trip of the batched sweep (16 KiB)
+static const int kBatchRefitDoubles = 62;    // h_refit_chain's record per problem (sums .. LtL)
+struct BatchDesc {      // one problem of a hypothesis round
+    int ptOff, N;            // its points: [ptOff, ptOff + N) of the segmented buffer
+    int hypBegin, hypCount;  // its hypotheses of this round
+    int64_t slotOff;         // its first slot in the round's model / count buffers
+    int64_t rowOff;          // its first row of the sampler table (MCV_FLAG_CV_SAMPLER)
+};
+struct BatchFin {       // one problem with a winner
+    int ptOff, N;
+    int64_t rowOff;
+    int64_t hyp;             // the winning hypothesis
+};
+struct BatchOne {       // the winner in full
+    double M[9];             // fp64 model (affine family: 6 values)
+    float f[8];              // the sweep's fp32 model (H: 8, affine family: 6; F sweeps M)
+    int status, pad;
+};
+struct BatchRed { int ptOff, N; };   // one problem of a batched reduction
+size_t batch_model_bytes(int model);
+// maxHyp: the largest hypCount of the table (sizes the grid); d_table: the CV sample rows or nullptr
+void launch_batch_generate(int model, const float* d_pts4, const BatchDesc* d_desc, int nDesc, int maxHyp,
+                           uint64_t seed, const int* d_table, void* d_models, int* d_counts, hipStream_t s);
+// errKind: f_error's kinds (F); 0 for the other families (op-by-op error)
+void launch_batch_sweep(int model, int errKind, const float* d_pts4, const BatchDesc* d_desc, int nDesc, int maxHyp,
+                        const void* d_models, int* d_counts, float thr2, hipStream_t s);
+void launch_batch_one(int model, const float* d_pts4, const BatchFin* d_fin, int nFin, uint64_t seed,
+                      const int* d_table, BatchOne* d_one, hipStream_t s);
+// d_mask: the segmented mask (written only for winners with a model); d_count[f] += inliers (zeroed by the caller)
+void launch_batch_mask(int model, int errKind, const float* d_pts4, const BatchFin* d_fin, int nFin, int maxN,
+                       const BatchOne* d_one, float thr2, uint8_t* d_mask, int* d_count, hipStream_t s);
+int batch_reduce_blocks(int maxN);   // partial rows per problem (x 45 doubles) of the reductions below
+// LM sums of lx = 8 (H), 6 (affine), 4 (similarity) parameters: d_par 8 doubles per problem in,
+// d_out 45 doubles per problem out (the single call's order). Both return the kernels launched.
+int launch_batch_reduce_lm(int lx, const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed,
+                           int maxN, const double* d_par, double* d_part, double* d_out, hipStream_t s);
+// h_refit_chain for every problem: d_rec = kBatchRefitDoubles per problem, laid out as h_refit_chain's red
+int launch_batch_refit_chain(const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed, int maxN,
+                             double* d_part, double* d_rec, hipStream_t s);
+
 // ---- shared (ransac_h.hip)
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,
                  uint64_t* d_out, hipStream_t s);

@@ -1,0 +1,598 @@
+// ransac_batch_host.cpp — cvFindModelBatch: B independent RANSAC problems of one 2-D model family
+// (homography, 8-point fundamental, affine, similarity) in one call whose kernel launches and stream
+// synchronisations do not grow with B.
+//
+//   all points -> one segmented float4 buffer, one H2D copy (+ one for OpenCV's sample tables)
+//   rounds:   batched generate + batched sweep over every problem still searching, one copy of the
+//             counts back, the single call's sequential replay per problem on the host
+//   finalize: every winner re-solved, masked and counted in two launches, one copy back
+//   refine:   the B Levenberg-Marquardt solvers in lockstep (lm_solver_step.h): each step is one batched
+//             reduction over the problems still iterating and one read-back; H runs the batched refit
+//             chain first. The sums keep reduce.h's order per problem, the host algebra is the single
+//             call's, so every problem returns the single call's bits.
+// Problems with exactly the sample size take the single export's direct solve (routed through it).
+#include "minicv_native.h"
+#include "mcv_runtime.h"
+#include "kernels.h"
+#include "linalg.h"
+#include "mcv_common.h"
+#include "hyp_homography.h"
+#include "lm_solver_step.h"
+#include "plan.h"
+
+#include <cmath>
+#include <cfloat>
+#include <cstring>
+#include <string>
+#include <vector>
+#include <memory>
+#include <algorithm>
+#include <chrono>
+
+namespace mcv {
+
+// Slots (problem x hypothesis) one round may hold. 2^21 slots are 151 MB of fundamental models (72 B),
+// 64 MB of homography models, 8 MB of counts: B = 1024 problems of the default 2000 iterations fit one
+// round. Above it every round gives each problem cap / problems hypotheses (at least one).
+static const int64_t kBatchSlotCap = (int64_t)1 << 21;
+static int64_t g_batch_cap = kBatchSlotCap;   // mcvTestBatchCap
+
+struct BatchStats {
+    long long launches = 0, syncs = 0, rounds = 0, lmRounds = 0, single = 0, problems = 0;
+    long long packUs = 0, tableUs = 0;   // host time: point conversion, OpenCV sample tables
+};
+static long long us_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+static thread_local BatchStats t_stats;
+
+// The index arithmetic of a batch call (mcvHostBatchLayout exposes it). Problems with more points than
+// the sample size m go to the device; they are numbered in order (device index d).
+//   point offset  offsets[p] (float4 units; nothing is padded: the sweep reads float4 points, not pairs)
+//   slot offset   d * per, 64-bit: problem d's first slot of a round in which every device problem runs
+//   row offset    d * iters: its first row of the sampler table
+//   per           hypotheses per problem per round = clamp(cap / D, 1, iters); rounds = ceil(iters / per)
+struct BatchLayout {
+    std::vector<int> dev;             // device problems
+    std::vector<int64_t> slotOff, rowOff;   // per problem (-1: not on the device)
+    int64_t iters = 1, per = 1, rounds = 0;
+};
+
+static void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L) {
+    L.dev.clear();
+    L.slotOff.assign((size_t)B, -1);
+    L.rowOff.assign((size_t)B, -1);
+    L.iters = std::max(maxIters, 1);
+    for (int p = 0; p < B; ++p)
+        if (offsets[p + 1] - offsets[p] > m) L.dev.push_back(p);
+    const int64_t D = (int64_t)L.dev.size();
+    if (cap < 1) cap = kBatchSlotCap;
+    L.per = D ? std::min(std::max<int64_t>(cap / D, 1), L.iters) : L.iters;
+    L.rounds = D ? (L.iters + L.per - 1) / L.per : 0;
+    for (int64_t d = 0; d < D; ++d) {
+        L.slotOff[(size_t)L.dev[(size_t)d]] = d * L.per;
+        L.rowOff[(size_t)L.dev[(size_t)d]] = d * L.iters;
+    }
+}
+
+struct BatchWs {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf<float> pts;
+    DevBuf<int> table, counts, cnt;
+    DevBuf<uint8_t> models, mask;
+    DevBuf<BatchDesc> desc;
+    DevBuf<BatchFin> fin;
+    DevBuf<BatchRed> red;
+    DevBuf<BatchOne> one;
+    DevBuf<double> par, part, out, rec;
+    PinnedBuf<float> h_pts;
+    PinnedBuf<int> h_table, h_counts, h_cnt;
+    PinnedBuf<uint8_t> h_mask;
+    PinnedBuf<BatchDesc> h_desc;
+    PinnedBuf<BatchFin> h_fin;
+    PinnedBuf<BatchRed> h_red;
+    PinnedBuf<BatchOne> h_one;
+    PinnedBuf<double> h_par, h_out, h_rec;
+    ~BatchWs() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+static BatchWs& thread_batch_ws() {
+    int dev = 0;
+    MCV_HIP(hipGetDevice(&dev));
+    thread_local std::vector<std::unique_ptr<BatchWs>> all;
+    for (auto& w : all)
+        if (w->device == dev) return *w;
+    all.emplace_back(new BatchWs());
+    all.back()->device = dev;
+    MCV_HIP(hipStreamCreateWithFlags(&all.back()->stream, hipStreamNonBlocking));
+    return *all.back();
+}
+
+static void batch_sync(hipStream_t s) {
+    MCV_HIP(hipGetLastError());
+    MCV_HIP(hipStreamSynchronize(s));
+    ++t_stats.syncs;
+}
+
+static const char* batch_model_name(int model) {
+    return model == MCV_MODEL_HOMOGRAPHY ? "homography" : model == MCV_MODEL_FUNDAMENTAL ? "fundamental"
+           : model == MCV_MODEL_AFFINE   ? "affine" : "similarity";
+}
+
+// Everything a call can be refused for without touching the device.
+static RansacConfig batch_check(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
+                                const RansacConfig* cfgp, const mcvM33d* models, const int* counts) {
+    if (!a || !b || !offsets || !models || !counts)
+        fail("cvFindModelBatch: null argument (a, b, offsets, models and counts are required)");
+    if (B < 0) fail("cvFindModelBatch: negative B (%d)", B);
+    if (offsets[0] != 0) fail("cvFindModelBatch: offsets[0] must be 0 (is %d)", offsets[0]);
+    for (int p = 0; p < B; ++p)
+        if (offsets[p + 1] < offsets[p])
+            fail("cvFindModelBatch: offsets decrease at problem %d (%d -> %d)", p, offsets[p], offsets[p + 1]);
+    if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
+        fail("cvFindModelBatch: unsupported model %d (homography, fundamental, affine, similarity)", model);
+    RansacConfig cfg = config_or_default(cfgp);
+    if (!cfgp && model != MCV_MODEL_HOMOGRAPHY) cfg.confidence = 0.99;   // the single exports' NULL defaults
+    check_flags(cfg, "cvFindModelBatch");
+    if (cfg.method != MCV_METHOD_RANSAC)
+        fail("cvFindModelBatch: unsupported method %d (only MCV_METHOD_RANSAC; LSQ and LMedS have no batch form)",
+             cfg.method);
+    if (cfg.flags & MCV_FLAG_FUSED_ERROR) fail("cvFindModelBatch: unsupported flag MCV_FLAG_FUSED_ERROR");
+    if (cfg.flags & MCV_FLAG_FAST_MINIMAL) fail("cvFindModelBatch: unsupported flag MCV_FLAG_FAST_MINIMAL");
+    if (cfg.flags & MCV_FLAG_SEVEN_POINT) fail("cvFindModelBatch: unsupported flag MCV_FLAG_SEVEN_POINT");
+    if (cfg.deviceCount > 1) fail("cvFindModelBatch: unsupported deviceCount %d (one GPU per call)", cfg.deviceCount);
+    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("cvFindModelBatch: confidence must be in (0,1)");
+    return cfg;
+}
+
+// The single export on one slice (N == sample size: its direct solve). Returns its count.
+static int batch_single(int model, const mcvV2d* a, const mcvV2d* b, int N, const RansacConfig* cfgp, double* M9,
+                        uint8_t* mask) {
+    ++t_stats.single;
+    if (model == MCV_MODEL_HOMOGRAPHY) return cvFindHomography(a, b, N, cfgp, (mcvM33d*)M9, mask);
+    if (model == MCV_MODEL_FUNDAMENTAL) return cvFindFundamentalMat(a, b, N, cfgp, (mcvM33d*)M9, mask);
+    double A6[6] = {0, 0, 0, 0, 0, 0};
+    const int c = model == MCV_MODEL_AFFINE ? cvEstimateAffine2D(a, b, N, cfgp, A6, mask)
+                                            : cvEstimateAffinePartial2D(a, b, N, cfgp, A6, mask);
+    if (c > 0) {
+        for (int k = 0; k < 6; ++k) M9[k] = A6[k];
+        M9[6] = 0; M9[7] = 0; M9[8] = 1;
+    }
+    return c;
+}
+
+// h_refit's host half (ransac_host.cpp) on the chained passes' record r[62].
+static bool h_refit_from_record(const double* r, double* H) {
+    const double* sums = r;
+    const double count = sums[4];
+    if (count <= 0) return false;
+    double c4[4] = {sums[0] / count, sums[1] / count, sums[2] / count, sums[3] / count};
+    const double* dev = r + 9;
+    for (int k = 0; k < 4; ++k)
+        if (std::fabs(dev[k]) < DBL_EPSILON) return false;
+    double s4[4] = {count / dev[0], count / dev[1], count / dev[2], count / dev[3]};
+    const double* ltl = r + 17;
+    double A[81], w[9], V[81];
+    int o = 0;
+    for (int j = 0; j < 9; ++j)
+        for (int k = j; k < 9; ++k) { A[j * 9 + k] = ltl[o]; A[k * 9 + j] = ltl[o]; ++o; }
+    jacobi_eigen(A, 9, w, V);
+    const double* H0 = V + 8 * 9;
+    const double invHnorm[9] = {1. / s4[0], 0, c4[0], 0, 1. / s4[1], c4[1], 0, 0, 1};
+    const double Hnorm2[9] = {s4[2], 0, -c4[2] * s4[2], 0, s4[3], -c4[3] * s4[3], 0, 0, 1};
+    double T[9], R[9];
+    mat3_mul(invHnorm, H0, T);
+    mat3_mul(T, Hnorm2, R);
+    const double sc = 1. / R[8];
+    for (int k = 0; k < 9; ++k) {
+        H[k] = R[k] * sc;
+        if (!std::isfinite(H[k])) return false;
+    }
+    return true;
+}
+
+struct RefineJob { int ptOff, N; double* M9; };   // a winner to refine, its model in place
+
+static void upload_red(BatchWs& W, const std::vector<const RefineJob*>& act, hipStream_t s) {
+    const size_t n = act.size();
+    W.red.ensure(n);
+    W.h_red.ensure(n);
+    for (size_t k = 0; k < n; ++k) W.h_red.p[k] = BatchRed{act[k]->ptOff, act[k]->N};
+    MCV_HIP(hipMemcpyAsync(W.red.p, W.h_red.p, n * sizeof(BatchRed), hipMemcpyHostToDevice, s));
+}
+
+// LMSolver(refine callback, 10) of every job in lockstep: per step one batched reduction over the jobs
+// still iterating, one read-back, then each job's own host algebra.
+template <int LX>
+static void batch_lm(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hipStream_t s) {
+    if (jobs.empty()) return;
+    std::vector<LmStepper<LX>> st(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        double x0[LX];
+        const double* M = jobs[j].M9;
+        if (LX == 8) for (int i = 0; i < 8; ++i) x0[i] = M[i];
+        else if (LX == 6) for (int i = 0; i < 6; ++i) x0[i] = M[i];
+        else { x0[0] = M[0]; x0[1] = M[3]; x0[2] = M[2]; x0[3] = M[5]; }
+        st[j].begin(x0, 10);
+    }
+    const size_t per = (size_t)batch_reduce_blocks(maxN);
+    for (;;) {
+        std::vector<const RefineJob*> act;
+        std::vector<size_t> who;
+        for (size_t j = 0; j < jobs.size(); ++j)
+            if (!st[j].finished()) { act.push_back(&jobs[j]); who.push_back(j); }
+        if (act.empty()) break;
+        const size_t n = act.size();
+        upload_red(W, act, s);
+        W.par.ensure(n * 8);
+        W.h_par.ensure(n * 8);
+        W.out.ensure(n * 45);
+        W.h_out.ensure(n * 45);
+        W.part.ensure(n * per * 45);
+        for (size_t k = 0; k < n; ++k) {
+            const double* x = st[who[k]].request();
+            for (int i = 0; i < 8; ++i) W.h_par.p[8 * k + i] = i < LX ? x[i] : 0.0;
+        }
+        MCV_HIP(hipMemcpyAsync(W.par.p, W.h_par.p, n * 8 * sizeof(double), hipMemcpyHostToDevice, s));
+        t_stats.launches += launch_batch_reduce_lm(LX, W.pts.p, W.mask.p, W.red.p, (int)n, maxN, W.par.p, W.part.p,
+                                                   W.out.p, s);
+        MCV_HIP(hipMemcpyAsync(W.h_out.p, W.out.p, n * 45 * sizeof(double), hipMemcpyDeviceToHost, s));
+        batch_sync(s);
+        ++t_stats.lmRounds;
+        for (size_t k = 0; k < n; ++k) st[who[k]].feed(W.h_out.p + 45 * k);
+    }
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        double* M = jobs[j].M9;
+        const double* h = st[j].x;
+        if (LX == 8) for (int i = 0; i < 8; ++i) M[i] = h[i];
+        else if (LX == 6) for (int i = 0; i < 6; ++i) M[i] = h[i];
+        else { M[0] = h[0]; M[1] = -h[1]; M[2] = h[2]; M[3] = h[1]; M[4] = h[0]; M[5] = h[3]; }
+    }
+}
+
+// HomographyEstimatorCallback::runKernel on every job's inliers: the chained passes for all of them, one
+// read-back, h_refit's algebra per job (a job whose refit fails keeps its model, as in h_finalize).
+static void batch_h_refit(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hipStream_t s) {
+    if (jobs.empty()) return;
+    const size_t n = jobs.size();
+    std::vector<const RefineJob*> act;
+    for (auto& j : jobs) act.push_back(&j);
+    upload_red(W, act, s);
+    W.rec.ensure(n * kBatchRefitDoubles);
+    W.h_rec.ensure(n * kBatchRefitDoubles);
+    W.part.ensure(n * (size_t)batch_reduce_blocks(maxN) * 45);
+    t_stats.launches += launch_batch_refit_chain(W.pts.p, W.mask.p, W.red.p, (int)n, maxN, W.part.p, W.rec.p, s);
+    MCV_HIP(hipMemcpyAsync(W.h_rec.p, W.rec.p, n * kBatchRefitDoubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    batch_sync(s);
+    for (size_t k = 0; k < n; ++k) {
+        double Hr[9];
+        if (h_refit_from_record(W.h_rec.p + k * kBatchRefitDoubles, Hr))
+            for (int i = 0; i < 9; ++i) jobs[k].M9[i] = Hr[i];
+    }
+}
+
+static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
+                            const RansacConfig* cfgp, mcvM33d* models, uint8_t* mask, int* counts) {
+    const RansacConfig cfg = batch_check(model, a, b, offsets, B, cfgp, models, counts);
+    t_stats = BatchStats();
+    t_stats.problems = B;
+    if (B == 0) return 0;
+    const int total = offsets[B];
+    std::memset(models, 0, (size_t)B * sizeof(mcvM33d));
+    std::memset(counts, 0, (size_t)B * sizeof(int));
+    if (mask) std::memset(mask, 0, (size_t)total);
+    require_device();
+
+    const int m = model_points(model);
+    const bool fixed = (cfg.flags & MCV_FLAG_FIXED_ITERS) != 0;
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    const int errKind = model == MCV_MODEL_FUNDAMENTAL ? f_error_kind(cfg) : 0;
+    int firstFail = -1;
+    std::string firstMsg;
+    auto failed = [&](int p, const std::string& msg) {
+        if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
+    };
+    int ok = 0;
+
+    BatchLayout L;
+    batch_layout(offsets, B, m, cfg.maxIters, g_batch_cap, L);
+    // the problems that never reach the device: too few points, or exactly the sample size
+    for (int p = 0; p < B; ++p) {
+        const int N = offsets[p + 1] - offsets[p];
+        char buf[160];
+        if (N < m) {
+            snprintf(buf, sizeof(buf), "need at least %d correspondences (N=%d)", m, N);
+            failed(p, buf);
+        } else if (N == m) {
+            const int c = batch_single(model, a + offsets[p], b + offsets[p], N, cfgp, models[p].M,
+                                       mask ? mask + offsets[p] : nullptr);
+            if (c > 0) { counts[p] = c; ++ok; }
+            else {
+                failed(p, mcvGetLastError());
+                std::memset(models[p].M, 0, sizeof(mcvM33d));
+                if (mask) std::memset(mask + offsets[p], 0, (size_t)N);
+            }
+        }
+    }
+    const size_t D = L.dev.size();
+    if (D) {
+        BatchWs& W = thread_batch_ws();
+        hipStream_t s = W.stream;
+        // ---- points: one conversion pass (OpenCV's convertTo(CV_32F)), one copy
+        W.h_pts.ensure((size_t)total * 4);
+        W.pts.ensure((size_t)total * 4);
+        auto t0 = std::chrono::steady_clock::now();
+        for (int i = 0; i < total; ++i) {
+            W.h_pts.p[4 * (size_t)i + 0] = (float)a[i].X;
+            W.h_pts.p[4 * (size_t)i + 1] = (float)a[i].Y;
+            W.h_pts.p[4 * (size_t)i + 2] = (float)b[i].X;
+            W.h_pts.p[4 * (size_t)i + 3] = (float)b[i].Y;
+        }
+        t_stats.packUs = us_since(t0);
+        MCV_HIP(hipMemcpyAsync(W.pts.p, W.h_pts.p, (size_t)total * 16, hipMemcpyHostToDevice, s));
+        // ---- OpenCV's sample stream: one cv::RNG((uint64)-1) stream per problem, as each single call draws
+        const int* d_table = nullptr;
+        if (cv_sampler(cfg)) {
+            const size_t rowInts = (size_t)L.iters * m;
+            W.h_table.ensure(D * rowInts);
+            W.table.ensure(D * rowInts);
+            std::vector<int> rows;
+            t0 = std::chrono::steady_clock::now();
+            for (size_t d = 0; d < D; ++d) {
+                const int p = L.dev[d];
+                cv_table_build(model, cfg, W.h_pts.p + 4 * (size_t)offsets[p], offsets[p + 1] - offsets[p], L.iters,
+                               rows);
+                std::memcpy(W.h_table.p + d * rowInts, rows.data(), rowInts * sizeof(int));
+            }
+            t_stats.tableUs = us_since(t0);
+            MCV_HIP(hipMemcpyAsync(W.table.p, W.h_table.p, D * rowInts * sizeof(int), hipMemcpyHostToDevice, s));
+            d_table = W.table.p;
+        }
+        // ---- hypothesis rounds
+        std::vector<mcvReplayState> st(D);
+        for (auto& x : st) mcvReplayInit(&x, cfg.maxIters);
+        std::vector<size_t> active(D);
+        for (size_t d = 0; d < D; ++d) active[d] = d;
+        const size_t slotsMax = D * (size_t)L.per;
+        W.models.ensure(slotsMax * batch_model_bytes(model));
+        W.counts.ensure(slotsMax);
+        W.h_counts.ensure(slotsMax);
+        W.desc.ensure(D);
+        W.h_desc.ensure(D);
+        for (int64_t begin = 0; !active.empty(); begin += L.per) {
+            // a round holds the hypotheses [begin, begin + per) of every problem still searching; the
+            // problems are compacted, so problem j of the round owns slots [j per, j per + count)
+            std::vector<size_t> run;
+            int maxHyp = 0;
+            for (size_t d : active) {
+                const int64_t left = (int64_t)st[d].niters - begin;
+                if (st[d].stopped || left <= 0) continue;
+                const int p = L.dev[d];
+                BatchDesc& X = W.h_desc.p[run.size()];
+                X.ptOff = offsets[p];
+                X.N = offsets[p + 1] - offsets[p];
+                X.hypBegin = (int)begin;
+                X.hypCount = (int)std::min<int64_t>(left, L.per);
+                X.slotOff = (int64_t)run.size() * L.per;
+                X.rowOff = L.rowOff[(size_t)p];
+                maxHyp = std::max(maxHyp, X.hypCount);
+                run.push_back(d);
+            }
+            active.swap(run);
+            if (active.empty()) break;
+            const size_t n = active.size();
+            MCV_HIP(hipMemcpyAsync(W.desc.p, W.h_desc.p, n * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+            launch_batch_generate(model, W.pts.p, W.desc.p, (int)n, maxHyp, cfg.seed, d_table, W.models.p, W.counts.p,
+                                  s);
+            launch_batch_sweep(model, errKind, W.pts.p, W.desc.p, (int)n, maxHyp, W.models.p, W.counts.p, thr2, s);
+            t_stats.launches += 2;
+            MCV_HIP(hipMemcpyAsync(W.h_counts.p, W.counts.p, n * (size_t)L.per * sizeof(int), hipMemcpyDeviceToHost,
+                                   s));
+            batch_sync(s);
+            ++t_stats.rounds;
+            for (size_t j = 0; j < n; ++j) {
+                const size_t d = active[j];
+                const BatchDesc& X = W.h_desc.p[j];
+                mcvReplayChunk(&st[d], W.h_counts.p + j * (size_t)L.per, begin, X.hypCount, X.N, m, cfg.confidence,
+                               fixed ? 1 : 0);
+                if (begin + X.hypCount >= st[d].niters) st[d].stopped = 1;
+            }
+        }
+        // ---- winners: re-solve, mask and count, all in two launches
+        std::vector<size_t> win;
+        int maxN = 0;
+        W.fin.ensure(D);
+        W.h_fin.ensure(D);
+        for (size_t d = 0; d < D; ++d) {
+            const int p = L.dev[d];
+            if (st[d].bestIndex < 0) {
+                char buf[160];
+                snprintf(buf, sizeof(buf), "RANSAC found no model with >= %d inliers", m);
+                failed(p, buf);
+                continue;
+            }
+            BatchFin& F = W.h_fin.p[win.size()];
+            F.ptOff = offsets[p];
+            F.N = offsets[p + 1] - offsets[p];
+            F.rowOff = L.rowOff[(size_t)p];
+            F.hyp = st[d].bestIndex;
+            maxN = std::max(maxN, F.N);
+            win.push_back(d);
+        }
+        if (!win.empty()) {
+            const size_t n = win.size();
+            W.one.ensure(n);
+            W.h_one.ensure(n);
+            W.cnt.ensure(n);
+            W.h_cnt.ensure(n);
+            W.mask.ensure((size_t)total);
+            W.h_mask.ensure((size_t)total);
+            MCV_HIP(hipMemcpyAsync(W.fin.p, W.h_fin.p, n * sizeof(BatchFin), hipMemcpyHostToDevice, s));
+            MCV_HIP(hipMemsetAsync(W.cnt.p, 0, n * sizeof(int), s));
+            MCV_HIP(hipMemsetAsync(W.mask.p, 0, (size_t)total, s));
+            launch_batch_one(model, W.pts.p, W.fin.p, (int)n, cfg.seed, d_table, W.one.p, s);
+            launch_batch_mask(model, errKind, W.pts.p, W.fin.p, (int)n, maxN, W.one.p, thr2, W.mask.p, W.cnt.p, s);
+            t_stats.launches += 2;
+            MCV_HIP(hipMemcpyAsync(W.h_one.p, W.one.p, n * sizeof(BatchOne), hipMemcpyDeviceToHost, s));
+            MCV_HIP(hipMemcpyAsync(W.h_cnt.p, W.cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+            MCV_HIP(hipMemcpyAsync(W.h_mask.p, W.mask.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            batch_sync(s);
+            std::vector<RefineJob> jobs;
+            int jobMaxN = 0;
+            for (size_t k = 0; k < n; ++k) {
+                const int p = L.dev[win[k]];
+                const BatchOne& o = W.h_one.p[k];
+                const BatchFin& F = W.h_fin.p[k];
+                if (o.status != 1) {
+                    char buf[160];
+                    snprintf(buf, sizeof(buf), "winning hypothesis %lld has no model (status %d)", (long long)F.hyp,
+                             o.status);
+                    failed(p, buf);
+                    continue;
+                }
+                const int c = W.h_cnt.p[k];
+                if (c <= 0) {   // cannot happen for a replay winner (its sweep count was >= m): fail closed
+                    failed(p, "the winning model has no inliers");
+                    continue;
+                }
+                counts[p] = c;
+                double* M = models[p].M;
+                if (affine_family(model)) {
+                    for (int i = 0; i < 6; ++i) M[i] = o.M[i];
+                    M[6] = 0; M[7] = 0; M[8] = 1;
+                } else {
+                    for (int i = 0; i < 9; ++i) M[i] = o.M[i];
+                }
+                if (mask) std::memcpy(mask + F.ptOff, W.h_mask.p + F.ptOff, (size_t)F.N);
+                ++ok;
+                // the single calls' refine conditions (h_finalize, a_finalize_impl); F is not refined
+                const bool refine = !(cfg.flags & MCV_FLAG_NO_REFINE) &&
+                                    (model == MCV_MODEL_HOMOGRAPHY ? (F.N > 4 && c > 0)
+                                                                   : (affine_family(model) && c > m));
+                if (refine) {
+                    jobs.push_back(RefineJob{F.ptOff, F.N, M});
+                    jobMaxN = std::max(jobMaxN, F.N);
+                }
+            }
+            if (model == MCV_MODEL_HOMOGRAPHY) {
+                batch_h_refit(W, jobs, jobMaxN, s);
+                batch_lm<8>(W, jobs, jobMaxN, s);
+            } else if (model == MCV_MODEL_AFFINE) {
+                batch_lm<6>(W, jobs, jobMaxN, s);
+            } else if (model == MCV_MODEL_SIMILARITY) {
+                batch_lm<4>(W, jobs, jobMaxN, s);
+            }
+        }
+    }
+    if (firstFail >= 0) {
+        // a problem that failed returns a zero model, count and mask slice; the first one is named
+        char buf[400];
+        snprintf(buf, sizeof(buf), "cvFindModelBatch (%s): problem %d: %s", batch_model_name(model), firstFail,
+                 firstMsg.c_str());
+        set_last_error(buf);
+    } else {
+        clear_last_error();
+    }
+    return ok;
+}
+
+}  // namespace mcv
+
+using namespace mcv;
+
+extern "C" MCV_API int cvFindModelBatch(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
+                                        const RansacConfig* cfg, mcvM33d* models, uint8_t* mask, int* counts) {
+    MCV_GUARD(-1, { return find_model_batch(model, a, b, offsets, B, cfg, models, mask, counts); })
+}
+
+extern "C" MCV_API int mcvHostBatchLayout(const int* offsets, int B, int m, int maxIters, long long cap,
+                                          long long* desc4, long long* info4) {
+    MCV_GUARD(-1, {
+        if (!offsets || B < 0 || m < 1 || (B > 0 && !desc4) || !info4) fail("mcvHostBatchLayout: bad argument");
+        BatchLayout L;
+        batch_layout(offsets, B, m, maxIters, cap, L);
+        for (int p = 0; p < B; ++p) {
+            desc4[4 * p + 0] = offsets[p];
+            desc4[4 * p + 1] = offsets[p + 1] - offsets[p];
+            desc4[4 * p + 2] = L.slotOff[(size_t)p];
+            desc4[4 * p + 3] = L.rowOff[(size_t)p];
+        }
+        info4[0] = (long long)L.dev.size();
+        info4[1] = L.per;
+        info4[2] = L.rounds;
+        info4[3] = (long long)L.dev.size() * L.per;
+        return (int)L.dev.size();
+    })
+}
+
+extern "C" MCV_API long long mcvTestBatchCap(long long cap) {
+    const long long prev = g_batch_cap;
+    g_batch_cap = cap > 0 ? cap : kBatchSlotCap;
+    return prev;
+}
+
+extern "C" MCV_API int mcvTestBatchStats(long long* stats16) {
+    if (!stats16) return 0;
+    for (int i = 0; i < 16; ++i) stats16[i] = 0;
+    stats16[0] = t_stats.launches;
+    stats16[1] = t_stats.syncs;
+    stats16[2] = t_stats.rounds;
+    stats16[3] = t_stats.lmRounds;
+    stats16[4] = t_stats.single;
+    stats16[5] = t_stats.problems;
+    stats16[6] = t_stats.packUs;
+    stats16[7] = t_stats.tableUs;
+    return 1;
+}
+
+extern "C" MCV_API int mcvTestBatchSweep(int model, const float* pts4, const int* offsets, int B, const void* models,
+                                         const int* modelOffsets, float thr2, int errKind, int* counts) {
+    MCV_GUARD(0, {
+        if (!pts4 || !offsets || !models || !modelOffsets || !counts || B <= 0)
+            fail("mcvTestBatchSweep: null argument or B <= 0");
+        if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
+            fail("mcvTestBatchSweep: unsupported model %d", model);
+        if (model == MCV_MODEL_FUNDAMENTAL ? (errKind < 0 || errKind > 3) : errKind != 0)
+            fail("mcvTestBatchSweep: unsupported errKind %d", errKind);
+        if (offsets[0] != 0 || modelOffsets[0] != 0) fail("mcvTestBatchSweep: offsets must start at 0");
+        int maxHyp = 0;
+        for (int p = 0; p < B; ++p) {
+            if (offsets[p + 1] < offsets[p] || modelOffsets[p + 1] < modelOffsets[p])
+                fail("mcvTestBatchSweep: decreasing offsets at problem %d", p);
+            maxHyp = std::max(maxHyp, modelOffsets[p + 1] - modelOffsets[p]);
+        }
+        const int total = offsets[B], nModels = modelOffsets[B];
+        if (nModels <= 0 || total <= 0) fail("mcvTestBatchSweep: nothing to sweep");
+        require_device();
+        const size_t mb = batch_model_bytes(model);
+        DevBuf<float> p;
+        DevBuf<uint8_t> mdl;
+        DevBuf<int> c;
+        DevBuf<BatchDesc> d;
+        std::vector<BatchDesc> h((size_t)B);
+        for (int k = 0; k < B; ++k) {
+            h[(size_t)k].ptOff = offsets[k];
+            h[(size_t)k].N = offsets[k + 1] - offsets[k];
+            h[(size_t)k].hypBegin = 0;
+            h[(size_t)k].hypCount = modelOffsets[k + 1] - modelOffsets[k];
+            h[(size_t)k].slotOff = modelOffsets[k];
+            h[(size_t)k].rowOff = 0;
+        }
+        p.ensure((size_t)total * 4);
+        mdl.ensure((size_t)nModels * mb);
+        c.ensure((size_t)nModels);
+        d.ensure((size_t)B);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)total * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(mdl.p, models, (size_t)nModels * mb, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(d.p, h.data(), (size_t)B * sizeof(BatchDesc), hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(c.p, 0, (size_t)nModels * 4));
+        launch_batch_sweep(model, errKind, p.p, d.p, B, maxHyp, mdl.p, c.p, thr2, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipMemcpy(counts, c.p, (size_t)nModels * 4, hipMemcpyDeviceToHost));
+        return 1;
+    })
+}

@@ -84,6 +84,8 @@ MODEL_PNP = 3
 MODEL_AFFINE = 4        # estimateAffine2D: 3-point samples, 2x3 model
 MODEL_SIMILARITY = 5    # estimateAffinePartial2D: 2-point samples, [a -b tx; b a ty]
 A_SWEEP_K = 8           # hypotheses per wave of the packed affine sweep (kernels.h kVerifyAHypPerWave)
+BATCH_TILE = 1024       # points per LDS tile of the batched sweep (kernels.h kBatchTile)
+BATCH_SLOT_CAP = 1 << 21   # slots per hypothesis round of cvFindModelBatch (ransac_batch_host.cpp)
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
 NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
@@ -118,6 +120,7 @@ SIGNATURES = {
     "cvFindEssentialMat": (_I, [_P, _P, _I, _D, V2d, _P, _P, _P]),
     "cvEstimateAffine2D": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvEstimateAffinePartial2D": (_I, [_P, _P, _I, _P, _P, _P]),
+    "cvFindModelBatch": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -193,6 +196,10 @@ SIGNATURES = {
     "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
     "mcvHostAffineRefine": (_I, [_I, _P, _I, _P, _P]),
     "mcvHostScaledCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
+    "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
+    "mcvTestBatchStats": (_I, [_P]),
+    "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),
 }
 
 _lib = None

@@ -109,6 +109,37 @@ def estimateAffinePartial2D(from_, to, params: RansacParams | None = None):
     return _estimate_affine(N.lib().cvEstimateAffinePartial2D, "cvEstimateAffinePartial2D", from_, to, params)
 
 
+def findModelBatch(model: int, srcs, dsts, params: RansacParams | None = None):
+    """cvFindModelBatch: B independent RANSAC problems of one family (N.MODEL_HOMOGRAPHY, N.MODEL_FUNDAMENTAL,
+    N.MODEL_AFFINE, N.MODEL_SIMILARITY) in one call. srcs / dsts: lists of (N_p, 2) arrays.
+    -> a list of (count, M (3x3 float64), mask (bool[N_p])) per problem, each equal to the single wrapper's
+    result on that pair; a problem without a model gives (0, zeros, all-False) and N.last_error() names the
+    first such problem. params None: the single export's own defaults. Raises NativeError when the whole
+    call is refused."""
+    if len(srcs) != len(dsts):
+        raise ValueError("srcs/dsts length mismatch")
+    B = len(srcs)
+    pa = [_v2d(x) for x in srcs]
+    pb = [_v2d(x) for x in dsts]
+    for x, y in zip(pa, pb):
+        if x.shape[0] != y.shape[0]:
+            raise ValueError("src/dst length mismatch")
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([x.shape[0] for x in pa])
+    total = int(offsets[B])
+    a = np.ascontiguousarray(np.concatenate(pa, axis=0)) if total else np.zeros((1, 2))
+    b = np.ascontiguousarray(np.concatenate(pb, axis=0)) if total else np.zeros((1, 2))
+    models = np.zeros((max(B, 1), 9), dtype=np.float64)
+    counts = np.zeros(max(B, 1), dtype=np.int32)
+    ms = np.zeros(max(total, 1), dtype=np.uint8)
+    cfg = params.to_c() if params is not None else None
+    ret = N.lib().cvFindModelBatch(int(model), a.ctypes.data, b.ctypes.data, offsets.ctypes.data, B,
+                                   N.C.addressof(cfg) if cfg is not None else None, models.ctypes.data,
+                                   ms.ctypes.data, counts.ctypes.data)
+    N.check(ret >= 0, "cvFindModelBatch")
+    return [(int(counts[p]), models[p].reshape(3, 3).copy(), ms[offsets[p]:offsets[p + 1]] != 0) for p in range(B)]
+
+
 def matchHamming(q, t, deviceCount: int = 1):
     """BFMatcher(NORM_HAMMING).knnMatch(k=2). q, t: uint8 [n][bytes]. -> (idx, dist, idx2, dist2).
     deviceCount > 1: cvMatchHammingMulti (query blocks over the visible GPUs, same answer)."""
