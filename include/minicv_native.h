@@ -523,9 +523,27 @@ MCV_API long long mcvTestRcpExhaustive(int mode, uint32_t* firstMismatches16);
 MCV_API long long mcvTestDivF64(int mode, unsigned long long seed, long long count, double* firstMismatches32);
 /* Device self-test: run the homography inlier sweep on caller-supplied fp32 models (8 floats each);
  * fused: 0 = op-by-op error (scalar sweep), 1 = fused (scalar sweep), 2 = fused through the packed-f32
- * sweep, 3 = op-by-op through the certified division-free sweep (the default path). */
+ * sweep, 3 = op-by-op through the certified division-free sweep (the default path: the form the
+ * size rule picks), 4 = the certified sweep's packed-f32 VALU form, forced, 5 = its bf16 matrix-core
+ * form, forced whatever the size. */
 MCV_API int mcvTestHomographySweep(const float* pts4, int N, const float* models8, int nModels, float thr2, int fused,
                                    int* counts);
+/* Device self-test: the affine forms W = h6 x + h7 y + 1, U = h0 x + h1 y + h2, V = h3 x + h4 y + h5 as
+ * the bf16 matrix-core form of the certified sweep produces them (three-way bf16 split of every f32
+ * operand, six products per variable, one v_mfma_f32_32x32x16_bf16 per form).
+ * wuv[(k * N + i) * 3 + {0, 1, 2}] = W, U, V of model k at correspondence i. Returns 1, 0 on failure. */
+MCV_API int mcvTestHMfmaWuv(const float* pts4, int N, const float* models8, int nModels, float* wuv);
+/* The form of the certified homography sweep. mode 0: automatic (the size rule), 1: the packed-f32 VALU
+ * kernel everywhere, 2: the bf16 matrix-core kernel in every launch and stage, 3: the matrix-core kernel
+ * in the full-width launches and the VALU kernel in the survivor stages; any other mode leaves the
+ * setting. Returns the previous mode, -1 on error. stats (may be NULL; 3 values), for the calling
+ * thread's last certified homography sweep (evaluate or mcvTestHomographySweep), read after its stream
+ * was synchronised: [0] the (32-point tile, hypothesis) rows the matrix-core kernel logged as undecided
+ * (rows of slots it writes only), [1] the waves whose event list overflowed, [2] the waves with a model
+ * outside the bound's domain (the slots of both kinds were recounted by the exact scalar sweep); all 0
+ * when the sweep ran the VALU kernel only. Not thread-safe, and the plan of the last evaluate must
+ * still exist and have been released, if at all, by the calling thread: tests only. */
+MCV_API int mcvTestHMfma(int mode, long long* stats);
 /* Device self-test: the LMedS rank kernel (lmeds.hip) on caller-supplied models: values[k] = the error
  * of rank `rank` (0-based, ascending; NaN last) of model k over pts4 (N float4 correspondences), NaN
  * when that element is a NaN. model MCV_MODEL_HOMOGRAPHY: 8 floats per model, errKind 0 = op-by-op,

@@ -38,8 +38,25 @@ void launch_h_verify_packed(const float* d_pts4, const void* d_pairs, int N, con
                             int hypCount, float thr2, const float* d_bbox, hipStream_t s);
 // Certified division-free sweep of the op-by-op error (the default) + exact recount of its redo slots;
 // d_bb = launch_abs_bound4 of the float4 points.
+// d_rec / d_stats given: the bf16 matrix-core form (mcv_h_verify_mfma) runs where `form` says so.
+// form (kHForm*): Auto = the size rule h_mfma_engages, Valu = mcv_h_verify_cert everywhere, Mfma = the
+// matrix-core kernel everywhere, Mixed = matrix-core for the full-width launches, VALU for survivor stages.
+enum { kHFormAuto = 0, kHFormValu = 1, kHFormMfma = 2, kHFormMixed = 3 };
+static const int kHMfmaStats = 3;   // d_stats: undecided rows logged, waves overflowed, waves outside the domain
 void launch_h_verify_certified(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
-                               int hypCount, float thr2, const double* d_bb, hipStream_t s);
+                               int hypCount, float thr2, const double* d_bb, hipStream_t s,
+                               const void* d_rec = nullptr, unsigned long long* d_stats = nullptr,
+                               int form = kHFormValu);
+// The matrix-core form's point records (h_rec_bytes(N) bytes): per correspondence, padded to a multiple
+// of 32, the bf16 pieces of x and y as the MFMA's B fragment words (16 B) and x', y' as f32 (8 B).
+size_t h_rec_bytes(int N);
+void launch_h_rec(const float* d_pts4, int N, void* d_rec, hipStream_t s);
+bool h_mfma_engages(int N, int hypCount, int form, bool staged);
+// W, U, V of the matrix-core form for every (model, correspondence): d_wuv[(k * N + i) * 3 + {0, 1, 2}]
+void launch_h_mfma_wuv(const void* d_rec, int N, const void* d_models, int nModels, float* d_wuv, hipStream_t s);
+// mcvTestHMfma's setting and the stats of a sweep run outside a plan (mcvTestHomographySweep)
+int h_mfma_form();
+void h_mfma_set_last(const unsigned long long* stats3);
 // The certified sweep in self-pruning stages, for callers that consume only the best key (the counts
 // of pruned slots stay partial). d_ctl: kHStageCtlInts ints (layout in ransac_h.hip, read back by
 // mcvTestHStaging); d_list: 2 x hypCount ints; d_pkey / d_pfail: launch_best's partials.
@@ -65,7 +82,8 @@ enum { kHStageNoCandidate = 1, kHStageSamplerFailure = 2, kHStageLate = 3, kHSta
        kHStageNotApplicable = 5 };
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
-                            uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s);
+                            uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec = nullptr,
+                            unsigned long long* d_stats = nullptr, int form = kHFormValu);
 void launch_h_mask(const float* d_pts4, int N, const float* hf8, float thr2, bool fused, uint8_t* d_mask,
                    int* d_count, hipStream_t s);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);

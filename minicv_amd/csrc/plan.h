@@ -67,6 +67,9 @@ struct Plan {
                               // affine / similarity: the generate's fp64 models (6 per hypothesis)
     DevBuf<uint8_t> hgen;     // homography: the split eigen generate's scratch (rotation log of one piece)
     DevBuf<float> pairs;      // paired point layout of the packed sweeps (homography 8, PnP 12 floats per 2)
+    DevBuf<char> hrec;        // homography matrix-core sweep: the bf16 point records (h_rec_bytes(N): 24 B per point)
+    DevBuf<unsigned long long> hmfmaStats;   // its undecided rows / overflowed / out-of-domain waves of the last sweep (kHMfmaStats)
+    bool hmfmaLast = false;   // the last certified homography sweep ran the matrix-core kernel
     DevBuf<int> hstageList;   // homography staged sweep: the two survivor lists (2 x hypCount slots)
     DevBuf<int> hstageCtl;    // homography staged sweep: the control block (kHStageCtlInts)
     int hstageLast = -1;      // last homography evaluate: 0 staged (the control block tells), else kHStage*

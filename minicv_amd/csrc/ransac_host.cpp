@@ -103,6 +103,16 @@ namespace mcv {
 static int g_hstage_mode = 0;
 // the plan of the calling thread's last homography evaluate (mcvTestHStaging reads its control block)
 static thread_local Plan* t_hstage_plan = nullptr;
+// mcvTestHMfma: the certified homography sweep's form (kHForm*), and where the calling thread's last
+// such sweep left its stats: a plan's device counters, or the values a sweep outside a plan reported
+static int g_hmfma_mode = kHFormAuto;
+static thread_local Plan* t_hmfma_plan = nullptr;
+static thread_local unsigned long long t_hmfma_last[kHMfmaStats] = {0, 0, 0};
+int h_mfma_form() { return g_hmfma_mode; }
+void h_mfma_set_last(const unsigned long long* stats3) {
+    t_hmfma_plan = nullptr;
+    for (int i = 0; i < kHMfmaStats; ++i) t_hmfma_last[i] = stats3[i];
+}
 
 void Plan::reserve(int n, int64_t hyps) {
     if (n > maxN) maxN = n;
@@ -156,6 +166,7 @@ hipStream_t Plan::own_stream() {
 
 Plan::~Plan() {
     if (t_hstage_plan == this) t_hstage_plan = nullptr;
+    if (t_hmfma_plan == this) t_hmfma_plan = nullptr;
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -334,13 +345,26 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
             P.hstageCtl.ensure(kHStageCtlInts);
             P.hstageList.ensure(2 * (size_t)hypCount);
         }
+        // the certified sweep's matrix-core form where the size rule (or mcvTestHMfma) engages it: its
+        // point records are written here, beside the pairs
+        const int form = g_hmfma_mode;
+        P.hmfmaLast = !fused && h_mfma_engages(N, hypCount, form, staged);
+        t_hmfma_plan = &P;
+        if (P.hmfmaLast) {
+            P.hrec.ensure(h_rec_bytes(N));
+            P.hmfmaStats.ensure(kHMfmaStats);
+            launch_h_rec(d_pts, N, P.hrec.p, s);
+        }
+        const void* d_rec = P.hmfmaLast ? P.hrec.p : nullptr;
+        unsigned long long* d_stats = P.hmfmaLast ? P.hmfmaStats.p : nullptr;
         ProfScope ps("h_verify", s);
         if (staged) {
             launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
-                                   P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s);
+                                   P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form);
         } else if (!fused) {
-            // default: OpenCV's op-by-op error, certified division-free packed sweep
-            launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s);
+            // default: OpenCV's op-by-op error, certified division-free sweep
+            launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s, d_rec,
+                                      d_stats, form);
         } else {
             launch_h_verify_packed(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bbox.p, s);
         }
@@ -816,6 +840,27 @@ extern "C" MCV_API int mcvTestHStaging(int mode, long long* stats) {
                     stats[3 + i] = std::min<long long>(2LL * ctl[kCtlBound + i], N);
                 for (int i = 0; i < kHStageMax; ++i) stats[10 + i] = ctl[kCtlAlive + i];
             }
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h). stats[3]: the undecided rows, the overflowed waves and the
+// out-of-domain waves of the
+// calling thread's last certified homography sweep. Call after synchronising the sweep's stream.
+extern "C" MCV_API int mcvTestHMfma(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hmfma_mode;
+        if (mode >= kHFormAuto && mode <= kHFormMixed) g_hmfma_mode = mode;
+        if (stats) {
+            unsigned long long v[kHMfmaStats];
+            for (int i = 0; i < kHMfmaStats; ++i) v[i] = t_hmfma_last[i];
+            const Plan* P = t_hmfma_plan;
+            if (P) {
+                for (int i = 0; i < kHMfmaStats; ++i) v[i] = 0;
+                if (P->hmfmaLast) MCV_HIP(hipMemcpy(v, P->hmfmaStats.p, sizeof(v), hipMemcpyDeviceToHost));
+            }
+            for (int i = 0; i < kHMfmaStats; ++i) stats[i] = (long long)v[i];
         }
         return prev;
     })

@@ -150,6 +150,28 @@ extern "C" MCV_API long long mcvTestDivF64(int mode, unsigned long long seed, lo
     })
 }
 
+// W, U, V as the certified sweep's matrix-core form computes them (the bf16 split and the MFMA dot).
+extern "C" MCV_API int mcvTestHMfmaWuv(const float* pts4, int N, const float* models8, int nModels, float* wuv) {
+    MCV_GUARD(0, {
+        require_device();
+        if (N <= 0 || nModels <= 0 || !pts4 || !models8 || !wuv) fail("bad arguments");
+        DevBuf<float> p, m, o;
+        DevBuf<char> rec;
+        const size_t no = (size_t)nModels * N * 3;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        o.ensure(no);
+        rec.ensure(h_rec_bytes(N));
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        launch_h_rec(p.p, N, rec.p, 0);
+        launch_h_mfma_wuv(rec.p, N, m.p, nModels, o.p, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipMemcpy(wuv, o.p, no * sizeof(float), hipMemcpyDeviceToHost));
+        return 1;
+    })
+}
+
 // Run the homography inlier sweep on caller-supplied fp32 models (host arrays): exercises the
 // rare exact-division paths of mcv_h_verify with crafted models (zero / denormal / huge
 // denominators) that random hypotheses practically never produce. fused: 0 = op-by-op error,
@@ -170,15 +192,25 @@ extern "C" MCV_API int mcvTestHomographySweep(const float* pts4, int N, const fl
         MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
         MCV_HIP(hipMemset(c.p, 0, (size_t)nModels * 4));
         launch_bbox(p.p, N, bb.p, 0);
-        if (fused == 3) {   // certified op-by-op sweep + exact recount of the slots it marks kStatusRedo
+        if (fused >= 3 && fused <= 5) {   // certified op-by-op sweep + exact recount of the slots it marks kStatusRedo
+            // 3: the form mcvTestHMfma's setting and the size rule pick; 4: the VALU kernel; 5: the matrix-core kernel
+            const int form = fused == 3 ? h_mfma_form() : (fused == 4 ? kHFormValu : kHFormMfma);
             DevBuf<float> pairs;
             DevBuf<double> b4;
+            DevBuf<char> rec;
+            DevBuf<unsigned long long> st;
             pairs.ensure((size_t)(N + 1) / 2 * 8);
             b4.ensure(4);
+            rec.ensure(h_rec_bytes(N));
+            st.ensure(kHMfmaStats);
             launch_h_pair(p.p, N, pairs.p, 0);
+            launch_h_rec(p.p, N, rec.p, 0);
             launch_abs_bound4(p.p, false, N, b4.p, nullptr, 0);
-            launch_h_verify_certified(p.p, pairs.p, N, m.p, c.p, nModels, thr2, b4.p, 0);
+            launch_h_verify_certified(p.p, pairs.p, N, m.p, c.p, nModels, thr2, b4.p, 0, rec.p, st.p, form);
             MCV_HIP(hipDeviceSynchronize());
+            unsigned long long hs[kHMfmaStats];
+            MCV_HIP(hipMemcpy(hs, st.p, sizeof(hs), hipMemcpyDeviceToHost));
+            h_mfma_set_last(hs);
         } else if (fused == 2) {   // packed sweep + exact recount of the slots it marks kStatusRedo
             DevBuf<float> pairs;
             pairs.ensure((size_t)(N + 1) / 2 * 8);

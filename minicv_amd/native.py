@@ -191,6 +191,8 @@ SIGNATURES = {
     "mcvTestRcpExhaustive": (C.c_longlong, [_I, _P]),
     "mcvTestDivF64": (C.c_longlong, [_I, C.c_ulonglong, C.c_longlong, _P]),
     "mcvTestHomographySweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
+    "mcvTestHMfmaWuv": (_I, [_P, _I, _P, _I, _P]),
+    "mcvTestHMfma": (_I, [_I, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
