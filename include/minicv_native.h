@@ -648,6 +648,24 @@ MCV_API int mcvTestEigLogCap(int cap);
  * number of stages; [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
  * [10..15] the slots alive entering each stage. Not thread-safe: tests only. */
 MCV_API int mcvTestHStaging(int mode, long long* stats);
+/* The per-cell inlier upper bound that drops hypotheses before stage 1 of the staged homography sweep.
+ * mode 0: automatic (where the staged sweep's own size rule holds, from 20000 correspondences), 1: whenever the
+ * sweep is staged, 2: never;
+ * any other mode leaves the setting. G, Gs: the 4-D grid of the points the candidate rejects and the 2-D grid
+ * of its inliers (1..6 and 1..24; 0 leaves them; defaults 4 and 12). Returns the previous mode, -1 on error.
+ * stats (may be NULL; 6 values), for the calling thread's last homography evaluate, read after its stream was
+ * synchronised: [0] 1 = the bound ran, 0 = it did not; [1] non-empty cells; [2] slots alive after the bound
+ * (entering stage 1); [3] cell slots (G^4 + Gs^2); [4] G; [5] Gs. Not thread-safe: tests only. */
+MCV_API int mcvTestHCellMode(int mode, int G, int Gs, long long* stats);
+/* The cell build and the bound on caller-supplied data: pts4 (N float4 correspondences), the candidate's
+ * model cand8, nModels models (8 floats each), the threshold and B. device 1: the kernels of the staged
+ * sweep; 0: their host twin (the same header, no device needed). Outputs: cellId[N]; boxes[8 cells] = min /
+ * max of x, y, x', y' per cell and sizes[cells] (cells = G^4 + Gs^2; an empty cell's box is NaN); ub[nModels]
+ * = the upper bound of each model's inlier count; bits[nModels * ceil(cells / 32)] = the cells certified as
+ * all-outlier (bit c & 31 of word c >> 5); *alive = the models with ub >= B. Returns 1, 0 on failure. */
+MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                              float thr2, int B, int G, int Gs, int device, int* cellId, float* boxes, int* sizes,
+                              int* ub, unsigned int* bits, int* alive);
 /* cvFindModelBatch's index arithmetic, as the export itself computes it (no device). Problems with more
  * than m (the sample size) correspondences run on the device and are numbered in order (d = 0, 1, ...).
  * desc4[4 p ..]: point offset (= offsets[p]: float4 points, no padding), N, slot offset (d * per, 64-bit;

@@ -64,6 +64,7 @@ static const int kHStageCtlInts = 32;
 static const int kCtlB = 0;        // the candidate's full count: a lower bound of the winning count
 static const int kCtlReason = 1;   // 0 = pruning engaged, else kHStage* (why everything runs to the end)
 static const int kCtlStages = 2;   // stages in use (2 + the later stages)
+static const int kCtlCells = 3;    // cell slots of the per-cell bound that ran before stage 1 (0: none)
 static const int kCtlBound = 4;    // kHStageMax + 1 boundaries, in pairs
 static const int kCtlAlive = 12;   // slots alive entering each stage
 static const int kCtlKey = 24;     // the candidate's packed key and the first failure (2 x 64 bit)
@@ -83,7 +84,27 @@ enum { kHStageNoCandidate = 1, kHStageSamplerFailure = 2, kHStageLate = 3, kHSta
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec = nullptr,
-                            unsigned long long* d_stats = nullptr, int form = kHFormValu);
+                            unsigned long long* d_stats = nullptr, int form = kHFormValu, int* d_cells = nullptr,
+                            int G = 0, int Gs = 0);
+// The per-cell bound before stage 1 (h_cell_bound.h): the cell table (h_cell_count(G, Gs) x
+// kHCellInts ints) is built with the candidate's count, the bound kernel writes the slots that can still
+// reach B to d_list and their number to ctl[kCtlAlive + 1]. The automatic rule engages it where the staged
+// sweep's own size rule holds and N >= kHCellMinN: the bound costs a slot about what 2200 correspondences of
+// the sweep cost, whatever N, and measured it wins at N = 20000 and 100000 from 2^16 / 2^18
+// hypotheses and loses at N = 5000 (2^20 hypotheses: 5.96 -> 6.17 ms).
+// d_cellOut / d_ub / d_bits: the test hook's outputs (nullptr in the sweep).
+static const int kHCellMinN = 20000;
+// stage 0 with the bound sweeps ~N / 64 points: every slot still runs stage 0, so with stage 1 listed it is the
+// largest full-width cost; cfg3 evaluate 13.00 ms at N / 16, 12.32-12.41 at N / 32, 11.94-12.01 at N / 64 (the
+// candidate's B is 50196 at all three)
+static const int kHCellPrefixDiv = 64;
+void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int64_t hypBegin, float thr2, int* d_ctl,
+                          const double* d_bb, int* d_cells, int G, int Gs, int* d_cellOut, hipStream_t s);
+void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
+                         const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
+                         hipStream_t s);
+void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
+                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive);
 void launch_h_mask(const float* d_pts4, int N, const float* hf8, float thr2, bool fused, uint8_t* d_mask,
                    int* d_count, hipStream_t s);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);

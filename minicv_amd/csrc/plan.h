@@ -73,6 +73,7 @@ struct Plan {
     DevBuf<int> hstageList;   // homography staged sweep: the two survivor lists (2 x hypCount slots)
     DevBuf<int> hstageCtl;    // homography staged sweep: the control block (kHStageCtlInts)
     int hstageLast = -1;      // last homography evaluate: 0 staged (the control block tells), else kHStage*
+    DevBuf<int> hcells;       // homography staged sweep: the per-cell bound's cell table (kHCellInts ints per cell)
     DevBuf<uint8_t> one;      // single-hypothesis output record
     DevBuf<double> ptsd;      // essential: double4 normalised correspondences
     DevBuf<double> raw;       // essential: uploaded V2d pairs (a then b)

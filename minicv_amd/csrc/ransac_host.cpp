@@ -13,6 +13,7 @@
 #include "linalg.h"
 #include "mcv_common.h"
 #include "hyp_homography.h"
+#include "h_cell_bound.h"
 #include "hyp_affine.h"
 #include "plan.h"
 #include "rank_select.h"
@@ -103,6 +104,10 @@ namespace mcv {
 static int g_hstage_mode = 0;
 // the plan of the calling thread's last homography evaluate (mcvTestHStaging reads its control block)
 static thread_local Plan* t_hstage_plan = nullptr;
+// mcvTestHCellMode: the per-cell bound before stage 1: 0 automatic, 1 whenever the sweep is staged, 2 never;
+// its two grids
+static int g_hcell_mode = 0;
+static int g_hcell_G = kHCellG, g_hcell_Gs = kHCellGs;
 // mcvTestHMfma: the certified homography sweep's form (kHForm*), and where the calling thread's last
 // such sweep left its stats: a plan's device counters, or the values a sweep outside a plan reported
 static int g_hmfma_mode = kHFormAuto;
@@ -336,14 +341,24 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
         // 0 when B itself is below the minimum count), and the true key for every other slot: the same
         // maximum, the same lowest-index tie-break, the same minimum-count rule. Adaptive replay, LMedS,
         // callers that pass d_counts, the fused error and the other models keep the single full sweep.
+        // The per-cell bound (h_cell_bound.h) drops slots before stage 1 on the same terms. A slot it drops has
+        // a full count of at most UB (every correspondence of a certified cell is an outlier of the slot's
+        // model under the op-by-op error: DESIGN.md §4), and UB < B. The count it keeps is its stage-0 partial,
+        // at most its full count and so below B. The candidate's own UB is at least its full count B, and a
+        // slot that reaches the winning count has UB >= that count >= B: neither is dropped (inclusive test).
+        // Everything else above stands as written. Engaged where the size rule itself stages the call and
+        // N >= kHCellMinN (kernels.h: the measured rows); forced staging of a small call keeps the plain stages.
         const bool stageable = !fused && d_key != nullptr && !needCounts;
         const bool staged = stageable && g_hstage_mode != 2 &&
                             (g_hstage_mode == 1 || (N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals));
         P.hstageLast = staged ? 0 : (stageable && g_hstage_mode == 2 ? kHStageForcedOff : kHStageNotApplicable);
         t_hstage_plan = &P;
+        const bool sized = N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals;
+        const bool cellBound = staged && g_hcell_mode != 2 && (g_hcell_mode == 1 || (sized && N >= kHCellMinN));
         if (staged) {
             P.hstageCtl.ensure(kHStageCtlInts);
             P.hstageList.ensure(2 * (size_t)hypCount);
+            if (cellBound) P.hcells.ensure((size_t)h_cell_count(g_hcell_G, g_hcell_Gs) * kHCellInts);
         }
         // the certified sweep's matrix-core form where the size rule (or mcvTestHMfma) engages it: its
         // point records are written here, beside the pairs
@@ -360,7 +375,8 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
         ProfScope ps("h_verify", s);
         if (staged) {
             launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
-                                   P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form);
+                                   P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form,
+                                   cellBound ? P.hcells.p : nullptr, g_hcell_G, g_hcell_Gs);
         } else if (!fused) {
             // default: OpenCV's op-by-op error, certified division-free sweep
             launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s, d_rec,
@@ -842,6 +858,99 @@ extern "C" MCV_API int mcvTestHStaging(int mode, long long* stats) {
             }
         }
         return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the per-cell bound's switch, grids and the last evaluate's figures.
+extern "C" MCV_API int mcvTestHCellMode(int mode, int G, int Gs, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hcell_mode;
+        if (mode >= 0 && mode <= 2) g_hcell_mode = mode;
+        if (G >= 1 && G <= kHCellMaxG) g_hcell_G = G;
+        if (Gs >= 1 && Gs <= kHCellMaxGs) g_hcell_Gs = Gs;
+        if (stats) {
+            for (int i = 0; i < 6; ++i) stats[i] = 0;
+            stats[4] = g_hcell_G;
+            stats[5] = g_hcell_Gs;
+            const Plan* P = t_hstage_plan;
+            if (P && P->hstageLast == 0) {
+                int ctl[kHStageCtlInts];
+                MCV_HIP(hipMemcpy(ctl, P->hstageCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+                const int cells = ctl[kCtlCells];
+                stats[0] = cells > 0;
+                stats[2] = ctl[kCtlAlive + 1];
+                stats[3] = cells;
+                if (cells > 0) {
+                    std::vector<int> tab((size_t)cells * kHCellInts);
+                    MCV_HIP(hipMemcpy(tab.data(), P->hcells.p, tab.size() * sizeof(int), hipMemcpyDeviceToHost));
+                    for (int c = 0; c < cells; ++c) stats[1] += tab[(size_t)c * kHCellInts + kHCellInts - 1] > 0;
+                }
+            }
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the cell build and the bound on given data, device or host twin.
+extern "C" MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* cand8, const float* models8,
+                                         int nModels, float thr2, int B, int G, int Gs, int device, int* cellId,
+                                         float* boxes, int* sizes, int* ub, unsigned int* bits, int* alive) {
+    MCV_GUARD(0, {
+        if (!pts4 || !cand8 || !models8 || !cellId || !boxes || !sizes || !ub || !bits || !alive)
+            fail("mcvTestHCellBound: null argument");
+        if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs)
+            fail("mcvTestHCellBound: bad sizes");
+        if (!device) {
+            h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes, sizes, ub, bits, alive);
+            return 1;
+        }
+        require_device();
+        const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
+        DevBuf<float> p, m, cand;
+        DevBuf<double> bb;
+        DevBuf<int> ctl, tab, cnt, list, dub, did;
+        DevBuf<uint32_t> dbits;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        cand.ensure(8);
+        bb.ensure(4);
+        ctl.ensure(kHStageCtlInts);
+        tab.ensure((size_t)cells * kHCellInts);
+        cnt.ensure(nModels);
+        list.ensure(nModels);
+        dub.ensure(nModels);
+        did.ensure(N);
+        dbits.ensure((size_t)nModels * words);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cand.p, cand8, 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(cnt.p, 0, (size_t)nModels * sizeof(int)));
+        MCV_HIP(hipMemset(dbits.p, 0, (size_t)nModels * words * sizeof(uint32_t)));
+        // a control block that names slot 0 of `cand` as the candidate (key: count 1, hypothesis 0)
+        int hctl[kHStageCtlInts] = {0};
+        const uint64_t key = (1ull << 32) | 0xFFFFFFFFull;
+        memcpy(hctl + kCtlKey, &key, sizeof(key));
+        MCV_HIP(hipMemcpy(ctl.p, hctl, sizeof(hctl), hipMemcpyHostToDevice));
+        launch_abs_bound4(p.p, false, N, bb.p, nullptr, 0);
+        launch_h_stage_count(p.p, N, cand.p, 0, thr2, ctl.p, bb.p, tab.p, G, Gs, did.p, 0);
+        MCV_HIP(hipDeviceSynchronize());
+        // B as given (the kernel counted the candidate's inliers into the same word)
+        MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
+        launch_h_cell_bound(m.p, cnt.p, nModels, thr2, bb.p, tab.p, G, Gs, ctl.p, list.p, dub.p, dbits.p, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        std::vector<int> htab((size_t)cells * kHCellInts);
+        MCV_HIP(hipMemcpy(htab.data(), tab.p, htab.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int c = 0; c < cells; ++c) {
+            for (int j = 0; j < 8; ++j) boxes[8 * c + j] = h_cell_dec(htab[(size_t)c * kHCellInts + j]);
+            sizes[c] = htab[(size_t)c * kHCellInts + kHCellInts - 1];
+        }
+        MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(ub, dub.p, (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(bits, dbits.p, (size_t)nModels * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
+        *alive = hctl[kCtlAlive + 1];
+        return 1;
     })
 }
 

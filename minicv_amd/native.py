@@ -193,6 +193,8 @@ SIGNATURES = {
     "mcvTestHomographySweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
     "mcvTestHMfmaWuv": (_I, [_P, _I, _P, _I, _P]),
     "mcvTestHMfma": (_I, [_I, _P]),
+    "mcvTestHCellMode": (_I, [_I, _I, _I, _P]),
+    "mcvTestHCellBound": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
