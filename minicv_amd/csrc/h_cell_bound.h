@@ -75,7 +75,7 @@ struct HCellModel {
     bool ok;
 };
 
-// Restates h_cert_offsets (ransac_h.hip, the VALU form; certT = kCertT, certSlop = kCertSlop): b_x from
+// Restates h_cert_offsets (h_cert.h, the VALU form; certT = kCertT, certSlop = kCertSlop): b_x from
 // above. The float round-ups there (b_in = RU(K1), b_x = RU((K2 + b_in)(1 + slop))) are bounded by a factor
 // 1 + 2^-23 each (the values are >= 2^-120: normal floats).
 MCV_HD HCellModel h_cell_model(const float* h, const double* bb, float thr2, double kappa, double certT,

@@ -370,7 +370,7 @@ MCV_HD int h_hypothesis(const float* pts4, int N, const Sampler& smp, uint64_t h
 // reference's Linux/AMD64 target — evaluates the expression unfused, clang's default
 // -ffp-contract=on on arm64 contracts it into FMAs):
 //   op by op (default): every operation rounded as written, IEEE division (h_error); the sweep
-//                    decides it without dividing (mcv_h_verify_cert, ransac_h.hip);
+//                    decides it without dividing (mcv_h_verify_cert, ransac_h_sweep.hip);
 //   fused (MCV_FLAG_FUSED_ERROR): w = fma(h6,x,fma(h7,y,1)); ww = RN(1/w);
 //                    ex = fma(fma(h0,x,fma(h1,y,h2)), ww, -mx); ey likewise; e = fma(ex,ex,ey*ey).
 // Inlier iff e <= (float)thr^2 in both.

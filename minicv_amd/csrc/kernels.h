@@ -14,7 +14,8 @@ static const int kVerifyPtsPerLane = 2;
 // Upper bound of reduction partial blocks (reduce.h).
 static const int kReduceMaxBlocksHost = 1024;
 
-// ---- homography (ransac_h.hip)
+// ---- homography (ransac_h_gen.hip, ransac_h_sweep.hip, ransac_h_mfma.hip, ransac_h_stage.hip,
+// ransac_h_refine.hip; the host side: ransac_h_host.cpp)
 struct HOneOut {
     double H[9];
     float hf[8];
@@ -25,14 +26,14 @@ void launch_h_one(const float* d_pts4, int N, Sampler smp, int64_t hyp, HOneOut*
 void launch_h_mask_one(const float* d_pts4, int N, const HOneOut* d_one, float thr2, bool fused, uint8_t* d_mask,
                        int* d_count, hipStream_t s);
 // d_scratch (h_gen_scratch_bytes(hypCount) bytes): the split eigen generate's rotation log, samples
-// and overflow list (ransac_h.hip); nullptr runs the one-pass solve.
+// and overflow list (ransac_h_gen.hip); nullptr runs the one-pass solve.
 void launch_h_generate(const float* d_pts4, int N, Sampler smp, int64_t hypBegin, int hypCount, void* d_models,
                        double* d_h64, int* d_counts, hipStream_t s, bool fast, void* d_scratch = nullptr);
 size_t h_gen_scratch_bytes(int hypCount);
 void launch_h_verify(const float* d_pts4, int N, const void* d_models, int* d_counts, int hypCount, float thr2,
                      bool fused, const float* d_bbox, hipStream_t s);
 void launch_bbox(const float* d_pts4, int N, float* d_bbox, hipStream_t s);
-// Packed-f32 sweep of the fused error over the paired layout (ransac_h.hip, HPair: 32 B per 2).
+// Packed-f32 sweep of the fused error over the paired layout (ransac_h_sweep.hip, HPair: 32 B per 2).
 void launch_h_pair(const float* d_pts4, int N, void* d_pairs, hipStream_t s);
 void launch_h_verify_packed(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, float thr2, const float* d_bbox, hipStream_t s);
@@ -58,7 +59,7 @@ void launch_h_mfma_wuv(const void* d_rec, int N, const void* d_models, int nMode
 int h_mfma_form();
 void h_mfma_set_last(const unsigned long long* stats3);
 // The certified sweep in self-pruning stages, for callers that consume only the best key (the counts
-// of pruned slots stay partial). d_ctl: kHStageCtlInts ints (layout in ransac_h.hip, read back by
+// of pruned slots stay partial). d_ctl: kHStageCtlInts ints (layout in h_cert.h, read back by
 // mcvTestHStaging); d_list: 2 x hypCount ints; d_pkey / d_pfail: launch_best's partials.
 static const int kHStageCtlInts = 32;
 static const int kCtlB = 0;        // the candidate's full count: a lower bound of the winning count
@@ -105,16 +106,11 @@ void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount
                          hipStream_t s);
 void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
                  int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive);
-void launch_h_mask(const float* d_pts4, int N, const float* hf8, float thr2, bool fused, uint8_t* d_mask,
-                   int* d_count, hipStream_t s);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);
 void h_refit_chain(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_red, hipStream_t s);
-void h_reduce_absdev(const float* d_pts4, int N, const uint8_t* d_mask, const double* c4, double* d_part,
-                     double* d_out, hipStream_t s);
-void h_reduce_ltl(const float* d_pts4, int N, const uint8_t* d_mask, const double* c4, const double* s4,
-                  double* d_part, double* d_out, hipStream_t s);
-void h_reduce_lm(const float* d_pts4, int N, const uint8_t* d_mask, const double* h8, bool wantJ, double* d_part,
-                 double* d_out, hipStream_t s);
+// d_out = {JtJ upper triangle (36), Jtr (8), |r|^2} of HomographyRefineCallback at h8
+void h_reduce_lm(const float* d_pts4, int N, const uint8_t* d_mask, const double* h8, double* d_part, double* d_out,
+                 hipStream_t s);
 
 // ---- affine / similarity (ransac_a.hip); m = 3 (affine) or 2 (similarity) point samples, lx = 6 / 4
 // refine parameters; both store AModelF (6 floats) per hypothesis
@@ -333,7 +329,7 @@ int launch_batch_reduce_lm(int lx, const float* d_pts4, const uint8_t* d_mask, c
 int launch_batch_refit_chain(const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed, int maxN,
                              double* d_part, double* d_rec, hipStream_t s);
 
-// ---- shared (ransac_h.hip)
+// ---- shared (ransac_common.hip)
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,
                  uint64_t* d_out, hipStream_t s);
 void launch_fill_u8(uint8_t* d, int n, uint8_t v, hipStream_t s);

@@ -1,6 +1,6 @@
 // lm_solver.h — LMSolver::create(callback, maxIters)->run(x): the classic LMSolverImpl restated
 // (OpenCV 4.x calib3d/src/levmarq.cpp [ext]; Marquardt-Nielsen lambda control, eigen-based solve), with
-// the callback left to the caller: the homography refine (ransac_host.cpp) and the affine / similarity
+// the callback left to the caller: the homography refine (ransac_h_host.cpp) and the affine / similarity
 // refines (ransac_a_host.cpp) run the same solver. The O(lx^2) algebra runs here, on the host.
 #pragma once
 

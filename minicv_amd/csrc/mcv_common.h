@@ -167,7 +167,7 @@ MCV_HD int SubsetSrc<M>::next(int N, int (&idx)[M]) {
 #pragma unroll
         for (int i = 0; i < M; ++i) idx[i] = row[i];
         // a row is a subset of [0, N) by construction (the table is rebuilt whenever N or the points
-        // change, ransac_host.cpp); an index outside it ends the stream instead of reading past pts
+        // change: cv_table_stale, ransac_host.cpp); an index outside it ends the stream instead of reading past pts
         bool in = true;
 #pragma unroll
         for (int i = 0; i < M; ++i) in = in && (unsigned)idx[i] < (unsigned)N;

@@ -1,5 +1,5 @@
 // pk_pair.h — the paired point layout and the packed-f32 helpers shared by the packed inlier sweeps
-// (ransac_h.hip: mcv_h_verify_pk, mcv_h_verify_cert; ransac_a.hip: mcv_a_verify_pk). Device code only.
+// (ransac_h_sweep.hip: mcv_h_verify_pk, mcv_h_verify_cert; ransac_h_mfma.hip; ransac_a.hip: mcv_a_verify_pk). Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,4 +1,6 @@
-// plan.h — device workspace of one RANSAC problem family (homography or fundamental) on one GPU.
+// plan.h — device workspace of one RANSAC problem family (homography, fundamental, affine / similarity,
+// essential or PnP) on one GPU, and what the shared framework (ransac_host.cpp) and the per-family host
+// files declare to each other.
 #pragma once
 
 #include "minicv_native.h"
@@ -121,6 +123,13 @@ inline void reduce_to_host(Plan& P, hipStream_t s, int V, double* out, F launch)
     for (int i = 0; i < V; ++i) out[i] = P.h_red.p[i];
 }
 
+// The winner's mask (P.mask) to the caller's host buffer, when it wants one. Synchronises s.
+inline void mask_to_host(Plan& P, uint8_t* mask, int N, hipStream_t s) {
+    if (!mask) return;
+    MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipStreamSynchronize(s));
+}
+
 // Opt-in kernel timing with HIP events recorded on the launch stream (bench.py's live roofline).
 // mcvProfileEnable(n): every n-th launch of each named scope is timed (n = 1: all of them). An event
 // pair costs the stream ~3 us each way, 17 % of the 36 us cfg2 Hamming step when every launch is
@@ -168,6 +177,7 @@ uint64_t cv_table_points_fp(int model, const float* h_pts4, int N);
 void cv_table_prepare(Plan& P, const void* d_pts, const float* h_pts4, int N, const RansacConfig& cfg, int64_t rows,
                       hipStream_t s);
 bool fused_error(const RansacConfig& cfg);
+bool fast_minimal(const RansacConfig& cfg);   // MCV_FLAG_FAST_MINIMAL
 RansacConfig config_or_default(const RansacConfig* cfg);
 int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, hipStream_t s,
                       const float* h_pts4 = nullptr);
@@ -183,8 +193,28 @@ int finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t
 void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                     int* d_counts, uint64_t* d_key, hipStream_t s, bool needCounts = true);
 
+// Per family: *_generate_chunk = one chunk's models, statuses and P.last (shared by the RANSAC evaluate and
+// lmeds_search); *_evaluate_chunk = generate + verify into d_counts; *_finalize = the winner's model and mask.
+
+// homography family (ransac_h_*.hip / ransac_h_host.cpp)
+void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s);
+// keyOnly: nobody reads d_counts beyond the best-key reduction, so the sweep may run in self-pruning stages
+void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, bool keyOnly, hipStream_t s);
+int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* H, uint8_t* d_mask,
+               hipStream_t s);
+int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
+                      int* sampleIdx, bool fast);
+void h_plan_forget(const Plan* P);   // ~Plan: drops the test hooks' references to the plan
+
 // fundamental-matrix family (ransac_f.hip / ransac_f_host.cpp)
+bool f_seven(int model, const RansacConfig& cfg);   // fundamental with MCV_FLAG_SEVEN_POINT
 int f_error_kind(const RansacConfig& cfg);
+void f_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s);
+void f_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s);
 int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* F, uint8_t* d_mask,
                hipStream_t s);
 int f_fit_all(Plan& P, const float* d_pts, int N, hipStream_t s, double* F);
@@ -193,8 +223,12 @@ int f_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, doub
 
 // affine / similarity family (ransac_a.hip / ransac_a_host.cpp)
 inline bool affine_family(int model) { return model == MCV_MODEL_AFFINE || model == MCV_MODEL_SIMILARITY; }
+void a_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s);
 void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                       int* d_counts, hipStream_t s);
+int a_host_hypothesis(int model, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
+                      int* sampleIdx);
 int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
                uint8_t* d_mask, hipStream_t s);
 

@@ -60,7 +60,7 @@ __global__ void mcv_a_one(const float* __restrict__ pts4, int N, Sampler smp, in
 }
 
 // ------------------------------------------------------------------------------------------
-// Packed-f32 inlier sweep. Layout and conventions of mcv_h_verify_pk (ransac_h.hip): HPair p holds
+// Packed-f32 inlier sweep. Layout and conventions of mcv_h_verify_pk (ransac_h_sweep.hip): HPair p holds
 // correspondences (2p, 2p + 1) as {x, y, X, Y} pairs; an odd N is padded with {0, 0, NaN, NaN}, whose
 // error is NaN (never an inlier). Wave w owns hypotheses [w K, w K + K): (F0,F1) (F2,F3) (F4,F5) as
 // three SGPR pairs each. A VOP3P op reads one SGPR pair (constant-bus limit), so the addends F2 / F5,

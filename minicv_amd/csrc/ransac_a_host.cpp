@@ -18,17 +18,24 @@
 
 namespace mcv {
 
+// One chunk of hypotheses; the winner is re-solved from its sample (a closed form: nothing to cache).
+// Shared by the RANSAC evaluate below and lmeds_search.
+void a_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s) {
+    P.last.clear();
+    launch_a_generate(model_points(P.model), d_pts, N, P.sampler(cfg), hypBegin, hypCount, P.models.p, P.h64.p,
+                      d_counts, s);
+}
+
 void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                       int* d_counts, hipStream_t s) {
     const double t = effective_threshold(cfg);
     const float thr2 = (float)(t * t);
     P.pairs.ensure((size_t)(N + 1) / 2 * 8);
     launch_h_pair(d_pts, N, P.pairs.p, s);
-    P.last.clear();   // the winner is re-solved from its sample (a closed form: nothing to cache)
     {
         ProfScope pg("a_generate", s);
-        launch_a_generate(model_points(P.model), d_pts, N, P.sampler(cfg), hypBegin, hypCount, P.models.p, P.h64.p,
-                          d_counts, s);
+        a_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
     }
     ProfScope ps("a_verify", s);
     launch_a_verify(P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, fused_error(cfg), s);
@@ -122,6 +129,22 @@ int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
     return a_finalize_impl(P, d_pts, N, cfg, hyp, model9, d_mask, s, false);
 }
 
+int a_host_hypothesis(int model, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
+                      int* sampleIdx) {
+    const int m = model_points(model);
+    if (N < m) fail("N < %d", m);
+    AModelF mf;
+    double A[6];
+    for (int k = 0; k < 6; ++k) { A[k] = 0; mf.a[k] = 0; }
+    int idx[3] = {-1, -1, -1};
+    const Sampler smp{seed, nullptr};
+    const int st = m == 3 ? a_hypothesis<3>(pts4, N, smp, (uint64_t)hyp, A, &mf, idx)
+                          : a_hypothesis<2>(pts4, N, smp, (uint64_t)hyp, A, &mf, idx);
+    for (int k = 0; k < 6; ++k) { model9[k] = A[k]; modelf9[k] = mf.a[k]; }
+    if (sampleIdx) for (int k = 0; k < m; ++k) sampleIdx[k] = idx[k];
+    return st;
+}
+
 static int estimate_affine(int model, const char* who, const mcvV2d* from, const mcvV2d* to, int N,
                            const RansacConfig* cfgp, double* A6, uint8_t* mask) {
     if (!from || !to || !A6 || N < 0) fail("%s: null argument or negative N", who);
@@ -154,10 +177,7 @@ static int estimate_affine(int model, const char* who, const mcvV2d* from, const
         }
         count = a_finalize(P, P.pts.p, N, fin, best, model9, P.mask.p, s);
         if (cfg.method == MCV_METHOD_LMEDS && count < m) fail("%s: LMedS model has %d inliers (< %d)", who, count, m);
-        if (mask) {
-            MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
-            MCV_HIP(hipStreamSynchronize(s));
-        }
+        mask_to_host(P, mask, N, s);
     }
     for (int k = 0; k < 6; ++k) A6[k] = model9[k];
     return count;

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_batch_reduce_final(const B
     block_sum<V>(acc, out + (size_t)r * outStride);
 }
 
-// The functors of the single call's refine passes (ransac_a.hip OpALM; ransac_h.hip OpSums, OpAbsDevD,
+// The functors of the single call's refine passes (ransac_a.hip OpALM; ransac_h_refine.hip OpSums, OpAbsDevD,
 // OpLtLD, OpLM), with the per-problem constants read from the problem's parameter row.
 template <int LX>
 struct BOpALM {
@@ -376,7 +376,7 @@ struct BOpHLM {     // 45: JtJ upper triangle (36), Jtr (8), |r|^2 (1)
     }
 };
 
-// mcv_refit_stats (ransac_h.hip) for every problem's record: the same IEEE divisions.
+// mcv_refit_stats (ransac_h_refine.hip) for every problem's record: the same IEEE divisions.
 __global__ void mcv_batch_refit_stats(double* __restrict__ rec, int nRed, int stage) {
     const int r = blockIdx.x * 64 + (threadIdx.x >> 2), k = threadIdx.x & 3;
     if (r >= nRed) return;

@@ -164,7 +164,7 @@ static int batch_single(int model, const mcvV2d* a, const mcvV2d* b, int N, cons
     return c;
 }
 
-// h_refit's host half (ransac_host.cpp) on the chained passes' record r[62].
+// h_refit's host half (ransac_h_host.cpp) on the chained passes' record r[62].
 static bool h_refit_from_record(const double* r, double* H) {
     const double* sums = r;
     const double count = sums[4];

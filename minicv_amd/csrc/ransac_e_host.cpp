@@ -10,7 +10,7 @@
 //   decomposeEssentialMat(E) -> R1, R2, t.
 //   recoverPose(E, p1, p2, R, t, focal, pp, mask): the 4 (R, +-t) candidates, DLT triangulation,
 //     cheirality with distance 50 over the masked points, first maximum of the 4 counts.
-// The sampling / replay / verify split is the same as for homographies (ransac_host.cpp).
+// The sampling / replay / verify split is the same as for homographies (ransac_host.cpp, ransac_h_host.cpp).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"

@@ -1,7 +1,9 @@
-// ransac_f_host.cpp — host side of cvFindFundamentalMat (new export; OpenCV 4.x
-// cv::findFundamentalMat(points1, points2, FM_RANSAC / FM_8POINT, thr, conf, maxIters, mask)
+// ransac_f_host.cpp — host side of the fundamental-matrix family: cvFindFundamentalMat (new export;
+// OpenCV 4.x cv::findFundamentalMat(points1, points2, FM_RANSAC / FM_8POINT, thr, conf, maxIters, mask)
 // semantics, restated [ext]): the RANSAC result is the best hypothesis' model (OpenCV does not
-// refit F on the inliers); FM_8POINT (method 0 here) fits all points.
+// refit F on the inliers); FM_8POINT (method 0 here) fits all points. The search is the shared
+// framework's (ransac_host.cpp); a chunk's generate + verify (8-point and 7-point) and the winner's
+// finalize are here.
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -20,6 +22,42 @@ namespace mcv {
 int f_error_kind(const RansacConfig& cfg) {
     const int e = cfg.errorKind == MCV_FERR_EPIPOLAR ? 1 : 0;
     return e * 2 + ((cfg.flags & MCV_FLAG_FUSED_ERROR) ? 0 : 1);
+}
+
+bool f_seven(int model, const RansacConfig& cfg) {
+    return model == MCV_MODEL_FUNDAMENTAL && (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0;
+}
+
+// One chunk of hypotheses. 8-point: P.last = this chunk (the winner's fp64 model can come straight from
+// its buffer: f_finalize). 7-point (OpenCV FM_RANSAC): 3 model slots per hypothesis (slot keys like
+// essential), nothing cached. Shared by the RANSAC evaluate below and lmeds_search.
+void f_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s) {
+    const Sampler smp = P.sampler(cfg);
+    if (f_seven(P.model, cfg)) {
+        P.last.clear();
+        launch_f7_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, d_counts, s);
+        return;
+    }
+    launch_f_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, d_counts, s, fast_minimal(cfg));
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 11 : 10, s);
+}
+
+void f_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s) {
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    if (f_seven(P.model, cfg)) {
+        f_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+    } else {
+        ProfScope pg("f_generate", s);
+        f_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+    }
+    P.bb4.ensure(4);
+    launch_abs_bound4(d_pts, false, N, P.bb4.p, nullptr, s);
+    ProfScope ps("f_verify", s);
+    const int nSlots = hypCount * model_slots_cfg(P.model, cfg);
+    launch_f_verify(d_pts, N, P.models.p, d_counts, nSlots, thr2, f_error_kind(cfg), s, P.bb4.p);
 }
 
 int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* F, uint8_t* d_mask,
@@ -109,6 +147,65 @@ int f_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, doub
 }  // namespace mcv
 
 using namespace mcv;
+
+extern "C" MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, const int N, const RansacConfig* cfgp,
+                                            mcvM33d* F, uint8_t* mask) {
+    MCV_GUARD(0, {
+        if (!a || !b || !F || N < 0) fail("cvFindFundamentalMat: null argument or negative N");
+        if (mask) std::memset(mask, 0, (size_t)N);
+        RansacConfig cfg = config_or_default(cfgp);
+        if (!cfgp) cfg.confidence = 0.99;
+        check_flags(cfg, "cvFindFundamentalMat");
+        const bool seven = (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0;
+        if (seven && cfg.method == MCV_METHOD_RANSAC && N != 7 && N < 15)
+            fail("cvFindFundamentalMat: 7-point FM_RANSAC needs N >= 15 (OpenCV uses LMeDS below that: use method 4; "
+                 "N=%d)", N);
+        if (!seven && N < 8) fail("cvFindFundamentalMat: need at least 8 correspondences (N=%d)", N);
+        if (seven && N < 7) fail("cvFindFundamentalMat: need at least 7 correspondences (N=%d)", N);
+        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
+            fail("cvFindFundamentalMat: unsupported method %d", cfg.method);
+        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
+            fail("cvFindFundamentalMat: confidence must be in (0,1)");
+        require_device();
+        Plan& P = thread_plan(MCV_MODEL_FUNDAMENTAL);
+        hipStream_t s = P.own_stream();
+        P.reserve(N, 1);
+        pack_points(P, a, b, N, P.pts.p, s);
+        double Fm[9];
+        int count = 0;
+        if (seven && N == 7) {
+            // findFundamentalMat with npoints == 7: run7Point once (the first of its models), mask all 1
+            launch_f7_direct(P.pts.p, (FOneOut*)P.one.p, s);
+            MCV_HIP(hipGetLastError());
+            FOneOut one;
+            MCV_HIP(hipMemcpyAsync(P.h_one.p, P.one.p, sizeof(FOneOut), hipMemcpyDeviceToHost, s));
+            MCV_HIP(hipStreamSynchronize(s));
+            std::memcpy(&one, P.h_one.p, sizeof(FOneOut));
+            if (one.status <= 0) fail("cvFindFundamentalMat: degenerate 7-point set");
+            for (int k = 0; k < 9; ++k) Fm[k] = one.F[k];
+            if (mask) std::memset(mask, 1, (size_t)N);
+            count = N;
+        } else if (cfg.method == MCV_METHOD_LSQ || (N == 8 && !(seven && cfg.method == MCV_METHOD_LMEDS))) {
+            count = f_fit_all(P, P.pts.p, N, s, Fm);
+            if (count <= 0) fail("cvFindFundamentalMat: degenerate point set");
+            if (mask) std::memset(mask, 1, (size_t)N);
+        } else if (cfg.method == MCV_METHOD_LMEDS) {
+            // 8-point, or 7-point at any N > 7 (the range below 15 is where OpenCV itself runs LMedS)
+            RansacConfig fin = cfg;
+            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+            count = f_finalize(P, P.pts.p, N, fin, best, Fm, P.mask.p, s);
+            if (count < (seven ? 7 : 8)) fail("cvFindFundamentalMat: LMedS model has %d inliers (< %d)", count, seven ? 7 : 8);
+            mask_to_host(P, mask, N, s);
+        } else {
+            const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
+            if (best < 0) fail("cvFindFundamentalMat: RANSAC found no model with >= %d inliers", seven ? 7 : 8);
+            count = f_finalize(P, P.pts.p, N, cfg, best, Fm, P.mask.p, s);
+            mask_to_host(P, mask, N, s);
+        }
+        for (int k = 0; k < 9; ++k) F->M[k] = Fm[k];
+        return count;
+    })
+}
 
 // Host build of one 7-point hypothesis (f7_hypothesis): F27 = up to 3 models, idx7 = the sample.
 extern "C" MCV_API int mcvHostF7(const float* pts4, int N, uint64_t seed, int64_t hyp, double* F27, int* idx7) {

@@ -1,0 +1,431 @@
+// ransac_h_host.cpp — host side of the homography family behind the C-ABI.
+//
+// cvFindHomography (new export, conventions of cvRecoverPose, MiniCVNative.cpp:197-215):
+//   pack V2d -> float4 on device  ->  RANSAC or LMedS of the shared framework (ransac_host.cpp) over
+//   h_evaluate_chunk (generate + the certified / staged / matrix-core / packed sweep; the decisions and
+//   their exactness argument are in it)  ->  h_finalize: mask of the winner, refit on its inliers (runKernel:
+//   GPU reductions + 9x9 Jacobi here), 10 Levenberg-Marquardt iterations (GPU reductions + 8x8 solve here).
+// Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
+// [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
+// Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHMfma).
+#include "minicv_native.h"
+#include "mcv_runtime.h"
+#include "kernels.h"
+#include "linalg.h"
+#include "mcv_common.h"
+#include "hyp_homography.h"
+#include "h_cell_bound.h"
+#include "plan.h"
+#include "lm_solver.h"
+
+#include <cmath>
+#include <cfloat>
+#include <cstring>
+#include <vector>
+#include <algorithm>
+
+namespace mcv {
+
+// mcvTestHStaging: 0 automatic, 1 staging regardless of the call's size, 2 never (tests only)
+static int g_hstage_mode = 0;
+// the plan of the calling thread's last homography evaluate (mcvTestHStaging reads its control block)
+static thread_local Plan* t_hstage_plan = nullptr;
+// mcvTestHCellMode: the per-cell bound before stage 1: 0 automatic, 1 whenever the sweep is staged, 2 never;
+// its two grids
+static int g_hcell_mode = 0;
+static int g_hcell_G = kHCellG, g_hcell_Gs = kHCellGs;
+// mcvTestHMfma: the certified homography sweep's form (kHForm*), and where the calling thread's last
+// such sweep left its stats: a plan's device counters, or the values a sweep outside a plan reported
+static int g_hmfma_mode = kHFormAuto;
+static thread_local Plan* t_hmfma_plan = nullptr;
+static thread_local unsigned long long t_hmfma_last[kHMfmaStats] = {0, 0, 0};
+int h_mfma_form() { return g_hmfma_mode; }
+void h_mfma_set_last(const unsigned long long* stats3) {
+    t_hmfma_plan = nullptr;
+    for (int i = 0; i < kHMfmaStats; ++i) t_hmfma_last[i] = stats3[i];
+}
+// Plan::~Plan: no thread-local of this file may outlive the plan it names
+void h_plan_forget(const Plan* P) {
+    if (t_hstage_plan == P) t_hstage_plan = nullptr;
+    if (t_hmfma_plan == P) t_hmfma_plan = nullptr;
+}
+
+// HomographyEstimatorCallback::runKernel over the masked correspondences (mask == NULL: all).
+bool h_refit(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H) {
+    // the three passes (sums -> centroids -> |deviations| -> scales -> LtL) chained on the device,
+    // one read-back; the host re-derives c4 / s4 with the same divisions and checks them
+    double r[62];
+    reduce_to_host(P, s, 62, r, [&](double* part, double* red) { h_refit_chain(d_pts, N, d_mask, part, red, s); });
+    const double* sums = r;
+    const double count = sums[4];
+    if (count <= 0) return false;
+    double c4[4] = {sums[0] / count, sums[1] / count, sums[2] / count, sums[3] / count};   // cm.x, cm.y, cM.x, cM.y
+    const double* dev = r + 9;
+    for (int k = 0; k < 4; ++k)
+        if (std::fabs(dev[k]) < DBL_EPSILON) return false;
+    double s4[4] = {count / dev[0], count / dev[1], count / dev[2], count / dev[3]};   // sm.x, sm.y, sM.x, sM.y
+    const double* ltl = r + 17;
+    double A[81], w[9], V[81];
+    int o = 0;
+    for (int j = 0; j < 9; ++j)
+        for (int k = j; k < 9; ++k) { A[j * 9 + k] = ltl[o]; A[k * 9 + j] = ltl[o]; ++o; }
+    jacobi_eigen(A, 9, w, V);
+    const double* H0 = V + 8 * 9;   // eigenvector of the smallest eigenvalue
+    const double invHnorm[9] = {1. / s4[0], 0, c4[0], 0, 1. / s4[1], c4[1], 0, 0, 1};
+    const double Hnorm2[9] = {s4[2], 0, -c4[2] * s4[2], 0, s4[3], -c4[3] * s4[3], 0, 0, 1};
+    double T[9], R[9];
+    mat3_mul(invHnorm, H0, T);
+    mat3_mul(T, Hnorm2, R);
+    const double sc = 1. / R[8];
+    for (int k = 0; k < 9; ++k) {
+        H[k] = R[k] * sc;
+        if (!std::isfinite(H[k])) return false;
+    }
+    return true;
+}
+
+// LMSolver::create(HomographyRefineCallback(src, dst), 10)->run(H8) — the classic LMSolverImpl
+// (Marquardt-Nielsen lambda control, eigen-based solve). The O(N) JtJ / Jtr / |r|^2 sums run on
+// the GPU; the 8x8 algebra runs here.
+void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H, int maxIters) {
+    auto compute = [&](const double* h, double* Aout, double* vout) -> double {
+        double buf[45];
+        reduce_to_host(P, s, 45, buf,
+                       [&](double* part, double* red) { h_reduce_lm(d_pts, N, d_mask, h, part, red, s); });
+        return lm_unpack_sums<8>(buf, Aout, vout);
+    };
+    lm_solver_run<8>(compute, H, maxIters);   // H[0..7]; H[8] stays
+}
+
+// One chunk of hypotheses: models, statuses, and P.last = this chunk (the winner's models can come straight
+// from its buffers: h_finalize). Shared by the RANSAC evaluate below and lmeds_search.
+void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, hipStream_t s) {
+    const Sampler smp = P.sampler(cfg);
+    if (!fast_minimal(cfg)) P.hgen.ensure(h_gen_scratch_bytes(hypCount));
+    launch_h_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, P.h64.p, d_counts, s, fast_minimal(cfg),
+                      fast_minimal(cfg) ? nullptr : P.hgen.p);
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
+}
+
+// Generate + verify one chunk of hypotheses. keyOnly: the caller consumes only the chunk's best key
+// (evaluate_chunk's reduction over d_counts), never the per-hypothesis counts.
+void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                      int* d_counts, bool keyOnly, hipStream_t s) {
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    const bool fused = fused_error(cfg);
+    P.pairs.ensure((size_t)(N + 1) / 2 * 8);
+    launch_h_pair(d_pts, N, P.pairs.p, s);
+    if (fused) {
+        launch_bbox(d_pts, N, P.bbox.p, s);
+    } else {
+        P.bb4.ensure(4);
+        launch_abs_bound4(d_pts, false, N, P.bb4.p, nullptr, s);
+    }
+    {
+        ProfScope pg("h_generate", s);
+        h_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+    }
+    // Staging decision. The certified sweep may run in self-pruning stages only where nobody reads
+    // the per-hypothesis counts: the caller gets the key alone. The key stays exact. B is the full
+    // count of one hypothesis with a model before any sampler failure (the candidate), so B <= the
+    // winning count. A slot is dropped only when count-so-far + points-left < B: its full count is
+    // below B, and so is the partial count it keeps (partial <= full). The candidate and every slot
+    // that reaches the winning count are never dropped (the test is inclusive, so ties stay) and end
+    // with full counts. The unchanged reduction (evaluate_chunk) therefore packs, for each dropped slot, a key
+    // below the candidate's whether it sees the partial or the full count (both < B; both map to key
+    // 0 when B itself is below the minimum count), and the true key for every other slot: the same
+    // maximum, the same lowest-index tie-break, the same minimum-count rule. Adaptive replay, LMedS,
+    // callers that pass d_counts, the fused error and the other models keep the single full sweep.
+    // The per-cell bound (h_cell_bound.h) drops slots before stage 1 on the same terms. A slot it drops has
+    // a full count of at most UB (every correspondence of a certified cell is an outlier of the slot's
+    // model under the op-by-op error: DESIGN.md §4), and UB < B. The count it keeps is its stage-0 partial,
+    // at most its full count and so below B. The candidate's own UB is at least its full count B, and a
+    // slot that reaches the winning count has UB >= that count >= B: neither is dropped (inclusive test).
+    // Everything else above stands as written. Engaged where the size rule itself stages the call and
+    // N >= kHCellMinN (kernels.h: the measured rows); forced staging of a small call keeps the plain stages.
+    const bool stageable = !fused && keyOnly;
+    const bool sized = N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals;
+    const bool staged = stageable && g_hstage_mode != 2 && (g_hstage_mode == 1 || sized);
+    P.hstageLast = staged ? 0 : (stageable && g_hstage_mode == 2 ? kHStageForcedOff : kHStageNotApplicable);
+    t_hstage_plan = &P;
+    const bool cellBound = staged && g_hcell_mode != 2 && (g_hcell_mode == 1 || (sized && N >= kHCellMinN));
+    if (staged) {
+        P.hstageCtl.ensure(kHStageCtlInts);
+        P.hstageList.ensure(2 * (size_t)hypCount);
+        if (cellBound) P.hcells.ensure((size_t)h_cell_count(g_hcell_G, g_hcell_Gs) * kHCellInts);
+    }
+    // the certified sweep's matrix-core form where the size rule (or mcvTestHMfma) engages it: its
+    // point records are written here, beside the pairs
+    const int form = g_hmfma_mode;
+    P.hmfmaLast = !fused && h_mfma_engages(N, hypCount, form, staged);
+    t_hmfma_plan = &P;
+    if (P.hmfmaLast) {
+        P.hrec.ensure(h_rec_bytes(N));
+        P.hmfmaStats.ensure(kHMfmaStats);
+        launch_h_rec(d_pts, N, P.hrec.p, s);
+    }
+    const void* d_rec = P.hmfmaLast ? P.hrec.p : nullptr;
+    unsigned long long* d_stats = P.hmfmaLast ? P.hmfmaStats.p : nullptr;
+    ProfScope ps("h_verify", s);
+    if (staged) {
+        launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
+                               P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form,
+                               cellBound ? P.hcells.p : nullptr, g_hcell_G, g_hcell_Gs);
+    } else if (!fused) {
+        // default: OpenCV's op-by-op error, certified division-free sweep
+        launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s, d_rec,
+                                  d_stats, form);
+    } else {
+        launch_h_verify_packed(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bbox.p, s);
+    }
+}
+
+// Winner -> mask (+ refit + LM). Returns inlier count, 0 on failure. Synchronises s.
+int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* H, uint8_t* d_mask,
+               hipStream_t s) {
+    const double t = effective_threshold(cfg);
+    const float thr2 = (float)(t * t);
+    // winner re-solve -> mask from the device-side record -> one read-back of both
+    HOneOut* d_one = (HOneOut*)P.one.p;
+    const Sampler smp = P.sampler(cfg);
+    const bool cached = P.last.covers(hyp, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20);
+    if (cached) {
+        // the winner's fp64 and fp32 models straight from the last chunk's buffers (the same code
+        // produced them) instead of a single-lane eigen re-solve (~0.4 ms); a winner has status 1
+        const int64_t local = hyp - P.last.begin;
+        MCV_HIP(hipMemcpyAsync(d_one->H, P.h64.p + 9 * local, 9 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        MCV_HIP(hipMemcpyAsync(d_one->hf, P.models.p + local * sizeof(HModelF), sizeof(HModelF),
+                               hipMemcpyDeviceToDevice, s));
+        P.h_i.p[1] = 1;
+        MCV_HIP(hipMemcpyAsync(&d_one->status, P.h_i.p + 1, sizeof(int), hipMemcpyHostToDevice, s));
+        queue_chunk_check(P, d_pts, N, s);
+    } else {
+        launch_h_one(d_pts, N, smp, hyp, d_one, s, fast_minimal(cfg));
+    }
+    MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
+    launch_h_mask_one(d_pts, N, d_one, thr2, fused_error(cfg), d_mask, P.count.p, s);
+    MCV_HIP(hipGetLastError());
+    HOneOut one;
+    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(HOneOut), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipStreamSynchronize(s));
+    if (cached && !chunk_fresh(P)) {   // the points changed since the chunk was evaluated: re-solve
+        P.last.clear();
+        return h_finalize(P, d_pts, N, cfg, hyp, H, d_mask, s);
+    }
+    std::memcpy(&one, P.h_one.p, sizeof(HOneOut));
+    if (one.status != 1) fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
+    const int count = P.h_i.p[0];
+    for (int k = 0; k < 9; ++k) H[k] = one.H[k];
+    if (cfg.flags & MCV_FLAG_NO_REFINE) return count;
+    if (N > 4 && count > 0) {
+        double Hr[9];
+        if (h_refit(P, d_pts, N, d_mask, s, Hr))
+            for (int k = 0; k < 9; ++k) H[k] = Hr[k];
+        h_lm_refine(P, d_pts, N, d_mask, s, H, 10);
+    }
+    return count;
+}
+
+int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
+                      int* sampleIdx, bool fast) {
+    if (N < 4) fail("N < 4");
+    HModelF mf;
+    for (int k = 0; k < 9; ++k) model9[k] = 0;
+    for (int k = 0; k < 8; ++k) mf.h[k] = 0;
+    EigWsLocal ws;
+    const int st = h_hypothesis(pts4, N, Sampler{seed, nullptr}, (uint64_t)hyp, model9, &mf, sampleIdx, ws,
+                                fast);
+    for (int k = 0; k < 8; ++k) modelf9[k] = mf.h[k];
+    modelf9[8] = 1.f;
+    return st;
+}
+
+}  // namespace mcv
+
+using namespace mcv;
+
+extern "C" MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, const int N, const RansacConfig* cfgp,
+                                        mcvM33d* H, uint8_t* mask) {
+    MCV_GUARD(0, {
+        if (!src || !dst || !H || N < 0) fail("cvFindHomography: null argument or negative N");
+        if (mask) std::memset(mask, 0, (size_t)N);
+        if (N < 4) fail("cvFindHomography: need at least 4 correspondences (N=%d)", N);
+        const RansacConfig cfg = config_or_default(cfgp);
+        check_flags(cfg, "cvFindHomography");
+        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
+            fail("cvFindHomography: unsupported method %d", cfg.method);
+        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
+            fail("cvFindHomography: confidence must be in (0,1)");
+        require_device();
+        Plan& P = thread_plan(MCV_MODEL_HOMOGRAPHY);
+        hipStream_t s = P.own_stream();
+        P.reserve(N, 1);
+        pack_points(P, src, dst, N, P.pts.p, s);
+        double Hm[9];
+        int count = 0;
+        if (cfg.method == MCV_METHOD_LSQ || N == 4) {
+            if (!h_refit(P, P.pts.p, N, nullptr, s, Hm)) fail("cvFindHomography: degenerate point set");
+            if (N > 4) h_lm_refine(P, P.pts.p, N, nullptr, s, Hm, 10);
+            if (mask) std::memset(mask, 1, (size_t)N);
+            count = N;
+        } else if (cfg.method == MCV_METHOD_LMEDS) {
+            // the winner's mask comes from the existing finalize with LMedS' own threshold
+            RansacConfig fin = cfg;
+            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+            count = h_finalize(P, P.pts.p, N, fin, best, Hm, P.mask.p, s);
+            if (count < 4) fail("cvFindHomography: LMedS model has %d inliers (< 4)", count);
+            mask_to_host(P, mask, N, s);
+        } else {
+            const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
+            if (best < 0) fail("cvFindHomography: RANSAC found no model with >= 4 inliers");
+            count = h_finalize(P, P.pts.p, N, cfg, best, Hm, P.mask.p, s);
+            mask_to_host(P, mask, N, s);
+        }
+        for (int k = 0; k < 9; ++k) H->M[k] = Hm[k];
+        return count;
+    })
+}
+
+// Test hook (declared in minicv_native.h). stats[16]: [0] -1 no homography evaluate on this thread yet,
+// 0 the stages pruned, else why not (kHStage*); [1] B; [2] stages; [3..9] stage boundaries in points;
+// [10..15] slots alive entering each stage. Call after synchronising the evaluate's stream.
+extern "C" MCV_API int mcvTestHStaging(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hstage_mode;
+        if (mode >= 0 && mode <= 2) g_hstage_mode = mode;
+        if (stats) {
+            for (int i = 0; i < 16; ++i) stats[i] = 0;
+            const Plan* P = t_hstage_plan;
+            stats[0] = P ? P->hstageLast : -1;
+            if (P && P->hstageLast == 0) {
+                int ctl[kHStageCtlInts];
+                MCV_HIP(hipMemcpy(ctl, P->hstageCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+                const int N = P->last.N;
+                stats[0] = ctl[kCtlReason];
+                stats[1] = ctl[kCtlB];
+                stats[2] = ctl[kCtlStages];
+                for (int i = 0; i <= kHStageMax; ++i)
+                    stats[3 + i] = std::min<long long>(2LL * ctl[kCtlBound + i], N);
+                for (int i = 0; i < kHStageMax; ++i) stats[10 + i] = ctl[kCtlAlive + i];
+            }
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the per-cell bound's switch, grids and the last evaluate's figures.
+extern "C" MCV_API int mcvTestHCellMode(int mode, int G, int Gs, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hcell_mode;
+        if (mode >= 0 && mode <= 2) g_hcell_mode = mode;
+        if (G >= 1 && G <= kHCellMaxG) g_hcell_G = G;
+        if (Gs >= 1 && Gs <= kHCellMaxGs) g_hcell_Gs = Gs;
+        if (stats) {
+            for (int i = 0; i < 6; ++i) stats[i] = 0;
+            stats[4] = g_hcell_G;
+            stats[5] = g_hcell_Gs;
+            const Plan* P = t_hstage_plan;
+            if (P && P->hstageLast == 0) {
+                int ctl[kHStageCtlInts];
+                MCV_HIP(hipMemcpy(ctl, P->hstageCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+                const int cells = ctl[kCtlCells];
+                stats[0] = cells > 0;
+                stats[2] = ctl[kCtlAlive + 1];
+                stats[3] = cells;
+                if (cells > 0) {
+                    std::vector<int> tab((size_t)cells * kHCellInts);
+                    MCV_HIP(hipMemcpy(tab.data(), P->hcells.p, tab.size() * sizeof(int), hipMemcpyDeviceToHost));
+                    for (int c = 0; c < cells; ++c) stats[1] += tab[(size_t)c * kHCellInts + kHCellInts - 1] > 0;
+                }
+            }
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the cell build and the bound on given data, device or host twin.
+extern "C" MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* cand8, const float* models8,
+                                         int nModels, float thr2, int B, int G, int Gs, int device, int* cellId,
+                                         float* boxes, int* sizes, int* ub, unsigned int* bits, int* alive) {
+    MCV_GUARD(0, {
+        if (!pts4 || !cand8 || !models8 || !cellId || !boxes || !sizes || !ub || !bits || !alive)
+            fail("mcvTestHCellBound: null argument");
+        if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs)
+            fail("mcvTestHCellBound: bad sizes");
+        if (!device) {
+            h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes, sizes, ub, bits, alive);
+            return 1;
+        }
+        require_device();
+        const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
+        DevBuf<float> p, m, cand;
+        DevBuf<double> bb;
+        DevBuf<int> ctl, tab, cnt, list, dub, did;
+        DevBuf<uint32_t> dbits;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        cand.ensure(8);
+        bb.ensure(4);
+        ctl.ensure(kHStageCtlInts);
+        tab.ensure((size_t)cells * kHCellInts);
+        cnt.ensure(nModels);
+        list.ensure(nModels);
+        dub.ensure(nModels);
+        did.ensure(N);
+        dbits.ensure((size_t)nModels * words);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cand.p, cand8, 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(cnt.p, 0, (size_t)nModels * sizeof(int)));
+        MCV_HIP(hipMemset(dbits.p, 0, (size_t)nModels * words * sizeof(uint32_t)));
+        // a control block that names slot 0 of `cand` as the candidate (key: count 1, hypothesis 0)
+        int hctl[kHStageCtlInts] = {0};
+        const uint64_t key = (1ull << 32) | 0xFFFFFFFFull;
+        memcpy(hctl + kCtlKey, &key, sizeof(key));
+        MCV_HIP(hipMemcpy(ctl.p, hctl, sizeof(hctl), hipMemcpyHostToDevice));
+        launch_abs_bound4(p.p, false, N, bb.p, nullptr, 0);
+        launch_h_stage_count(p.p, N, cand.p, 0, thr2, ctl.p, bb.p, tab.p, G, Gs, did.p, 0);
+        MCV_HIP(hipDeviceSynchronize());
+        // B as given (the kernel counted the candidate's inliers into the same word)
+        MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
+        launch_h_cell_bound(m.p, cnt.p, nModels, thr2, bb.p, tab.p, G, Gs, ctl.p, list.p, dub.p, dbits.p, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        std::vector<int> htab((size_t)cells * kHCellInts);
+        MCV_HIP(hipMemcpy(htab.data(), tab.p, htab.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int c = 0; c < cells; ++c) {
+            for (int j = 0; j < 8; ++j) boxes[8 * c + j] = h_cell_dec(htab[(size_t)c * kHCellInts + j]);
+            sizes[c] = htab[(size_t)c * kHCellInts + kHCellInts - 1];
+        }
+        MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(ub, dub.p, (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(bits, dbits.p, (size_t)nModels * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
+        *alive = hctl[kCtlAlive + 1];
+        return 1;
+    })
+}
+
+// Test hook (declared in minicv_native.h). stats[3]: the undecided rows, the overflowed waves and the
+// out-of-domain waves of the
+// calling thread's last certified homography sweep. Call after synchronising the sweep's stream.
+extern "C" MCV_API int mcvTestHMfma(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hmfma_mode;
+        if (mode >= kHFormAuto && mode <= kHFormMixed) g_hmfma_mode = mode;
+        if (stats) {
+            unsigned long long v[kHMfmaStats];
+            for (int i = 0; i < kHMfmaStats; ++i) v[i] = t_hmfma_last[i];
+            const Plan* P = t_hmfma_plan;
+            if (P) {
+                for (int i = 0; i < kHMfmaStats; ++i) v[i] = 0;
+                if (P->hmfmaLast) MCV_HIP(hipMemcpy(v, P->hmfmaStats.p, sizeof(v), hipMemcpyDeviceToHost));
+            }
+            for (int i = 0; i < kHMfmaStats; ++i) stats[i] = (long long)v[i];
+        }
+        return prev;
+    })
+}

@@ -1,0 +1,365 @@
+// ransac_h_stage.hip — the staged homography sweep on gfx950: the certified sweep run in stages that
+// prune themselves (launch_h_verify_staged), for callers that consume only the best key. Here: the
+// control block's init, the candidate's exact count and the cell table (mcv_h_stage_count), the stage
+// planner, the survivor compaction, the per-cell bound (mcv_h_cell_bound, h_cell_bound.h) and its host
+// twin. The stages themselves are the sweeps of ransac_h_sweep.hip / ransac_h_mfma.hip.
+#include <algorithm>
+#include <vector>
+#include "mcv_common.h"
+#include "hyp_homography.h"
+#include "h_cert.h"
+#include "h_cell_bound.h"
+
+namespace mcv {
+
+// ------------------------------------------------------------------------------------------
+// Staged sweep: the small kernels between the stages (launch_h_verify_staged).
+// ------------------------------------------------------------------------------------------
+// cells: the cell slots of the per-cell bound (0: the bound is off and stage 1 takes every slot; else the
+// bound kernel counts the slots it keeps into ctl[kCtlAlive + 1], from 0).
+__global__ void mcv_h_stage_init(int* __restrict__ ctl, int pa, int hypCount, int cells) {
+    const int i = threadIdx.x;
+    if (i >= kHStageCtlInts) return;
+    int v = 0;
+    if (i == kCtlBound + 1) v = pa;
+    if (i == kCtlAlive || (i == kCtlAlive + 1 && cells == 0)) v = hypCount;
+    if (i == kCtlCells) v = cells;
+    ctl[i] = v;
+}
+
+// Empty cell table: min slots at INT_MAX, max slots at INT_MIN (ordered-integer encoding), size 0.
+__global__ void mcv_h_cell_init(int* __restrict__ cells, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int f = i % kHCellInts;
+    cells[i] = f == kHCellInts - 1 ? 0 : ((f & 1) ? INT32_MIN : INT32_MAX);
+}
+
+// The cell table of the per-cell bound (h_cell_bound.h), filled by mcv_h_stage_count.
+struct HCellArgs {
+    int* cells;          // kHCellInts ints per cell, set up by mcv_h_cell_init (nullptr: no table)
+    const double* bb;    // the point set's extents (launch_abs_bound4)
+    int G, Gs;
+    int lds;             // 1: each block gathers a private table in LDS (dynamic shared memory) and flushes it
+    int* cellOut;        // test hook: every point's cell (nullptr in the sweep)
+};
+
+__device__ __forceinline__ void h_cell_add(int* t, const float4& q) {
+    const int ex = h_cell_enc(q.x), ey = h_cell_enc(q.y), emx = h_cell_enc(q.z), emy = h_cell_enc(q.w);
+    atomicMin(t + 0, ex);
+    atomicMax(t + 1, ex);
+    atomicMin(t + 2, ey);
+    atomicMax(t + 3, ey);
+    atomicMin(t + 4, emx);
+    atomicMax(t + 5, emx);
+    atomicMin(t + 6, emy);
+    atomicMax(t + 7, emy);
+    atomicAdd(t + 8, 1);
+}
+
+// The candidate (best partial count of stage 0) counted over all N correspondences with the exact
+// op-by-op error: ctl[kCtlB] (zeroed by mcv_h_stage_init). No candidate (key 0): B stays 0.
+// With a cell table: every correspondence also goes to its cell (the candidate's inliers to the 2-D
+// grid, the rest to the 4-D grid): the cell's min / max of x, y, x', y' and its size, all
+// order-independent, so the table is deterministic.
+__global__ __launch_bounds__(1024) void mcv_h_stage_count(const float4* __restrict__ pts, int N,
+                                                          const HModelF* __restrict__ models, int64_t hypBegin,
+                                                          float thr2, int* __restrict__ ctl, HCellArgs ca) {
+    extern __shared__ int tab[];
+    const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
+    if (key == 0) return;
+    const int64_t hyp = (int64_t)(0xFFFFFFFFull - (key & 0xFFFFFFFFull));
+    const HModelF m = models[hyp - hypBegin];
+    const int nt = ca.cells ? h_cell_count(ca.G, ca.Gs) * kHCellInts : 0;
+    double b4[4] = {0, 0, 0, 0};
+    if (ca.cells) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b4[j] = ca.bb[j];
+    }
+    if (ca.lds) {
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+            const int f = i % kHCellInts;
+            tab[i] = f == kHCellInts - 1 ? 0 : ((f & 1) ? INT32_MIN : INT32_MAX);
+        }
+        __syncthreads();
+    }
+    const int stride = gridDim.x * blockDim.x;
+    for (int base = blockIdx.x * blockDim.x; base < N; base += stride) {   // block-uniform trip count
+        const int i = base + threadIdx.x;
+        bool in = false;
+        if (i < N) {
+            const float4 q = pts[i];
+            in = h_error(m.h, q.x, q.y, q.z, q.w) <= thr2;
+            if (ca.cells) {
+                const int c = h_cell_index(q.x, q.y, q.z, q.w, in, b4, ca.G, ca.Gs);   // always in [0, cells)
+                if (ca.cellOut) ca.cellOut[i] = c;
+                h_cell_add((ca.lds ? tab : ca.cells) + c * kHCellInts, q);
+            }
+        }
+        const uint64_t b = __ballot(in);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(ctl + kCtlB, (int)__popcll(b));
+    }
+    if (ca.lds) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+            const int f = i % kHCellInts;
+            if (tab[i - f + kHCellInts - 1] == 0) continue;   // the block saw no point of this cell
+            if (f == kHCellInts - 1) atomicAdd(ca.cells + i, tab[i]);
+            else if (f & 1) atomicMax(ca.cells + i, tab[i]);
+            else atomicMin(ca.cells + i, tab[i]);
+        }
+    }
+}
+
+// One thread: the stage boundaries from B. The first boundary is the first point count at which a
+// slot can fall below the bound (N - B) plus the slack, rounded up to a trip; the later stages split
+// the rest evenly. Pruning switches itself off (stage 1 runs every slot to the end) without a
+// candidate, with a sampler failure in the chunk (the host then reads every count) and when the first
+// boundary lies beyond latest/256 of the pairs.
+__global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int later, int slackPts, int latest256) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int nPairs = (N + 1) / 2;
+    const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
+    const int64_t fail = *(const int64_t*)(ctl + kCtlKey + 2);
+    const int pa = ctl[kCtlBound + 1];
+    int reason = 0;
+    int p1 = nPairs;
+    if (key == 0) reason = kHStageNoCandidate;
+    else if (fail != INT64_MAX) reason = kHStageSamplerFailure;
+    else {
+        const int64_t pts = (int64_t)N - ctl[kCtlB] + slackPts;
+        const int64_t pr = ((pts + 1) / 2 + trip - 1) / trip * trip;
+        p1 = pr < pa ? pa : (pr > nPairs ? nPairs : (int)pr);
+        if ((int64_t)p1 * 256 > (int64_t)nPairs * latest256) reason = kHStageLate;
+    }
+    if (reason) p1 = nPairs;
+    ctl[kCtlReason] = reason;
+    ctl[kCtlStages] = 2 + later;
+    ctl[kCtlBound + 2] = p1;
+    const int trips = (nPairs - p1) / trip;   // whole trips left after the first boundary
+    for (int s = 1; s <= later; ++s) {
+        int b = s == later ? nPairs : p1 + (int)((int64_t)trips * s / later) * trip;
+        ctl[kCtlBound + 2 + s] = b;
+    }
+}
+
+// Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
+// whose count can still reach B, count + (N - processed) >= B. Inclusive, so ties survive; a status
+// (count < 0: no model, no sample, the exact-recount mark) never enters a list. Any order: ballot
+// and one atomic per wave.
+__global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict__ counts, int hypCount, int N,
+                                                           int* __restrict__ ctl, int stage,
+                                                           const int* __restrict__ src, int* __restrict__ dst) {
+    if (ctl[kCtlReason] != 0) return;
+    const int n = src ? ctl[kCtlAlive + stage - 1] : hypCount;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int done2 = 2 * ctl[kCtlBound + stage];
+    const int left = N - (done2 < N ? done2 : N);
+    bool keep = false;
+    int slot = 0;
+    if (i < n) {
+        slot = src ? src[i] : i;
+        const int c = counts[slot];
+        keep = c >= 0 && c + left >= ctl[kCtlB];
+    }
+    const uint64_t b = __ballot(keep);
+    if (b == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(ctl + kCtlAlive + stage, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
+}
+
+// The per-cell bound (h_cell_bound.h), lane = slot: UB = the sizes of the cells the model does not certify
+// as all-outlier, an upper bound of the slot's full count. Slots with a model and UB >= B (inclusive: ties
+// survive) enter the survivor list of stage 1 as mcv_h_stage_compact writes its lists (ballot, one
+// atomic per wave, any order); their number goes to ctl[kCtlAlive + 1]. A status (count < 0: no model, no
+// sample, stage 0's exact-recount mark) never enters the list. Where pruning is off on the device
+// (ctl[kCtlReason] != 0) every slot with a model is kept. The cells are wave-uniform (scalar loads); all
+// stores are per lane. ubOut / bitsOut (test hook): every slot's UB and its certified-cell bitmap
+// (bitWords zeroed words per slot).
+__global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restrict__ models,
+                                                        const int* __restrict__ counts, int hypCount, float thr2,
+                                                        double kappa, const double* __restrict__ bb,
+                                                        const int* __restrict__ cells, int nCells, int* ctl,
+                                                        int* __restrict__ dst, int* __restrict__ ubOut,
+                                                        uint32_t* __restrict__ bitsOut, int bitWords) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool have = i < hypCount && counts[i] >= 0;
+    bool keep = have;
+    if (ctl[kCtlReason] == 0 && __ballot(have) != 0) {
+        const HModelF m = models[i < hypCount ? i : hypCount - 1];
+        double b4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b4[j] = bb[j];
+        const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
+        int ub = 0;
+        for (int c = 0; c < nCells; ++c) {
+            const int* e = cells + c * kHCellInts;
+            const int size = e[kHCellInts - 1];
+            if (size == 0) continue;
+            float box[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
+            const bool cert = h_cell_certified(m.h, cm, box);
+            ub += cert ? 0 : size;
+            if (bitsOut && cert && i < hypCount) bitsOut[(size_t)i * bitWords + (c >> 5)] |= 1u << (c & 31);
+        }
+        if (ubOut && i < hypCount) ubOut[i] = ub;
+        keep = have && ub >= ctl[kCtlB];
+    }
+    const uint64_t b = __ballot(keep);
+    if (b == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(ctl + kCtlAlive + 1, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = i;
+}
+
+// The certified sweep in stages that prune themselves (the caller consumes only the best key): stage 0
+// sweeps a prefix, its best partial count names a candidate, the candidate's full count B bounds the
+// winning count from below, and from the first boundary on only the slots that can still reach B go on
+// (kernels above; the exactness argument is at the caller's staging decision). Everything is enqueued
+// on s: the boundaries and the live counts stay on the device, the grids are sized for every slot and
+// the waves beyond the live count exit at once.
+// Cell table + candidate count. With d_cells: blocks of 1024 threads, at most 64 of them, each gathering a
+// private table in LDS where it fits (up to kHCellLdsCells cells), so the global atomics are one flush of the
+// non-empty cells per block; larger grids add straight to the global table.
+static constexpr int kHCellLdsCells = 1024;   // 36 KB of LDS
+void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int64_t hypBegin, float thr2, int* d_ctl,
+                          const double* d_bb, int* d_cells, int G, int Gs, int* d_cellOut, hipStream_t s) {
+    if (!d_cells) {
+        hipLaunchKernelGGL(mcv_h_stage_count, dim3((N + 255) / 256), dim3(256), 0, s, (const float4*)d_pts4, N,
+                           (const HModelF*)d_models, hypBegin, thr2, d_ctl, HCellArgs{nullptr, nullptr, 0, 0, 0, nullptr});
+        return;
+    }
+    const int nCells = h_cell_count(G, Gs), nt = nCells * kHCellInts;
+    hipLaunchKernelGGL(mcv_h_cell_init, dim3((nt + 255) / 256), dim3(256), 0, s, d_cells, nt);
+    const int lds = nCells <= kHCellLdsCells;
+    const int blocks = std::min(lds ? 64 : 256, (N + 1023) / 1024);
+    hipLaunchKernelGGL(mcv_h_stage_count, dim3(blocks), dim3(1024), lds ? nt * sizeof(int) : 0, s,
+                       (const float4*)d_pts4, N, (const HModelF*)d_models, hypBegin, thr2, d_ctl,
+                       HCellArgs{d_cells, d_bb, G, Gs, lds, d_cellOut});
+}
+
+void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
+                         const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
+                         hipStream_t s) {
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    const int nCells = h_cell_count(G, Gs);
+    hipLaunchKernelGGL(mcv_h_cell_bound, dim3((hypCount + 255) / 256), dim3(256), 0, s, (const HModelF*)d_models,
+                       d_counts, hypCount, thr2, h_cell_kappa(slopes.a.x, slopes.a.y), d_bb, d_cells, nCells, d_ctl,
+                       d_list, d_ub, d_bits, (nCells + 31) / 32);
+}
+
+// Host twin of the cell build and the bound (mcvTestHCellBound): the same header, the same arithmetic.
+void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
+                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive) {
+    const int nCells = h_cell_count(G, Gs), words = (nCells + 31) / 32;
+    double bb[4] = {0, 0, 0, 0};
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double v = pts4[4 * i + j];
+            bb[j] = v == v ? fmax(bb[j], fabs(v)) : __builtin_inf();
+        }
+    std::vector<int> tab((size_t)nCells * kHCellInts);
+    for (size_t i = 0; i < tab.size(); ++i) {
+        const int f = (int)(i % kHCellInts);
+        tab[i] = f == kHCellInts - 1 ? 0 : ((f & 1) ? INT32_MIN : INT32_MAX);
+    }
+    for (int i = 0; i < N; ++i) {
+        const float* q = pts4 + 4 * i;
+        const bool in = h_error(cand8, q[0], q[1], q[2], q[3]) <= thr2;
+        const int c = h_cell_index(q[0], q[1], q[2], q[3], in, bb, G, Gs);
+        if (cellId) cellId[i] = c;
+        int* t = tab.data() + (size_t)c * kHCellInts;
+        for (int j = 0; j < 4; ++j) {
+            const int e = h_cell_enc(q[j]);
+            t[2 * j] = std::min(t[2 * j], e);
+            t[2 * j + 1] = std::max(t[2 * j + 1], e);
+        }
+        ++t[8];
+    }
+    for (int c = 0; c < nCells; ++c) {
+        for (int j = 0; j < 8; ++j) boxes[8 * c + j] = h_cell_dec(tab[(size_t)c * kHCellInts + j]);
+        sizes[c] = tab[(size_t)c * kHCellInts + 8];
+    }
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    const double kappa = h_cell_kappa(slopes.a.x, slopes.a.y);
+    int kept = 0;
+    for (int k = 0; k < nModels; ++k) {
+        const float* h = models8 + 8 * k;
+        const HCellModel cm = h_cell_model(h, bb, thr2, kappa, kCertT, kCertSlop);
+        int u = 0;
+        for (int w = 0; w < words; ++w) bits[(size_t)k * words + w] = 0;
+        for (int c = 0; c < nCells; ++c) {
+            if (sizes[c] == 0) continue;
+            const bool cert = h_cell_certified(h, cm, boxes + 8 * c);
+            u += cert ? 0 : sizes[c];
+            if (cert) bits[(size_t)k * words + (c >> 5)] |= 1u << (c & 31);
+        }
+        ub[k] = u;
+        kept += u >= B;
+    }
+    if (alive) *alive = kept;
+}
+
+// d_ctl: kHStageCtlInts ints; d_list: 2 x hypCount ints (the survivor lists, ping-pong).
+// d_cells (h_cell_count(G, Gs) x kHCellInts ints; nullptr: no per-cell bound): the cell table is built beside
+// the candidate's count, mcv_h_cell_bound drops the slots whose upper bound is below B before stage 1, and
+// stage 1 runs through its list.
+void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
+                            int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
+                            uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec,
+                            unsigned long long* d_stats, int form, int* d_cells, int G, int Gs) {
+    constexpr int TRIP = 64 * kCertNP;
+    if (d_stats) (void)hipMemsetAsync(d_stats, 0, kHMfmaStats * sizeof(unsigned long long), s);
+    const bool mfma = d_rec && d_stats && h_mfma_engages(N, hypCount, form, true);
+    // stages that run a list keep the VALU kernel; kHFormMfma is the A/B partner
+    const bool mfmaList = mfma && form == kHFormMfma;
+    const int nFull = N / 2 / TRIP * TRIP;
+    // stage 0: ~N / kHStagePrefixDiv points (N / kHCellPrefixDiv with the per-cell bound: stage 0 is then the
+    // one full-width stage left), a whole number of trips (at least one where N has one)
+    int pa = (N / (d_cells ? kHCellPrefixDiv : kHStagePrefixDiv) / 2 + TRIP / 2) / TRIP * TRIP;
+    if (pa < TRIP) pa = TRIP;
+    if (pa > nFull) pa = nFull;
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    auto stage = [&](int st, const int* list) {
+        const HStageArgs sa{d_ctl, list, st};
+        if (list ? mfmaList : mfma)
+            launch_h_mfma_sweep(d_pts4, d_rec, N, d_models, d_counts, hypCount, thr2, slopes, d_bb, sa, d_stats, s);
+        else
+            launch_h_cert_sweep(d_pairs, N, d_models, d_counts, hypCount, thr2, slopes, d_bb, sa, s);
+    };
+    auto recount = [&]() {   // the slots marked kStatusRedo, over all N, by the exact scalar sweep
+        launch_h_recount(d_pts4, N, d_models, d_counts, hypCount, thr2, false, nullptr, s);
+    };
+    int* lists[2] = {d_list, d_list + hypCount};
+    hipLaunchKernelGGL(mcv_h_stage_init, dim3(1), dim3(64), 0, s, d_ctl, pa, hypCount,
+                       d_cells ? h_cell_count(G, Gs) : 0);
+    stage(0, nullptr);
+    // candidate: the best partial count before any sampler failure (minimum count 0: any model will do)
+    launch_best(d_counts, hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
+    launch_h_stage_count(d_pts4, N, d_models, hypBegin, thr2, d_ctl, d_bb, d_cells, G, Gs, nullptr, s);
+    hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, TRIP, kHStageLater,
+                       N / kHStageSlackDiv, kHStageLatest256);
+    // the list of stage 1 is lists[1 & 1], the source of the first count-based compaction
+    if (d_cells)
+        launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
+                            s);
+    stage(1, d_cells ? lists[1] : nullptr);
+    for (int st = 2; st < 2 + kHStageLater; ++st) {
+        // the first compaction sees the recount marks (count < 0) before the recount overwrites them
+        hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_counts, hypCount, N,
+                           d_ctl, st, st == 2 && !d_cells ? (const int*)nullptr : (const int*)lists[(st - 1) & 1],
+                           lists[st & 1]);
+        if (st == 2) recount();
+        stage(st, lists[st & 1]);
+    }
+    // a wave of a later stage that left the fast path (event overflow in the tail) marked its slots too
+    recount();
+}
+
+}  // namespace mcv

@@ -19,7 +19,7 @@ from minicv_amd import opencv, synthetic as S
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-# the certificate's constant for one matrix-core dot, in u * sum |terms| (kMfmaDotC, ransac_h.hip), and its
+# the certificate's constant for one matrix-core dot, in u * sum |terms| (kMfmaDotC, h_cert.h), and its
 # absolute term for pieces and sums the matrix core may flush below 2^-126
 DOT_C = 8.5
 THR2 = float(np.float32(5e-3 ** 2))
