@@ -168,4 +168,14 @@ MCV_HD void a_lm_terms(const double* h, double x, double y, double X, double Y, 
 
 MCV_HD constexpr int a_lm_values(int lx) { return lx * (lx + 1) / 2 + lx + 1; }   // 28 (affine), 15 (similarity)
 
+// 2x3 matrix <-> the refine's parameters (similarity: a, b, tx, ty of [a -b tx; b a ty]); host side.
+inline void a_to_params(int lx, const double* A, double* h) {
+    if (lx == 6) for (int i = 0; i < 6; ++i) h[i] = A[i];
+    else { h[0] = A[0]; h[1] = A[3]; h[2] = A[2]; h[3] = A[5]; }
+}
+inline void a_from_params(int lx, const double* h, double* A) {
+    if (lx == 6) for (int i = 0; i < 6; ++i) A[i] = h[i];
+    else { A[0] = h[0]; A[1] = -h[1]; A[2] = h[2]; A[3] = h[1]; A[4] = h[0]; A[5] = h[3]; }
+}
+
 }  // namespace mcv

@@ -107,6 +107,16 @@ void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount
 void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
                  int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);
+// The refit record: what HomographyEstimatorCallback::runKernel's three passes, chained on the device, leave
+// per problem (h_refit_chain: one record; launch_batch_refit_chain: one per problem) and what the host half
+// (h_refit_from_record, plan.h) reads.
+static const int kRefitSums = 0;     // 5: sum dst.x, dst.y, src.x, src.y, count
+static const int kRefitCount = 4;    //    the count among them
+static const int kRefitC4 = 5;       // 4: centroids cm.x, cm.y, cM.x, cM.y = sums / count
+static const int kRefitDev = 9;      // 4: sum |dst - cm|, |src - cM|
+static const int kRefitS4 = 13;      // 4: scales sm.x, sm.y, sM.x, sM.y = count / deviation sums
+static const int kRefitLtL = 17;     // 45: upper triangle of LtL, row-major
+static const int kRefitDoubles = 62;
 void h_refit_chain(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_red, hipStream_t s);
 // d_out = {JtJ upper triangle (36), Jtr (8), |r|^2} of HomographyRefineCallback at h8
 void h_reduce_lm(const float* d_pts4, int N, const uint8_t* d_mask, const double* h8, double* d_part, double* d_out,
@@ -290,7 +300,6 @@ void launch_error_rank(int model, const float* d_pts4, int N, const void* d_mode
 // ---- batched 2-D model RANSAC (ransac_batch.hip): B problems of one family per launch. All problems'
 // float4 points sit in one segmented buffer; the tables below name each problem's share of it.
 static const int kBatchTile = 1024;          // points staged in LDS per trip of the batched sweep (16 KiB)
-static const int kBatchRefitDoubles = 62;    // h_refit_chain's record per problem (sums .. LtL)
 struct BatchDesc {      // one problem of a hypothesis round
     int ptOff, N;            // its points: [ptOff, ptOff + N) of the segmented buffer
     int hypBegin, hypCount;  // its hypotheses of this round
@@ -325,7 +334,7 @@ int batch_reduce_blocks(int maxN);   // partial rows per problem (x 45 doubles) 
 // d_out 45 doubles per problem out (the single call's order). Both return the kernels launched.
 int launch_batch_reduce_lm(int lx, const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed,
                            int maxN, const double* d_par, double* d_part, double* d_out, hipStream_t s);
-// h_refit_chain for every problem: d_rec = kBatchRefitDoubles per problem, laid out as h_refit_chain's red
+// h_refit_chain for every problem: d_rec = one refit record (kRefitDoubles) per problem
 int launch_batch_refit_chain(const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed, int maxN,
                              double* d_part, double* d_rec, hipStream_t s);
 

@@ -152,6 +152,15 @@ struct ProfScope {
         }
     }
 };
+// n correspondences a[i] -> b[i] as float4 {a.X, a.Y, b.X, b.Y} (OpenCV: points.convertTo(CV_32F))
+inline void pack_float4(const mcvV2d* a, const mcvV2d* b, int n, float* dst) {
+    for (int i = 0; i < n; ++i) {
+        dst[4 * (size_t)i + 0] = (float)a[i].X;
+        dst[4 * (size_t)i + 1] = (float)a[i].Y;
+        dst[4 * (size_t)i + 2] = (float)b[i].X;
+        dst[4 * (size_t)i + 3] = (float)b[i].Y;
+    }
+}
 void pack_points(Plan& P, const mcvV2d* a, const mcvV2d* b, int N, float* d_dst, hipStream_t s);
 size_t point_bytes(int model, int N);   // device point buffer: 16 N (H / F float4), 32 N (E double4, PnP)
 // Evaluate side: P.last = this chunk, and the fingerprint of its points -> P.fp[0] (async).
@@ -206,6 +215,8 @@ int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
                hipStream_t s);
 int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
                       int* sampleIdx, bool fast);
+// runKernel's host half on one refit record (kernels.h kRefit*) -> H; false: degenerate, H is not a model
+bool h_refit_from_record(const double* r, double* H);
 void h_plan_forget(const Plan* P);   // ~Plan: drops the test hooks' references to the plan
 
 // fundamental-matrix family (ransac_f.hip / ransac_f_host.cpp)

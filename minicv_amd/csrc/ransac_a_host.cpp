@@ -41,29 +41,17 @@ void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     launch_a_verify(P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, fused_error(cfg), s);
 }
 
-// 2x3 matrix <-> refine parameters (similarity: a, b, tx, ty of [a -b tx; b a ty]).
-static void a_to_params(int lx, const double* A, double* h) {
-    if (lx == 6) for (int i = 0; i < 6; ++i) h[i] = A[i];
-    else { h[0] = A[0]; h[1] = A[3]; h[2] = A[2]; h[3] = A[5]; }
-}
-static void a_from_params(int lx, const double* h, double* A) {
-    if (lx == 6) for (int i = 0; i < 6; ++i) A[i] = h[i];
-    else { A[0] = h[0]; A[1] = -h[1]; A[2] = h[2]; A[3] = h[1]; A[4] = h[0]; A[5] = h[3]; }
-}
-
 // LMSolver::create(Affine2DRefineCallback / AffinePartial2DRefineCallback, 10)->run: the sums over the
 // inliers on the GPU (reduce.h's block order), the solver on the host (lm_solver.h).
 template <int LX>
 static void a_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* A) {
     double h[LX];
     a_to_params(LX, A, h);
-    auto compute = [&](const double* x, double* Aout, double* vout) -> double {
-        double buf[a_lm_values(LX)];
+    auto sums = [&](const double* x, double* buf) {
         reduce_to_host(P, s, a_lm_values(LX), buf,
                        [&](double* part, double* red) { a_reduce_lm(LX, d_pts, N, d_mask, x, part, red, s); });
-        return lm_unpack_sums<LX>(buf, Aout, vout);
     };
-    lm_solver_run<LX>(compute, h, 10);
+    lm_solver_run<LX>(sums, h, 10);
     a_from_params(LX, h, A);
 }
 
@@ -74,17 +62,15 @@ static int a_lm_refine_host(const float* pts4, int N, const uint8_t* mask, doubl
     a_to_params(LX, A, h);
     int used = 0;
     for (int i = 0; i < N; ++i) used += (!mask || mask[i]) ? 1 : 0;
-    auto compute = [&](const double* x, double* Aout, double* vout) -> double {
-        double buf[a_lm_values(LX)];
+    auto sums = [&](const double* x, double* buf) {
         for (int k = 0; k < a_lm_values(LX); ++k) buf[k] = 0;
         for (int i = 0; i < N; ++i) {
             if (mask && !mask[i]) continue;
             const float* q = pts4 + 4 * (size_t)i;
             a_lm_terms<LX>(x, (double)q[0], (double)q[1], (double)q[2], (double)q[3], buf);
         }
-        return lm_unpack_sums<LX>(buf, Aout, vout);
     };
-    lm_solver_run<LX>(compute, h, 10);
+    lm_solver_run<LX>(sums, h, 10);
     a_from_params(LX, h, A);
     return used;
 }

@@ -22,12 +22,14 @@
 //   mcv_batch_reduce_*         reduce.h's two-stage fixed-order reduction over many problems at once:
 //                              problem r's partials are those of reduce_blocks(N_r) blocks of 256 threads
 //                              strided by its own grid, reduced by block_sum and summed in block order by
-//                              reduce_final's pattern — the single call's sums bit for bit.
+//                              reduce_final's pattern, over the per-point terms the single call's functors
+//                              use (a_lm_terms, h_refine_terms.h) — the single call's sums bit for bit.
 #include <algorithm>
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "hyp_fundamental.h"
 #include "hyp_affine.h"
+#include "h_refine_terms.h"
 #include "jacobi_eig.h"
 #include "reduce.h"
 #include "kernels.h"
@@ -246,13 +248,6 @@ __global__ __launch_bounds__(256) void mcv_batch_mask(const float4* __restrict__
 // Batched fixed-order reductions. Grid of the pass: blocksPer x nRed blocks of kReduceThreads
 // (blocksPer = reduce_blocks(largest N)); the blocks past a problem's own reduce_blocks(N_r) leave.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reduce_blocks_dev(int n) {
-    int b = (n + kReduceThreads - 1) / kReduceThreads;
-    if (b < 1) b = 1;
-    if (b > kReduceMaxBlocks) b = kReduceMaxBlocks;
-    return b;
-}
-
 // Op: init(pts, mask, par) once per thread, then operator()(i, acc) as reduce.h's functors.
 template <int V, class Op>
 __global__ __launch_bounds__(kReduceThreads) void mcv_batch_reduce_pass(const float4* __restrict__ pts,
@@ -262,7 +257,7 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_batch_reduce_pass(const fl
                                                                         int parStride, double* __restrict__ partials) {
     const int r = blockIdx.x / blocksPer, b = blockIdx.x % blocksPer;
     const BatchRed D = red[r];
-    const int nb = reduce_blocks_dev(D.N);
+    const int nb = reduce_blocks(D.N);
     if (b >= nb) return;   // uniform over the workgroup
     Op op;
     op.init(pts + D.ptOff, mask + D.ptOff, par + (int64_t)r * parStride);
@@ -279,7 +274,7 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_batch_reduce_final(const B
                                                                          const double* __restrict__ partials,
                                                                          double* __restrict__ out, int outStride) {
     const int r = blockIdx.x;
-    const int nb = reduce_blocks_dev(red[r].N);
+    const int nb = reduce_blocks(red[r].N);
     const double* part = partials + (size_t)r * blocksPer * V;
     double acc[V];
 #pragma unroll
@@ -291,8 +286,9 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_batch_reduce_final(const B
     block_sum<V>(acc, out + (size_t)r * outStride);
 }
 
-// The functors of the single call's refine passes (ransac_a.hip OpALM; ransac_h_refine.hip OpSums, OpAbsDevD,
-// OpLtLD, OpLM), with the per-problem constants read from the problem's parameter row.
+// The functors of the single call's refine passes (ransac_a.hip OpALM; ransac_h_refine.hip OpSums, OpAbsDev,
+// OpLtL, OpLM) over the same per-point terms (a_lm_terms, h_refine_terms.h): here the constants come from the
+// problem's parameter row and the mask is always present.
 template <int LX>
 struct BOpALM {
     const float4* pts; const uint8_t* mask; double h[LX];
@@ -313,38 +309,29 @@ struct BOpSums {   // 5: sum dst.x, dst.y, src.x, src.y, count
     __device__ void operator()(int i, double (&a)[5]) const {
         if (!mask[i]) return;
         const float4 q = pts[i];
-        a[0] += (double)q.z; a[1] += (double)q.w; a[2] += (double)q.x; a[3] += (double)q.y; a[4] += 1.0;
+        h_sums_terms((double)q.x, (double)q.y, (double)q.z, (double)q.w, a);
     }
 };
-struct BOpAbsDev {  // 4: sum |dst - cm|, |src - cM|; par = the problem's refit record (kBatchRefitDoubles)
+struct BOpAbsDev {  // 4: sum |dst - cm|, |src - cM|; par = the problem's refit record
     const float4* pts; const uint8_t* mask; const double* c4;
-    __device__ void init(const float4* p, const uint8_t* m, const double* par) { pts = p; mask = m; c4 = par + 5; }
+    __device__ void init(const float4* p, const uint8_t* m, const double* par) {
+        pts = p; mask = m; c4 = par + kRefitC4;
+    }
     __device__ void operator()(int i, double (&a)[4]) const {
         if (!mask[i]) return;
         const float4 q = pts[i];
-        a[0] += fabs((double)q.z - c4[0]); a[1] += fabs((double)q.w - c4[1]);
-        a[2] += fabs((double)q.x - c4[2]); a[3] += fabs((double)q.y - c4[3]);
+        h_absdev_terms(c4, (double)q.x, (double)q.y, (double)q.z, (double)q.w, a);
     }
 };
-struct BOpLtL {     // 45: upper triangle of LtL, row-major
+struct BOpLtL {     // 45: upper triangle of LtL; par = the problem's refit record
     const float4* pts; const uint8_t* mask; const double* c4; const double* s4;
     __device__ void init(const float4* p, const uint8_t* m, const double* par) {
-        pts = p; mask = m; c4 = par + 5; s4 = par + 13;
+        pts = p; mask = m; c4 = par + kRefitC4; s4 = par + kRefitS4;
     }
     __device__ void operator()(int i, double (&a)[45]) const {
         if (!mask[i]) return;
-        const double cmx = c4[0], cmy = c4[1], cMx = c4[2], cMy = c4[3];
-        const double smx = s4[0], smy = s4[1], sMx = s4[2], sMy = s4[3];
         const float4 q = pts[i];
-        const double x = ((double)q.z - cmx) * smx, y = ((double)q.w - cmy) * smy;
-        const double X = ((double)q.x - cMx) * sMx, Y = ((double)q.y - cMy) * sMy;
-        const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
-        const double Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
-        int o = 0;
-#pragma unroll
-        for (int j = 0; j < 9; ++j)
-#pragma unroll
-            for (int k = j; k < 9; ++k) a[o++] += Lx[j] * Lx[k] + Ly[j] * Ly[k];
+        h_ltl_terms(c4, s4, (double)q.x, (double)q.y, (double)q.z, (double)q.w, a);
     }
 };
 struct BOpHLM {     // 45: JtJ upper triangle (36), Jtr (8), |r|^2 (1)
@@ -357,32 +344,15 @@ struct BOpHLM {     // 45: JtJ upper triangle (36), Jtr (8), |r|^2 (1)
     __device__ void operator()(int i, double (&a)[45]) const {
         if (!mask[i]) return;
         const float4 q = pts[i];
-        const double Mx = q.x, My = q.y;
-        double ww = h[6] * Mx + h[7] * My + 1.;
-        ww = fabs(ww) > kDblEpsilon ? 1. / ww : 0;
-        const double xi = (h[0] * Mx + h[1] * My + h[2]) * ww;
-        const double yi = (h[3] * Mx + h[4] * My + h[5]) * ww;
-        const double rx = xi - (double)q.z, ry = yi - (double)q.w;
-        const double Jx[8] = {Mx * ww, My * ww, ww, 0, 0, 0, -Mx * ww * xi, -My * ww * xi};
-        const double Jy[8] = {0, 0, 0, Mx * ww, My * ww, ww, -Mx * ww * yi, -My * ww * yi};
-        int o = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int k = j; k < 8; ++k) a[o++] += Jx[j] * Jx[k] + Jy[j] * Jy[k];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[36 + j] += Jx[j] * rx + Jy[j] * ry;
-        a[44] += rx * rx + ry * ry;
+        h_lm_terms(h, (double)q.x, (double)q.y, (double)q.z, (double)q.w, a);
     }
 };
 
-// mcv_refit_stats (ransac_h_refine.hip) for every problem's record: the same IEEE divisions.
+// The step between the chained passes (h_refine_terms.h) on every problem's record: 4 lanes per record.
 __global__ void mcv_batch_refit_stats(double* __restrict__ rec, int nRed, int stage) {
     const int r = blockIdx.x * 64 + (threadIdx.x >> 2), k = threadIdx.x & 3;
     if (r >= nRed) return;
-    double* red = rec + (size_t)r * kBatchRefitDoubles;
-    if (stage == 0) red[5 + k] = red[k] / red[4];
-    else red[13 + k] = red[4] / red[9 + k];
+    refit_stats_step(rec + (size_t)r * kRefitDoubles, k, stage);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -505,13 +475,13 @@ int launch_batch_reduce_lm(int lx, const float* d_pts4, const uint8_t* d_mask, c
 
 int launch_batch_refit_chain(const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed, int maxN,
                              double* d_part, double* d_rec, hipStream_t s) {
-    const int R = kBatchRefitDoubles;
+    const int R = kRefitDoubles;
     const int sb = (nRed + 63) / 64;
-    batch_reduce<5, BOpSums>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec, R, s);
+    batch_reduce<5, BOpSums>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec + kRefitSums, R, s);
     hipLaunchKernelGGL(mcv_batch_refit_stats, dim3(sb), dim3(256), 0, s, d_rec, nRed, 0);
-    batch_reduce<4, BOpAbsDev>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec + 9, R, s);
+    batch_reduce<4, BOpAbsDev>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec + kRefitDev, R, s);
     hipLaunchKernelGGL(mcv_batch_refit_stats, dim3(sb), dim3(256), 0, s, d_rec, nRed, 1);
-    batch_reduce<45, BOpLtL>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec + 17, R, s);
+    batch_reduce<45, BOpLtL>(d_pts4, d_mask, d_red, nRed, maxN, d_rec, R, d_part, d_rec + kRefitLtL, R, s);
     return 8;
 }
 

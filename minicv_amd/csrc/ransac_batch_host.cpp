@@ -6,10 +6,12 @@
 //   rounds:   batched generate + batched sweep over every problem still searching, one copy of the
 //             counts back, the single call's sequential replay per problem on the host
 //   finalize: every winner re-solved, masked and counted in two launches, one copy back
-//   refine:   the B Levenberg-Marquardt solvers in lockstep (lm_solver_step.h): each step is one batched
-//             reduction over the problems still iterating and one read-back; H runs the batched refit
-//             chain first. The sums keep reduce.h's order per problem, the host algebra is the single
-//             call's, so every problem returns the single call's bits.
+//   refine:   the B Levenberg-Marquardt solvers in lockstep (lm_solver.h's LmStepper, the controller the
+//             single call loops over): each step is one batched reduction over the problems still
+//             iterating and one read-back; H runs the batched refit chain first. The sums keep reduce.h's
+//             order per problem over the single call's per-point terms, and the host algebra is the single
+//             call's own functions (LmStepper, h_refit_from_record, a_to_params / a_from_params), so
+//             every problem returns the single call's bits.
 // Problems with exactly the sample size take the single export's direct solve (routed through it).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
@@ -17,7 +19,8 @@
 #include "linalg.h"
 #include "mcv_common.h"
 #include "hyp_homography.h"
-#include "lm_solver_step.h"
+#include "hyp_affine.h"
+#include "lm_solver.h"
 #include "plan.h"
 
 #include <cmath>
@@ -164,36 +167,6 @@ static int batch_single(int model, const mcvV2d* a, const mcvV2d* b, int N, cons
     return c;
 }
 
-// h_refit's host half (ransac_h_host.cpp) on the chained passes' record r[62].
-static bool h_refit_from_record(const double* r, double* H) {
-    const double* sums = r;
-    const double count = sums[4];
-    if (count <= 0) return false;
-    double c4[4] = {sums[0] / count, sums[1] / count, sums[2] / count, sums[3] / count};
-    const double* dev = r + 9;
-    for (int k = 0; k < 4; ++k)
-        if (std::fabs(dev[k]) < DBL_EPSILON) return false;
-    double s4[4] = {count / dev[0], count / dev[1], count / dev[2], count / dev[3]};
-    const double* ltl = r + 17;
-    double A[81], w[9], V[81];
-    int o = 0;
-    for (int j = 0; j < 9; ++j)
-        for (int k = j; k < 9; ++k) { A[j * 9 + k] = ltl[o]; A[k * 9 + j] = ltl[o]; ++o; }
-    jacobi_eigen(A, 9, w, V);
-    const double* H0 = V + 8 * 9;
-    const double invHnorm[9] = {1. / s4[0], 0, c4[0], 0, 1. / s4[1], c4[1], 0, 0, 1};
-    const double Hnorm2[9] = {s4[2], 0, -c4[2] * s4[2], 0, s4[3], -c4[3] * s4[3], 0, 0, 1};
-    double T[9], R[9];
-    mat3_mul(invHnorm, H0, T);
-    mat3_mul(T, Hnorm2, R);
-    const double sc = 1. / R[8];
-    for (int k = 0; k < 9; ++k) {
-        H[k] = R[k] * sc;
-        if (!std::isfinite(H[k])) return false;
-    }
-    return true;
-}
-
 struct RefineJob { int ptOff, N; double* M9; };   // a winner to refine, its model in place
 
 static void upload_red(BatchWs& W, const std::vector<const RefineJob*>& act, hipStream_t s) {
@@ -212,10 +185,8 @@ static void batch_lm(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hipStre
     std::vector<LmStepper<LX>> st(jobs.size());
     for (size_t j = 0; j < jobs.size(); ++j) {
         double x0[LX];
-        const double* M = jobs[j].M9;
-        if (LX == 8) for (int i = 0; i < 8; ++i) x0[i] = M[i];
-        else if (LX == 6) for (int i = 0; i < 6; ++i) x0[i] = M[i];
-        else { x0[0] = M[0]; x0[1] = M[3]; x0[2] = M[2]; x0[3] = M[5]; }
+        if constexpr (LX == 8) std::memcpy(x0, jobs[j].M9, 8 * sizeof(double));   // H[0..7]; H[8] stays
+        else a_to_params(LX, jobs[j].M9, x0);
         st[j].begin(x0, 10);
     }
     const size_t per = (size_t)batch_reduce_blocks(maxN);
@@ -245,11 +216,8 @@ static void batch_lm(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hipStre
         for (size_t k = 0; k < n; ++k) st[who[k]].feed(W.h_out.p + 45 * k);
     }
     for (size_t j = 0; j < jobs.size(); ++j) {
-        double* M = jobs[j].M9;
-        const double* h = st[j].x;
-        if (LX == 8) for (int i = 0; i < 8; ++i) M[i] = h[i];
-        else if (LX == 6) for (int i = 0; i < 6; ++i) M[i] = h[i];
-        else { M[0] = h[0]; M[1] = -h[1]; M[2] = h[2]; M[3] = h[1]; M[4] = h[0]; M[5] = h[3]; }
+        if constexpr (LX == 8) std::memcpy(jobs[j].M9, st[j].x, 8 * sizeof(double));
+        else a_from_params(LX, st[j].x, jobs[j].M9);
     }
 }
 
@@ -261,15 +229,15 @@ static void batch_h_refit(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hi
     std::vector<const RefineJob*> act;
     for (auto& j : jobs) act.push_back(&j);
     upload_red(W, act, s);
-    W.rec.ensure(n * kBatchRefitDoubles);
-    W.h_rec.ensure(n * kBatchRefitDoubles);
+    W.rec.ensure(n * kRefitDoubles);
+    W.h_rec.ensure(n * kRefitDoubles);
     W.part.ensure(n * (size_t)batch_reduce_blocks(maxN) * 45);
     t_stats.launches += launch_batch_refit_chain(W.pts.p, W.mask.p, W.red.p, (int)n, maxN, W.part.p, W.rec.p, s);
-    MCV_HIP(hipMemcpyAsync(W.h_rec.p, W.rec.p, n * kBatchRefitDoubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    MCV_HIP(hipMemcpyAsync(W.h_rec.p, W.rec.p, n * kRefitDoubles * sizeof(double), hipMemcpyDeviceToHost, s));
     batch_sync(s);
     for (size_t k = 0; k < n; ++k) {
         double Hr[9];
-        if (h_refit_from_record(W.h_rec.p + k * kBatchRefitDoubles, Hr))
+        if (h_refit_from_record(W.h_rec.p + k * kRefitDoubles, Hr))
             for (int i = 0; i < 9; ++i) jobs[k].M9[i] = Hr[i];
     }
 }
@@ -326,12 +294,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
         W.h_pts.ensure((size_t)total * 4);
         W.pts.ensure((size_t)total * 4);
         auto t0 = std::chrono::steady_clock::now();
-        for (int i = 0; i < total; ++i) {
-            W.h_pts.p[4 * (size_t)i + 0] = (float)a[i].X;
-            W.h_pts.p[4 * (size_t)i + 1] = (float)a[i].Y;
-            W.h_pts.p[4 * (size_t)i + 2] = (float)b[i].X;
-            W.h_pts.p[4 * (size_t)i + 3] = (float)b[i].Y;
-        }
+        pack_float4(a, b, total, W.h_pts.p);
         t_stats.packUs = us_since(t0);
         MCV_HIP(hipMemcpyAsync(W.pts.p, W.h_pts.p, (size_t)total * 16, hipMemcpyHostToDevice, s));
         // ---- OpenCV's sample stream: one cv::RNG((uint64)-1) stream per problem, as each single call draws

@@ -451,7 +451,7 @@ void f_reduce_eucdev(const float* d_pts4, int N, const uint8_t* d_mask, const do
 
 void f_reduce_ata(const float* d_pts4, int N, const uint8_t* d_mask, const double* c4, const double* s4,
                   double* d_part, double* d_out, hipStream_t s) {
-    // c4 = {c2x, c2y, c1x, c1y} and s4 likewise (OpSums / OpAbsDevD order, ransac_h_refine.hip: dst first)
+    // c4 = {c2x, c2y, c1x, c1y} and s4 likewise (OpSums / OpAbsDev order, ransac_h_refine.hip: dst first)
     OpFAtA op{(const float4*)d_pts4, d_mask, c4[2], c4[3], s4[2], s4[3], c4[0], c4[1], s4[0], s4[1]};
     run_reduce<45>(N, op, d_part, d_out, s);
 }

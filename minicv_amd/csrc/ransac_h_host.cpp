@@ -50,21 +50,18 @@ void h_plan_forget(const Plan* P) {
     if (t_hmfma_plan == P) t_hmfma_plan = nullptr;
 }
 
-// HomographyEstimatorCallback::runKernel over the masked correspondences (mask == NULL: all).
-bool h_refit(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H) {
-    // the three passes (sums -> centroids -> |deviations| -> scales -> LtL) chained on the device,
-    // one read-back; the host re-derives c4 / s4 with the same divisions and checks them
-    double r[62];
-    reduce_to_host(P, s, 62, r, [&](double* part, double* red) { h_refit_chain(d_pts, N, d_mask, part, red, s); });
-    const double* sums = r;
-    const double count = sums[4];
+// The host half of HomographyEstimatorCallback::runKernel on a refit record (kernels.h kRefit*): the single
+// call's and every batched problem's. It re-derives c4 / s4 with the device's divisions and checks them.
+bool h_refit_from_record(const double* r, double* H) {
+    const double* sums = r + kRefitSums;
+    const double count = r[kRefitCount];
     if (count <= 0) return false;
     double c4[4] = {sums[0] / count, sums[1] / count, sums[2] / count, sums[3] / count};   // cm.x, cm.y, cM.x, cM.y
-    const double* dev = r + 9;
+    const double* dev = r + kRefitDev;
     for (int k = 0; k < 4; ++k)
         if (std::fabs(dev[k]) < DBL_EPSILON) return false;
     double s4[4] = {count / dev[0], count / dev[1], count / dev[2], count / dev[3]};   // sm.x, sm.y, sM.x, sM.y
-    const double* ltl = r + 17;
+    const double* ltl = r + kRefitLtL;
     double A[81], w[9], V[81];
     int o = 0;
     for (int j = 0; j < 9; ++j)
@@ -84,17 +81,24 @@ bool h_refit(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStrea
     return true;
 }
 
+// HomographyEstimatorCallback::runKernel over the masked correspondences (mask == NULL: all): the three
+// passes (sums -> centroids -> |deviations| -> scales -> LtL) chained on the device, one read-back.
+bool h_refit(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H) {
+    double r[kRefitDoubles];
+    reduce_to_host(P, s, kRefitDoubles, r,
+                   [&](double* part, double* red) { h_refit_chain(d_pts, N, d_mask, part, red, s); });
+    return h_refit_from_record(r, H);
+}
+
 // LMSolver::create(HomographyRefineCallback(src, dst), 10)->run(H8) — the classic LMSolverImpl
 // (Marquardt-Nielsen lambda control, eigen-based solve). The O(N) JtJ / Jtr / |r|^2 sums run on
 // the GPU; the 8x8 algebra runs here.
 void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipStream_t s, double* H, int maxIters) {
-    auto compute = [&](const double* h, double* Aout, double* vout) -> double {
-        double buf[45];
+    auto sums = [&](const double* h, double* buf) {
         reduce_to_host(P, s, 45, buf,
                        [&](double* part, double* red) { h_reduce_lm(d_pts, N, d_mask, h, part, red, s); });
-        return lm_unpack_sums<8>(buf, Aout, vout);
     };
-    lm_solver_run<8>(compute, H, maxIters);   // H[0..7]; H[8] stays
+    lm_solver_run<8>(sums, H, maxIters);   // H[0..7]; H[8] stays
 }
 
 // One chunk of hypotheses: models, statuses, and P.last = this chunk (the winner's models can come straight

@@ -191,14 +191,8 @@ uint64_t device_fingerprint(Plan& P, const void* d_pts, int N, hipStream_t s) {
 
 void pack_points(Plan& P, const mcvV2d* a, const mcvV2d* b, int N, float* d_dst, hipStream_t s) {
     P.h_pack.ensure((size_t)N * 4);
-    float* h = P.h_pack.p;
-    for (int i = 0; i < N; ++i) {   // OpenCV: points.convertTo(CV_32F)
-        h[4 * i + 0] = (float)a[i].X;
-        h[4 * i + 1] = (float)a[i].Y;
-        h[4 * i + 2] = (float)b[i].X;
-        h[4 * i + 3] = (float)b[i].Y;
-    }
-    MCV_HIP(hipMemcpyAsync(d_dst, h, (size_t)N * 16, hipMemcpyHostToDevice, s));
+    pack_float4(a, b, N, P.h_pack.p);
+    MCV_HIP(hipMemcpyAsync(d_dst, P.h_pack.p, (size_t)N * 16, hipMemcpyHostToDevice, s));
     MCV_HIP(hipStreamSynchronize(s));
 }
 

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(kReduceThreads) void reduce_final(int nblocks, cons
     block_sum<V>(acc, out);
 }
 
-inline int reduce_blocks(int n) {
+// Blocks of a pass over n correspondences (host: the grid; device: a batched pass's share of its grid).
+__host__ __device__ inline int reduce_blocks(int n) {
     int b = (n + kReduceThreads - 1) / kReduceThreads;
     if (b < 1) b = 1;
     if (b > kReduceMaxBlocks) b = kReduceMaxBlocks;

@@ -246,6 +246,25 @@ def test_batch_equals_single_calls(gpu, model, error_kind, sampler):
     assert (refined > 0) == (model != F)   # the lockstep refine ran (F has none)
 
 
+CLAMP_N = 256 * 1024 + 1   # the first N past reduce.h's block-count clamp (1024 blocks of 256 threads)
+
+
+@pytest.mark.parametrize("model", [H, A, SIM], ids=NAME.get)   # F has no refine
+def test_batch_equals_single_calls_past_the_reduction_clamp(gpu, model):
+    """The refine's reductions where a block strides over more than one trip of points (the clamp is code the
+    single and the batched pass share), beside a problem far below it in the same launches."""
+    probs = [problem(model, CLAMP_N, 41, 0.3), problem(model, 257, 42, 0.3)]
+    p = opencv.RansacParams(threshold=THR[model], confidence=0.995 if model == H else 0.99, max_iters=64,
+                            fixed_iters=True, **SAMPLERS["philox1"])
+    got = opencv.findModelBatch(model, [s for s, _ in probs], [d for _, d in probs], p)
+    st = stats()
+    assert st["single"] == 0 and st["B"] == 2 and st["lm"] > 0
+    for k, (src, dst) in enumerate(probs):
+        exp = single(model, src, dst, p)
+        assert exp[0] > SAMPLE[model]   # a winner with inliers beyond its sample: both calls refined it
+        assert_same(got[k], exp, (k, len(src)))
+
+
 @pytest.mark.parametrize("model", MODELS, ids=NAME.get)
 def test_null_config_is_the_single_exports_default(gpu, model):
     probs = batch_problems(model, 5, 7)
