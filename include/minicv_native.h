@@ -351,6 +351,13 @@ MCV_API int mcvL2LastExactScans(void);
 /* GEMM form of the calling thread's last L2 match: 16 = f16 split (every |x| < 2^15, dim <= 128),
  * 32 = f32; synchronises that match's stream. */
 MCV_API int mcvL2LastGemmForm(void);
+/* Train chunks per batch of 32 queued queries (T) in the exact scan of the calling thread's last L2
+ * match, 0 when nothing was queued; T = 1 is the form in which the scan writes the final results
+ * itself. Computed on the host by the kernels' own rule; synchronises that match's stream. */
+MCV_API int mcvL2LastScanChunks(void);
+/* Query tiles per wave (1 or 2) of the calling thread's last fp4 GEMM-form Hamming launch on the
+ * current device; 0 when the last launch took the popcount form or none ran. */
+MCV_API int mcvHammingLastQueryTiles(void);
 
 /* Last error message of the calling thread ("" if none). */
 MCV_API const char* mcvGetLastError(void);

@@ -359,8 +359,10 @@ int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                          int* d_dist, int* d_idx2, int* d_dist2, hipStream_t s, int form = kHammingFormGemm);
 int launch_match_l2(const float* d_q, int nq, const float* d_t, int nt, int dim, int* d_idx, float* d_dist,
                     int* d_idx2, float* d_dist2, hipStream_t s);
+int hamming_last_query_tiles();
 int l2_last_exact_scans();
 int l2_last_gemm_form();
+int l2_last_scan_chunks();
 // uint8 descriptors under L2 on the int8 matrix cores (match_l2u8.hip): exact, the outputs of
 // launch_match_l2 on the same bytes as fp32. check_match_l2u8 throws on a dim / nq / nt outside the
 // kernel's range (no device needed).

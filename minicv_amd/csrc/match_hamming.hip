@@ -541,8 +541,18 @@ struct HammingWork {
     DevBuf<uint2> part;
     DevBuf<unsigned> arrivals;   // per query block of the GEMM form (zero between launches)
     size_t arrivalsZeroed = 0;
+    int lastQueryTiles = 0;   // QT of the last GEMM-form launch, 0 after a popcount-form one (diagnostics)
     StreamFence fence;   // calls on different streams take turns on these buffers
 };
+
+// Per host thread and device (DevBuf does not follow a device switch).
+static HammingWork& hamming_work() {
+    int dev = 0;
+    MCV_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 16) fail("cvMatchHamming: device %d outside the 16 per-thread workspaces", dev);
+    thread_local HammingWork works[16];
+    return works[dev];
+}
 
 // The GEMM form's launch: WPB waves per block, QT query tiles per wave; stream-K ranges over the resident
 // blocks (occupancy of this instantiation).
@@ -591,11 +601,7 @@ int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
     if (bytesPerDesc < 1 || bytesPerDesc > 64) fail("cvMatchHamming: bytesPerDesc %d outside [1, 64]", bytesPerDesc);
     if (nt < 0 || nt > (int)kIdxMask) fail("cvMatchHamming: nt %d outside [0, 2^22)", nt);
     if (nq <= 0) return 0;
-    int dev = 0;   // per host thread and device (DevBuf does not follow a device switch)
-    MCV_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) fail("cvMatchHamming: device %d outside the 16 per-thread workspaces", dev);
-    thread_local HammingWork works[16];
-    HammingWork& wk = works[dev];
+    HammingWork& wk = hamming_work();
     wk.fence.enter(s);
     const int W = bytesPerDesc <= 32 ? 8 : 16;
     const uint32_t* q = (const uint32_t*)d_q;
@@ -625,6 +631,7 @@ int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
         // 11.2-11.4 -> 10.0-10.1 / 14.4-14.6 -> 13.4 us; cfg2 17.7 -> 18.2-18.5 and 10k x 40k 46.0 -> 64.1
         // us the other way)
         const int64_t steps2 = (int64_t)((nq + 255) / 256) * ((nt + 31) / 32);
+        wk.lastQueryTiles = steps2 <= 8192 ? 1 : 2;
         if (steps2 <= 8192)
             launch_ham_gemm<4, 1>(wk, W, q, nq, t, nt, d_idx, d_dist, d_idx2, d_dist2, s);
         else
@@ -635,6 +642,7 @@ int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
     }
     // popcount form: one query per lane, one SGPR vector per staged group, ~16384 waves
     // (scripts/sweep_hamming.sh: 2 queries per lane and 2-vector groups screened slower)
+    wk.lastQueryTiles = 0;
     constexpr int targetWaves = 16384, Q = 1, NB = 1;
     const int qwaves = (nq + 64 * Q - 1) / (64 * Q);
     int nchunks = (targetWaves + qwaves - 1) / qwaves;
@@ -656,6 +664,10 @@ int launch_match_hamming(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
     wk.fence.leave(s);
     return nq;
 }
+
+// Query tiles per wave (QT) of this thread's last GEMM-form launch on the current device; 0 after a
+// popcount-form launch or when none ran (diagnostics: the tests prove which instantiation they reached).
+int hamming_last_query_tiles() { return hamming_work().lastQueryTiles; }
 
 }  // namespace mcv
 

@@ -996,7 +996,7 @@ __device__ __forceinline__ void top2d_push(double& a1, int& k1, double& a2, int&
     else if (lex_less_d(e, j, a2, k2)) { a2 = e; k2 = j; }
 }
 
-__device__ __forceinline__ int l2_scan_chunks(int nbatch, int blocks) {
+__host__ __device__ __forceinline__ int l2_scan_chunks(int nbatch, int blocks) {
     return nbatch >= blocks ? 1 : blocks / nbatch;
 }
 
@@ -1566,6 +1566,17 @@ int l2_last_gemm_form() {
     unsigned d = 0;
     for (int i = 0; i < kL2MaxSlots; ++i) d = m[i * kL2SlotStride] > d ? m[i * kL2SlotStride] : d;
     return d < kL2F16MaxBits ? 16 : 32;
+}
+
+// Train chunks per batch (T) of the last launch_match_l2's exact scan, 0 when nothing was queued: the
+// rule the scan and merge kernels apply on the device (l2_scan_chunks over the same work units), from
+// the queue length read back (diagnostics; synchronises that launch's stream).
+int l2_last_scan_chunks() {
+    const int n = l2_last_exact_scans();
+    const int nbatch = (n + kL2ScanQ - 1) / kL2ScanQ;
+    if (nbatch == 0) return 0;
+    const int units = l2_last_gemm_form() == 16 ? kL2ScanBlocks * (kL2ScanThreadsU / 256) : kL2ScanBlocks;
+    return l2_scan_chunks(nbatch, units);
 }
 
 }  // namespace mcv

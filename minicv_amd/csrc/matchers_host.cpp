@@ -232,3 +232,11 @@ extern "C" MCV_API int mcvL2LastExactScans(void) {
 extern "C" MCV_API int mcvL2LastGemmForm(void) {
     MCV_GUARD(-1, { return l2_last_gemm_form(); })
 }
+
+extern "C" MCV_API int mcvL2LastScanChunks(void) {
+    MCV_GUARD(-1, { return l2_last_scan_chunks(); })
+}
+
+extern "C" MCV_API int mcvHammingLastQueryTiles(void) {
+    MCV_GUARD(-1, { return hamming_last_query_tiles(); })
+}

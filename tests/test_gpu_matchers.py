@@ -27,7 +27,8 @@ def test_hamming_golden(gpu):
 
 
 @pytest.mark.parametrize("nq,nt,nbytes", [(1, 1, 32), (1, 2, 32), (63, 65, 32), (1000, 777, 32), (513, 4099, 64),
-                                          (300, 300, 61), (257, 1000, 16), (100, 100, 1), (2000, 3000, 32)])
+                                          (300, 300, 61), (257, 1000, 16), (100, 100, 1), (2000, 3000, 32),
+                                          (2305, 26250, 64), (2305, 26250, 61)])   # two query tiles per wave
 def test_hamming_shapes(gpu, oracle, nq, nt, nbytes):
     q, t, _ = S.hamming_problem(nq, nt, nbytes=nbytes, seed=nq + nt)
     check_hamming(oracle, q, t)
