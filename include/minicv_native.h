@@ -264,6 +264,36 @@ MCV_API int cvFindModelBatch(int model, const mcvV2d* a, const mcvV2d* b, const 
 MCV_API int cvFindEssentialMat(const mcvV2d* a, const mcvV2d* b, const int N, double focal, mcvV2d pp,
                                const RansacConfig* cfg, mcvM33d* E, uint8_t* mask);
 
+/* B independent cvFindEssentialMat problems in one call, in cvFindModelBatch's conventions: problem p owns
+ * correspondences [offsets[p], offsets[p+1]) of a / b (offsets: B + 1 ints, offsets[0] == 0, non-decreasing).
+ * focal[B], pp[B]: per problem. cfg: one for all (NULL: cvFindEssentialMat's defaults with its NULL cfg).
+ * E[B], mask: uint8[offsets[B]] (may be NULL), counts[B].
+ * Problem p returns exactly what cvFindEssentialMat returns for its slice with focal[p], pp[p] and cfg: the
+ * same count, mask bytes and nine doubles. A problem on which the single call returns 0 (N < 5, no model,
+ * N == 5 with several solutions, a focal that is zero or not finite) gets count 0, a zero E and a zero mask
+ * slice; the others are untouched and mcvGetLastError() names the first failed problem's index and its
+ * message. The kernel launches and stream synchronisations of a call do not grow with B (problems with
+ * exactly 5 correspondences take the single export, one by one).
+ * cfg: method MCV_METHOD_RANSAC; flags any of MCV_FLAG_CV_SAMPLER (one cv::RNG((uint64)-1) stream per
+ * problem), MCV_FLAG_FIXED_ITERS, MCV_FLAG_NO_REFINE (accepted, no effect: E has no refine); every problem
+ * uses cfg->seed. Other methods, MCV_FLAG_FUSED_ERROR, MCV_FLAG_FAST_MINIMAL, deviceCount > 1 and the retired
+ * bit 4 fail the whole call; every argument check runs before the device is touched.
+ * Returns the number of problems with a model (0 for B == 0), -1 on a bad argument or a device failure. */
+MCV_API int cvFindEssentialMatBatch(const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
+                                    const double* focal, const mcvV2d* pp, const RansacConfig* cfg,
+                                    mcvM33d* E, uint8_t* mask, int* counts);
+/* B independent cvRecoverPose problems in one call. configs[B]: per problem (focal, principal point,
+ * probability, threshold); every problem runs OpenCV's sample stream with 1000 iterations, as cvRecoverPose
+ * does. R[B], t[B], ms: uint8[offsets[B]] = the RANSAC masks, good[B] = cvRecoverPose's return.
+ * Problem p returns exactly what cvRecoverPose returns for its slice with configs[p]: the same count, mask
+ * bytes and doubles of R and t. A problem on which the single call fails gets good 0, zero R and t and a
+ * zero mask slice, and mcvGetLastError() names the first such problem. One difference from the single call:
+ * cvRecoverPose leaves ms all 1 when N == 5 gives several solutions; the batch zeroes that slice.
+ * A Probability outside (0, 1) fails the whole call, as do null arguments and bad offsets.
+ * Returns the number of problems with a pose (0 for B == 0), -1 on a bad argument or a device failure. */
+MCV_API int cvRecoverPoseBatch(const RecoverPoseConfig* configs, const mcvV2d* pa, const mcvV2d* pb,
+                               const int* offsets, int B, mcvM33d* R, mcvV3d* t, uint8_t* ms, int* good);
+
 /* cvSolvePnPRansac with a full RansacConfig (threshold = reprojection error in pixels; seed, fixed iterations, fused error, NO_REFINE). */
 MCV_API mcvBool cvSolvePnPRansacCfg(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int N, const mcvM33d K,
                                  const double* distortionCoeffs, const RansacConfig* cfg, mcvV3d* tVec, mcvV3d* rVec,
@@ -698,6 +728,20 @@ MCV_API int mcvTestBatchStats(long long* stats16);
  * counts[k] = inliers of model k over its problem's points. Returns 1, 0 on failure. */
 MCV_API int mcvTestBatchSweep(int model, const float* pts4, const int* offsets, int B, const void* models,
                               const int* modelOffsets, float thr2, int errKind, int* counts);
+/* The essential batches (cvFindEssentialMatBatch, cvRecoverPoseBatch) share the hooks above: their layout is
+ * mcvHostBatchLayout with m = 5 and their own default cap of 2^18 hypotheses per round (pass it: cap <= 0
+ * means the 2-D default); mcvTestBatchCap overrides their cap too (a cap other than the 2-D default holds for
+ * both; cap <= 0 restores both defaults); mcvTestBatchStats reports the calling thread's last batch call of
+ * either kind ([3] is 0, [6] the host microseconds staging the raw points and the descriptors, [8] the
+ * problems summed over the hypothesis rounds they ran in: below [2] x the device problems once a problem has
+ * stopped early and dropped out of the later rounds).
+ * Device self-test: the batched essential sweep (mcv_batch_e_sweep) on caller-supplied models. pts4d: the
+ * segmented double4 normalised points, problem p owning [offsets[p], offsets[p+1]); its models are
+ * [modelOffsets[p], modelOffsets[p+1]) of models9 (9 doubles each, row-major E); thr2[B]: one threshold per
+ * problem; kind: 0 fused / 1 op-by-op Sampson error. counts[k] = points of model k's problem with
+ * f_error <= thr2. Returns 1, 0 on failure. */
+MCV_API int mcvTestBatchSweepE(const double* pts4d, const int* offsets, int B, const double* models9,
+                               const int* modelOffsets, const float* thr2, int kind, int* counts);
 MCV_API void mcvHostPhilox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                            uint32_t* out4);
 /* Host twin of CameraPose.findScaled: the same candidates and costs as cvFindScaledPoseCosts,

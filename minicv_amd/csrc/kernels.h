@@ -338,6 +338,58 @@ int launch_batch_reduce_lm(int lx, const float* d_pts4, const uint8_t* d_mask, c
 int launch_batch_refit_chain(const float* d_pts4, const uint8_t* d_mask, const BatchRed* d_red, int nRed, int maxN,
                              double* d_part, double* d_rec, hipStream_t s);
 
+// ---- batched essential-matrix RANSAC (ransac_batch_e.hip; the generate: ransac_e5.hip). All problems'
+// double4 normalised points sit in one segmented buffer. A hypothesis round gives problem j of the round
+// `stride` columns of the flat five-point stage, 10 stride model slots / counts and a dense region of the
+// same capacity at 10 j stride (BatchDesc.slotOff = j stride counts hypotheses).
+static const int kBatchETile = 512;          // double4 points staged in LDS per trip of the sweep (16 KiB)
+struct BatchEPack {     // one problem of the pack
+    int ptOff, N;
+    double focal, cx, cy;
+};
+struct BatchESweep {    // one problem of the sweep
+    int ptOff, N;
+    int64_t denseOff;        // its first model of the dense buffer
+    int64_t countOff;        // its first count: model i's lands at countOff + denseSlot[denseOff + i]
+    float thr2;
+    int pad;
+};
+struct BatchEFetch {    // one model to copy out of a dense region
+    int64_t denseOff;
+    int prob;                // the region's counter: nDense[prob]
+    int slot;                // the model's slot within the problem's round: hypothesis * 10 + k
+    int outIdx;              // out[outIdx] = the model, found[outIdx] = stamp
+    int stamp;
+};
+struct BatchEFin {      // one winner of the mask
+    int ptOff, N;
+    float thr2;
+    int modelIdx;            // its model: models[modelIdx]
+};
+struct BatchEPose {     // one winner of the cheirality test: the four [R | t] candidates
+    int ptOff, N;
+    double P[4][12];
+};
+// The three kernels of launch_e5_generate over a round (returns the kernels launched); d_stage:
+// e5_stage_bytes(nDesc * stride) bytes, d_nDense: nDesc counters.
+int launch_e5_batch_generate(const double* d_pts4, const BatchDesc* d_desc, int nDesc, int stride, uint64_t seed,
+                             const int* d_table, void* d_dense, int* d_denseSlot, int* d_nDense, int* d_counts,
+                             void* d_stage, hipStream_t s);
+void launch_batch_e_pack(const double* d_a, const double* d_b, const BatchEPack* d_desc, int nDesc, int maxN,
+                         double* d_pts4, hipStream_t s);
+// maxModels: the largest dense count possible (sizes the grid); d_denseSlot nullptr: model i counts at countOff + i
+void launch_batch_e_sweep(int kind, const double* d_pts4, const BatchESweep* d_desc, int nDesc, int maxModels,
+                          const void* d_dense, const int* d_denseSlot, const int* d_nDense, int* d_counts,
+                          hipStream_t s);
+void launch_batch_e_fetch(const BatchEFetch* d_fetch, int nFetch, const void* d_dense, const int* d_denseSlot,
+                          const int* d_nDense, double* d_out9, int* d_found, hipStream_t s);
+// d_mask: the segmented mask; d_count[f] += inliers (zeroed by the caller)
+void launch_batch_e_mask(int kind, const double* d_pts4, const BatchEFin* d_fin, int nFin, int maxN,
+                         const double* d_models9, uint8_t* d_mask, int* d_count, hipStream_t s);
+// d_good4[4 f + k] += masked points of winner f passing candidate k's test (zeroed by the caller)
+void launch_batch_e_cheirality(const double* d_pts4, const uint8_t* d_mask, const BatchEPose* d_pose, int nPose,
+                               int maxN, double dist, int* d_good4, hipStream_t s);
+
 // ---- shared (ransac_common.hip)
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,
                  uint64_t* d_out, hipStream_t s);

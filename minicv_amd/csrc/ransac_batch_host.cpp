@@ -39,29 +39,20 @@ namespace mcv {
 // round. Above it every round gives each problem cap / problems hypotheses (at least one).
 static const int64_t kBatchSlotCap = (int64_t)1 << 21;
 static int64_t g_batch_cap = kBatchSlotCap;   // mcvTestBatchCap
+// The essential batches count hypotheses, not slots: one costs 2292 B of five-point stage, 720 B of dense
+// models and 80 B of counts and slot indices, ~3.1 KB, so 2^18 of them are 0.8 GB (B = 256 problems of the
+// default 1000 iterations fit one round).
+// mcvTestBatchCap overrides both: a cap other than the 2-D default holds for this family too.
+static const int64_t kBatchHypCapE = (int64_t)1 << 18;
+int64_t batch_cap_essential() { return g_batch_cap == kBatchSlotCap ? kBatchHypCapE : g_batch_cap; }
 
-struct BatchStats {
-    long long launches = 0, syncs = 0, rounds = 0, lmRounds = 0, single = 0, problems = 0;
-    long long packUs = 0, tableUs = 0;   // host time: point conversion, OpenCV sample tables
-};
 static long long us_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
 }
 static thread_local BatchStats t_stats;
+BatchStats& batch_stats() { return t_stats; }
 
-// The index arithmetic of a batch call (mcvHostBatchLayout exposes it). Problems with more points than
-// the sample size m go to the device; they are numbered in order (device index d).
-//   point offset  offsets[p] (float4 units; nothing is padded: the sweep reads float4 points, not pairs)
-//   slot offset   d * per, 64-bit: problem d's first slot of a round in which every device problem runs
-//   row offset    d * iters: its first row of the sampler table
-//   per           hypotheses per problem per round = clamp(cap / D, 1, iters); rounds = ceil(iters / per)
-struct BatchLayout {
-    std::vector<int> dev;             // device problems
-    std::vector<int64_t> slotOff, rowOff;   // per problem (-1: not on the device)
-    int64_t iters = 1, per = 1, rounds = 0;
-};
-
-static void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L) {
+void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L) {
     L.dev.clear();
     L.slotOff.assign((size_t)B, -1);
     L.rowOff.assign((size_t)B, -1);
@@ -509,6 +500,7 @@ extern "C" MCV_API int mcvTestBatchStats(long long* stats16) {
     stats16[5] = t_stats.problems;
     stats16[6] = t_stats.packUs;
     stats16[7] = t_stats.tableUs;
+    stats16[8] = t_stats.problemRounds;
     return 1;
 }
 

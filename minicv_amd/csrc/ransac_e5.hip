@@ -45,10 +45,32 @@ struct E5StoreGlobal {
     __device__ void operator()(int r, int c, double v) { A[(size_t)(20 * r + c) * H + i] = v; }
 };
 
+// BATCH (cvFindEssentialMatBatch / cvRecoverPoseBatch, ransac_batch_e_host.cpp): the grid is (block within
+// problem, problem); the problem's point slice, hypothesis range and sampler rows come from its BatchDesc,
+// and the hypothesis writes column slotOff + i of the round's flat stage. The columns between a problem's
+// hypCount and the round's stride get status 0, so mcv_e5_lu (which runs on the flat stage) skips them.
+template <bool BATCH>
 __global__ __launch_bounds__(64) void mcv_e5_coeffs(const double* __restrict__ pts4, int N, Sampler smp,
-                                                    int64_t hypBegin, int hypCount, E5StageView st) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= hypCount) return;
+                                                    int64_t hypBegin, int hypCount, E5StageView st,
+                                                    const BatchDesc* __restrict__ desc, int blocksPer, int stride) {
+    int i = blockIdx.x * 64 + threadIdx.x;
+    if constexpr (BATCH) {
+        const BatchDesc D = desc[blockIdx.x / blocksPer];
+        const int local = (blockIdx.x % blocksPer) * 64 + threadIdx.x;
+        if (local >= stride) return;
+        i = (int)D.slotOff + local;
+        if (local >= D.hypCount) {
+            st.status[i] = 0;
+            return;
+        }
+        pts4 += 4 * (int64_t)D.ptOff;
+        N = D.N;
+        if (smp.table) smp.table += D.rowOff * 5;
+        hypBegin = (int64_t)D.hypBegin + local - i;   // hypBegin + i below = the problem's hypothesis
+        hypCount = st.H;
+    } else {
+        if (i >= hypCount) return;
+    }
     SubsetSrc<5> src(smp, (uint64_t)(hypBegin + i));
     int idx[5];
     int got = 0;
@@ -164,12 +186,29 @@ __global__ __launch_bounds__(64) void mcv_e5_lu(E5StageView st) {
 // chain is latency-bound at one wave, 29.5 -> 25.8 ms per 2^20 hypotheses. Splitting solvePoly into a
 // kernel of its own (roots through the stage) measured 24.0 + 2.3 ms: solvePoly itself holds the
 // registers; three / four waves per SIMD spill 58 / 121 VGPRs and lose.
+// BATCH: the grid is (block within problem, problem), so no wave straddles two problems; a problem appends
+// to its own dense region (at 10 slotOff, capacity 10 per hypothesis of the round: it cannot overflow) through
+// its own counter nDense[problem], and denseSlot holds the slot within the problem (hypothesis * 10 + k).
+template <bool BATCH>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void mcv_e5_roots(E5StageView st, EModel* __restrict__ dense,
                                                    int* __restrict__ denseSlot, int* __restrict__ nDense,
-                                                   int* __restrict__ counts) {
+                                                   int* __restrict__ counts, const BatchDesc* __restrict__ desc,
+                                                   int blocksPer) {
     const int lane = threadIdx.x;
-    const int i = blockIdx.x * 64 + lane;
-    const bool act = i < st.H;
+    int i = blockIdx.x * 64 + lane;
+    bool act = i < st.H;
+    int slotBase = 0;   // BATCH: the problem's first column of the stage; denseSlot is relative to it
+    if constexpr (BATCH) {
+        const int prob = blockIdx.x / blocksPer;
+        const BatchDesc D = desc[prob];
+        const int local = (blockIdx.x % blocksPer) * 64 + lane;
+        act = local < D.hypCount;
+        slotBase = (int)D.slotOff;
+        i = slotBase + (act ? local : 0);
+        dense += (int64_t)slotBase * kEMaxModels;
+        denseSlot += (int64_t)slotBase * kEMaxModels;
+        nDense += prob;
+    }
     const int status = act ? st.status[i] : 0;
     FprCplx roots[10];
     double b[39];
@@ -223,7 +262,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             EModel em;
             (void)fpr_model(b, e, roots[r].re, em.e);
             dense[base + t] = em;
-            denseSlot[base + t] = i * kEMaxModels + t;
+            denseSlot[base + t] = (i - slotBase) * kEMaxModels + t;
             ++t;
         }
     }
@@ -273,9 +312,29 @@ void launch_e5_generate(const double* d_pts4, int N, Sampler smp, int64_t hypBeg
     if (hypCount <= 0) return;
     const E5StageView st = E5StageView::at(d_stage, hypCount);
     const dim3 g((hypCount + 63) / 64);
-    hipLaunchKernelGGL(mcv_e5_coeffs, g, dim3(64), 0, s, d_pts4, N, smp, hypBegin, hypCount, st);
+    hipLaunchKernelGGL(mcv_e5_coeffs<false>, g, dim3(64), 0, s, d_pts4, N, smp, hypBegin, hypCount, st,
+                       (const BatchDesc*)nullptr, 0, 0);
     hipLaunchKernelGGL(mcv_e5_lu, dim3((hypCount + 1) / 2), dim3(64), 0, s, st);
-    hipLaunchKernelGGL(mcv_e5_roots, g, dim3(64), 0, s, st, (EModel*)d_dense, d_denseSlot, d_nDense, d_counts);
+    hipLaunchKernelGGL(mcv_e5_roots<false>, g, dim3(64), 0, s, st, (EModel*)d_dense, d_denseSlot, d_nDense, d_counts,
+                       (const BatchDesc*)nullptr, 0);
+}
+
+// The same three kernels over a round of a batch: nDesc problems of `stride` stage columns each (problem j
+// owns columns [j stride, j stride + hypCount_j)). d_nDense: one counter per problem (zeroed here).
+int launch_e5_batch_generate(const double* d_pts4, const BatchDesc* d_desc, int nDesc, int stride, uint64_t seed,
+                             const int* d_table, void* d_dense, int* d_denseSlot, int* d_nDense, int* d_counts,
+                             void* d_stage, hipStream_t s) {
+    (void)hipMemsetAsync(d_nDense, 0, (size_t)nDesc * sizeof(int), s);
+    const int H = nDesc * stride;
+    const E5StageView st = E5StageView::at(d_stage, H);
+    const int per = (stride + 63) / 64;
+    const dim3 g((unsigned)per * nDesc);
+    hipLaunchKernelGGL(mcv_e5_coeffs<true>, g, dim3(64), 0, s, d_pts4, 0, Sampler{seed, d_table}, (int64_t)0, 0, st,
+                       d_desc, per, stride);
+    hipLaunchKernelGGL(mcv_e5_lu, dim3((H + 1) / 2), dim3(64), 0, s, st);
+    hipLaunchKernelGGL(mcv_e5_roots<true>, g, dim3(64), 0, s, st, (EModel*)d_dense, d_denseSlot, d_nDense, d_counts,
+                       d_desc, per);
+    return 3;
 }
 
 void launch_e5_one(const double* d_pts4, int N, Sampler smp, int64_t hyp, EOneOut* d_out, hipStream_t s) {

@@ -23,9 +23,9 @@
 
 namespace mcv {
 
-static const double kCheiralityDist = 50.0;   // recoverPose's distanceThresh for the focal/pp overload
+const double kCheiralityDist = 50.0;   // recoverPose's distanceThresh for the focal/pp overload
 
-static int e_kind(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FUSED_ERROR) ? 0 : 1; }
+int e_kind(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FUSED_ERROR) ? 0 : 1; }
 // MCV_FLAG_FAST_MINIMAL: the replacement five-point solver (Gauss-Jordan null space, polynomial-product
 // constraints, Illinois real roots) instead of the reference's (fivepoint.cpp / five_point_ref.h).
 static bool e_fast(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FAST_MINIMAL) != 0; }
@@ -174,7 +174,7 @@ static EResult e_find(Plan& P, const mcvV2d* a, const mcvV2d* b, int N, double f
     return r;
 }
 
-static RansacConfig e_config(const RansacConfig* cfgp) {
+RansacConfig e_config(const RansacConfig* cfgp) {
     if (cfgp) return *cfgp;
     RansacConfig c;
     std::memset(&c, 0, sizeof(c));
@@ -186,14 +186,14 @@ static RansacConfig e_config(const RansacConfig* cfgp) {
     return c;
 }
 
-static RansacConfig e_config(const RecoverPoseConfig* rc) {
+RansacConfig e_config(const RecoverPoseConfig* rc) {
     RansacConfig c = e_config((const RansacConfig*)nullptr);
     c.threshold = rc->InlierThreshold;
     c.confidence = rc->Probability;
     return c;
 }
 
-static void e_check(const RansacConfig& cfg, const char* who) {
+void e_check(const RansacConfig& cfg, const char* who) {
     check_flags(cfg, who);
     if (cfg.method != MCV_METHOD_RANSAC) fail("%s: only RANSAC (method 8) is supported for E", who);
     if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);

@@ -86,6 +86,8 @@ MODEL_SIMILARITY = 5    # estimateAffinePartial2D: 2-point samples, [a -b tx; b 
 A_SWEEP_K = 8           # hypotheses per wave of the packed affine sweep (kernels.h kVerifyAHypPerWave)
 BATCH_TILE = 1024       # points per LDS tile of the batched sweep (kernels.h kBatchTile)
 BATCH_SLOT_CAP = 1 << 21   # slots per hypothesis round of cvFindModelBatch (ransac_batch_host.cpp)
+BATCH_E_TILE = 512         # double4 points per LDS tile of the batched essential sweep (kernels.h kBatchETile)
+BATCH_E_HYP_CAP = 1 << 18  # hypotheses per round of the essential batches (ransac_batch_host.cpp)
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
 NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
@@ -121,6 +123,8 @@ SIGNATURES = {
     "cvEstimateAffine2D": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvEstimateAffinePartial2D": (_I, [_P, _P, _I, _P, _P, _P]),
     "cvFindModelBatch": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "cvFindEssentialMatBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "cvRecoverPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -206,6 +210,7 @@ SIGNATURES = {
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),
     "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),
+    "mcvTestBatchSweepE": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

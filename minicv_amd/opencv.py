@@ -236,6 +236,76 @@ def recoverPose(cfg: N.RecoverPoseConfig, a, b):
     return res, np.array(m.M[:]).reshape(3, 3), np.array([t.X, t.Y, t.Z]), ms[:pa.shape[0]]
 
 
+def _segments(as_, bs):
+    """Lists of (N_p, 2) arrays -> (offsets int32[B + 1], a, b concatenated, total)."""
+    if len(as_) != len(bs):
+        raise ValueError("as/bs length mismatch")
+    pa = [_v2d(x) for x in as_]
+    pb = [_v2d(x) for x in bs]
+    for x, y in zip(pa, pb):
+        if x.shape[0] != y.shape[0]:
+            raise ValueError("a/b length mismatch")
+    B = len(pa)
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([x.shape[0] for x in pa])
+    total = int(offsets[B])
+    a = np.ascontiguousarray(np.concatenate(pa, axis=0)) if total else np.zeros((1, 2))
+    b = np.ascontiguousarray(np.concatenate(pb, axis=0)) if total else np.zeros((1, 2))
+    return offsets, a, b, total
+
+
+def findEssentialMatBatch(as_, bs, focals, pps, params: RansacParams | None = None):
+    """cvFindEssentialMatBatch: B independent findEssentialMat problems in one call. as_ / bs: lists of
+    (N_p, 2) arrays; focals: B focal lengths; pps: B principal points.
+    -> a list of (count, E (3x3 float64), mask (bool[N_p])) per problem, each equal to findEssentialMat's
+    result on that pair; a problem without a model gives (0, zeros, all-False) and N.last_error() names the
+    first such problem. params None: findEssentialMat's native defaults. Raises NativeError when the whole
+    call is refused."""
+    offsets, a, b, total = _segments(as_, bs)
+    B = len(as_)
+    f = np.ascontiguousarray(np.asarray(focals, dtype=np.float64).reshape(-1))
+    pp = np.ascontiguousarray(np.asarray(pps, dtype=np.float64).reshape(-1, 2))
+    if f.shape[0] != B or pp.shape[0] != B:
+        raise ValueError("focals / pps must have one entry per problem")
+    if B == 0:
+        f, pp = np.zeros(1), np.zeros((1, 2))
+    Es = np.zeros((max(B, 1), 9), dtype=np.float64)
+    counts = np.zeros(max(B, 1), dtype=np.int32)
+    ms = np.zeros(max(total, 1), dtype=np.uint8)
+    cfg = params.to_c() if params is not None else None
+    ret = N.lib().cvFindEssentialMatBatch(a.ctypes.data, b.ctypes.data, offsets.ctypes.data, B, f.ctypes.data,
+                                          pp.ctypes.data, N.C.addressof(cfg) if cfg is not None else None,
+                                          Es.ctypes.data, ms.ctypes.data, counts.ctypes.data)
+    N.check(ret >= 0, "cvFindEssentialMatBatch")
+    return [(int(counts[p]), Es[p].reshape(3, 3).copy(), ms[offsets[p]:offsets[p + 1]] != 0) for p in range(B)]
+
+
+def recoverPoseBatch(cfgs, as_, bs):
+    """cvRecoverPoseBatch: B independent recoverPose problems in one call. cfgs: one RecoverPoseConfig for
+    all, or a list of B. -> a list of (good, R, t, mask bytes) per problem, each equal to recoverPose's result
+    on that pair; a failed problem gives (0, zeros, zeros, zeros) and N.last_error() names the first one.
+    Raises NativeError when the whole call is refused."""
+    offsets, a, b, total = _segments(as_, bs)
+    B = len(as_)
+    if isinstance(cfgs, N.RecoverPoseConfig):
+        cfgs = [cfgs] * B
+    if len(cfgs) != B:
+        raise ValueError("cfgs must be one config or one per problem")
+    carr = (N.RecoverPoseConfig * max(B, 1))()
+    for p, c in enumerate(cfgs):
+        carr[p] = N.RecoverPoseConfig(c.FocalLength, N.V2d(c.PrincipalPoint.X, c.PrincipalPoint.Y), c.Probability,
+                                      c.InlierThreshold)
+    Rs = np.zeros((max(B, 1), 9), dtype=np.float64)
+    ts = np.zeros((max(B, 1), 3), dtype=np.float64)
+    good = np.zeros(max(B, 1), dtype=np.int32)
+    ms = np.zeros(max(total, 1), dtype=np.uint8)
+    ret = N.lib().cvRecoverPoseBatch(N.C.addressof(carr), a.ctypes.data, b.ctypes.data, offsets.ctypes.data, B,
+                                     Rs.ctypes.data, ts.ctypes.data, ms.ctypes.data, good.ctypes.data)
+    N.check(ret >= 0, "cvRecoverPoseBatch")
+    return [(int(good[p]), Rs[p].reshape(3, 3).copy(), ts[p].copy(), ms[offsets[p]:offsets[p + 1]].copy())
+            for p in range(B)]
+
+
 def recoverPoses(cfg: N.RecoverPoseConfig, a, b):
     """OpenCV.recoverPoses (OpenCV.fs:863-870): -> (R1, R2, t, mask bytes); the bool result is
     ignored like the F# wrapper does (outputs keep their initial values on failure)."""
