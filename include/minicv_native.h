@@ -340,6 +340,39 @@ MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const DetectorResul
                                     int norm, const RansacConfig* rcfg, mcvM33d* M, int* pairs, uint8_t* mask,
                                     int maxPairs, int* matchCount);
 
+/* B matching problems over nImages images. Problem p matches images[imagePairs[2p]] (queries) to
+ * images[imagePairs[2p+1]] (train). pairs / dist: CSR over the problems, problem p owns
+ * [offsets[p], offsets[p+1]) (offsets: B + 1 ints, written by the call, offsets[0] == 0).
+ * pairs[2k], pairs[2k+1]: feature indices inside the two images, ascending in the first.
+ * dist may be NULL. Returns offsets[B], -1 on failure.
+ * Problem p returns exactly what cvMatchFeaturesNorm(&images[i], &images[j], cfg, norm, ...) returns: the same
+ * count, pairs and dist bits (cfg NULL: ratio 0.8, no cross-check, no max distance). An empty image on
+ * either side gives an empty slice; i == j is legal. Descriptors: uint8 only, one element type and one
+ * width for all images. MCV_NORM_AUTO / MCV_NORM_HAMMING: Hamming, 1 - 64 bytes per row, fewer than 2^22
+ * features per image; MCV_NORM_L2: byte SIFT, dim 1 - 512, cvMatchL2U8's exact integer definition. float32
+ * descriptors fail the whole call (use cvMatchFeaturesNorm per pair), as do a bad image index, mixed
+ * widths or element types, null arguments, negative sizes, DescriptorEntries not a multiple of
+ * PointCount, an unknown norm and a total above maxPairs (the sum of the query images' PointCount over
+ * the problems is always enough); every argument check runs before the device is touched.
+ * Every image's descriptors go to the device once per call and are padded / shifted / normed once, however
+ * many pairs the image is in. The call's kernel launches (at most 6), stream synchronisations (at most 2)
+ * and copies (at most 5: the host arrays are staged through pinned buffers) do not depend on B or nImages. */
+MCV_API int cvMatchFeaturesBatch(const DetectorResult* images, int nImages, const int* imagePairs, int B,
+                                 const MatchConfig* cfg, int norm, int* pairs, float* dist, int maxPairs,
+                                 int* offsets);
+
+/* The same, then cvFindModelBatch (mcfg->model) on the matched keypoints of every pair (coordinates float
+ * widened to double; offsets and rcfg passed through unchanged): the counts, mask bytes and nine doubles
+ * are those of that call. models[B], mask: uint8[maxPairs] indexed like pairs, counts[B]; all required.
+ * A pair with fewer matches than the sample size gets count 0, a zero model and a zero mask slice, and
+ * mcvGetLastError() names the first such pair. Accepts the models and configurations cvFindModelBatch
+ * accepts; the rest fails the whole call before the device is touched.
+ * Returns the number of pairs with a model, -1 on failure. */
+MCV_API int cvMatchAndFindModelBatch(const DetectorResult* images, int nImages, const int* imagePairs, int B,
+                                     const MatchConfig* mcfg, int norm, const RansacConfig* rcfg,
+                                     int* pairs, int maxPairs, int* offsets, mcvM33d* models, uint8_t* mask,
+                                     int* counts);
+
 /* Brute-force Hamming matcher (BFMatcher NORM_HAMMING, knn k = 2). q: [nq][bytesPerDesc],
  * t: [nt][bytesPerDesc] row-major bytes; bytesPerDesc in [1, 64]; nt < 2^22.
  * Outputs per query: best train index / distance and second best (idx2/dist2 may be NULL;
@@ -742,6 +775,29 @@ MCV_API int mcvTestBatchSweep(int model, const float* pts4, const int* offsets, 
  * f_error <= thr2. Returns 1, 0 on failure. */
 MCV_API int mcvTestBatchSweepE(const double* pts4d, const int* offsets, int B, const double* models9,
                                const int* modelOffsets, const float* thr2, int kind, int* counts);
+/* The index arithmetic of cvMatchFeaturesBatch, as the export computes it (no device). featureCounts[nImages],
+ * imagePairs[2 B]; norm picks the kernel form (MCV_NORM_L2: int8 matrix cores, else XOR / popcount).
+ * Directed problem d < B is pair d (query image first); with crossCheck, d in [B, 2B) is pair d - B reversed.
+ * problems5[5 d ..] (may be NULL): query image, train image, nq, nt, output offset (the queries of the
+ * problems before d). info4: directed problems D, query rows per workgroup, workgroups G, queries of the B
+ * forward problems. wgTable (may be NULL; room for maxWorkgroups entries): G x (problem, query tile), the
+ * problems in descending nt (ties: ascending d), each problem's tiles ascending; a problem with nq == 0
+ * has none. Returns G, -1 on a bad argument. */
+MCV_API int mcvHostMatchBatchLayout(const int* featureCounts, int nImages, const int* imagePairs, int B,
+                                    int crossCheck, int norm, int* problems5, int* info4, int* wgTable,
+                                    int maxWorkgroups);
+/* The calling thread's last cvMatchFeaturesBatch / cvMatchAndFindModelBatch (matching part) /
+ * mcvTestMatchBatchKnn: stats8[0] kernel launches, [1] stream synchronisations, [2] directed problems,
+ * [3] workgroups of the knn launch, [4] host <-> device copies. Returns 1. */
+MCV_API int mcvTestMatchBatchStats(long long* stats8);
+/* Device self-test: the batched knn-2 kernel alone, before any filter. rows: the images' descriptor rows
+ * one image after the other ([sum featureCounts][dim] uint8); directedPairs[2 D]: (query image, train
+ * image) per directed problem; norm MCV_NORM_HAMMING or MCV_NORM_L2. Outputs: problem after problem, nq
+ * entries each; dist / dist2: int32 for Hamming (missing place: -1 / INT_MAX), float for L2 (-1 / +inf).
+ * Returns the number of entries, -1 on failure. */
+MCV_API int mcvTestMatchBatchKnn(const uint8_t* rows, const int* featureCounts, int nImages, int dim,
+                                 const int* directedPairs, int D, int norm, int* idx, void* dist, int* idx2,
+                                 void* dist2);
 MCV_API void mcvHostPhilox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                            uint32_t* out4);
 /* Host twin of CameraPose.findScaled: the same candidates and costs as cvFindScaledPoseCosts,

@@ -422,6 +422,28 @@ void check_match_l2u8(const char* who, int nq, int nt, int dim);
 int launch_match_l2u8(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim, int* d_idx, float* d_dist,
                       int* d_idx2, float* d_dist2, hipStream_t s);
 
+// ---- batched matching (match_batch.hip): B directed problems over one buffer of all images' rows
+// A directed problem: queries = rows [qRow, qRow + nq), train = rows [tRow, tRow + nt) of the
+// concatenated buffer; its outputs start at outOff of the concatenated idx / dist arrays.
+struct MatchBatchProblem {
+    int qRow, nq, tRow, nt, outOff;
+};
+static constexpr int kMatchBatchRowsHamming = 64;   // query rows per workgroup, XOR / popcount form
+static constexpr int kMatchBatchRowsL2 = 128;       // the same, int8 matrix-core form
+// d_src [rows][dim] -> d_dst [rows][KP] (KP a power of two in [32, 512]); shift: x ^ 0x80 and d_norms.
+void launch_match_batch_prep(const uint8_t* d_src, int rows, int dim, int KP, bool shift, uint8_t* d_dst,
+                             int* d_norms, hipStream_t s);
+// d_wg: nwg x (problem, query tile). W = words per padded row (8 or 16).
+void launch_match_batch_hamming(const uint8_t* d_rows, int W, const MatchBatchProblem* d_prob, const int* d_wg,
+                                int nwg, int* d_idx, int* d_dist, int* d_idx2, int* d_dist2, hipStream_t s);
+void launch_match_batch_l2u8(const uint8_t* d_rows, const int* d_norms, int KP, const MatchBatchProblem* d_prob,
+                             const int* d_wg, int nwg, int* d_idx, float* d_dist, int* d_idx2, float* d_dist2,
+                             hipStream_t s);
+void launch_match_batch_compact(const int* d_idx, const int* d_di1, const int* d_di2, const float* d_df1,
+                                const float* d_df2, const MatchBatchProblem* d_prob, const int* d_qStart, int B,
+                                bool cross, int totalQ, float ratio, float maxDist, uint8_t* d_keep, int* d_cnt,
+                                int* d_off, int* d_pairs, float* d_dist, int* d_offsets, hipStream_t s);
+
 // ---- CameraPose.findScaled (scaled_pose.hip)
 struct ScaledSetup;
 void launch_scaled(const ScaledSetup& S, const double* d_w3, const double* d_o2, int N, double* d_soa,

@@ -282,6 +282,8 @@ struct BatchLayout {
     int64_t iters = 1, per = 1, rounds = 0;
 };
 void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L);
+// Throws what cvFindModelBatch refuses a (model, cfg) for, with its message; no device needed.
+void batch_check_config(int model, const RansacConfig* cfg);
 int64_t batch_cap_essential();   // hypotheses a round of the essential batches may hold (mcvTestBatchCap)
 
 }  // namespace mcv

@@ -142,6 +142,15 @@ static RansacConfig batch_check(int model, const mcvV2d* a, const mcvV2d* b, con
     return cfg;
 }
 
+// batch_check's configuration part alone (model, cfg), for callers that build the points themselves.
+void batch_check_config(int model, const RansacConfig* cfgp) {
+    static const int off0[1] = {0};
+    const mcvV2d v{};
+    mcvM33d m;
+    int c = 0;
+    (void)batch_check(model, &v, &v, off0, 0, cfgp, &m, &c);
+}
+
 // The single export on one slice (N == sample size: its direct solve). Returns its count.
 static int batch_single(int model, const mcvV2d* a, const mcvV2d* b, int N, const RansacConfig* cfgp, double* M9,
                         uint8_t* mask) {

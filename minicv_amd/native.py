@@ -88,6 +88,8 @@ BATCH_TILE = 1024       # points per LDS tile of the batched sweep (kernels.h kB
 BATCH_SLOT_CAP = 1 << 21   # slots per hypothesis round of cvFindModelBatch (ransac_batch_host.cpp)
 BATCH_E_TILE = 512         # double4 points per LDS tile of the batched essential sweep (kernels.h kBatchETile)
 BATCH_E_HYP_CAP = 1 << 18  # hypotheses per round of the essential batches (ransac_batch_host.cpp)
+MATCH_BATCH_ROWS_HAMMING = 64   # query rows per workgroup of the batched matcher (kernels.h)
+MATCH_BATCH_ROWS_L2 = 128
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
 NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
@@ -130,6 +132,8 @@ SIGNATURES = {
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "cvMatchFeaturesNorm": (_I, [_P, _P, _P, _I, _P, _P, _I]),
     "cvMatchAndFindModelNorm": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "cvMatchFeaturesBatch": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "cvMatchAndFindModelBatch": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "cvMatchHamming": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cvMatchL2": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "cvMatchHammingMulti": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -211,6 +215,9 @@ SIGNATURES = {
     "mcvTestBatchStats": (_I, [_P]),
     "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),
     "mcvTestBatchSweepE": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
+    "mcvHostMatchBatchLayout": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I]),
+    "mcvTestMatchBatchStats": (_I, [_P]),
+    "mcvTestMatchBatchKnn": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -512,3 +512,53 @@ def matchAndFindModel(a: Features, b: Features, model: int = N.MODEL_HOMOGRAPHY,
     N.check(cnt > 0, "cvMatchAndFindModel")
     k = mc.value
     return cnt, np.array(M.M[:]).reshape(3, 3), pairs[:k].copy(), mask[:k] != 0
+
+
+def _image_batch(images, pairs):
+    structs = (N.DetectorResult * max(len(images), 1))(*[f.struct for f in images])
+    ip = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    B = ip.shape[0]
+    n_img = len(images)
+    cap = sum(images[i].struct.PointCount for i in ip[:, 0] if 0 <= i < n_img)   # always enough
+    return structs, ip, B, cap
+
+
+def matchFeaturesBatch(images, pairs, ratio: float = 0.8, cross_check: bool = False, max_distance: float = 0.0,
+                       norm: int = N.NORM_AUTO):
+    """cvMatchFeaturesBatch: images = a list of Features (uint8 descriptors of one width), pairs = a list of
+    (query image, train image) indices. One call for all pairs; every image goes to the device once.
+    -> a list of (pairs int32 [k][2], dist float32 [k]) per pair, each equal to matchFeatures(images[i],
+    images[j], ...) with the same settings."""
+    structs, ip, B, cap = _image_batch(images, pairs)
+    out = np.zeros((max(cap, 1), 2), dtype=np.int32)
+    dist = np.zeros(max(cap, 1), dtype=np.float32)
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    cfg = _mcfg(ratio, cross_check, max_distance, N.MODEL_HOMOGRAPHY)
+    k = N.lib().cvMatchFeaturesBatch(N.C.addressof(structs), len(images), ip.ctypes.data, B, N.C.addressof(cfg),
+                                     int(norm), out.ctypes.data, dist.ctypes.data, cap, offsets.ctypes.data)
+    N.check(k >= 0, "cvMatchFeaturesBatch")
+    return [(out[offsets[p]:offsets[p + 1]].copy(), dist[offsets[p]:offsets[p + 1]].copy()) for p in range(B)]
+
+
+def matchAndFindModelBatch(images, pairs, model: int = N.MODEL_HOMOGRAPHY, ratio: float = 0.8,
+                           cross_check: bool = False, max_distance: float = 0.0, params: RansacParams | None = None,
+                           norm: int = N.NORM_AUTO):
+    """cvMatchAndFindModelBatch: matchFeaturesBatch, then findModelBatch(model) on the matched keypoints of
+    every pair. -> a list of (count, M 3x3, pairs int32 [k][2], mask bool[k]) per pair; a pair without a
+    model gives (0, zeros, its pairs, all-False) and N.last_error() names the first such pair. params None:
+    cvFindModelBatch's own defaults."""
+    structs, ip, B, cap = _image_batch(images, pairs)
+    out = np.zeros((max(cap, 1), 2), dtype=np.int32)
+    mask = np.zeros(max(cap, 1), dtype=np.uint8)
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    models = np.zeros((max(B, 1), 9), dtype=np.float64)
+    counts = np.zeros(max(B, 1), dtype=np.int32)
+    cfg = _mcfg(ratio, cross_check, max_distance, model)
+    rc = params.to_c() if params is not None else None
+    ret = N.lib().cvMatchAndFindModelBatch(N.C.addressof(structs), len(images), ip.ctypes.data, B, N.C.addressof(cfg),
+                                           int(norm), N.C.addressof(rc) if rc is not None else None, out.ctypes.data,
+                                           cap, offsets.ctypes.data, models.ctypes.data, mask.ctypes.data,
+                                           counts.ctypes.data)
+    N.check(ret >= 0, "cvMatchAndFindModelBatch")
+    return [(int(counts[p]), models[p].reshape(3, 3).copy(), out[offsets[p]:offsets[p + 1]].copy(),
+             mask[offsets[p]:offsets[p + 1]] != 0) for p in range(B)]
