@@ -299,6 +299,29 @@ MCV_API mcvBool cvSolvePnPRansacCfg(const mcvV2d* imgPoints, const mcvV3d* world
                                  const double* distortionCoeffs, const RansacConfig* cfg, mcvV3d* tVec, mcvV3d* rVec,
                                  int* inlierCount, int* outInliers);
 
+/* B independent cvSolvePnPRansacCfg problems in one call, in cvFindModelBatch's conventions: problem p owns
+ * correspondences [offsets[p], offsets[p+1]) of imgPoints / worldPoints (offsets: B + 1 ints, offsets[0] == 0,
+ * non-decreasing). K[B]: per problem; distortionCoeffs: 4 per problem (k1, k2, p1, p2), or NULL: none.
+ * cfg: one for all (NULL: cvSolvePnPRansacCfg's NULL defaults: 100 iterations, 8 px, 0.99, kind 0, OpenCV's
+ * sample stream). tVecs[B], rVecs[B]; mask: uint8[offsets[B]], required: the RANSAC inliers of each problem's
+ * best hypothesis (the single call's index list is its non-zero positions); counts[B]: the inlier counts.
+ * Problem p returns exactly what cvSolvePnPRansacCfg returns for its slice with K[p], its coefficients and
+ * cfg: the same success flag, inlier set and bits of rVec and tVec, refined poses included. A problem on
+ * which the single call returns false or fails (N < 4, no hypothesis with at least 4 inliers, a direct solve
+ * without a solution, fx or fy zero or not finite) gets count 0, a zero pose and a zero mask slice; the
+ * others are untouched and mcvGetLastError() names the first failed problem's index and its message.
+ * The kernel launches, stream synchronisations and copies of a call do not grow with B (problems with exactly
+ * the sample size, N == 4 and N == 5 for the 5-point kinds, take the single export, one by one).
+ * cfg: method MCV_METHOD_RANSAC; every pnpKind; flags any of MCV_FLAG_CV_SAMPLER (one cv::RNG((uint64)-1)
+ * stream per problem), MCV_FLAG_FIXED_ITERS, MCV_FLAG_NO_REFINE; every problem uses cfg->seed. Other methods,
+ * MCV_FLAG_FUSED_ERROR, MCV_FLAG_FAST_MINIMAL, deviceCount > 1, a confidence outside (0, 1) and the retired
+ * bit 4 fail the whole call, as do null arguments, a negative B and bad offsets; every argument check runs
+ * before the device is touched.
+ * Returns the number of problems with a pose (0 for B == 0), -1 on a bad argument or a device failure. */
+MCV_API int cvSolvePnPRansacBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int* offsets, int B,
+                                  const mcvM33d* K, const double* distortionCoeffs, const RansacConfig* cfg,
+                                  mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask, int* counts);
+
 /* Device-resident match -> RANSAC hand-off. Inputs are the reference's
  * DetectorResult (MiniCVNative.h:23-29: KeyPoint2d[PointCount] + row-major descriptors,
  * DescriptorElementType 0 = uint8 -> Hamming, 5 = float32 -> L2). Matching a -> b (knn 2), then
@@ -775,6 +798,17 @@ MCV_API int mcvTestBatchSweep(int model, const float* pts4, const int* offsets, 
  * f_error <= thr2. Returns 1, 0 on failure. */
 MCV_API int mcvTestBatchSweepE(const double* pts4d, const int* offsets, int B, const double* models9,
                                const int* modelOffsets, const float* thr2, int kind, int* counts);
+/* cvSolvePnPRansacBatch shares the hooks above as well: its layout is mcvHostBatchLayout with m = 4 (P3P /
+ * AP3P) or 5 (the other kinds) and its own default cap of 2^18 hypotheses per round; mcvTestBatchCap overrides
+ * it like the essential cap; mcvTestBatchStats reports [3] the lockstep LM steps (at most 21), [6] the host
+ * microseconds staging the raw points and cameras, [8] as for the essential batches and [9] the host <->
+ * device copies enqueued.
+ * Device self-test: the batched PnP sweep (mcv_batch_pnp_sweep) on caller-supplied poses. pts8: the segmented
+ * PnpPoint rows (8 floats: X, Y, Z, u, v, 3 pad), problem p owning [offsets[p], offsets[p+1]); cam8: 8 doubles
+ * per problem (fx, fy, cx, cy, k1, k2, p1, p2); its poses are [poseOffsets[p], poseOffsets[p+1]) of poses12
+ * (R row-major, then t). counts[k] = points of pose k's problem with pnp_error <= thr2. Returns 1, 0 on failure. */
+MCV_API int mcvTestBatchSweepPnp(const float* pts8, const int* offsets, int B, const double* cam8 /* 8 per problem */,
+                                 const double* poses12, const int* poseOffsets, float thr2, int* counts);
 /* The index arithmetic of cvMatchFeaturesBatch, as the export computes it (no device). featureCounts[nImages],
  * imagePairs[2 B]; norm picks the kernel form (MCV_NORM_L2: int8 matrix cores, else XOR / popcount).
  * Directed problem d < B is pair d (query image first); with crossCheck, d in [B, 2B) is pair d - B reversed.

@@ -390,6 +390,63 @@ void launch_batch_e_mask(int kind, const double* d_pts4, const BatchEFin* d_fin,
 void launch_batch_e_cheirality(const double* d_pts4, const uint8_t* d_mask, const BatchEPose* d_pose, int nPose,
                                int maxN, double dist, int* d_good4, hipStream_t s);
 
+// ---- batched PnP RANSAC (ransac_batch_pnp.hip: sweep, fetch, mask; the batch forms of the generate and of
+// the refine passes: ransac_pnp.hip, beside the single forms they share their bodies with). All problems'
+// PnpPoint rows sit in one segmented buffer; cams = 8 doubles (cam8) per device problem. A hypothesis round
+// gives problem j of the round the slots [j stride, j stride + hypCount) of the pose / count buffers (and of
+// the EPnP scratch's columns); the slots past hypCount carry kStatusNoSample and are never read back.
+static const int kBatchPnpTile = 512;    // PnpPoint rows (32 B) staged in LDS per workgroup of the sweep (16 KiB)
+static const int kBatchPnpWidth = 64;    // lanes = poses per workgroup of the sweep
+struct BatchPnpDesc {   // one problem of a hypothesis round
+    BatchDesc d;
+    int cam, pad;            // its camera: cams + 8 cam
+};
+struct BatchPnpFetch {  // one pose to copy out of a round's buffer: best[out] = models[slot]
+    int64_t slot;
+    int out, pad;
+};
+struct BatchPnpFin {    // one winner of the mask: pose best[pose], camera cams + 8 cam
+    int ptOff, N;
+    int pose, cam;
+};
+struct BatchPnpLmJob {  // one job of a batched LM reduction (OpPnpLM's constants)
+    int ptOff, N;
+    double cam[8], R[9], t[3], dR[27];
+};
+struct BatchPnpEpnpJob {   // one job of the batched inlier EPnP
+    int ptOff, N;            // its slice of the mask / index / pw / us buffers
+    int n, nblk;             // the inlier count once the host knows it (n < 0: read count[job]); ceil(N / kEpnpBlock)
+    int64_t partOff;         // its partials: part + partOff, kMtmSums nblk doubles
+    double cam[8];
+    EpnpPassArgs A;
+};
+// The AP3P generate / the five EPnP stages over a round: stride slots per problem, table = the CV sample rows
+// or nullptr. d_scratch: kEpnpSplitDoubles x (nDesc stride) doubles (EPnP). Returns the kernels launched.
+int launch_pnp_batch_generate(const void* d_pts, const BatchPnpDesc* d_desc, int nDesc, int stride, const double* d_cams,
+                              uint64_t seed, const int* d_table, bool epnp, void* d_models, int* d_counts,
+                              double* d_scratch, hipStream_t s);
+// counts[slot] += points of the slot's problem with pnp_error <= thr2 (slots with a negative status untouched)
+void launch_batch_pnp_sweep(const void* d_pts, const BatchPnpDesc* d_desc, int nDesc, int maxHyp, int maxN,
+                            const double* d_cams, const void* d_models, int* d_counts, float thr2, hipStream_t s);
+void launch_batch_pnp_fetch(const BatchPnpFetch* d_fetch, int nFetch, const void* d_models, void* d_best, hipStream_t s);
+// d_mask: the segmented mask; d_count[f] += inliers (zeroed by the caller)
+void launch_batch_pnp_mask(const void* d_pts, const BatchPnpFin* d_fin, int nFin, int maxN, const double* d_cams,
+                           const void* d_best, float thr2, uint8_t* d_mask, int* d_count, hipStream_t s);
+// pnp_reduce_lm (wantJ) for every job: d_part = nJobs x reduce_blocks(maxN) x 28, d_out = nJobs x 28. Returns 2.
+int launch_pnp_batch_reduce_lm(const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs, int nJobs,
+                               int maxN, double* d_part, double* d_out, hipStream_t s);
+// The inlier EPnP's device steps for every job (grid y = job). compact + prep: d_idx / d_pw / d_us are segmented
+// like the mask (idx + ptOff, pw + 3 ptOff, us + 2 ptOff), d_count one int per job. Returns 2.
+int launch_pnp_batch_epnp_prep(const void* d_pts, const uint8_t* d_mask, const BatchPnpEpnpJob* d_jobs, int nJobs,
+                               int maxN, int* d_idx, int* d_count, double* d_pw, double* d_us, hipStream_t s);
+// One pass: job j's partials land at d_part + partOff + regionOff(nblk) as part[acc * nblk + blk], nblk the
+// blocks of its inlier count; region: 0 = offset 0, 1 = offset 3 nblkMax (Pw0 beside SumPw), 2 = offset 9 nblk
+// (Abt beside Pc). prevRegion >= 0: the pass takes its means from that region's partials (Pw0, Abt).
+// Returns the kernels launched (1 up to 65535 jobs, the grid's y limit).
+int launch_pnp_batch_epnp_pass(int mode, const BatchPnpEpnpJob* d_jobs, int nJobs, int maxNblk, const int* d_count,
+                               const double* d_pw, const double* d_us, int nacc, int region, int prevRegion,
+                               double* d_part, hipStream_t s);
+
 // ---- shared (ransac_common.hip)
 void launch_best(const int* d_counts, int n, int64_t hypBegin, int minCount, uint64_t* d_pkey, int64_t* d_pfail,
                  uint64_t* d_out, hipStream_t s);

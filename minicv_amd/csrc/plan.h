@@ -249,6 +249,8 @@ void p_evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
 int p_finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
                uint8_t* d_mask, hipStream_t s);
 bool pnp_cfg_epnp(const RansacConfig& cfg);   // minimal sets of 5 for EPnP (solverKind 0/1/3/4)
+// cvSolvePnPRansac's configuration: OpenCV's sample stream, RANSAC, the given budget / threshold / kind
+RansacConfig pnp_config(int iters, float thr, double conf, int kind);
 
 // essential-matrix family (ransac_e.hip / ransac_e_host.cpp)
 void e_evaluate_chunk(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
@@ -268,6 +270,7 @@ struct BatchStats {
     long long launches = 0, syncs = 0, rounds = 0, lmRounds = 0, single = 0, problems = 0;
     long long packUs = 0, tableUs = 0;   // host time: point conversion, OpenCV sample tables
     long long problemRounds = 0;         // essential batches: problems summed over the rounds they ran in
+    long long copies = 0;                // PnP batch: host <-> device copies enqueued
 };
 BatchStats& batch_stats();   // the calling thread's last batch call (mcvTestBatchStats)
 // The index arithmetic of a batch call (mcvHostBatchLayout exposes it). Problems with more points than
@@ -285,5 +288,6 @@ void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, B
 // Throws what cvFindModelBatch refuses a (model, cfg) for, with its message; no device needed.
 void batch_check_config(int model, const RansacConfig* cfg);
 int64_t batch_cap_essential();   // hypotheses a round of the essential batches may hold (mcvTestBatchCap)
+int64_t batch_cap_pnp();         // the same for cvSolvePnPRansacBatch
 
 }  // namespace mcv

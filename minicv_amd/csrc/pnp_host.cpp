@@ -16,6 +16,7 @@
 #include "hyp_pnp.h"
 #include "pnp_pk.h"
 #include "sqpnp.h"
+#include "pnp_refine.h"
 
 #include <cmath>
 #include <cfloat>
@@ -172,56 +173,19 @@ static int pnp_mask_count(Plan& P, const void* d_pts, int N, const RansacConfig&
 // steps, stop when the step is below FLT_EPSILON relative to the parameters or the cost stalls.
 void pnp_lm(Plan& P, const void* d_pts, int N, const uint8_t* d_mask, double* rvec, double* t, int maxIters,
             hipStream_t s) {
-    double p[6] = {rvec[0], rvec[1], rvec[2], t[0], t[1], t[2]};
-    auto eval = [&](const double* q, bool wantJ, double* A, double* g) -> double {
+    // the controller is PnpLmStepper (pnp_refine.h), which the batched call runs in lockstep over its winners
+    PnpLmStepper st;
+    st.begin(rvec, t, maxIters);
+    while (!st.finished()) {
+        const double* q = st.request();
         double R[9], dR[27], buf[28];
-        rodrigues(q, R, wantJ ? dR : nullptr);
+        rodrigues(q, R, dR);
         reduce_to_host(P, s, 28, buf, [&](double* part, double* red) {
-            pnp_reduce_lm(d_pts, N, d_mask, P.pnpCam, R, q + 3, wantJ ? dR : nullptr, wantJ, part, red, s);
+            pnp_reduce_lm(d_pts, N, d_mask, P.pnpCam, R, q + 3, dR, true, part, red, s);
         });
-        if (wantJ) {
-            int o = 0;
-            for (int j = 0; j < 6; ++j)
-                for (int k = j; k < 6; ++k) { A[6 * j + k] = buf[o]; A[6 * k + j] = buf[o]; ++o; }
-            for (int j = 0; j < 6; ++j) g[j] = buf[21 + j];
-        }
-        return buf[27];
-    };
-    double A[36], g[6];
-    double S = eval(p, true, A, g);
-    double lambda = 1e-3;
-    for (int it = 0; it < maxIters; ++it) {
-        double M[36], rhs[6], d[6];
-        for (int k = 0; k < 36; ++k) M[k] = A[k];
-        for (int k = 0; k < 6; ++k) {
-            M[7 * k] = A[7 * k] + lambda * std::max(A[7 * k], DBL_EPSILON);
-            rhs[k] = -g[k];
-        }
-        eig_solve(M, 6, rhs, d);
-        double q[6], dn = 0, pn = 0;
-        for (int k = 0; k < 6; ++k) {
-            q[k] = p[k] + d[k];
-            dn = std::max(dn, std::fabs(d[k]));
-            pn = std::max(pn, std::fabs(p[k]));
-        }
-        // the normal equations at q ride along with its cost (one synchronisation per step); on
-        // acceptance they equal the re-evaluation at the new p (same sums, same order)
-        double Aq[36], gq[6];
-        const double Sq = eval(q, true, Aq, gq);
-        if (Sq < S) {
-            const bool stall = (S - Sq) <= FLT_EPSILON * S;
-            for (int k = 0; k < 6; ++k) p[k] = q[k];
-            lambda = std::max(lambda * 0.1, 1e-12);
-            S = Sq;
-            std::memcpy(A, Aq, sizeof(Aq));
-            std::memcpy(g, gq, sizeof(gq));
-            if (stall || dn <= FLT_EPSILON * (pn + FLT_EPSILON)) break;
-        } else {
-            lambda *= 10;
-            if (dn <= FLT_EPSILON * (pn + FLT_EPSILON) || lambda > 1e16) break;
-        }
+        st.feed(buf);
     }
-    for (int k = 0; k < 3; ++k) { rvec[k] = p[k]; t[k] = p[3 + k]; }
+    st.result(rvec, t);
 }
 
 // Virtual visual servoing (solvePnPRefineVVS restated): v = -lambda (L^T L)^+ L^T e on the
@@ -318,47 +282,23 @@ static void epnp_device(Plan& P, const double* d_pw, const double* d_us, int n, 
         epnp_sums(part, 0, 3, nblk, sum);
         epnp_sums(part, off1, 6, nblk, p6);
     }
-    for (int j = 0; j < 3; ++j) A.c0[j] = sum[j] / n;
-    const double P3[3][3] = {{p6[0], p6[1], p6[2]}, {p6[1], p6[3], p6[4]}, {p6[2], p6[4], p6[5]}};
-    epnp_control(sum, P3, n, A.C);
+    // the algebra between the passes is EpnpHostSolve (pnp_refine.h), shared with the batched call
+    EpnpHostSolve H;
+    H.first(A, sum, p6, n);
     launch(kEpnpPassMtm, kMtmSums, 0, nullptr);
     fetch((size_t)kMtmSums * nblk);
     epnp_sums(part, 0, kMtmSums, nblk, mtm);
-    EpnpBetas B;
-    epnp_betas(mtm, A.C, B);
-    double al0[4];
-    epnp_alphas(A.C, p0, al0);
-    for (int N = 0; N < 3; ++N) {
-        epnp_ccs(B, B.betas[N + 1], A.ccs[N]);
-        double pc[3];
-        epnp_pc(al0, A.ccs[N], pc);
-        if (pc[2] < 0.0)   // solve_for_sign on the first point; -ccs gives exactly the negated pcs
-            for (int j = 0; j < 4; ++j)
-                for (int k = 0; k < 3; ++k) A.ccs[N][j][k] = -A.ccs[N][j][k];
-    }
-    for (int j = 0; j < 3; ++j) A.pw0[j] = sum[j] / n;
+    H.mtm(A, mtm, p0);
     launch(kEpnpPassPc, 9, 0, nullptr);
     launch(kEpnpPassAbt, 27, off1, P.part.p);   // pc0 from Pc's partials on the device
     fetch(off1 + (size_t)27 * nblk);
     epnp_sums(part, 0, 9, nblk, pcs);
     epnp_sums(part, off1, 27, nblk, abt);
-    for (int N = 0; N < 3; ++N)
-        for (int j = 0; j < 3; ++j) A.pc0[N][j] = pcs[3 * N + j] / n;
-    for (int N = 0; N < 3; ++N) {
-        double ab[3][3];
-        for (int j = 0; j < 3; ++j)
-            for (int k = 0; k < 3; ++k) ab[j][k] = abt[9 * N + 3 * j + k];
-        epnp_rt(ab, A.pc0[N], A.pw0, A.R[N], A.t[N]);
-    }
+    H.abt(A, pcs, abt);
     launch(kEpnpPassReproj, 3, 0, nullptr);
     fetch((size_t)3 * nblk);
     epnp_sums(part, 0, 3, nblk, rep3);
-    const double rep[4] = {0, rep3[0] / n, rep3[1] / n, rep3[2] / n};
-    const int N = epnp_pick(rep) - 1;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) R9[3 * i + j] = A.R[N][i][j];
-        t3[i] = A.t[N][i];
-    }
+    H.pick(A, rep3, R9, t3);
 }
 
 // solvePnP(SOLVEPNP_SQPNP) (reference MiniCVNative.cpp:72-74, :82): undistortPoints' normalised
@@ -529,7 +469,7 @@ static PnpResult pnp_ransac(Plan& P, const mcvV2d* img, const mcvV3d* world, int
     return res;
 }
 
-static RansacConfig pnp_config(int iters, float thr, double conf, int kind) {
+RansacConfig pnp_config(int iters, float thr, double conf, int kind) {
     RansacConfig c;
     std::memset(&c, 0, sizeof(c));
     c.threshold = (double)thr;

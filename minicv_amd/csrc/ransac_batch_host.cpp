@@ -45,6 +45,11 @@ static int64_t g_batch_cap = kBatchSlotCap;   // mcvTestBatchCap
 // mcvTestBatchCap overrides both: a cap other than the 2-D default holds for this family too.
 static const int64_t kBatchHypCapE = (int64_t)1 << 18;
 int64_t batch_cap_essential() { return g_batch_cap == kBatchSlotCap ? kBatchHypCapE : g_batch_cap; }
+// The PnP batch counts hypotheses too: an EPnP hypothesis holds kEpnpSplitDoubles = 291 doubles of split-solve
+// scratch (2328 B), a 96 B pose and a 4 B count, so 2^18 of them are 0.64 GB (B = 1024 problems of the default
+// 100 iterations fit one round with room to spare). AP3P rounds hold only the poses and counts.
+static const int64_t kBatchHypCapPnp = (int64_t)1 << 18;
+int64_t batch_cap_pnp() { return g_batch_cap == kBatchSlotCap ? kBatchHypCapPnp : g_batch_cap; }
 
 static long long us_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -510,6 +515,7 @@ extern "C" MCV_API int mcvTestBatchStats(long long* stats16) {
     stats16[6] = t_stats.packUs;
     stats16[7] = t_stats.tableUs;
     stats16[8] = t_stats.problemRounds;
+    stats16[9] = t_stats.copies;
     return 1;
 }
 

@@ -15,6 +15,9 @@
 //                        O(n) loops; the O(1) algebra between the passes runs on the host (epnp.h).
 //   OpPnpLM / OpPnpVVS   fixed-order fp64 reductions for the LM refit / VVS refinement.
 //   mcv_pnp_ap3p         solveAp3p export: one AP3P solve (3 points).
+//   BATCH forms          cvSolvePnPRansacBatch: the generate kernels, mcv_mask_compact,
+//                        mcv_epnp_prep_f32, mcv_epnp_pass and the LM reduction over many problems at once,
+//                        compiled from the same bodies; their launchers are at the end of the file.
 #include "mcv_common.h"
 #include "hyp_pnp.h"
 #include "pnp_pk.h"
@@ -39,13 +42,65 @@ __global__ __launch_bounds__(256) void mcv_pnp_pack(const double* __restrict__ i
     out[i] = p;
 }
 
+static __host__ __device__ PnpCamera to_cam(const double* cam8) {
+    PnpCamera c;
+    c.fx = cam8[0]; c.fy = cam8[1]; c.cx = cam8[2]; c.cy = cam8[3];
+    c.k1 = cam8[4]; c.k2 = cam8[5]; c.p1 = cam8[6]; c.p2 = cam8[7];
+    return c;
+}
+
+// BATCH (cvSolvePnPRansacBatch, ransac_batch_pnp_host.cpp): the grid is (block within problem, problem); the
+// lane's problem supplies the point slice, the hypothesis range, the camera and the sampler rows (smp.table =
+// the call's table, the problem's rows from rowOff), and the lane's slot is slotOff + its index in the round.
+// Slots of the problem's stride past its hypCount get kStatusNoSample. The hypothesis itself is the same call.
+struct PnpBatchLane {
+    const PnpPoint* pts;
+    int N;
+    PnpCamera cam;
+    Sampler smp;
+    uint64_t hyp;
+    int64_t slot;
+    bool live, pad;   // pad: a slot of the stride past the problem's hypotheses
+};
+template <int M>
+__device__ __forceinline__ PnpBatchLane pnp_batch_lane(const PnpPoint* pts, Sampler smp, const BatchPnpDesc* desc,
+                                                       int blocksPer, int stride, const double* cams, int lanes) {
+    const BatchPnpDesc D = desc[blockIdx.x / blocksPer];
+    const int i = (blockIdx.x % blocksPer) * lanes + threadIdx.x;
+    PnpBatchLane L;
+    L.pts = pts + D.d.ptOff;
+    L.N = D.d.N;
+    L.cam = to_cam(cams + 8 * (size_t)D.cam);
+    L.smp.seed = smp.seed;
+    L.smp.table = smp.table ? smp.table + D.d.rowOff * M : nullptr;
+    L.hyp = (uint64_t)(D.d.hypBegin + i);
+    L.slot = D.d.slotOff + i;
+    L.live = i < D.d.hypCount;
+    L.pad = !L.live && i < stride;
+    return L;
+}
+
 // AP3P: one hypothesis per lane, one kernel.
+template <bool BATCH>
 __global__ __launch_bounds__(64) void mcv_pnp_generate(const PnpPoint* __restrict__ pts, int N, PnpCamera cam,
                                                        Sampler smp, int64_t hypBegin, int hypCount,
                                                        PnpPose* __restrict__ models, int* __restrict__ counts,
-                                                       bool fast) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= hypCount) return;
+                                                       bool fast, const BatchPnpDesc* __restrict__ desc,
+                                                       int blocksPer, int stride, const double* __restrict__ cams) {
+    int64_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (BATCH) {
+        const PnpBatchLane L = pnp_batch_lane<4>(pts, smp, desc, blocksPer, stride, cams, 64);
+        if (L.pad) counts[L.slot] = kStatusNoSample;
+        if (!L.live) return;
+        pts = L.pts; N = L.N; cam = L.cam; smp = L.smp;
+        hypBegin = (int64_t)L.hyp;
+        i = L.slot;
+        models += i;
+        counts += i;
+        i = 0;
+    } else {
+        if (i >= hypCount) return;
+    }
     PnpPose p;
     const int st = pnp_hypothesis(pts, N, cam, smp, (uint64_t)(hypBegin + i), p, nullptr, fast);
     if (st == 1) {
@@ -59,9 +114,22 @@ __global__ __launch_bounds__(64) void mcv_pnp_generate(const PnpPoint* __restric
 // EPnP: pnp_hypothesis_epnp split in five kernels (hyp_pnp.h, EpnpSplit). The sweeps kernel keeps half
 // of each lane's 12 x 12 in LDS (37 KB per wave, four waves per CU) and half in registers; the betas
 // kernel keeps L_6x10 / rho in a per-lane LDS slice; the others hold no LDS.
+// BATCH: the scratch's column is the lane's slot (X.s = the round's slots); the three middle kernels run over
+// the round's slots as they are (a slot without a sample is skipped by its status), and the pose kernel
+// takes the camera of the slot's problem (slot / stride).
+template <bool BATCH>
 __global__ __launch_bounds__(256) void mcv_epnp_split_mtm(const PnpPoint* __restrict__ pts, int N, PnpCamera cam,
                                                           Sampler smp, int64_t hypBegin, int hypCount, EpnpSplit X,
-                                                          int* __restrict__ counts) {
+                                                          int* __restrict__ counts,
+                                                          const BatchPnpDesc* __restrict__ desc, int blocksPer,
+                                                          int stride, const double* __restrict__ cams) {
+    if constexpr (BATCH) {
+        const PnpBatchLane L = pnp_batch_lane<5>(pts, smp, desc, blocksPer, stride, cams, 256);
+        if (L.pad) counts[L.slot] = kStatusNoSample;
+        if (!L.live) return;
+        counts[L.slot] = pnp_epnp_split_mtm(L.pts, L.N, L.cam, L.smp, L.hyp, X, L.slot) == 1 ? 0 : kStatusNoSample;
+        return;
+    }
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= hypCount) return;
     counts[i] = pnp_epnp_split_mtm(pts, N, cam, smp, (uint64_t)(hypBegin + i), X, i) == 1 ? 0 : kStatusNoSample;
@@ -84,10 +152,14 @@ __global__ __launch_bounds__(64) void mcv_epnp_split_betas(EpnpSplit X, const in
     if (i >= hypCount || counts[i] < 0) return;
     pnp_epnp_split_betas(X, i, lds + threadIdx.x * 67);
 }
+template <bool BATCH>
 __global__ __launch_bounds__(256) void mcv_epnp_split_pose(PnpCamera cam, EpnpSplit X, PnpPose* __restrict__ models,
-                                                           const int* __restrict__ counts, int hypCount) {
+                                                           const int* __restrict__ counts, int hypCount,
+                                                           const BatchPnpDesc* __restrict__ desc, int stride,
+                                                           const double* __restrict__ cams) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= hypCount || counts[i] < 0) return;
+    if constexpr (BATCH) cam = to_cam(cams + 8 * (size_t)desc[i / stride].cam);
     PnpPose p;
     pnp_epnp_split_pose(cam, X, i, p);
     models[i] = p;
@@ -586,8 +658,17 @@ struct OpPnpVVS {
 // ---- EPnP on a large point set (the inlier solve of solvePnPRansac, solvePnP(EPNP)) ----------
 // Mask -> ascending index list (one block, 1024 threads, chunked ballot scan): the inliers in the
 // order compressElems keeps them.
+// jobs (the batched inlier EPnP): block j compacts job j's slice of the segmented mask into its slice of idx.
 __global__ __launch_bounds__(1024) void mcv_mask_compact(const uint8_t* __restrict__ mask, int N,
-                                                         int* __restrict__ idx, int* __restrict__ count) {
+                                                         int* __restrict__ idx, int* __restrict__ count,
+                                                         const BatchPnpEpnpJob* __restrict__ jobs) {
+    if (jobs) {
+        const int ptOff = jobs[blockIdx.x].ptOff;
+        mask += ptOff;
+        idx += ptOff;
+        N = jobs[blockIdx.x].N;
+        count += blockIdx.x;
+    }
     __shared__ int wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int base = 0;
@@ -613,8 +694,18 @@ __global__ __launch_bounds__(1024) void mcv_mask_compact(const uint8_t* __restri
 // Points of the solve in double: pw = world, us = undistortPoints (double result) * f + c.
 __global__ __launch_bounds__(256) void mcv_epnp_prep_f32(const PnpPoint* __restrict__ pts, const int* __restrict__ idx,
                                                          int n, PnpCamera c, double* __restrict__ pw,
-                                                         double* __restrict__ us, const int* __restrict__ nDev) {
+                                                         double* __restrict__ us, const int* __restrict__ nDev,
+                                                         const BatchPnpEpnpJob* __restrict__ jobs) {
     const int i = blockIdx.x * 256 + threadIdx.x;
+    if (jobs) {   // grid y = the job: its slices of the segmented buffers, its camera, its device count
+        const BatchPnpEpnpJob& J = jobs[blockIdx.y];
+        pts += J.ptOff;
+        idx += J.ptOff;
+        pw += 3 * (size_t)J.ptOff;
+        us += 2 * (size_t)J.ptOff;
+        c = to_cam(J.cam);
+        nDev += blockIdx.y;
+    }
     if (nDev) n = *nDev;
     if (i >= n) return;
     const PnpPoint p = pts[idx ? idx[i] : i];
@@ -690,11 +781,32 @@ __device__ __forceinline__ void epnp_pass_term(const double* __restrict__ pw, co
 // would. The terms of a tile of kEpnpTile points are computed by all lanes in parallel into LDS
 // first, so the ordered chains only add. Partials part[acc * nblk + blk], summed over blocks in
 // order on the host.
-template <int MODE>
+// BATCH (the batched inlier EPnP): grid y = the job; its point slices, arguments, count and partial regions
+// come from its table row (kernels.h BatchPnpEpnpJob), n / nblk / part / prev below are then derived from it
+// and the body is the same.
+__device__ __forceinline__ int64_t epnp_batch_region(int region, int nblkMax, int nblk) {
+    return region == 1 ? (int64_t)3 * nblkMax : (region == 2 ? (int64_t)9 * nblk : 0);
+}
+template <int MODE, bool BATCH>
 __global__ __launch_bounds__(256) void mcv_epnp_pass(const double* __restrict__ pw, const double* __restrict__ us,
                                                      int n, EpnpPassArgs A, int nacc, int nblk,
                                                      double* __restrict__ part, const int* __restrict__ nDev,
-                                                     const double* __restrict__ prev) {
+                                                     const double* __restrict__ prev,
+                                                     const BatchPnpEpnpJob* __restrict__ jobs, int region,
+                                                     int prevRegion) {
+    if constexpr (BATCH) {
+        const BatchPnpEpnpJob& J = jobs[blockIdx.y];
+        n = J.n >= 0 ? J.n : nDev[blockIdx.y];
+        nDev = nullptr;
+        nblk = (n + kEpnpBlock - 1) / kEpnpBlock;
+        if ((int)blockIdx.x >= nblk) return;
+        A = J.A;
+        pw += 3 * (size_t)J.ptOff;
+        us += 2 * (size_t)J.ptOff;
+        double* base = part + J.partOff;
+        part = base + epnp_batch_region(region, J.nblk, nblk);
+        prev = prevRegion >= 0 ? base + epnp_batch_region(prevRegion, J.nblk, nblk) : nullptr;
+    }
     if (nDev) {   // the grid covers the upper bound: blocks past the device count's write nothing
         n = *nDev;
         nblk = (n + kEpnpBlock - 1) / kEpnpBlock;
@@ -794,13 +906,6 @@ __global__ __launch_bounds__(256) void mcv_epnp_pass(const double* __restrict__ 
 }
 
 // ---- launchers --------------------------------------------------------------------------------
-static PnpCamera to_cam(const double* cam8) {
-    PnpCamera c;
-    c.fx = cam8[0]; c.fy = cam8[1]; c.cx = cam8[2]; c.cy = cam8[3];
-    c.k1 = cam8[4]; c.k2 = cam8[5]; c.p1 = cam8[6]; c.p2 = cam8[7];
-    return c;
-}
-
 void launch_pnp_pack(const double* d_img, const double* d_world, int N, void* d_pts, hipStream_t s) {
     if (N <= 0) return;
     hipLaunchKernelGGL(mcv_pnp_pack, dim3((N + 255) / 256), dim3(256), 0, s, d_img, d_world, N, (PnpPoint*)d_pts);
@@ -809,8 +914,9 @@ void launch_pnp_pack(const double* d_img, const double* d_world, int N, void* d_
 void launch_pnp_generate(const void* d_pts, int N, const double* cam8, Sampler smp, int64_t hypBegin, int hypCount,
                          bool epnp, void* d_models, int* d_counts, double* d_epnpScratch, hipStream_t s, bool fast) {
     if (!epnp) {
-        hipLaunchKernelGGL(mcv_pnp_generate, dim3((hypCount + 63) / 64), dim3(64), 0, s, (const PnpPoint*)d_pts, N,
-                           to_cam(cam8), smp, hypBegin, hypCount, (PnpPose*)d_models, d_counts, fast);
+        hipLaunchKernelGGL(mcv_pnp_generate<false>, dim3((hypCount + 63) / 64), dim3(64), 0, s, (const PnpPoint*)d_pts,
+                           N, to_cam(cam8), smp, hypBegin, hypCount, (PnpPose*)d_models, d_counts, fast,
+                           (const BatchPnpDesc*)nullptr, 0, 0, (const double*)nullptr);
         return;
     }
     // sub-ranges of at most kEpnpPiece hypotheses reuse one scratch of kEpnpPiece x kEpnpSplitDoubles
@@ -825,12 +931,14 @@ void launch_pnp_generate(const void* d_pts, int N, const double* cam8, Sampler s
         const int n = std::min(piece, hypCount - off);
         int* cnt = d_counts + off;
         PnpPose* mdl = (PnpPose*)d_models + off;
-        hipLaunchKernelGGL(mcv_epnp_split_mtm, dim3((n + 255) / 256), dim3(256), 0, s, (const PnpPoint*)d_pts, N, cam,
-                           smp, hypBegin + off, n, X, cnt);
+        hipLaunchKernelGGL(mcv_epnp_split_mtm<false>, dim3((n + 255) / 256), dim3(256), 0, s, (const PnpPoint*)d_pts, N,
+                           cam, smp, hypBegin + off, n, X, cnt, (const BatchPnpDesc*)nullptr, 0, 0,
+                           (const double*)nullptr);
         hipLaunchKernelGGL(mcv_epnp_split_sweeps, dim3((n + 63) / 64), dim3(64), 0, s, X, (const int*)cnt, n);
         hipLaunchKernelGGL(mcv_epnp_split_tail, dim3((n + 255) / 256), dim3(256), 0, s, X, (const int*)cnt, n);
         hipLaunchKernelGGL(mcv_epnp_split_betas, dim3((n + 63) / 64), dim3(64), 0, s, X, (const int*)cnt, n);
-        hipLaunchKernelGGL(mcv_epnp_split_pose, dim3((n + 255) / 256), dim3(256), 0, s, cam, X, mdl, (const int*)cnt, n);
+        hipLaunchKernelGGL(mcv_epnp_split_pose<false>, dim3((n + 255) / 256), dim3(256), 0, s, cam, X, mdl,
+                           (const int*)cnt, n, (const BatchPnpDesc*)nullptr, 0, (const double*)nullptr);
     }
 }
 
@@ -916,7 +1024,8 @@ void launch_pnp_solve5(const void* d_pts, const double* cam8, PnpOneOut* d_out, 
 }
 
 void launch_mask_compact(const uint8_t* d_mask, int N, int* d_idx, int* d_count, hipStream_t s) {
-    hipLaunchKernelGGL(mcv_mask_compact, dim3(1), dim3(1024), 0, s, d_mask, N, d_idx, d_count);
+    hipLaunchKernelGGL(mcv_mask_compact, dim3(1), dim3(1024), 0, s, d_mask, N, d_idx, d_count,
+                       (const BatchPnpEpnpJob*)nullptr);
 }
 
 // d_n applies to the fp32 points (the inlier solve); the fp64 form always takes n.
@@ -925,7 +1034,7 @@ void launch_epnp_prep(const void* d_pts, const int* d_idx, const double* d_img, 
     if (n <= 0) return;
     if (d_pts)
         hipLaunchKernelGGL(mcv_epnp_prep_f32, dim3((n + 255) / 256), dim3(256), 0, s, (const PnpPoint*)d_pts, d_idx, n,
-                           to_cam(cam8), d_pw, d_us, d_n);
+                           to_cam(cam8), d_pw, d_us, d_n, (const BatchPnpEpnpJob*)nullptr);
     else
         hipLaunchKernelGGL(mcv_epnp_prep_f64, dim3((n + 255) / 256), dim3(256), 0, s, d_img, d_world, n, to_cam(cam8),
                            d_pw, d_us, normalized);
@@ -937,15 +1046,16 @@ void launch_epnp_pass(int mode, const double* d_pw, const double* d_us, int n, c
     const int nblk = (n + kEpnpBlock - 1) / kEpnpBlock;
     if (nblk <= 0) return;
     const dim3 grid(nblk), block(256);   // nacc <= 78 accumulators, one lane each
+    const BatchPnpEpnpJob* const kNoJobs = nullptr;
     switch (mode) {
-        case kEpnpPassSumPw: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassSumPw>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassPw0: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassPw0>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassMtm: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassMtm>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassPc: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassPc>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassAbt: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassAbt>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassSqp: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassSqp>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        case kEpnpPassSqpDepth: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassSqpDepth>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev); break;
-        default: hipLaunchKernelGGL(mcv_epnp_pass<kEpnpPassReproj>, grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev);
+        case kEpnpPassSumPw: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassSumPw, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassPw0: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassPw0, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassMtm: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassMtm, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassPc: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassPc, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassAbt: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassAbt, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassSqp: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassSqp, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        case kEpnpPassSqpDepth: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassSqpDepth, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1); break;
+        default: hipLaunchKernelGGL((mcv_epnp_pass<kEpnpPassReproj, false>), grid, block, 0, s, d_pw, d_us, n, a, nacc, nblk, d_part, d_n, d_prev, kNoJobs, 0, -1);
     }
 }
 
@@ -995,6 +1105,131 @@ void pnp_reduce_vvs(const void* d_pts, int N, const uint8_t* d_mask, const doubl
     for (int k = 0; k < 9; ++k) op.R[k] = R9[k];
     for (int k = 0; k < 3; ++k) op.t[k] = t3[k];
     run_reduce<28>(N, op, d_part, d_out, s);
+}
+
+// ---- batch forms (cvSolvePnPRansacBatch) -------------------------------------------------------
+static const int kGridYMax = 65535;
+int launch_pnp_batch_generate(const void* d_pts, const BatchPnpDesc* d_desc, int nDesc, int stride, const double* d_cams,
+                              uint64_t seed, const int* d_table, bool epnp, void* d_models, int* d_counts,
+                              double* d_scratch, hipStream_t s) {
+    const PnpPoint* pts = (const PnpPoint*)d_pts;
+    const Sampler smp{seed, d_table};
+    const PnpCamera none{};
+    if (!epnp) {
+        const int per = (stride + 63) / 64;
+        hipLaunchKernelGGL(mcv_pnp_generate<true>, dim3((unsigned)per * nDesc), dim3(64), 0, s, pts, 0, none, smp,
+                           (int64_t)0, 0, (PnpPose*)d_models, d_counts, false, d_desc, per, stride, d_cams);
+        return 1;
+    }
+    const int64_t S = (int64_t)nDesc * stride;
+    const int n = (int)S;
+    const EpnpSplit X{d_scratch, d_scratch + kMtmSums * S, d_scratch + (kMtmSums + kEpnpCtx) * S,
+                      d_scratch + (kMtmSums + kEpnpCtx + 144) * S, S};
+    const int per = (stride + 255) / 256;
+    hipLaunchKernelGGL(mcv_epnp_split_mtm<true>, dim3((unsigned)per * nDesc), dim3(256), 0, s, pts, 0, none, smp,
+                       (int64_t)0, 0, X, d_counts, d_desc, per, stride, d_cams);
+    hipLaunchKernelGGL(mcv_epnp_split_sweeps, dim3((n + 63) / 64), dim3(64), 0, s, X, (const int*)d_counts, n);
+    hipLaunchKernelGGL(mcv_epnp_split_tail, dim3((n + 255) / 256), dim3(256), 0, s, X, (const int*)d_counts, n);
+    hipLaunchKernelGGL(mcv_epnp_split_betas, dim3((n + 63) / 64), dim3(64), 0, s, X, (const int*)d_counts, n);
+    hipLaunchKernelGGL(mcv_epnp_split_pose<true>, dim3((n + 255) / 256), dim3(256), 0, s, none, X, (PnpPose*)d_models,
+                       (const int*)d_counts, n, d_desc, stride, d_cams);
+    return 5;
+}
+
+// pnp_reduce_lm's two stages for many jobs at once (ransac_batch.hip's pattern): job r's partials are those of
+// reduce_blocks(N_r) blocks strided by its own grid, summed in block order by reduce_final's loop.
+__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_pass(const PnpPoint* __restrict__ pts,
+                                                                               const uint8_t* __restrict__ mask,
+                                                                               const BatchPnpLmJob* __restrict__ jobs,
+                                                                               int blocksPer,
+                                                                               double* __restrict__ partials) {
+    const int r = blockIdx.x / blocksPer, b = blockIdx.x % blocksPer;
+    const BatchPnpLmJob& J = jobs[r];
+    const int N = J.N;
+    const int nb = reduce_blocks(N);
+    if (b >= nb) return;   // uniform over the workgroup
+    OpPnpLM op;
+    op.pts = pts + J.ptOff;
+    op.mask = mask + J.ptOff;
+    op.c = to_cam(J.cam);
+    for (int k = 0; k < 9; ++k) op.R[k] = J.R[k];
+    for (int k = 0; k < 3; ++k) op.t[k] = J.t[k];
+    for (int k = 0; k < 27; ++k) op.dR[k] = J.dR[k];
+    op.wantJ = true;
+    double acc[28];
+#pragma unroll
+    for (int v = 0; v < 28; ++v) acc[v] = 0;
+    for (int i = b * kReduceThreads + threadIdx.x; i < N; i += nb * kReduceThreads) op(i, acc);
+    block_sum<28>(acc, partials + ((size_t)r * blocksPer + b) * 28);
+}
+
+__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_final(const BatchPnpLmJob* __restrict__ jobs,
+                                                                                int blocksPer,
+                                                                                const double* __restrict__ partials,
+                                                                                double* __restrict__ out) {
+    const int r = blockIdx.x;
+    const int nb = reduce_blocks(jobs[r].N);
+    const double* part = partials + (size_t)r * blocksPer * 28;
+    double acc[28];
+#pragma unroll
+    for (int v = 0; v < 28; ++v) acc[v] = 0;
+    for (int b = threadIdx.x; b < nb; b += kReduceThreads) {
+#pragma unroll
+        for (int v = 0; v < 28; ++v) acc[v] += part[(size_t)b * 28 + v];
+    }
+    block_sum<28>(acc, out + (size_t)r * 28);
+}
+
+int launch_pnp_batch_reduce_lm(const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs, int nJobs,
+                               int maxN, double* d_part, double* d_out, hipStream_t s) {
+    const int per = reduce_blocks(maxN);
+    hipLaunchKernelGGL(mcv_pnp_batch_reduce_lm_pass, dim3((unsigned)per * nJobs), dim3(kReduceThreads), 0, s,
+                       (const PnpPoint*)d_pts, d_mask, d_jobs, per, d_part);
+    hipLaunchKernelGGL(mcv_pnp_batch_reduce_lm_final, dim3(nJobs), dim3(kReduceThreads), 0, s, d_jobs, per,
+                       (const double*)d_part, d_out);
+    return 2;
+}
+
+int launch_pnp_batch_epnp_prep(const void* d_pts, const uint8_t* d_mask, const BatchPnpEpnpJob* d_jobs, int nJobs,
+                               int maxN, int* d_idx, int* d_count, double* d_pw, double* d_us, hipStream_t s) {
+    const PnpCamera none{};
+    hipLaunchKernelGGL(mcv_mask_compact, dim3(nJobs), dim3(1024), 0, s, d_mask, 0, d_idx, d_count, d_jobs);
+    int launches = 1;
+    for (int j0 = 0; j0 < nJobs; j0 += kGridYMax, ++launches) {   // grid y holds 65535 jobs: one launch below that
+        const int nj = std::min(kGridYMax, nJobs - j0);
+        hipLaunchKernelGGL(mcv_epnp_prep_f32, dim3((maxN + 255) / 256, nj), dim3(256), 0, s, (const PnpPoint*)d_pts,
+                           (const int*)d_idx, maxN, none, d_pw, d_us, (const int*)d_count + j0, d_jobs + j0);
+    }
+    return launches;
+}
+
+int launch_pnp_batch_epnp_pass(int mode, const BatchPnpEpnpJob* d_jobs, int nJobs, int maxNblk, const int* d_count,
+                               const double* d_pw, const double* d_us, int nacc, int region, int prevRegion,
+                               double* d_part, hipStream_t s) {
+    if (maxNblk <= 0 || nJobs <= 0) return 0;
+    if (nJobs > kGridYMax) {   // grid y holds 65535 jobs: one launch below that
+        int launches = 0;
+        for (int j0 = 0; j0 < nJobs; j0 += kGridYMax)
+            launches += launch_pnp_batch_epnp_pass(mode, d_jobs + j0, std::min(kGridYMax, nJobs - j0), maxNblk,
+                                                   d_count + j0, d_pw, d_us, nacc, region, prevRegion, d_part, s);
+        return launches;
+    }
+    const dim3 grid(maxNblk, nJobs), block(256);
+    const EpnpPassArgs a{};
+    const double* const noPrev = nullptr;
+#define MCV_PASS(M)                                                                                                   \
+    hipLaunchKernelGGL((mcv_epnp_pass<M, true>), grid, block, 0, s, d_pw, d_us, 0, a, nacc, 0, d_part, d_count, noPrev, \
+                       d_jobs, region, prevRegion)
+    switch (mode) {
+        case kEpnpPassSumPw: MCV_PASS(kEpnpPassSumPw); break;
+        case kEpnpPassPw0: MCV_PASS(kEpnpPassPw0); break;
+        case kEpnpPassMtm: MCV_PASS(kEpnpPassMtm); break;
+        case kEpnpPassPc: MCV_PASS(kEpnpPassPc); break;
+        case kEpnpPassAbt: MCV_PASS(kEpnpPassAbt); break;
+        default: MCV_PASS(kEpnpPassReproj);
+    }
+#undef MCV_PASS
+    return 1;
 }
 
 }  // namespace mcv

@@ -88,6 +88,9 @@ BATCH_TILE = 1024       # points per LDS tile of the batched sweep (kernels.h kB
 BATCH_SLOT_CAP = 1 << 21   # slots per hypothesis round of cvFindModelBatch (ransac_batch_host.cpp)
 BATCH_E_TILE = 512         # double4 points per LDS tile of the batched essential sweep (kernels.h kBatchETile)
 BATCH_E_HYP_CAP = 1 << 18  # hypotheses per round of the essential batches (ransac_batch_host.cpp)
+BATCH_PNP_TILE = 512       # PnpPoint rows per LDS tile of the batched PnP sweep (kernels.h kBatchPnpTile)
+BATCH_PNP_WIDTH = 64       # poses (lanes) per workgroup of that sweep (kernels.h kBatchPnpWidth)
+BATCH_PNP_HYP_CAP = 1 << 18  # hypotheses per round of cvSolvePnPRansacBatch (ransac_batch_host.cpp)
 MATCH_BATCH_ROWS_HAMMING = 64   # query rows per workgroup of the batched matcher (kernels.h)
 MATCH_BATCH_ROWS_L2 = 128
 E_SLOTS = 10
@@ -128,6 +131,7 @@ SIGNATURES = {
     "cvFindEssentialMatBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cvRecoverPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
+    "cvSolvePnPRansacBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "cvMatchFeaturesNorm": (_I, [_P, _P, _P, _I, _P, _P, _I]),
@@ -215,6 +219,7 @@ SIGNATURES = {
     "mcvTestBatchStats": (_I, [_P]),
     "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),
     "mcvTestBatchSweepE": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
+    "mcvTestBatchSweepPnp": (_I, [_P, _P, _I, _P, _P, _P, _F, _P]),
     "mcvHostMatchBatchLayout": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I]),
     "mcvTestMatchBatchStats": (_I, [_P]),
     "mcvTestMatchBatchKnn": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),

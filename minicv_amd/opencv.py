@@ -402,6 +402,60 @@ def solvePnPRansac(img, world, K, dist=None, kind: str = "AP3P", iterations: int
     return bool(ok), np.array([r.X, r.Y, r.Z]), np.array([t.X, t.Y, t.Z]), inl[:cnt.value].copy()
 
 
+def solvePnPRansacBatch(imgs, worlds, Ks, dists=None, kind: str = "AP3P", params: RansacParams | None = None):
+    """cvSolvePnPRansacBatch: B independent solvePnPRansac problems in one call. imgs / worlds: lists of
+    (N_p, 2) / (N_p, 3) arrays; Ks: B camera matrices; dists: None (no distortion) or B rows of (k1, k2, p1, p2).
+    -> a list of (ok, rvec, tvec, inlier indices int32[count]) per problem, each equal to
+    solvePnPRansac(..., kind=kind, params=params) on that problem; a problem without a pose gives
+    (False, zeros, zeros, empty) and N.last_error() names the first such problem. params None: the native
+    defaults (100 iterations, 8 px, 0.99, OpenCV's sample stream). Raises NativeError when the whole call is
+    refused."""
+    if len(imgs) != len(worlds):
+        raise ValueError("imgs/worlds length mismatch")
+    B = len(imgs)
+    pi = [_v2d(x) for x in imgs]
+    pw = [_v3d(x) for x in worlds]
+    for x, y in zip(pi, pw):
+        if x.shape[0] != y.shape[0]:
+            raise ValueError("img/world length mismatch")
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([x.shape[0] for x in pi])
+    total = int(offsets[B])
+    img = np.ascontiguousarray(np.concatenate(pi, axis=0)) if total else np.zeros((1, 2))
+    world = np.ascontiguousarray(np.concatenate(pw, axis=0)) if total else np.zeros((1, 3))
+    K = np.ascontiguousarray(np.asarray(Ks, dtype=np.float64).reshape(-1, 9)) if B else np.zeros((1, 9))
+    if B and K.shape[0] != B:
+        raise ValueError("Ks must have one camera matrix per problem")
+    d = None
+    if dists is not None:
+        d = np.ascontiguousarray(np.asarray(dists, dtype=np.float64).reshape(-1, 4)) if B else np.zeros((1, 4))
+        if B and d.shape[0] != B:
+            raise ValueError("dists must have one row of 4 coefficients per problem")
+    cfg = None
+    if params is not None or kind != "Iterative":
+        cfg = params.to_c() if params is not None else _pnp_default_cfg()
+        cfg.pnpKind = SOLVER_KIND[kind]
+    ts = np.zeros((max(B, 1), 3), dtype=np.float64)
+    rs = np.zeros((max(B, 1), 3), dtype=np.float64)
+    counts = np.zeros(max(B, 1), dtype=np.int32)
+    ms = np.zeros(max(total, 1), dtype=np.uint8)
+    ret = N.lib().cvSolvePnPRansacBatch(img.ctypes.data, world.ctypes.data, offsets.ctypes.data, B, K.ctypes.data,
+                                        d.ctypes.data if d is not None else None,
+                                        N.C.addressof(cfg) if cfg is not None else None, ts.ctypes.data,
+                                        rs.ctypes.data, ms.ctypes.data, counts.ctypes.data)
+    N.check(ret >= 0, "cvSolvePnPRansacBatch")
+    return [(bool(counts[p] > 0), rs[p].copy(), ts[p].copy(),
+             np.flatnonzero(ms[offsets[p]:offsets[p + 1]]).astype(np.int32)) for p in range(B)]
+
+
+def _pnp_default_cfg() -> N.RansacConfig:
+    """cvSolvePnPRansac's configuration at its defaults (pnp_config(100, 8, 0.99, kind))."""
+    c = N.RansacConfig()
+    c.threshold, c.confidence, c.maxIters, c.method = 8.0, 0.99, 100, N.METHOD_RANSAC
+    c.flags = N.FLAG_CV_SAMPLER
+    return c
+
+
 def solvePnP(img, world, K, dist=None, kind: str = "AP3P"):
     """cvSolvePnP -> (ok, rvec, tvec)."""
     pi, pw = _v2d(img), _v3d(world)
