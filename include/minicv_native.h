@@ -742,8 +742,9 @@ MCV_API int mcvTestEigLogCap(int cap);
  * [10..15] the slots alive entering each stage. Not thread-safe: tests only. */
 MCV_API int mcvTestHStaging(int mode, long long* stats);
 /* The per-cell inlier upper bound that drops hypotheses before stage 1 of the staged homography sweep.
- * mode 0: automatic (where the staged sweep's own size rule holds, from 20000 correspondences), 1: whenever the
- * sweep is staged, 2: never;
+ * mode 0: automatic (where the staged sweep's own size rule holds, from 20000 correspondences; its second pass,
+ * the candidate-relative test and the per-slot points-left of the later compactions, from 35000), 1: both
+ * passes whenever the sweep is staged, 2: never;
  * any other mode leaves the setting. G, Gs: the 4-D grid of the points the candidate rejects and the 2-D grid
  * of its inliers (1..6 and 1..24; 0 leaves them; defaults 4 and 12). Returns the previous mode, -1 on error.
  * stats (may be NULL; 6 values), for the calling thread's last homography evaluate, read after its stream was
@@ -759,6 +760,15 @@ MCV_API int mcvTestHCellMode(int mode, int G, int Gs, long long* stats);
 MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
                               float thr2, int B, int G, int Gs, int device, int* cellId, float* boxes, int* sizes,
                               int* ub, unsigned int* bits, int* alive);
+/* The bound's second pass on caller-supplied data: the union of the box test above and the candidate-relative
+ * test (cells of the candidate's inliers, index >= G^4), arguments as for mcvTestHCellBound. bounds[nBounds]
+ * (1..4 of them): stage boundaries in pairs of points, each within 0..(N + 1) / 2; boundary b stands for the
+ * first min(2 b, N) correspondences. Outputs: cellId[N]; ub[nModels]; bits as above, of the union test;
+ * left[j * nModels + k] = the correspondences of model k's uncertified cells with index >= min(2 bounds[j], N);
+ * *alive = the models with ub >= B. Returns 1, 0 on failure. */
+MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                            float thr2, int B, int G, int Gs, const int* bounds, int nBounds, int device,
+                            int* cellId, int* ub, unsigned int* bits, int* left, int* alive);
 /* cvFindModelBatch's index arithmetic, as the export itself computes it (no device). Problems with more
  * than m (the sample size) correspondences run on the device and are numbered in order (d = 0, 1, ...).
  * desc4[4 p ..]: point offset (= offsets[p]: float4 points, no padding), N, slot offset (d * per, 64-bit;

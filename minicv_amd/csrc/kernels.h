@@ -68,6 +68,7 @@ static const int kCtlStages = 2;   // stages in use (2 + the later stages)
 static const int kCtlCells = 3;    // cell slots of the per-cell bound that ran before stage 1 (0: none)
 static const int kCtlBound = 4;    // kHStageMax + 1 boundaries, in pairs
 static const int kCtlAlive = 12;   // slots alive entering each stage
+static const int kCtlPre = 18;     // slots the per-cell bound's box pass hands to the second pass
 static const int kCtlKey = 24;     // the candidate's packed key and the first failure (2 x 64 bit)
 static const int kHStageMax = 6;          // stages: the prefix, the run to the first boundary, <= 4 later ones
 static const int kHStagePrefixDiv = 16;   // stage 0 sweeps ~N / 16 points
@@ -82,19 +83,35 @@ static const int kHStageMinN = 4096;
 // why a staged evaluation pruned nothing (control block / mcvTestHStaging stats[0]; 0 = it pruned)
 enum { kHStageNoCandidate = 1, kHStageSamplerFailure = 2, kHStageLate = 3, kHStageForcedOff = 4,
        kHStageNotApplicable = 5 };
+// the per-cell bound's other buffers (with d_cells): cell ids (N ints), prefix table (kHStageLater x cells ints),
+// per-slot points left in uncertified cells (kHStageLater x hypCount ints)
+struct HCellBufs {
+    int *id, *pref, *left;
+};
+static const int kHCellLater = kHStageMax - 2;   // the most later boundaries a slot keeps a `left` figure for
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec = nullptr,
                             unsigned long long* d_stats = nullptr, int form = kHFormValu, int* d_cells = nullptr,
-                            int G = 0, int Gs = 0);
+                            int G = 0, int Gs = 0, HCellBufs d_cell = HCellBufs{nullptr, nullptr, nullptr});
 // The per-cell bound before stage 1 (h_cell_bound.h): the cell table (h_cell_count(G, Gs) x
 // kHCellInts ints) is built with the candidate's count, the bound kernel writes the slots that can still
 // reach B to d_list and their number to ctl[kCtlAlive + 1]. The automatic rule engages it where the staged
 // sweep's own size rule holds and N >= kHCellMinN: the bound costs a slot about what 2200 correspondences of
 // the sweep cost, whatever N, and measured it wins at N = 20000 and 100000 from 2^16 / 2^18
 // hypotheses and loses at N = 5000 (2^20 hypotheses: 5.96 -> 6.17 ms).
-// d_cellOut / d_ub / d_bits: the test hook's outputs (nullptr in the sweep).
+// A second pass over that list (mcv_h_cell_rel) adds the candidate-relative test on the cells of the
+// candidate's inliers and writes each kept slot's `left` per later boundary: with d_listPre the first pass
+// writes there (length in ctl[kCtlPre]) the slots the relative test can still drop and to d_list the others
+// (their `left` in d_left: the points not yet processed), and the second pass appends to d_list.
+// d_cellOut / d_ub / d_bits: the test hooks' outputs (nullptr in the sweep, but for the cell ids the prefix
+// table is built from).
 static const int kHCellMinN = 20000;
+// the second pass (candidate-relative test, per-slot `left`) from this many correspondences: it costs a slot
+// it visits about what 7000 correspondences of the sweep cost, whatever N, and what it saves grows with N.
+// Measured at 2^20 hypotheses: N = 20000 level at 50 % outliers and 1-2 % slower at 70 %;
+// N = 35000, 50000, 70000, 100000 faster at 50 % and level at 70 %.
+static const int kHCellRelMinN = 35000;
 // stage 0 with the bound sweeps ~N / 64 points: every slot still runs stage 0, so with stage 1 listed it is the
 // largest full-width cost; cfg3 evaluate 13.00 ms at N / 16, 12.32-12.41 at N / 32, 11.94-12.01 at N / 64 (the
 // candidate's B is 50196 at all three)
@@ -103,7 +120,16 @@ void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int6
                           const double* d_bb, int* d_cells, int G, int Gs, int* d_cellOut, hipStream_t s);
 void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
                          const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
-                         hipStream_t s);
+                         hipStream_t s, int* d_listPre = nullptr, int* d_left = nullptr, int nLater = 0, int N = 0);
+void launch_h_cell_prefix(const int* d_cellId, int N, const int* d_ctl, int nLater, int G, int Gs, int* d_pref,
+                          hipStream_t s);
+void launch_h_cell_rel(const void* d_models, const void* d_candModels, int64_t hypBegin, int hypCount, float thr2,
+                       const double* d_bb, const int* d_cells, int G, int Gs, const int* d_pref, int nLater,
+                       int* d_ctl, const int* d_src, int* d_list, int* d_left, int* d_ub, uint32_t* d_bits,
+                       hipStream_t s);
+void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2,
+                     int B, int G, int Gs, const int* bounds, int nBounds, int* cellId, int* ub, uint32_t* bits,
+                     int* left, int* alive);
 void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
                  int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);

@@ -76,6 +76,9 @@ struct Plan {
     DevBuf<int> hstageCtl;    // homography staged sweep: the control block (kHStageCtlInts)
     int hstageLast = -1;      // last homography evaluate: 0 staged (the control block tells), else kHStage*
     DevBuf<int> hcells;       // homography staged sweep: the per-cell bound's cell table (kHCellInts ints per cell)
+    DevBuf<int> hcellId;      // its cell of every correspondence (N)
+    DevBuf<int> hcellPref;    // its prefix table: per later boundary and cell, the cell's points before the boundary
+    DevBuf<int> hcellLeft;    // per later boundary and slot: the unprocessed points of the slot's uncertified cells
     DevBuf<uint8_t> one;      // single-hypothesis output record
     DevBuf<double> ptsd;      // essential: double4 normalised correspondences
     DevBuf<double> raw;       // essential: uploaded V2d pairs (a then b)

@@ -7,7 +7,8 @@
 //   GPU reductions + 9x9 Jacobi here), 10 Levenberg-Marquardt iterations (GPU reductions + 8x8 solve here).
 // Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
 // [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
-// Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHMfma).
+// Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHCellRel,
+// mcvTestHMfma).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -147,6 +148,17 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     // model under the op-by-op error: DESIGN.md §4), and UB < B. The count it keeps is its stage-0 partial,
     // at most its full count and so below B. The candidate's own UB is at least its full count B, and a
     // slot that reaches the winning count has UB >= that count >= B: neither is dropped (inclusive test).
+    // The bound's second pass adds the candidate-relative test on the cells of the candidate's inliers: more
+    // certified cells with the same meaning (every correspondence of the cell is an outlier of the slot's model
+    // under the op-by-op error), so UB stays an upper bound and the paragraph above holds as it stands. With h
+    // = the candidate the relative form is negative, so the candidate certifies none of its own inlier cells.
+    // With the bound the later compactions read points-left per slot: left = the correspondences not yet
+    // processed that lie in cells the bound did not certify for the slot's model. The unprocessed points of
+    // certified cells are outliers of that model, so only `left` of the N - processed points can still add to
+    // the count: full count <= count-so-far + left <= count-so-far + N - processed. A slot dropped on
+    // count-so-far + left < B has a full count below B, exactly what the first paragraph needs of a dropped
+    // slot; the candidate (full count B) and every slot that reaches the winning count have count-so-far +
+    // left >= full count >= B at every boundary and are never dropped (inclusive test, so ties stay).
     // Everything else above stands as written. Engaged where the size rule itself stages the call and
     // N >= kHCellMinN (kernels.h: the measured rows); forced staging of a small call keeps the plain stages.
     const bool stageable = !fused && keyOnly;
@@ -155,10 +167,20 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     P.hstageLast = staged ? 0 : (stageable && g_hstage_mode == 2 ? kHStageForcedOff : kHStageNotApplicable);
     t_hstage_plan = &P;
     const bool cellBound = staged && g_hcell_mode != 2 && (g_hcell_mode == 1 || (sized && N >= kHCellMinN));
+    // the bound's second pass costs a slot the same whatever N and saves in proportion to N (kernels.h)
+    const bool cellRel = cellBound && (g_hcell_mode == 1 || N >= kHCellRelMinN);
     if (staged) {
         P.hstageCtl.ensure(kHStageCtlInts);
         P.hstageList.ensure(2 * (size_t)hypCount);
-        if (cellBound) P.hcells.ensure((size_t)h_cell_count(g_hcell_G, g_hcell_Gs) * kHCellInts);
+        if (cellBound) {
+            const size_t cells = (size_t)h_cell_count(g_hcell_G, g_hcell_Gs);
+            P.hcells.ensure(cells * kHCellInts);
+            if (cellRel) {
+                P.hcellId.ensure((size_t)N);
+                P.hcellPref.ensure(cells * kHStageLater);
+                P.hcellLeft.ensure((size_t)hypCount * kHStageLater);
+            }
+        }
     }
     // the certified sweep's matrix-core form where the size rule (or mcvTestHMfma) engages it: its
     // point records are written here, beside the pairs
@@ -176,7 +198,9 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     if (staged) {
         launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
                                P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form,
-                               cellBound ? P.hcells.p : nullptr, g_hcell_G, g_hcell_Gs);
+                               cellBound ? P.hcells.p : nullptr, g_hcell_G, g_hcell_Gs,
+                               cellRel ? HCellBufs{P.hcellId.p, P.hcellPref.p, P.hcellLeft.p}
+                                       : HCellBufs{nullptr, nullptr, nullptr});
     } else if (!fused) {
         // default: OpenCV's op-by-op error, certified division-free sweep
         launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s, d_rec,
@@ -407,6 +431,71 @@ extern "C" MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* 
         MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(ub, dub.p, (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(bits, dbits.p, (size_t)nModels * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
+        *alive = hctl[kCtlAlive + 1];
+        return 1;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the per-cell bound's second pass (box test + candidate-relative
+// test, UB, the `left` figures) on given data and boundaries, device or host twin.
+extern "C" MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                                       float thr2, int B, int G, int Gs, const int* bounds, int nBounds, int device,
+                                       int* cellId, int* ub, unsigned int* bits, int* left, int* alive) {
+    MCV_GUARD(0, {
+        if (!pts4 || !cand8 || !models8 || !bounds || !cellId || !ub || !bits || !left || !alive)
+            fail("mcvTestHCellRel: null argument");
+        if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs || nBounds < 1 ||
+            nBounds > kHCellLater)
+            fail("mcvTestHCellRel: bad sizes");
+        for (int j = 0; j < nBounds; ++j)
+            if (bounds[j] < 0 || bounds[j] > (N + 1) / 2) fail("mcvTestHCellRel: boundary out of range");
+        if (!device) {
+            h_cell_rel_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, bounds, nBounds, cellId, ub, bits, left,
+                            alive);
+            return 1;
+        }
+        require_device();
+        const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
+        DevBuf<float> p, m, cand;
+        DevBuf<double> bb;
+        DevBuf<int> ctl, tab, list, dub, did, pref, dleft;
+        DevBuf<uint32_t> dbits;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        cand.ensure(8);
+        bb.ensure(4);
+        ctl.ensure(kHStageCtlInts);
+        tab.ensure((size_t)cells * kHCellInts);
+        list.ensure(nModels);
+        dub.ensure(nModels);
+        did.ensure(N);
+        pref.ensure((size_t)cells * nBounds);
+        dleft.ensure((size_t)nModels * nBounds);
+        dbits.ensure((size_t)nModels * words);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cand.p, cand8, 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(dbits.p, 0, (size_t)nModels * words * sizeof(uint32_t)));
+        // a control block that names slot 0 of `cand` as the candidate and carries the given boundaries
+        int hctl[kHStageCtlInts] = {0};
+        const uint64_t key = (1ull << 32) | 0xFFFFFFFFull;
+        memcpy(hctl + kCtlKey, &key, sizeof(key));
+        for (int j = 0; j < nBounds; ++j) hctl[kCtlBound + 2 + j] = bounds[j];
+        MCV_HIP(hipMemcpy(ctl.p, hctl, sizeof(hctl), hipMemcpyHostToDevice));
+        launch_abs_bound4(p.p, false, N, bb.p, nullptr, 0);
+        launch_h_stage_count(p.p, N, cand.p, 0, thr2, ctl.p, bb.p, tab.p, G, Gs, did.p, 0);
+        MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
+        launch_h_cell_prefix(did.p, N, ctl.p, nBounds, G, Gs, pref.p, 0);
+        launch_h_cell_rel(m.p, cand.p, 0, nModels, thr2, bb.p, tab.p, G, Gs, pref.p, nBounds, ctl.p, nullptr, list.p,
+                          dleft.p, dub.p, dbits.p, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(ub, dub.p, (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(bits, dbits.p, (size_t)nModels * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(left, dleft.p, (size_t)nModels * nBounds * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
         *alive = hctl[kCtlAlive + 1];
         return 1;

@@ -1,8 +1,10 @@
 // ransac_h_stage.hip — the staged homography sweep on gfx950: the certified sweep run in stages that
 // prune themselves (launch_h_verify_staged), for callers that consume only the best key. Here: the
 // control block's init, the candidate's exact count and the cell table (mcv_h_stage_count), the stage
-// planner, the survivor compaction, the per-cell bound (mcv_h_cell_bound, h_cell_bound.h) and its host
-// twin. The stages themselves are the sweeps of ransac_h_sweep.hip / ransac_h_mfma.hip.
+// planner, the survivor compaction, the per-cell bound (h_cell_bound.h: mcv_h_cell_bound, the box pass over
+// every slot; mcv_h_cell_rel, the second pass with the candidate-relative test and the per-slot `left`;
+// mcv_h_cell_prefix, its prefix table) and the host twins. The stages themselves are the sweeps of
+// ransac_h_sweep.hip / ransac_h_mfma.hip.
 #include <algorithm>
 #include <vector>
 #include "mcv_common.h"
@@ -144,22 +146,27 @@ __global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int lat
 }
 
 // Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
-// whose count can still reach B, count + (N - processed) >= B. Inclusive, so ties survive; a status
+// whose count can still reach B, count + left >= B. Inclusive, so ties survive; a status
 // (count < 0: no model, no sample, the exact-recount mark) never enters a list. Any order: ballot
-// and one atomic per wave.
+// and one atomic per wave. left: without the per-cell bound (slotLeft == nullptr) the points not yet
+// processed, N - processed; with it the slot's own figure, the unprocessed points of the cells the bound
+// did not certify for the slot's model (slotLeft[(stage - 2) * hypCount + slot], written by mcv_h_cell_rel,
+// or by mcv_h_cell_bound for the slots it keeps out of the second pass).
 __global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict__ counts, int hypCount, int N,
                                                            int* __restrict__ ctl, int stage,
-                                                           const int* __restrict__ src, int* __restrict__ dst) {
+                                                           const int* __restrict__ src, int* __restrict__ dst,
+                                                           const int* __restrict__ slotLeft) {
     if (ctl[kCtlReason] != 0) return;
     const int n = src ? ctl[kCtlAlive + stage - 1] : hypCount;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int done2 = 2 * ctl[kCtlBound + stage];
-    const int left = N - (done2 < N ? done2 : N);
+    const int rest = N - (done2 < N ? done2 : N);
     bool keep = false;
     int slot = 0;
     if (i < n) {
         slot = src ? src[i] : i;
         const int c = counts[slot];
+        const int left = slotLeft ? slotLeft[(size_t)(stage - 2) * hypCount + slot] : rest;
         keep = c >= 0 && c + left >= ctl[kCtlB];
     }
     const uint64_t b = __ballot(keep);
@@ -171,6 +178,25 @@ __global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict
     if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
 }
 
+// Appends the lanes with `keep` to a survivor list (ballot, one atomic per wave, any order).
+__device__ __forceinline__ void h_list_push(bool keep, int slot, int* total, int* __restrict__ dst) {
+    const uint64_t b = __ballot(keep);
+    if (b == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(total, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
+}
+
+// The second pass's buffers as the box pass sees them (pre == nullptr: no second pass, the test hook).
+struct HCellPre {
+    int* pre;        // the list of the slots the second pass can still drop; its length goes to ctl[kCtlPre]
+    int* slotLeft;   // nLater x hypCount ints
+    int relBase;     // first cell of the candidate's inliers (G^4)
+    int nLater, N;
+};
+
 // The per-cell bound (h_cell_bound.h), lane = slot: UB = the sizes of the cells the model does not certify
 // as all-outlier, an upper bound of the slot's full count. Slots with a model and UB >= B (inclusive: ties
 // survive) enter the survivor list of stage 1 as mcv_h_stage_compact writes its lists (ballot, one
@@ -179,22 +205,29 @@ __global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict
 // (ctl[kCtlReason] != 0) every slot with a model is kept. The cells are wave-uniform (scalar loads); all
 // stores are per lane. ubOut / bitsOut (test hook): every slot's UB and its certified-cell bitmap
 // (bitWords zeroed words per slot).
+// With the second pass behind it (mcv_h_cell_rel, hp.pre != nullptr) a kept slot goes one of two ways. The
+// relative test certifies cells of the candidate's inliers only, so it can take a slot below B only when the
+// uncertified cells of the other points alone hold fewer than B: those slots go to hp.pre for the second
+// pass. The others stay whatever the relative test finds; they go straight to dst, and their `left` is the
+// compaction's old figure, the points not yet processed (an upper bound of any slot's `left`). Where
+// pruning is off on the device the second pass does nothing and every slot with a model goes to dst.
 __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restrict__ models,
                                                         const int* __restrict__ counts, int hypCount, float thr2,
                                                         double kappa, const double* __restrict__ bb,
                                                         const int* __restrict__ cells, int nCells, int* ctl,
-                                                        int* __restrict__ dst, int* __restrict__ ubOut,
-                                                        uint32_t* __restrict__ bitsOut, int bitWords) {
+                                                        int* __restrict__ dst, HCellPre hp,
+                                                        int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
+                                                        int bitWords) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool have = i < hypCount && counts[i] >= 0;
-    bool keep = have;
+    bool keep = have, second = false;
     if (ctl[kCtlReason] == 0 && __ballot(have) != 0) {
         const HModelF m = models[i < hypCount ? i : hypCount - 1];
         double b4[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) b4[j] = bb[j];
         const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
-        int ub = 0;
+        int ub = 0, ubRel = 0;   // ubRel: the part of ub in the cells of the candidate's inliers
         for (int c = 0; c < nCells; ++c) {
             const int* e = cells + c * kHCellInts;
             const int size = e[kHCellInts - 1];
@@ -204,18 +237,125 @@ __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restric
             for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
             const bool cert = h_cell_certified(m.h, cm, box);
             ub += cert ? 0 : size;
+            if (hp.pre && c >= hp.relBase) ubRel += cert ? 0 : size;
             if (bitsOut && cert && i < hypCount) bitsOut[(size_t)i * bitWords + (c >> 5)] |= 1u << (c & 31);
         }
         if (ubOut && i < hypCount) ubOut[i] = ub;
-        keep = have && ub >= ctl[kCtlB];
+        const int B = ctl[kCtlB];
+        keep = have && ub >= B;
+        if (hp.pre) {
+            second = keep && ub - ubRel < B;
+            keep = keep && !second;
+            if (keep) {
+#pragma unroll
+                for (int j = 0; j < kHCellLater; ++j) {
+                    if (j >= hp.nLater) continue;
+                    const int d2 = 2 * ctl[kCtlBound + 2 + j];
+                    hp.slotLeft[(size_t)j * hypCount + i] = hp.N - (d2 < hp.N ? d2 : hp.N);
+                }
+            }
+            h_list_push(second, i, ctl + kCtlPre, hp.pre);
+        }
     }
-    const uint64_t b = __ballot(keep);
-    if (b == 0) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(ctl + kCtlAlive + 1, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = i;
+    h_list_push(keep, i, ctl + kCtlAlive + 1, dst);
+}
+
+// The prefix table of the per-slot `left` figures: pref[j * nCells + c] = the points of cell c with index
+// below min(2 * boundary, N) for the boundary that ends stage 1 + j (j < nLater), the convention of
+// mcv_h_stage_compact. Zeroed before the launch; each block gathers a histogram in LDS (nLater * nCells ints)
+// and adds its non-zero entries. Integer adds: any order gives the same table. Does nothing where pruning is
+// off on the device (without a candidate the cell ids were never written).
+__global__ __launch_bounds__(1024) void mcv_h_cell_prefix(const int* __restrict__ cellId, int N,
+                                                          const int* __restrict__ ctl, int nLater, int nCells,
+                                                          int* __restrict__ pref) {
+    extern __shared__ int hist[];
+    if (ctl[kCtlReason] != 0) return;
+    const int nt = nLater * nCells;
+    for (int i = threadIdx.x; i < nt; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    int lim[kHCellLater];
+#pragma unroll
+    for (int j = 0; j < kHCellLater; ++j) {
+        const int d2 = j < nLater ? 2 * ctl[kCtlBound + 2 + j] : 0;
+        lim[j] = d2 < N ? d2 : N;
+    }
+    const int stride = gridDim.x * blockDim.x;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+        const int c = cellId[i];
+        if ((unsigned)c >= (unsigned)nCells) continue;   // never: mcv_h_stage_count wrote every id in range
+#pragma unroll
+        for (int j = 0; j < kHCellLater; ++j)
+            if (j < nLater && i < lim[j]) atomicAdd(hist + j * nCells + c, 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += blockDim.x)
+        if (hist[i]) atomicAdd(pref + i, hist[i]);
+}
+
+// The second pass of the per-cell bound, lane = entry of the list the first pass wrote (src; nullptr: every
+// slot below hypCount, the test hook): the box test again per cell, the candidate-relative test
+// (h_cell_bound.h) on the cells of the candidate's inliers (index >= relBase), UB over the cells neither
+// certifies, and per later boundary j the slot's `left`: the points of those cells that the sweep has not
+// processed at that boundary, size - pref. Slots with UB >= B (inclusive) are appended to dst behind the
+// slots the first pass put there (ctl[kCtlAlive + 1] counts both), their `left` figures go to
+// slotLeft[j * hypCount + slot]. The candidate is the slot the
+// control block's key names, read from candModels (the chunk's models; the hook's own buffer). Nothing to do
+// where pruning is off on the device: the first pass then wrote the final list. Cells, prefix table and
+// candidate are wave-uniform; all stores are per lane.
+__global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict__ models,
+                                                      const HModelF* __restrict__ candModels, int64_t hypBegin,
+                                                      int hypCount, float thr2, double kappa,
+                                                      const double* __restrict__ bb, const int* __restrict__ cells,
+                                                      int nCells, int relBase, const int* __restrict__ pref,
+                                                      int nLater, int* ctl, const int* __restrict__ src,
+                                                      int* __restrict__ dst, int* __restrict__ slotLeft,
+                                                      int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
+                                                      int bitWords) {
+    if (ctl[kCtlReason] != 0) return;
+    const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
+    if (key == 0) return;   // never with pruning on
+    const int n = src ? ctl[kCtlPre] : hypCount;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= n) return;
+    const bool have = i < n;
+    const int slot = have ? (src ? src[i] : i) : 0;
+    const HModelF m = models[slot];
+    const HModelF cand = candModels[(int64_t)(0xFFFFFFFFull - (key & 0xFFFFFFFFull)) - hypBegin];
+    double b4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b4[j] = bb[j];
+    const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
+    const HCellModel cc = h_cell_model(cand.h, b4, thr2, kappa, kCertT, kCertSlop);
+    const HCellRel rel = h_cell_rel(m.h, cm, cand.h, cc);
+    int ub = 0;
+    int left[kHCellLater];
+#pragma unroll
+    for (int j = 0; j < kHCellLater; ++j) left[j] = 0;
+    for (int c = 0; c < nCells; ++c) {
+        const int* e = cells + c * kHCellInts;
+        const int size = e[kHCellInts - 1];
+        if (size == 0) continue;
+        float box[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
+        bool cert = h_cell_certified(m.h, cm, box);
+        if (c >= relBase && !cert) cert = h_cell_rel_certified(m.h, cm, cand.h, cc, rel, box);
+        if (!cert) {
+            ub += size;
+#pragma unroll
+            for (int j = 0; j < kHCellLater; ++j)
+                if (j < nLater) left[j] += size - pref[j * nCells + c];
+        }
+        if (bitsOut && cert && have) bitsOut[(size_t)slot * bitWords + (c >> 5)] |= 1u << (c & 31);
+    }
+    if (ubOut && have) ubOut[slot] = ub;
+    const bool keep = have && ub >= ctl[kCtlB];
+    if (have) {
+#pragma unroll
+        for (int j = 0; j < kHCellLater; ++j)
+            if (j < nLater) slotLeft[(size_t)j * hypCount + slot] = left[j];
+    }
+    h_list_push(keep, slot, ctl + kCtlAlive + 1, dst);
 }
 
 // The certified sweep in stages that prune themselves (the caller consumes only the best key): stage 0
@@ -246,12 +386,37 @@ void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int6
 
 void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
                          const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
-                         hipStream_t s) {
+                         hipStream_t s, int* d_listPre, int* d_left, int nLater, int N) {
     const HCertSlopes slopes = h_cert_slopes_host(thr2);
     const int nCells = h_cell_count(G, Gs);
     hipLaunchKernelGGL(mcv_h_cell_bound, dim3((hypCount + 255) / 256), dim3(256), 0, s, (const HModelF*)d_models,
                        d_counts, hypCount, thr2, h_cell_kappa(slopes.a.x, slopes.a.y), d_bb, d_cells, nCells, d_ctl,
-                       d_list, d_ub, d_bits, (nCells + 31) / 32);
+                       d_list, HCellPre{d_listPre, d_left, G * G * G * G, nLater, N}, d_ub, d_bits, (nCells + 31) / 32);
+}
+
+// d_pref: nLater x cells ints, from the cell ids mcv_h_stage_count kept and the control block's boundaries
+void launch_h_cell_prefix(const int* d_cellId, int N, const int* d_ctl, int nLater, int G, int Gs, int* d_pref,
+                          hipStream_t s) {
+    const int nCells = h_cell_count(G, Gs);
+    const size_t bytes = (size_t)nLater * nCells * sizeof(int);   // at most 4 x 1872 ints of LDS
+    (void)hipMemsetAsync(d_pref, 0, bytes, s);
+    const int blocks = std::min(64, (N + 1023) / 1024);
+    hipLaunchKernelGGL(mcv_h_cell_prefix, dim3(blocks), dim3(1024), bytes, s, d_cellId, N, d_ctl, nLater, nCells,
+                       d_pref);
+}
+
+// The second pass over d_src (the first pass's list, its length in ctl[kCtlPre]; nullptr: every slot).
+// d_left: nLater x hypCount ints.
+void launch_h_cell_rel(const void* d_models, const void* d_candModels, int64_t hypBegin, int hypCount, float thr2,
+                       const double* d_bb, const int* d_cells, int G, int Gs, const int* d_pref, int nLater,
+                       int* d_ctl, const int* d_src, int* d_list, int* d_left, int* d_ub, uint32_t* d_bits,
+                       hipStream_t s) {
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    const int nCells = h_cell_count(G, Gs);
+    hipLaunchKernelGGL(mcv_h_cell_rel, dim3((hypCount + 255) / 256), dim3(256), 0, s, (const HModelF*)d_models,
+                       (const HModelF*)d_candModels, hypBegin, hypCount, thr2, h_cell_kappa(slopes.a.x, slopes.a.y),
+                       d_bb, d_cells, nCells, G * G * G * G, d_pref, nLater, d_ctl, d_src, d_list, d_left, d_ub,
+                       d_bits, (nCells + 31) / 32);
 }
 
 // Host twin of the cell build and the bound (mcvTestHCellBound): the same header, the same arithmetic.
@@ -306,14 +471,69 @@ void h_cell_host(const float* pts4, int N, const float* cand8, const float* mode
     if (alive) *alive = kept;
 }
 
+// Host twin of the second pass (mcvTestHCellRel): the union of the box test and the candidate-relative test,
+// UB and the `left` figures at the given boundaries (in pairs of points, the control block's unit).
+void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2,
+                     int B, int G, int Gs, const int* bounds, int nBounds, int* cellId, int* ub, uint32_t* bits,
+                     int* left, int* alive) {
+    const int nCells = h_cell_count(G, Gs), words = (nCells + 31) / 32, relBase = G * G * G * G;
+    std::vector<float> boxes((size_t)nCells * 8);
+    std::vector<int> sizes(nCells), u0(nModels);
+    std::vector<uint32_t> b0((size_t)nModels * words);
+    h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes.data(), sizes.data(), u0.data(),
+                b0.data(), nullptr);
+    double bb[4] = {0, 0, 0, 0};
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double v = pts4[4 * i + j];
+            bb[j] = v == v ? fmax(bb[j], fabs(v)) : __builtin_inf();
+        }
+    std::vector<int> pref((size_t)nBounds * nCells, 0);
+    for (int j = 0; j < nBounds; ++j) {
+        const int64_t d2 = 2 * (int64_t)bounds[j];
+        const int lim = d2 < N ? (int)d2 : N;
+        for (int i = 0; i < lim; ++i) ++pref[(size_t)j * nCells + cellId[i]];
+    }
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    const double kappa = h_cell_kappa(slopes.a.x, slopes.a.y);
+    const HCellModel cc = h_cell_model(cand8, bb, thr2, kappa, kCertT, kCertSlop);
+    int kept = 0;
+    for (int k = 0; k < nModels; ++k) {
+        const float* h = models8 + 8 * k;
+        const HCellModel cm = h_cell_model(h, bb, thr2, kappa, kCertT, kCertSlop);
+        const HCellRel rel = h_cell_rel(h, cm, cand8, cc);
+        int u = 0;
+        for (int w = 0; w < words; ++w) bits[(size_t)k * words + w] = 0;
+        for (int j = 0; j < nBounds; ++j) left[(size_t)j * nModels + k] = 0;
+        for (int c = 0; c < nCells; ++c) {
+            if (sizes[c] == 0) continue;
+            const float* box = boxes.data() + 8 * c;
+            bool cert = h_cell_certified(h, cm, box);
+            if (c >= relBase && !cert) cert = h_cell_rel_certified(h, cm, cand8, cc, rel, box);
+            if (cert) {
+                bits[(size_t)k * words + (c >> 5)] |= 1u << (c & 31);
+                continue;
+            }
+            u += sizes[c];
+            for (int j = 0; j < nBounds; ++j) left[(size_t)j * nModels + k] += sizes[c] - pref[(size_t)j * nCells + c];
+        }
+        ub[k] = u;
+        kept += u >= B;
+    }
+    if (alive) *alive = kept;
+}
+
 // d_ctl: kHStageCtlInts ints; d_list: 2 x hypCount ints (the survivor lists, ping-pong).
 // d_cells (h_cell_count(G, Gs) x kHCellInts ints; nullptr: no per-cell bound): the cell table is built beside
 // the candidate's count, mcv_h_cell_bound drops the slots whose upper bound is below B before stage 1, and
-// stage 1 runs through its list.
+// stage 1 runs through its list. d_cell (with d_cells; id == nullptr: the box pass alone, the compactions
+// on N - processed): every point's cell id (N ints), the prefix table
+// (kHStageLater x cells ints) and the per-slot `left` figures (kHStageLater x hypCount ints) that the later
+// compactions use in place of N - processed (why that is exact: the caller's staging decision).
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec,
-                            unsigned long long* d_stats, int form, int* d_cells, int G, int Gs) {
+                            unsigned long long* d_stats, int form, int* d_cells, int G, int Gs, HCellBufs d_cell) {
     constexpr int TRIP = 64 * kCertNP;
     if (d_stats) (void)hipMemsetAsync(d_stats, 0, kHMfmaStats * sizeof(unsigned long long), s);
     const bool mfma = d_rec && d_stats && h_mfma_engages(N, hypCount, form, true);
@@ -342,19 +562,29 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
     stage(0, nullptr);
     // candidate: the best partial count before any sampler failure (minimum count 0: any model will do)
     launch_best(d_counts, hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
-    launch_h_stage_count(d_pts4, N, d_models, hypBegin, thr2, d_ctl, d_bb, d_cells, G, Gs, nullptr, s);
+    const bool rel = d_cells && d_cell.id;   // the bound's second pass and the per-slot `left`
+    launch_h_stage_count(d_pts4, N, d_models, hypBegin, thr2, d_ctl, d_bb, d_cells, G, Gs, rel ? d_cell.id : nullptr, s);
     hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, TRIP, kHStageLater,
                        N / kHStageSlackDiv, kHStageLatest256);
-    // the list of stage 1 is lists[1 & 1], the source of the first count-based compaction
-    if (d_cells)
+    // the list of stage 1 is lists[1 & 1], the source of the first count-based compaction: the box pass writes
+    // lists[1] (the slots the relative test cannot drop) and lists[0] (the others), the second pass (box +
+    // candidate-relative test, the per-slot `left`) appends what it keeps of lists[0] to lists[1]
+    if (d_cells && !rel)
         launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
                             s);
+    if (rel) {
+        launch_h_cell_prefix(d_cell.id, N, d_ctl, kHStageLater, G, Gs, d_cell.pref, s);
+        launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
+                            s, lists[0], d_cell.left, kHStageLater, N);
+        launch_h_cell_rel(d_models, d_models, hypBegin, hypCount, thr2, d_bb, d_cells, G, Gs, d_cell.pref,
+                          kHStageLater, d_ctl, lists[0], lists[1], d_cell.left, nullptr, nullptr, s);
+    }
     stage(1, d_cells ? lists[1] : nullptr);
     for (int st = 2; st < 2 + kHStageLater; ++st) {
         // the first compaction sees the recount marks (count < 0) before the recount overwrites them
         hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_counts, hypCount, N,
                            d_ctl, st, st == 2 && !d_cells ? (const int*)nullptr : (const int*)lists[(st - 1) & 1],
-                           lists[st & 1]);
+                           lists[st & 1], rel ? (const int*)d_cell.left : (const int*)nullptr);
         if (st == 2) recount();
         stage(st, lists[st & 1]);
     }
