@@ -739,8 +739,17 @@ MCV_API int mcvTestEigLogCap(int cap);
  * candidate, 2 = sampler failure in the chunk, 3 = first boundary too late, 4 = forced off (mode 2),
  * 5 = the call did not qualify, -1 = no evaluate yet; [1] B, the candidate's full count; [2] the
  * number of stages; [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
- * [10..15] the slots alive entering each stage. Not thread-safe: tests only. */
+ * [10..15] the slots alive entering each stage ([10]: the slots stage 0 swept, fewer than the chunk's where
+ * stage 0 ran on a leading subset, see mcvTestHStage0Slots; [4] then reads 0). Not thread-safe: tests only. */
 MCV_API int mcvTestHStaging(int mode, long long* stats);
+/* The slots stage 0 of the staged homography sweep covers where the per-cell bound runs. Stage 0 only names the
+ * candidate, so it may sweep its prefix for a leading subset of the chunk's slots (into a scratch buffer); stage 1
+ * then runs the bound's list from point 0. slots 0: automatic (max(2^14, hypotheses / 16) from 2^18 hypotheses,
+ * every slot below), > 0: that many at any size (every slot where the chunk has no more), -1: leaves the setting.
+ * Returns the previous value, -1 on error. With a subset, mcvTestHStaging's stats[10] (alive[0]) is the number of
+ * slots stage 0 swept, not the chunk's, and stats[4] (the boundary stage 1 starts at) reads 0. Not thread-safe:
+ * tests only. */
+MCV_API int mcvTestHStage0Slots(int slots);
 /* The per-cell inlier upper bound that drops hypotheses before stage 1 of the staged homography sweep.
  * mode 0: automatic (where the staged sweep's own size rule holds, from 20000 correspondences; its second pass,
  * the candidate-relative test and the per-slot points-left of the later compactions, from 35000), 1: both
@@ -769,6 +778,22 @@ MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* cand8, cons
 MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
                             float thr2, int B, int G, int Gs, const int* bounds, int nBounds, int device,
                             int* cellId, int* ub, unsigned int* bits, int* left, int* alive);
+/* The certified fp32 prefilter in front of the box test of both bound passes. For one (model, cell) it answers
+ * certified, not certified or undecided; undecided pairs run the fp64 box test, and a decided verdict always
+ * equals the fp64 test's, so every output of the bound is the same with the prefilter on or off. mode 0:
+ * automatic (on), 1: off (fp64 alone); any other mode leaves the setting. It applies to the staged sweep and to
+ * mcvTestHCellBound / mcvTestHCellRel, device and host twin. Returns the previous mode, -1 on error. stats (may be
+ * NULL; 2 values), for the calling thread's last staged evaluate with the bound (read after its stream was
+ * synchronised) or call of one of those two hooks: [0] the (model, cell) tests the prefilter decided, [1] those it
+ * left to fp64 (all of them with the prefilter off); lanes without a model are not counted. A staged evaluate
+ * counts only after the first call of this hook (the counters cost atomics). Not thread-safe: tests only. */
+MCV_API int mcvTestHCellPre(int mode, long long* stats);
+/* The prefilter's verdict on caller-supplied data, arguments as for mcvTestHCellBound (B is not read).
+ * verdicts[k * cells + c] for model k and cell c: 0 not certified, 1 certified, 2 undecided; an empty cell is
+ * undecided or not certified, never certified. Returns 1, 0 on failure. */
+MCV_API int mcvTestHCellPreVerdicts(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                                    float thr2, int B, int G, int Gs, int device, int* cellId, float* boxes,
+                                    int* sizes, unsigned char* verdicts);
 /* cvFindModelBatch's index arithmetic, as the export itself computes it (no device). Problems with more
  * than m (the sample size) correspondences run on the device and are numbered in order (d = 0, 1, ...).
  * desc4[4 p ..]: point offset (= offsets[p]: float4 points, no padding), N, slot offset (d * per, 64-bit;

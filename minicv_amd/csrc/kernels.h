@@ -70,6 +70,8 @@ static const int kCtlBound = 4;    // kHStageMax + 1 boundaries, in pairs
 static const int kCtlAlive = 12;   // slots alive entering each stage
 static const int kCtlPre = 18;     // slots the per-cell bound's box pass hands to the second pass
 static const int kCtlKey = 24;     // the candidate's packed key and the first failure (2 x 64 bit)
+static const int kCtlFailAll = 30; // stage 0 on a subset: the chunk's first failure from a pass over every status
+                                   // (64 bit; the key that pass packs lands in the two ints before it, unread)
 static const int kHStageMax = 6;          // stages: the prefix, the run to the first boundary, <= 4 later ones
 static const int kHStagePrefixDiv = 16;   // stage 0 sweeps ~N / 16 points
 static const int kHStageSlackDiv = 64;    // first boundary at N - B + N / 64 points
@@ -89,11 +91,27 @@ struct HCellBufs {
     int *id, *pref, *left;
 };
 static const int kHCellLater = kHStageMax - 2;   // the most later boundaries a slot keeps a `left` figure for
+// what the two bound passes read beside the cell table: the record list of the non-empty cells (h_cell_pre.h:
+// h_cell_rec_ints(cells) ints, written by launch_h_cell_pre; always needed), the switch of the box test's fp32
+// prefilter (0: fp64 runs alone) and two counters, the (model, cell) tests of the passes and the undecided of
+// them (nullptr: not counted)
+struct HCellPreBufs {
+    int* rec;
+    int on;
+    unsigned long long* stats;
+};
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec = nullptr,
                             unsigned long long* d_stats = nullptr, int form = kHFormValu, int* d_cells = nullptr,
-                            int G = 0, int Gs = 0, HCellBufs d_cell = HCellBufs{nullptr, nullptr, nullptr});
+                            int G = 0, int Gs = 0, HCellBufs d_cell = HCellBufs{nullptr, nullptr, nullptr},
+                            HCellPreBufs d_pre = HCellPreBufs{nullptr, 0, nullptr}, int* d_s0 = nullptr,
+                            int s0Slots = 0);
+// Stage 0 on a leading subset of the slots (with the per-cell bound only): stage 0 exists to name a candidate, and
+// the first slots name as good a one as all of them. It sweeps the prefix for the first S slots into
+// d_s0 (S ints), launch_best over d_s0 names the candidate, and stage 1 runs its list from point 0. The rule:
+// S = max(kHStage0MinSlots, hypCount / kHStage0Div) from kHStage0MinHyps hypotheses; mcvTestHStage0Slots forces S.
+static const int kHStage0MinHyps = 1 << 18, kHStage0MinSlots = 1 << 14, kHStage0Div = 16;
 // The per-cell bound before stage 1 (h_cell_bound.h): the cell table (h_cell_count(G, Gs) x
 // kHCellInts ints) is built with the candidate's count, the bound kernel writes the slots that can still
 // reach B to d_list and their number to ctl[kCtlAlive + 1]. The automatic rule engages it where the staged
@@ -120,18 +138,23 @@ void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int6
                           const double* d_bb, int* d_cells, int G, int Gs, int* d_cellOut, hipStream_t s);
 void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
                          const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
-                         hipStream_t s, int* d_listPre = nullptr, int* d_left = nullptr, int nLater = 0, int N = 0);
+                         hipStream_t s, int* d_listPre, int* d_left, int nLater, int N, HCellPreBufs pre);
+void launch_h_cell_pre(const int* d_cells, int G, int Gs, float thr2, int* d_rec, hipStream_t s);
+// the prefilter's verdict (h_cell_pre.h kHCellPre*) per (model, cell): nModels x cells bytes
+void launch_h_cell_pre_verdicts(const void* d_models, int nModels, float thr2, const double* d_bb, const int* d_cells,
+                                const int* d_rec, int G, int Gs, uint8_t* d_out, hipStream_t s);
 void launch_h_cell_prefix(const int* d_cellId, int N, const int* d_ctl, int nLater, int G, int Gs, int* d_pref,
                           hipStream_t s);
 void launch_h_cell_rel(const void* d_models, const void* d_candModels, int64_t hypBegin, int hypCount, float thr2,
                        const double* d_bb, const int* d_cells, int G, int Gs, const int* d_pref, int nLater,
                        int* d_ctl, const int* d_src, int* d_list, int* d_left, int* d_ub, uint32_t* d_bits,
-                       hipStream_t s);
+                       hipStream_t s, HCellPreBufs pre);
 void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2,
                      int B, int G, int Gs, const int* bounds, int nBounds, int* cellId, int* ub, uint32_t* bits,
-                     int* left, int* alive);
+                     int* left, int* alive, bool pre = false, long long* stats = nullptr);
 void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
-                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive);
+                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive,
+                 bool pre = false, long long* stats = nullptr, uint8_t* verdicts = nullptr);
 void h_reduce_sums(const float* d_pts4, int N, const uint8_t* d_mask, double* d_part, double* d_out, hipStream_t s);
 // The refit record: what HomographyEstimatorCallback::runKernel's three passes, chained on the device, leave
 // per problem (h_refit_chain: one record; launch_batch_refit_chain: one per problem) and what the host half

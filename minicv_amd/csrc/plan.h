@@ -79,6 +79,9 @@ struct Plan {
     DevBuf<int> hcellId;      // its cell of every correspondence (N)
     DevBuf<int> hcellPref;    // its prefix table: per later boundary and cell, the cell's points before the boundary
     DevBuf<int> hcellLeft;    // per later boundary and slot: the unprocessed points of the slot's uncertified cells
+    DevBuf<int> hstage0;      // stage 0 on a leading subset of the slots: its counts (the subset's slots)
+    DevBuf<int> hcellRec;     // the bound passes' record list of the non-empty cells (h_cell_pre.h: h_cell_rec_ints)
+    DevBuf<unsigned long long> hcellPreStats;   // its (model, cell) tests and the undecided of them, last bound passes
     DevBuf<uint8_t> one;      // single-hypothesis output record
     DevBuf<double> ptsd;      // essential: double4 normalised correspondences
     DevBuf<double> raw;       // essential: uploaded V2d pairs (a then b)

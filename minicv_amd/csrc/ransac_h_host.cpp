@@ -8,7 +8,7 @@
 // Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
 // [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
 // Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHCellRel,
-// mcvTestHMfma).
+// mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -16,6 +16,7 @@
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "h_cell_bound.h"
+#include "h_cell_pre.h"
 #include "plan.h"
 #include "lm_solver.h"
 
@@ -35,6 +36,14 @@ static thread_local Plan* t_hstage_plan = nullptr;
 // its two grids
 static int g_hcell_mode = 0;
 static int g_hcell_G = kHCellG, g_hcell_Gs = kHCellGs;
+// mcvTestHCellPre: the box test's fp32 prefilter (h_cell_pre.h): 0 automatic (on), 1 off; and where the calling
+// thread's last bound passes left their counters: a plan's device counters, or a hook call's own figures
+static int g_hcell_pre_mode = 0;
+static bool g_hcell_pre_count = false;   // staged evaluates count only once the hook was called (two atomics a wave)
+// mcvTestHStage0Slots: the slots stage 0 sweeps where the bound runs: 0 the rule (kernels.h), else that many
+static int g_hstage0_slots = 0;
+static thread_local Plan* t_hcell_pre_plan = nullptr;
+static thread_local long long t_hcell_pre_last[2] = {0, 0};
 // mcvTestHMfma: the certified homography sweep's form (kHForm*), and where the calling thread's last
 // such sweep left its stats: a plan's device counters, or the values a sweep outside a plan reported
 static int g_hmfma_mode = kHFormAuto;
@@ -49,6 +58,7 @@ void h_mfma_set_last(const unsigned long long* stats3) {
 void h_plan_forget(const Plan* P) {
     if (t_hstage_plan == P) t_hstage_plan = nullptr;
     if (t_hmfma_plan == P) t_hmfma_plan = nullptr;
+    if (t_hcell_pre_plan == P) t_hcell_pre_plan = nullptr;
 }
 
 // The host half of HomographyEstimatorCallback::runKernel on a refit record (kernels.h kRefit*): the single
@@ -152,6 +162,23 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     // certified cells with the same meaning (every correspondence of the cell is an outlier of the slot's model
     // under the op-by-op error), so UB stays an upper bound and the paragraph above holds as it stands. With h
     // = the candidate the relative form is negative, so the candidate certifies none of its own inlier cells.
+    // Both passes put a certified fp32 prefilter in front of the box test (h_cell_pre.h): a decided verdict is the
+    // fp64 test's, the rest run fp64, so UB, the lists and `left` are the same bits either way.
+    // Stage 0 on a leading subset of the slots (with the bound, from kHStage0MinHyps hypotheses or by the hook): its
+    // counts go to a scratch buffer and only name the candidate; any slot with a model before the first failure
+    // serves, so B is still one hypothesis' full count and B <= the winning count. The counts buffer keeps what
+    // the generate wrote (0 or a status) until stage 1, which runs its list from point 0. Dropped slots: a slot the
+    // bound drops now holds 0 instead of a stage-0 partial; 0 is at most its full count and below B (a slot is
+    // dropped only on UB < B, so B >= 1). B = 0 and the minimum-count rule: with B = 0 nothing has UB < B, nothing
+    // is dropped, and a key below the minimum count maps to 0 from 0 as from any partial. Sampler failure: the
+    // subset's reduction does not see the other slots' statuses, so one more pass over every status gives the
+    // chunk's first failure; the plan takes the earlier of the two, and any failure switches pruning off
+    // (kHStageSamplerFailure) with stage 1 running every slot from 0 to the end: full counts for the host's
+    // fallback. No candidate among the subset (key 0), and the late-boundary rule: the same, every slot from 0 to
+    // the end. Recount marks: kStatusRedo marks of slots outside the subset first appear in stage 1; the first
+    // compaction reads them (count < 0: not listed) before the recount overwrites them, as it does for the marks
+    // stage 1 always could set; a mark stage 0 left in the scratch buffer is set again by stage 1, which tests the
+    // same model against the same extents.
     // With the bound the later compactions read points-left per slot: left = the correspondences not yet
     // processed that lie in cells the bound did not certify for the slot's model. The unprocessed points of
     // certified cells are outliers of that model, so only `left` of the N - processed points can still add to
@@ -169,12 +196,22 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     const bool cellBound = staged && g_hcell_mode != 2 && (g_hcell_mode == 1 || (sized && N >= kHCellMinN));
     // the bound's second pass costs a slot the same whatever N and saves in proportion to N (kernels.h)
     const bool cellRel = cellBound && (g_hcell_mode == 1 || N >= kHCellRelMinN);
+    // stage 0 on a leading subset of the slots, where the bound runs and the chunk is large (or the hook says so)
+    int stage0Slots = 0;
+    if (cellBound) {
+        if (g_hstage0_slots > 0) stage0Slots = g_hstage0_slots;
+        else if (hypCount >= kHStage0MinHyps) stage0Slots = std::max(kHStage0MinSlots, hypCount / kHStage0Div);
+        if (stage0Slots >= hypCount) stage0Slots = 0;
+    }
     if (staged) {
         P.hstageCtl.ensure(kHStageCtlInts);
         P.hstageList.ensure(2 * (size_t)hypCount);
         if (cellBound) {
             const size_t cells = (size_t)h_cell_count(g_hcell_G, g_hcell_Gs);
             P.hcells.ensure(cells * kHCellInts);
+            P.hcellRec.ensure(h_cell_rec_ints((int)cells));
+            if (stage0Slots) P.hstage0.ensure((size_t)stage0Slots);
+            P.hcellPreStats.ensure(2);
             if (cellRel) {
                 P.hcellId.ensure((size_t)N);
                 P.hcellPref.ensure(cells * kHStageLater);
@@ -194,13 +231,19 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     }
     const void* d_rec = P.hmfmaLast ? P.hrec.p : nullptr;
     unsigned long long* d_stats = P.hmfmaLast ? P.hmfmaStats.p : nullptr;
+    t_hcell_pre_plan = cellBound && g_hcell_pre_count ? &P : nullptr;
+    t_hcell_pre_last[0] = t_hcell_pre_last[1] = 0;
     ProfScope ps("h_verify", s);
     if (staged) {
         launch_h_verify_staged(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, hypBegin, thr2, P.bb4.p,
                                P.hstageCtl.p, P.hstageList.p, P.pkey.p, P.pfail.p, s, d_rec, d_stats, form,
                                cellBound ? P.hcells.p : nullptr, g_hcell_G, g_hcell_Gs,
                                cellRel ? HCellBufs{P.hcellId.p, P.hcellPref.p, P.hcellLeft.p}
-                                       : HCellBufs{nullptr, nullptr, nullptr});
+                                       : HCellBufs{nullptr, nullptr, nullptr},
+                               cellBound ? HCellPreBufs{P.hcellRec.p, g_hcell_pre_mode == 0,
+                                                        g_hcell_pre_count ? P.hcellPreStats.p : nullptr}
+                                         : HCellPreBufs{nullptr, 0, nullptr},
+                               stage0Slots ? P.hstage0.p : nullptr, stage0Slots);
     } else if (!fused) {
         // default: OpenCV's op-by-op error, certified division-free sweep
         launch_h_verify_certified(d_pts, P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, P.bb4.p, s, d_rec,
@@ -383,16 +426,23 @@ extern "C" MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* 
             fail("mcvTestHCellBound: null argument");
         if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs)
             fail("mcvTestHCellBound: bad sizes");
+        t_hcell_pre_plan = nullptr;
+        t_hcell_pre_last[0] = t_hcell_pre_last[1] = 0;
         if (!device) {
-            h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes, sizes, ub, bits, alive);
+            h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes, sizes, ub, bits, alive,
+                        g_hcell_pre_mode == 0, t_hcell_pre_last);
             return 1;
         }
         require_device();
         const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
         DevBuf<float> p, m, cand;
+        DevBuf<unsigned long long> pst;
         DevBuf<double> bb;
-        DevBuf<int> ctl, tab, cnt, list, dub, did;
+        DevBuf<int> ctl, tab, cnt, list, dub, did, pre;
         DevBuf<uint32_t> dbits;
+        pre.ensure(h_cell_rec_ints(cells));
+        pst.ensure(2);
+        MCV_HIP(hipMemset(pst.p, 0, 2 * sizeof(unsigned long long)));
         p.ensure((size_t)N * 4);
         m.ensure((size_t)nModels * 8);
         cand.ensure(8);
@@ -419,9 +469,12 @@ extern "C" MCV_API int mcvTestHCellBound(const float* pts4, int N, const float* 
         MCV_HIP(hipDeviceSynchronize());
         // B as given (the kernel counted the candidate's inliers into the same word)
         MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
-        launch_h_cell_bound(m.p, cnt.p, nModels, thr2, bb.p, tab.p, G, Gs, ctl.p, list.p, dub.p, dbits.p, 0);
+        launch_h_cell_pre(tab.p, G, Gs, thr2, pre.p, 0);
+        launch_h_cell_bound(m.p, cnt.p, nModels, thr2, bb.p, tab.p, G, Gs, ctl.p, list.p, dub.p, dbits.p, 0, nullptr,
+                            nullptr, 0, 0, HCellPreBufs{pre.p, g_hcell_pre_mode == 0, pst.p});
         MCV_HIP(hipGetLastError());
         MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(t_hcell_pre_last, pst.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         std::vector<int> htab((size_t)cells * kHCellInts);
         MCV_HIP(hipMemcpy(htab.data(), tab.p, htab.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int c = 0; c < cells; ++c) {
@@ -450,14 +503,21 @@ extern "C" MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* ca
             fail("mcvTestHCellRel: bad sizes");
         for (int j = 0; j < nBounds; ++j)
             if (bounds[j] < 0 || bounds[j] > (N + 1) / 2) fail("mcvTestHCellRel: boundary out of range");
+        t_hcell_pre_plan = nullptr;
+        t_hcell_pre_last[0] = t_hcell_pre_last[1] = 0;
         if (!device) {
             h_cell_rel_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, bounds, nBounds, cellId, ub, bits, left,
-                            alive);
+                            alive, g_hcell_pre_mode == 0, t_hcell_pre_last);
             return 1;
         }
         require_device();
         const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
         DevBuf<float> p, m, cand;
+        DevBuf<int> pre;
+        DevBuf<unsigned long long> pst;
+        pre.ensure(h_cell_rec_ints(cells));
+        pst.ensure(2);
+        MCV_HIP(hipMemset(pst.p, 0, 2 * sizeof(unsigned long long)));
         DevBuf<double> bb;
         DevBuf<int> ctl, tab, list, dub, did, pref, dleft;
         DevBuf<uint32_t> dbits;
@@ -488,16 +548,102 @@ extern "C" MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* ca
         MCV_HIP(hipDeviceSynchronize());
         MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
         launch_h_cell_prefix(did.p, N, ctl.p, nBounds, G, Gs, pref.p, 0);
+        launch_h_cell_pre(tab.p, G, Gs, thr2, pre.p, 0);
         launch_h_cell_rel(m.p, cand.p, 0, nModels, thr2, bb.p, tab.p, G, Gs, pref.p, nBounds, ctl.p, nullptr, list.p,
-                          dleft.p, dub.p, dbits.p, 0);
+                          dleft.p, dub.p, dbits.p, 0, HCellPreBufs{pre.p, g_hcell_pre_mode == 0, pst.p});
         MCV_HIP(hipGetLastError());
         MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(t_hcell_pre_last, pst.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(ub, dub.p, (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(bits, dbits.p, (size_t)nModels * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(left, dleft.p, (size_t)nModels * nBounds * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
         *alive = hctl[kCtlAlive + 1];
+        return 1;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the slots stage 0 sweeps where the per-cell bound runs.
+extern "C" MCV_API int mcvTestHStage0Slots(int slots) {
+    MCV_GUARD(-1, {
+        const int prev = g_hstage0_slots;
+        if (slots >= 0) g_hstage0_slots = slots;
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the prefilter's switch and the counters of the calling thread's last
+// bound passes (a staged evaluate: call after synchronising its stream) or hook call.
+extern "C" MCV_API int mcvTestHCellPre(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hcell_pre_mode;
+        if (mode == 0 || mode == 1) g_hcell_pre_mode = mode;
+        g_hcell_pre_count = true;
+        if (stats) {
+            unsigned long long v[2] = {(unsigned long long)t_hcell_pre_last[0], (unsigned long long)t_hcell_pre_last[1]};
+            const Plan* P = t_hcell_pre_plan;
+            if (P) MCV_HIP(hipMemcpy(v, P->hcellPreStats.p, sizeof(v), hipMemcpyDeviceToHost));
+            stats[0] = (long long)(v[0] - v[1]);
+            stats[1] = (long long)v[1];
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the prefilter's three-way verdict for every (model, cell) of the table
+// that mcvTestHCellBound builds from the same arguments, device kernel or host twin.
+extern "C" MCV_API int mcvTestHCellPreVerdicts(const float* pts4, int N, const float* cand8, const float* models8,
+                                               int nModels, float thr2, int B, int G, int Gs, int device, int* cellId,
+                                               float* boxes, int* sizes, unsigned char* verdicts) {
+    MCV_GUARD(0, {
+        if (!pts4 || !cand8 || !models8 || !cellId || !boxes || !sizes || !verdicts)
+            fail("mcvTestHCellPreVerdicts: null argument");
+        if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs)
+            fail("mcvTestHCellPreVerdicts: bad sizes");
+        const int cells = h_cell_count(G, Gs), words = (cells + 31) / 32;
+        if (!device) {
+            std::vector<int> ub(nModels);
+            std::vector<uint32_t> bits((size_t)nModels * words);
+            h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes, sizes, ub.data(), bits.data(),
+                        nullptr, false, nullptr, verdicts);
+            return 1;
+        }
+        require_device();
+        DevBuf<float> p, m, cand;
+        DevBuf<double> bb;
+        DevBuf<int> ctl, tab, did, pre;
+        DevBuf<uint8_t> dv;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        cand.ensure(8);
+        bb.ensure(4);
+        ctl.ensure(kHStageCtlInts);
+        tab.ensure((size_t)cells * kHCellInts);
+        did.ensure(N);
+        dv.ensure((size_t)nModels * cells);
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cand.p, cand8, 32, hipMemcpyHostToDevice));
+        int hctl[kHStageCtlInts] = {0};
+        const uint64_t key = (1ull << 32) | 0xFFFFFFFFull;   // slot 0 of `cand` is the candidate
+        memcpy(hctl + kCtlKey, &key, sizeof(key));
+        MCV_HIP(hipMemcpy(ctl.p, hctl, sizeof(hctl), hipMemcpyHostToDevice));
+        launch_abs_bound4(p.p, false, N, bb.p, nullptr, 0);
+        launch_h_stage_count(p.p, N, cand.p, 0, thr2, ctl.p, bb.p, tab.p, G, Gs, did.p, 0);
+        pre.ensure(h_cell_rec_ints(cells));
+        launch_h_cell_pre(tab.p, G, Gs, thr2, pre.p, 0);
+        launch_h_cell_pre_verdicts(m.p, nModels, thr2, bb.p, tab.p, pre.p, G, Gs, dv.p, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        std::vector<int> htab((size_t)cells * kHCellInts);
+        MCV_HIP(hipMemcpy(htab.data(), tab.p, htab.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int c = 0; c < cells; ++c) {
+            for (int j = 0; j < 8; ++j) boxes[8 * c + j] = h_cell_dec(htab[(size_t)c * kHCellInts + j]);
+            sizes[c] = htab[(size_t)c * kHCellInts + kHCellInts - 1];
+        }
+        MCV_HIP(hipMemcpy(cellId, did.p, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(verdicts, dv.p, (size_t)nModels * cells, hipMemcpyDeviceToHost));
         return 1;
     })
 }

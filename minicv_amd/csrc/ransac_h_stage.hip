@@ -3,7 +3,8 @@
 // control block's init, the candidate's exact count and the cell table (mcv_h_stage_count), the stage
 // planner, the survivor compaction, the per-cell bound (h_cell_bound.h: mcv_h_cell_bound, the box pass over
 // every slot; mcv_h_cell_rel, the second pass with the candidate-relative test and the per-slot `left`;
-// mcv_h_cell_prefix, its prefix table) and the host twins. The stages themselves are the sweeps of
+// mcv_h_cell_prefix, its prefix table; mcv_h_cell_pre_build, the record list of the non-empty cells with the floats
+// of the box test's fp32 prefilter, h_cell_pre.h) and the host twins. The stages themselves are the sweeps of
 // ransac_h_sweep.hip / ransac_h_mfma.hip.
 #include <algorithm>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "hyp_homography.h"
 #include "h_cert.h"
 #include "h_cell_bound.h"
+#include "h_cell_pre.h"
 
 namespace mcv {
 
@@ -19,12 +21,14 @@ namespace mcv {
 // ------------------------------------------------------------------------------------------
 // cells: the cell slots of the per-cell bound (0: the bound is off and stage 1 takes every slot; else the
 // bound kernel counts the slots it keeps into ctl[kCtlAlive + 1], from 0).
-__global__ void mcv_h_stage_init(int* __restrict__ ctl, int pa, int hypCount, int cells) {
+// swept0: the slots stage 0 sweeps (hypCount, or the leading subset).
+__global__ void mcv_h_stage_init(int* __restrict__ ctl, int pa, int hypCount, int cells, int swept0) {
     const int i = threadIdx.x;
     if (i >= kHStageCtlInts) return;
     int v = 0;
     if (i == kCtlBound + 1) v = pa;
-    if (i == kCtlAlive || (i == kCtlAlive + 1 && cells == 0)) v = hypCount;
+    if (i == kCtlAlive) v = swept0;
+    if (i == kCtlAlive + 1 && cells == 0) v = hypCount;
     if (i == kCtlCells) v = cells;
     ctl[i] = v;
 }
@@ -118,11 +122,21 @@ __global__ __launch_bounds__(1024) void mcv_h_stage_count(const float4* __restri
 // the rest evenly. Pruning switches itself off (stage 1 runs every slot to the end) without a
 // candidate, with a sampler failure in the chunk (the host then reads every count) and when the first
 // boundary lies beyond latest/256 of the pairs.
-__global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int later, int slackPts, int latest256) {
+// subset: stage 0 swept only a leading subset of the slots, into a scratch buffer. The candidate's key is the
+// subset's; the chunk's first sampler failure is the earlier of the subset's and the one a pass over every slot's
+// status left in ctl[kCtlFailAll]; and stage 1 starts at point 0 (boundary 1 is reset), since the counts buffer
+// holds no stage-0 partials.
+__global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int later, int slackPts, int latest256,
+                                 int subset) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const int nPairs = (N + 1) / 2;
     const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
-    const int64_t fail = *(const int64_t*)(ctl + kCtlKey + 2);
+    int64_t fail = *(const int64_t*)(ctl + kCtlKey + 2);
+    if (subset) {
+        const int64_t all = *(const int64_t*)(ctl + kCtlFailAll);
+        fail = all < fail ? all : fail;
+        *(int64_t*)(ctl + kCtlKey + 2) = fail;
+    }
     const int pa = ctl[kCtlBound + 1];
     int reason = 0;
     int p1 = nPairs;
@@ -143,6 +157,7 @@ __global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int lat
         int b = s == later ? nPairs : p1 + (int)((int64_t)trips * s / later) * trip;
         ctl[kCtlBound + 2 + s] = b;
     }
+    if (subset) ctl[kCtlBound + 1] = 0;
 }
 
 // Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
@@ -197,6 +212,83 @@ struct HCellPre {
     int nLater, N;
 };
 
+// The record list of the non-empty cells (h_cell_pre.h: kHCellRec*), once per call: one block, the cells in
+// table order (ballot + a scan over the block's waves), so the list is deterministic.
+__global__ __launch_bounds__(1024) void mcv_h_cell_pre_build(const int* __restrict__ cells, int nCells, double kappa,
+                                                             int* __restrict__ rec) {
+    __shared__ int wsum[16];
+    __shared__ int base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < nCells; c0 += 1024) {   // block-uniform trip count
+        const int c = c0 + threadIdx.x;
+        const int size = c < nCells ? cells[c * kHCellInts + kHCellInts - 1] : 0;
+        const uint64_t b = __ballot(size > 0);
+        if (lane == 0) wsum[wave] = (int)__popcll(b);
+        __syncthreads();
+        if (size > 0) {
+            int at = base + (int)__popcll(b & ((1ull << lane) - 1));
+            for (int w = 0; w < wave; ++w) at += wsum[w];
+            int* r = rec + kHCellRecHead + at * kHCellRecInts;   // at <= c < nCells
+            float box[8], q[kHCellPreFloats];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(cells[c * kHCellInts + j]);
+            h_cell_pre_box(box, kappa, q);
+#pragma unroll
+            for (int j = 0; j < kHCellPreFloats; ++j) r[j] = __float_as_int(q[j]);
+            r[kHCellPreFloats] = size;
+            r[kHCellPreFloats + 1] = c;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int w = 0; w < 16; ++w) base += wsum[w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rec[0] = base;
+}
+
+// The box test of one non-empty cell (e: its table entry; r: its record; on: the prefilter's switch; all
+// wave-uniform) for the lanes with a model (active; the verdict of the others is not used): the fp32 prefilter, and
+// the fp64 test for the lanes it leaves undecided, skipped when the wave has none. undecided: the wave's count of
+// such lanes (wave-uniform).
+__device__ __forceinline__ bool h_cell_box_test(const float* h, const HCellModel& cm, const HCellPreModel& pm,
+                                                const int* e, const int* r, int on, bool active,
+                                                int& undecided) {
+    int v = kHCellPreUndecided;
+    if (on) {
+        float qq[kHCellPreFloats];
+#pragma unroll
+        for (int j = 0; j < kHCellPreFloats; ++j) qq[j] = __int_as_float(r[j]);
+        v = h_cell_pre(h, pm, qq);
+    }
+    bool cert = v == kHCellPreCert;
+    // a lane without a model (a status, the tail of the grid) holds whatever its slot's model bytes are: it never
+    // sends the wave into the fp64 body and is not counted
+    const bool und = active && v == kHCellPreUndecided;
+    const uint64_t open = __ballot(und);
+    if (open) {
+        undecided += (int)__popcll(open);
+        if (und) {
+            float box[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
+            cert = h_cell_certified(h, cm, box);
+        }
+    }
+    return cert;
+}
+
+// One wave's figures into the counters (stats == nullptr, the sweep unless mcvTestHCellPre asked: nothing): tested
+// cells x its lanes with a model, and the undecided of them.
+__device__ __forceinline__ void h_cell_pre_stats(unsigned long long* stats, int tested, bool active, int undecided) {
+    if (!stats) return;
+    const uint64_t lanes = __ballot(active);
+    if ((threadIdx.x & 63) != 0) return;
+    atomicAdd(stats, (unsigned long long)tested * (unsigned long long)__popcll(lanes));
+    if (undecided) atomicAdd(stats + 1, (unsigned long long)undecided);
+}
+
 // The per-cell bound (h_cell_bound.h), lane = slot: UB = the sizes of the cells the model does not certify
 // as all-outlier, an upper bound of the slot's full count. Slots with a model and UB >= B (inclusive: ties
 // survive) enter the survivor list of stage 1 as mcv_h_stage_compact writes its lists (ballot, one
@@ -217,7 +309,7 @@ __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restric
                                                         const int* __restrict__ cells, int nCells, int* ctl,
                                                         int* __restrict__ dst, HCellPre hp,
                                                         int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
-                                                        int bitWords) {
+                                                        int bitWords, HCellPreBufs pa) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool have = i < hypCount && counts[i] >= 0;
     bool keep = have, second = false;
@@ -227,20 +319,20 @@ __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restric
 #pragma unroll
         for (int j = 0; j < 4; ++j) b4[j] = bb[j];
         const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
+        const HCellPreModel pm = h_cell_pre_model(cm, b4);
         int ub = 0, ubRel = 0;   // ubRel: the part of ub in the cells of the candidate's inliers
-        for (int c = 0; c < nCells; ++c) {
-            const int* e = cells + c * kHCellInts;
-            const int size = e[kHCellInts - 1];
-            if (size == 0) continue;
-            float box[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
-            const bool cert = h_cell_certified(m.h, cm, box);
+        const int tested = pa.rec[0];   // the non-empty cells
+        int undecided = 0;              // wave-uniform
+        for (int k = 0; k < tested; ++k) {
+            const int* r = pa.rec + kHCellRecHead + k * kHCellRecInts;
+            const int size = r[kHCellPreFloats], c = r[kHCellPreFloats + 1];
+            const bool cert = h_cell_box_test(m.h, cm, pm, cells + c * kHCellInts, r, pa.on, have, undecided);
             ub += cert ? 0 : size;
             if (hp.pre && c >= hp.relBase) ubRel += cert ? 0 : size;
             if (bitsOut && cert && i < hypCount) bitsOut[(size_t)i * bitWords + (c >> 5)] |= 1u << (c & 31);
         }
         if (ubOut && i < hypCount) ubOut[i] = ub;
+        h_cell_pre_stats(pa.stats, tested, have, undecided);
         const int B = ctl[kCtlB];
         keep = have && ub >= B;
         if (hp.pre) {
@@ -310,7 +402,7 @@ __global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict_
                                                       int nLater, int* ctl, const int* __restrict__ src,
                                                       int* __restrict__ dst, int* __restrict__ slotLeft,
                                                       int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
-                                                      int bitWords) {
+                                                      int bitWords, HCellPreBufs pa) {
     if (ctl[kCtlReason] != 0) return;
     const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
     if (key == 0) return;   // never with pruning on
@@ -327,19 +419,24 @@ __global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict_
     const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
     const HCellModel cc = h_cell_model(cand.h, b4, thr2, kappa, kCertT, kCertSlop);
     const HCellRel rel = h_cell_rel(m.h, cm, cand.h, cc);
+    const HCellPreModel pm = h_cell_pre_model(cm, b4);
     int ub = 0;
     int left[kHCellLater];
 #pragma unroll
     for (int j = 0; j < kHCellLater; ++j) left[j] = 0;
-    for (int c = 0; c < nCells; ++c) {
+    const int tested = pa.rec[0];   // the non-empty cells
+    int undecided = 0;              // wave-uniform
+    for (int k = 0; k < tested; ++k) {
+        const int* r = pa.rec + kHCellRecHead + k * kHCellRecInts;
+        const int size = r[kHCellPreFloats], c = r[kHCellPreFloats + 1];
         const int* e = cells + c * kHCellInts;
-        const int size = e[kHCellInts - 1];
-        if (size == 0) continue;
-        float box[8];
+        bool cert = h_cell_box_test(m.h, cm, pm, e, r, pa.on, have, undecided);
+        if (c >= relBase && !cert) {
+            float box[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
-        bool cert = h_cell_certified(m.h, cm, box);
-        if (c >= relBase && !cert) cert = h_cell_rel_certified(m.h, cm, cand.h, cc, rel, box);
+            for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(e[j]);
+            cert = h_cell_rel_certified(m.h, cm, cand.h, cc, rel, box);
+        }
         if (!cert) {
             ub += size;
 #pragma unroll
@@ -349,6 +446,7 @@ __global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict_
         if (bitsOut && cert && have) bitsOut[(size_t)slot * bitWords + (c >> 5)] |= 1u << (c & 31);
     }
     if (ubOut && have) ubOut[slot] = ub;
+    h_cell_pre_stats(pa.stats, tested, have, undecided);
     const bool keep = have && ub >= ctl[kCtlB];
     if (have) {
 #pragma unroll
@@ -386,12 +484,63 @@ void launch_h_stage_count(const float* d_pts4, int N, const void* d_models, int6
 
 void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount, float thr2, const double* d_bb,
                          const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
-                         hipStream_t s, int* d_listPre, int* d_left, int nLater, int N) {
+                         hipStream_t s, int* d_listPre, int* d_left, int nLater, int N, HCellPreBufs pre) {
     const HCertSlopes slopes = h_cert_slopes_host(thr2);
     const int nCells = h_cell_count(G, Gs);
     hipLaunchKernelGGL(mcv_h_cell_bound, dim3((hypCount + 255) / 256), dim3(256), 0, s, (const HModelF*)d_models,
                        d_counts, hypCount, thr2, h_cell_kappa(slopes.a.x, slopes.a.y), d_bb, d_cells, nCells, d_ctl,
-                       d_list, HCellPre{d_listPre, d_left, G * G * G * G, nLater, N}, d_ub, d_bits, (nCells + 31) / 32);
+                       d_list, HCellPre{d_listPre, d_left, G * G * G * G, nLater, N}, d_ub, d_bits, (nCells + 31) / 32,
+                       pre);
+}
+
+// The record list of the non-empty cells (h_cell_rec_ints(cells) ints) from the cell table, for the two bound
+// passes: they loop over it whether the prefilter is on or off.
+void launch_h_cell_pre(const int* d_cells, int G, int Gs, float thr2, int* d_rec, hipStream_t s) {
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    hipLaunchKernelGGL(mcv_h_cell_pre_build, dim3(1), dim3(1024), 0, s, d_cells, h_cell_count(G, Gs),
+                       h_cell_kappa(slopes.a.x, slopes.a.y), d_rec);
+}
+
+// mcvTestHCellPreVerdicts: lane = model, the prefilter's verdict for every cell of the table (empty ones too).
+__global__ __launch_bounds__(256) void mcv_h_cell_pre_verdicts(const HModelF* __restrict__ models, int nModels,
+                                                               float thr2, double kappa, const double* __restrict__ bb,
+                                                               const int* __restrict__ cells, int nCells,
+                                                               const int* __restrict__ rec,
+                                                               uint8_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nModels) return;
+    const HModelF m = models[i];
+    double b4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b4[j] = bb[j];
+    const HCellModel cm = h_cell_model(m.h, b4, thr2, kappa, kCertT, kCertSlop);
+    const HCellPreModel pm = h_cell_pre_model(cm, b4);
+    for (int c = 0; c < nCells; ++c) {
+        if (cells[c * kHCellInts + kHCellInts - 1] != 0) continue;   // non-empty: from its record, below
+        float box[8], q[kHCellPreFloats];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) box[j] = h_cell_dec(cells[c * kHCellInts + j]);
+        h_cell_pre_box(box, kappa, q);
+        out[(size_t)i * nCells + c] = (uint8_t)h_cell_pre(m.h, pm, q);
+    }
+    // the floats mcv_h_cell_pre_build wrote, as the two bound passes read them
+    const int nRec = rec[0];
+    for (int k = 0; k < nRec; ++k) {
+        const int* r = rec + kHCellRecHead + k * kHCellRecInts;
+        float q[kHCellPreFloats];
+#pragma unroll
+        for (int j = 0; j < kHCellPreFloats; ++j) q[j] = __int_as_float(r[j]);
+        const int c = r[kHCellPreFloats + 1];
+        if ((unsigned)c < (unsigned)nCells) out[(size_t)i * nCells + c] = (uint8_t)h_cell_pre(m.h, pm, q);
+    }
+}
+
+void launch_h_cell_pre_verdicts(const void* d_models, int nModels, float thr2, const double* d_bb, const int* d_cells,
+                                const int* d_rec, int G, int Gs, uint8_t* d_out, hipStream_t s) {
+    const HCertSlopes slopes = h_cert_slopes_host(thr2);
+    hipLaunchKernelGGL(mcv_h_cell_pre_verdicts, dim3((nModels + 255) / 256), dim3(256), 0, s,
+                       (const HModelF*)d_models, nModels, thr2, h_cell_kappa(slopes.a.x, slopes.a.y), d_bb, d_cells,
+                       h_cell_count(G, Gs), d_rec, d_out);
 }
 
 // d_pref: nLater x cells ints, from the cell ids mcv_h_stage_count kept and the control block's boundaries
@@ -410,18 +559,40 @@ void launch_h_cell_prefix(const int* d_cellId, int N, const int* d_ctl, int nLat
 void launch_h_cell_rel(const void* d_models, const void* d_candModels, int64_t hypBegin, int hypCount, float thr2,
                        const double* d_bb, const int* d_cells, int G, int Gs, const int* d_pref, int nLater,
                        int* d_ctl, const int* d_src, int* d_list, int* d_left, int* d_ub, uint32_t* d_bits,
-                       hipStream_t s) {
+                       hipStream_t s, HCellPreBufs pre) {
     const HCertSlopes slopes = h_cert_slopes_host(thr2);
     const int nCells = h_cell_count(G, Gs);
     hipLaunchKernelGGL(mcv_h_cell_rel, dim3((hypCount + 255) / 256), dim3(256), 0, s, (const HModelF*)d_models,
                        (const HModelF*)d_candModels, hypBegin, hypCount, thr2, h_cell_kappa(slopes.a.x, slopes.a.y),
                        d_bb, d_cells, nCells, G * G * G * G, d_pref, nLater, d_ctl, d_src, d_list, d_left, d_ub,
-                       d_bits, (nCells + 31) / 32);
+                       d_bits, (nCells + 31) / 32, pre);
 }
 
-// Host twin of the cell build and the bound (mcvTestHCellBound): the same header, the same arithmetic.
+// The device's h_cell_box_test on the host: the prefilter (pre) and fp64 for what it leaves undecided.
+// stats (may be nullptr): [0] tests, [1] undecided of them.
+static bool h_cell_box_host(const float* h, const HCellModel& cm, const HCellPreModel& pm, const float* box, bool pre,
+                            double kappa, long long* stats, uint8_t* verdict) {
+    int v = kHCellPreUndecided;
+    if (pre || verdict) {
+        float q[kHCellPreFloats];
+        h_cell_pre_box(box, kappa, q);
+        const int pv = h_cell_pre(h, pm, q);
+        if (verdict) *verdict = (uint8_t)pv;
+        if (pre) v = pv;
+    }
+    if (stats) {
+        ++stats[0];
+        stats[1] += v == kHCellPreUndecided;
+    }
+    return v == kHCellPreUndecided ? h_cell_certified(h, cm, box) : v == kHCellPreCert;
+}
+
+// Host twin of the cell build and the bound (mcvTestHCellBound): the same headers, the same arithmetic.
+// pre: with the fp32 prefilter in front (as the device kernels run it); stats: its counters; verdicts (nModels x
+// cells bytes): its three-way verdict for every cell, empty ones included (mcvTestHCellPreVerdicts).
 void h_cell_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2, int B,
-                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive) {
+                 int G, int Gs, int* cellId, float* boxes, int* sizes, int* ub, uint32_t* bits, int* alive, bool pre,
+                 long long* stats, uint8_t* verdicts) {
     const int nCells = h_cell_count(G, Gs), words = (nCells + 31) / 32;
     double bb[4] = {0, 0, 0, 0};
     for (int i = 0; i < N; ++i)
@@ -457,11 +628,20 @@ void h_cell_host(const float* pts4, int N, const float* cand8, const float* mode
     for (int k = 0; k < nModels; ++k) {
         const float* h = models8 + 8 * k;
         const HCellModel cm = h_cell_model(h, bb, thr2, kappa, kCertT, kCertSlop);
+        const HCellPreModel pm = h_cell_pre_model(cm, bb);
         int u = 0;
         for (int w = 0; w < words; ++w) bits[(size_t)k * words + w] = 0;
         for (int c = 0; c < nCells; ++c) {
-            if (sizes[c] == 0) continue;
-            const bool cert = h_cell_certified(h, cm, boxes + 8 * c);
+            uint8_t* vd = verdicts ? verdicts + (size_t)k * nCells + c : nullptr;
+            if (sizes[c] == 0) {
+                if (vd) {
+                    float q[kHCellPreFloats];
+                    h_cell_pre_box(boxes + 8 * c, kappa, q);
+                    *vd = (uint8_t)h_cell_pre(h, pm, q);
+                }
+                continue;
+            }
+            const bool cert = h_cell_box_host(h, cm, pm, boxes + 8 * c, pre, kappa, stats, vd);
             u += cert ? 0 : sizes[c];
             if (cert) bits[(size_t)k * words + (c >> 5)] |= 1u << (c & 31);
         }
@@ -475,13 +655,13 @@ void h_cell_host(const float* pts4, int N, const float* cand8, const float* mode
 // UB and the `left` figures at the given boundaries (in pairs of points, the control block's unit).
 void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* models8, int nModels, float thr2,
                      int B, int G, int Gs, const int* bounds, int nBounds, int* cellId, int* ub, uint32_t* bits,
-                     int* left, int* alive) {
+                     int* left, int* alive, bool pre, long long* stats) {
     const int nCells = h_cell_count(G, Gs), words = (nCells + 31) / 32, relBase = G * G * G * G;
     std::vector<float> boxes((size_t)nCells * 8);
     std::vector<int> sizes(nCells), u0(nModels);
     std::vector<uint32_t> b0((size_t)nModels * words);
     h_cell_host(pts4, N, cand8, models8, nModels, thr2, B, G, Gs, cellId, boxes.data(), sizes.data(), u0.data(),
-                b0.data(), nullptr);
+                b0.data(), nullptr, false, nullptr, nullptr);
     double bb[4] = {0, 0, 0, 0};
     for (int i = 0; i < N; ++i)
         for (int j = 0; j < 4; ++j) {
@@ -502,13 +682,14 @@ void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* 
         const float* h = models8 + 8 * k;
         const HCellModel cm = h_cell_model(h, bb, thr2, kappa, kCertT, kCertSlop);
         const HCellRel rel = h_cell_rel(h, cm, cand8, cc);
+        const HCellPreModel pm = h_cell_pre_model(cm, bb);
         int u = 0;
         for (int w = 0; w < words; ++w) bits[(size_t)k * words + w] = 0;
         for (int j = 0; j < nBounds; ++j) left[(size_t)j * nModels + k] = 0;
         for (int c = 0; c < nCells; ++c) {
             if (sizes[c] == 0) continue;
             const float* box = boxes.data() + 8 * c;
-            bool cert = h_cell_certified(h, cm, box);
+            bool cert = h_cell_box_host(h, cm, pm, box, pre, kappa, stats, nullptr);
             if (c >= relBase && !cert) cert = h_cell_rel_certified(h, cm, cand8, cc, rel, box);
             if (cert) {
                 bits[(size_t)k * words + (c >> 5)] |= 1u << (c & 31);
@@ -523,6 +704,9 @@ void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* 
     if (alive) *alive = kept;
 }
 
+// With the per-cell bound and d_s0 (s0Slots ints, fewer than hypCount) stage 0 sweeps the prefix for the first
+// s0Slots slots only, into d_s0: it exists to name the candidate. d_counts then keeps the generate's 0 / status
+// until stage 1, which runs the bound's list from point 0 (the plan resets boundary 1).
 // d_ctl: kHStageCtlInts ints; d_list: 2 x hypCount ints (the survivor lists, ping-pong).
 // d_cells (h_cell_count(G, Gs) x kHCellInts ints; nullptr: no per-cell bound): the cell table is built beside
 // the candidate's count, mcv_h_cell_bound drops the slots whose upper bound is below B before stage 1, and
@@ -533,10 +717,16 @@ void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* 
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec,
-                            unsigned long long* d_stats, int form, int* d_cells, int G, int Gs, HCellBufs d_cell) {
+                            unsigned long long* d_stats, int form, int* d_cells, int G, int Gs, HCellBufs d_cell,
+                            HCellPreBufs d_pre, int* d_s0, int s0Slots) {
     constexpr int TRIP = 64 * kCertNP;
+    // stage 0 on the first s0 slots only, into d_s0 (0: on every slot, into d_counts); only with the bound, whose
+    // list stage 1 then runs from point 0
+    const int s0 = d_cells && d_s0 && s0Slots > 0 && s0Slots < hypCount ? s0Slots : 0;
     if (d_stats) (void)hipMemsetAsync(d_stats, 0, kHMfmaStats * sizeof(unsigned long long), s);
     const bool mfma = d_rec && d_stats && h_mfma_engages(N, hypCount, form, true);
+    // the form's engage rule goes by the launch's width
+    const bool mfma0 = s0 ? d_rec && d_stats && h_mfma_engages(N, s0, form, true) : mfma;
     // stages that run a list keep the VALU kernel; kHFormMfma is the A/B partner
     const bool mfmaList = mfma && form == kHFormMfma;
     const int nFull = N / 2 / TRIP * TRIP;
@@ -548,36 +738,46 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
     const HCertSlopes slopes = h_cert_slopes_host(thr2);
     auto stage = [&](int st, const int* list) {
         const HStageArgs sa{d_ctl, list, st};
-        if (list ? mfmaList : mfma)
-            launch_h_mfma_sweep(d_pts4, d_rec, N, d_models, d_counts, hypCount, thr2, slopes, d_bb, sa, d_stats, s);
+        int* cnt = st == 0 && s0 ? d_s0 : d_counts;
+        const int width = st == 0 && s0 ? s0 : hypCount;
+        if (list ? mfmaList : (st == 0 ? mfma0 : mfma))
+            launch_h_mfma_sweep(d_pts4, d_rec, N, d_models, cnt, width, thr2, slopes, d_bb, sa, d_stats, s);
         else
-            launch_h_cert_sweep(d_pairs, N, d_models, d_counts, hypCount, thr2, slopes, d_bb, sa, s);
+            launch_h_cert_sweep(d_pairs, N, d_models, cnt, width, thr2, slopes, d_bb, sa, s);
     };
     auto recount = [&]() {   // the slots marked kStatusRedo, over all N, by the exact scalar sweep
         launch_h_recount(d_pts4, N, d_models, d_counts, hypCount, thr2, false, nullptr, s);
     };
     int* lists[2] = {d_list, d_list + hypCount};
     hipLaunchKernelGGL(mcv_h_stage_init, dim3(1), dim3(64), 0, s, d_ctl, pa, hypCount,
-                       d_cells ? h_cell_count(G, Gs) : 0);
+                       d_cells ? h_cell_count(G, Gs) : 0, s0 ? s0 : hypCount);
+    if (s0) {
+        // the subset's statuses as the generate wrote them, and the chunk's first sampler failure from one pass
+        // over every slot's status (d_counts holds 0 or a status until stage 1): the key that pass packs is not read
+        (void)hipMemcpyAsync(d_s0, d_counts, (size_t)s0 * sizeof(int), hipMemcpyDeviceToDevice, s);
+        launch_best(d_counts, hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlFailAll - 2), s);
+    }
     stage(0, nullptr);
     // candidate: the best partial count before any sampler failure (minimum count 0: any model will do)
-    launch_best(d_counts, hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
+    launch_best(s0 ? d_s0 : d_counts, s0 ? s0 : hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
     const bool rel = d_cells && d_cell.id;   // the bound's second pass and the per-slot `left`
     launch_h_stage_count(d_pts4, N, d_models, hypBegin, thr2, d_ctl, d_bb, d_cells, G, Gs, rel ? d_cell.id : nullptr, s);
     hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, TRIP, kHStageLater,
-                       N / kHStageSlackDiv, kHStageLatest256);
+                       N / kHStageSlackDiv, kHStageLatest256, s0 ? 1 : 0);
     // the list of stage 1 is lists[1 & 1], the source of the first count-based compaction: the box pass writes
     // lists[1] (the slots the relative test cannot drop) and lists[0] (the others), the second pass (box +
     // candidate-relative test, the per-slot `left`) appends what it keeps of lists[0] to lists[1]
+    if (d_cells && d_pre.stats) (void)hipMemsetAsync(d_pre.stats, 0, 2 * sizeof(unsigned long long), s);
+    if (d_cells) launch_h_cell_pre(d_cells, G, Gs, thr2, d_pre.rec, s);
     if (d_cells && !rel)
         launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
-                            s);
+                            s, nullptr, nullptr, 0, 0, d_pre);
     if (rel) {
         launch_h_cell_prefix(d_cell.id, N, d_ctl, kHStageLater, G, Gs, d_cell.pref, s);
         launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
-                            s, lists[0], d_cell.left, kHStageLater, N);
+                            s, lists[0], d_cell.left, kHStageLater, N, d_pre);
         launch_h_cell_rel(d_models, d_models, hypBegin, hypCount, thr2, d_bb, d_cells, G, Gs, d_cell.pref,
-                          kHStageLater, d_ctl, lists[0], lists[1], d_cell.left, nullptr, nullptr, s);
+                          kHStageLater, d_ctl, lists[0], lists[1], d_cell.left, nullptr, nullptr, s, d_pre);
     }
     stage(1, d_cells ? lists[1] : nullptr);
     for (int st = 2; st < 2 + kHStageLater; ++st) {

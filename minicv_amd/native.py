@@ -210,6 +210,9 @@ SIGNATURES = {
     "mcvTestHCellMode": (_I, [_I, _I, _I, _P]),
     "mcvTestHCellBound": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcvTestHCellRel": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mcvTestHCellPre": (_I, [_I, _P]),
+    "mcvTestHStage0Slots": (_I, [_I]),
+    "mcvTestHCellPreVerdicts": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
