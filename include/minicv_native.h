@@ -485,6 +485,35 @@ MCV_API int cvFindScaledPoseCosts(const mcvCamera* srcCam, const mcvV3d* worldPo
                                   int N, const mcvM33d* rotation, const mcvV3d* translation, double* scales,
                                   double* costs);
 
+/* Track triangulation — Ray.intersection (src/MiniCV/Utilities.fs:100-165), the reference's managed
+ * multi-view triangulator, for T independent tracks in one call. Tracks are a CSR: offsets[T + 1]
+ * ints over the rays (or observations), offsets[0] == 0, non-decreasing, at most MCV_MAX_TRACK_LEN
+ * per track. All arithmetic is fp64 in the managed evaluation order. Per track, rays in
+ * input order:
+ *   dedupe: ray j is dropped when an earlier ray i < j equals it on all six doubles (HashSet.ofList;
+ *     the kept rays stay in input order, which fixes the order F# leaves unspecified);
+ *   pairs i < j of the kept rays, lexicographic: kept when |cross(dir_i, dir_j)| > sin 2 deg (the
+ *     double 0x1.1de58c9f7dc27p-5, the reference's asin test without the asin), both closest-point
+ *     parameters are > 0 (getClosestTs) and the midpoint of the two closest points is finite;
+ *   point = (sum of the kept midpoints, one sequential chain in pair order) / their number.
+ * Writes points[t] and pairCounts[t] = the number of midpoints; a track without one (F# None) gets
+ * pairCounts[t] = 0 and a point of three quiet NaNs. cvIntersectRays takes the rays as given
+ * (directions of unit length, as the reference assumes); cvTriangulateTracks builds them with
+ * Camera.unproject1 (Camera.fs:85-91) from cameras[cameraIdx[k]] and observations[k], and fills the
+ * optional per-track statistics in avgReprojectionError's form (CameraPose.fs:77-92): visible[t] =
+ * the track's observations (duplicates included) in which Camera.project1 sees the point, cost[t] =
+ * the sequential sum of |project1 - obs|^2 over them divided by visible[t], +inf when none (always
+ * for a track without a point). Either of cost / visible may be null.
+ * Return the number of tracks with pairCounts > 0; T == 0 returns 0. Return -1 with a message and
+ * write nothing on a null required pointer, negative T, bad offsets, a track over the cap, a camera
+ * index outside [0, nCameras), or when no HIP device is visible. */
+#define MCV_MAX_TRACK_LEN 4096
+typedef struct { mcvV3d origin, direction; } mcvRay3d;   /* Aardvark Ray3d: 48 B */
+MCV_API int cvIntersectRays(const mcvRay3d* rays, const int* offsets, int T, mcvV3d* points, int* pairCounts);
+MCV_API int cvTriangulateTracks(const mcvCamera* cameras, int nCameras, const int* cameraIdx,
+                                const mcvV2d* observations, const int* offsets, int T, mcvV3d* points,
+                                int* pairCounts, double* cost, int* visible);
+
 /* ------------------------------------------------------------------------------------------
  * (3) Device-level API: device pointers, caller's stream (hipStream_t as void*), current device.
  *     Points on device are packed fp32 correspondences float4 {x, y, x', y'} (16 B each).
@@ -577,6 +606,13 @@ MCV_API int mcvMatchL2U8Device(const uint8_t* d_q, int nq, const uint8_t* d_t, i
 MCV_API int mcvFindScaledPoseDevice(const mcvCamera* srcCam, const mcvV3d* d_world, const mcvV2d* d_obs, int N,
                                     const mcvM33d* rotation, const mcvV3d* translation, double* outCost,
                                     double* outScale, void* stream);
+
+/* cvTriangulateTracks with every array (cameras and offsets included) on the device. Runs on the
+ * null stream and synchronises it before returning; the argument checks run on the device first
+ * (one extra synchronisation), so a bad call still writes nothing. cost / visible may be null. */
+MCV_API int mcvTriangulateTracksDevice(const mcvCamera* d_cameras, int nCameras, const int* d_cameraIdx,
+                                       const mcvV2d* d_observations, const int* d_offsets, int T,
+                                       mcvV3d* d_points, int* d_pairCounts, double* d_cost, int* d_visible);
 
 /* Opt-in kernel timing: HIP events recorded around the inlier-sweep launches on their stream.
  * mcvProfileRead returns the number of launches of `kernel` ("h_verify", "f_verify", "a_verify") and their
@@ -873,6 +909,16 @@ MCV_API void mcvHostPhilox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
  * computed by the host-compiled kernel code with the reference's sequential sums (list order). */
 MCV_API int mcvHostScaledCosts(const mcvCamera* srcCam, const mcvV3d* worldPoints, const mcvV2d* observations, int N,
                                const mcvM33d* rotation, const mcvV3d* translation, double* scales, double* costs);
+/* Host twins of cvIntersectRays / cvTriangulateTracks: the same arguments, checks, outputs and
+ * return value, computed sequentially by the host-compiled kernel arithmetic (hyp_rays.h). No GPU. */
+MCV_API int mcvHostIntersectRays(const mcvRay3d* rays, const int* offsets, int T, mcvV3d* points, int* pairCounts);
+MCV_API int mcvHostTriangulateTracks(const mcvCamera* cameras, int nCameras, const int* cameraIdx,
+                                     const mcvV2d* observations, const int* offsets, int T, mcvV3d* points,
+                                     int* pairCounts, double* cost, int* visible);
+/* Counters of the calling thread's last cvIntersectRays / cvTriangulateTracks / mcvTriangulateTracksDevice
+ * call that reached the device: stats8 = {kernel launches, stream synchronisations, host<->device
+ * copies, memsets, short tracks (at most 16 rays), long tracks, 0, 0}. Returns 0. */
+MCV_API int mcvTestTriangulateStats(long long* stats8);
 
 #ifdef __cplusplus
 }

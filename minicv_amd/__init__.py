@@ -10,8 +10,9 @@ from .native import RansacConfig, NativeError
 from .opencv import RansacParams, findHomography, findFundamentalMat, matchHamming, matchL2, matchL2U8, \
     recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch
 from . import camera
-from .camera import Camera, CameraPose, findScaled
+from .camera import Camera, CameraPose, findScaled, triangulateTracks
 
 __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomography", "findFundamentalMat",
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
-           "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch", "camera", "Camera", "CameraPose", "findScaled"]
+           "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch", "camera", "Camera", "CameraPose", "findScaled",
+           "triangulateTracks"]

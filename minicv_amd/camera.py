@@ -149,3 +149,80 @@ def findScaledCosts(srcCam: Camera, world: np.ndarray, obs: np.ndarray, pose: Ca
                                      C.addressof(t), sc.ctypes.data, co.ctypes.data) < 0:
         raise RuntimeError(f"cvFindScaledPoseCosts failed: {N.last_error()}")
     return sc, co
+
+
+def cameras_array(cameras) -> np.ndarray:
+    """Cameras as (n, 14) float64 rows in mcvCamera's field order (location, forward, up, right, focal)."""
+    if isinstance(cameras, np.ndarray):
+        return np.ascontiguousarray(cameras, np.float64).reshape(-1, 14)
+    return np.array([np.concatenate([_v3(c.location), _v3(c.forward), _v3(c.up), _v3(c.right),
+                                     np.asarray(c.focal, np.float64).reshape(2)]) for c in cameras],
+                    np.float64).reshape(-1, 14)
+
+
+def unproject1(c: Camera, pt) -> np.ndarray:
+    """Camera.unproject1 (Camera.fs:85-91) -> the ray as six doubles (origin, direction). Scalar
+    Python floats in the managed evaluation order, as hyp_rays.h ray_unproject."""
+    x, y = (float(v) for v in np.asarray(pt, np.float64).reshape(2))
+    f = [float(v) for v in np.asarray(c.focal, np.float64).reshape(2)]
+    r, u, fw = ([float(v) for v in _v3(a)] for a in (c.right, c.up, c.forward))
+    a, b = x / f[0], y / f[1]
+    d = [a * r[k] + b * u[k] + fw[k] for k in range(3)]
+    l = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    inv = 1.0 / l if l != 0.0 else 0.0
+    return np.array([*(float(v) for v in _v3(c.location)), *(v * inv if l != 0.0 else 0.0 for v in d)])
+
+
+def _offsets(offsets) -> np.ndarray:
+    off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    if off.size < 1:
+        raise ValueError("offsets needs T + 1 entries")
+    return off
+
+
+def _nonnull(a: np.ndarray, shape) -> np.ndarray:
+    """An empty array may have no storage: the exports want real pointers."""
+    return a if a.size else np.zeros(shape, a.dtype)
+
+
+def intersectRays(rays, offsets):
+    """cvIntersectRays: Ray.intersection (Utilities.fs:159-165) of T tracks given as a CSR over
+    rays[n, 6] (origin, direction). -> (points[T, 3], pairCounts[T]); a track without a point (the
+    F# None) has pairCounts 0 and a NaN point. Raises NativeError when the native call fails."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    off = _offsets(offsets)
+    T = off.size - 1
+    pts, cnt = np.empty((T, 3)), np.empty(T, np.int32)
+    k = N.lib().cvIntersectRays(_nonnull(rays, (1, 6)).ctypes.data, off.ctypes.data, T, _nonnull(pts, (1, 3)).ctypes.data,
+                                _nonnull(cnt, 1).ctypes.data)
+    N.check(k >= 0, "cvIntersectRays")
+    return pts, cnt
+
+
+def intersection(rays):
+    """Ray.intersection (Utilities.fs:159-165): the point of one list of rays, or None."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    pts, cnt = intersectRays(rays, [0, rays.shape[0]])
+    return pts[0] if cnt[0] > 0 else None
+
+
+def triangulateTracks(cameras, cameraIdx, obs, offsets, stats: bool = False):
+    """cvTriangulateTracks: unproject1 of every observation and Ray.intersection per track.
+    cameras: Camera records or (n, 14) rows; cameraIdx[n], obs[n, 2], offsets[T + 1] (CSR).
+    -> (points[T, 3], pairCounts[T]), plus (cost[T], visible[T]) with stats=True."""
+    cams = cameras_array(cameras)
+    idx = np.ascontiguousarray(cameraIdx, np.int32).reshape(-1)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+    off = _offsets(offsets)
+    if idx.shape[0] != obs.shape[0]:
+        raise ValueError("cameraIdx and obs differ in length")
+    T = off.size - 1
+    pts, cnt = np.empty((T, 3)), np.empty(T, np.int32)
+    cost, vis = (np.empty(T), np.empty(T, np.int32)) if stats else (None, None)
+    k = N.lib().cvTriangulateTracks(_nonnull(cams, (1, 14)).ctypes.data, cams.shape[0], _nonnull(idx, 1).ctypes.data,
+                                    _nonnull(obs, (1, 2)).ctypes.data, off.ctypes.data, T,
+                                    _nonnull(pts, (1, 3)).ctypes.data, _nonnull(cnt, 1).ctypes.data,
+                                    _nonnull(cost, 1).ctypes.data if stats else None,
+                                    _nonnull(vis, 1).ctypes.data if stats else None)
+    N.check(k >= 0, "cvTriangulateTracks")
+    return (pts, cnt, cost, vis) if stats else (pts, cnt)

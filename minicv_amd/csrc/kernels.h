@@ -555,4 +555,23 @@ struct ScaledSetup;
 void launch_scaled(const ScaledSetup& S, const double* d_w3, const double* d_o2, int N, double* d_soa,
                    double* d_scales, uint8_t* d_used, double* d_costs, long long* d_out, hipStream_t s);
 
+// ---- Ray.intersection over many tracks (triangulate.hip)
+static const int kTriShortMax = 16;   // tracks of at most this many rays: one lane each; longer: one workgroup each
+// d_ctr: kTriCtrs counters, zeroed by the caller before the launches below.
+//   [0] long tracks queued, [1] tracks with a point, [2] first bad track + 1 (validation), [3] its kind,
+//   [4] first bad observation + 1
+static const int kTriCtrs = 8;
+// Checks the CSR offsets and (d_cameraIdx != nullptr) the camera indices on the device: two launches.
+void launch_tri_validate(const int* d_offsets, int T, const int* d_cameraIdx, int nCameras, unsigned int* d_ctr,
+                         hipStream_t s);
+// Camera.unproject1 of every observation of the T tracks into d_rays (6 doubles each): one launch.
+void launch_tri_unproject(const double* d_cameras, const int* d_cameraIdx, const double* d_obs,
+                          const int* d_offsets, int T, double* d_rays, hipStream_t s);
+// Points and pair counts of T tracks over d_rays: two launches (short tracks and the long-track queue).
+void launch_tri_intersect(const double* d_rays, const int* d_offsets, int T, double* d_points, int* d_pairCounts,
+                          int* d_longList, unsigned int* d_ctr, hipStream_t s);
+// Per-track cost / visible (either may be null, not both): one launch.
+void launch_tri_stats(const double* d_cameras, const int* d_cameraIdx, const double* d_obs, const int* d_offsets,
+                      int T, const double* d_points, double* d_cost, int* d_visible, hipStream_t s);
+
 }  // namespace mcv

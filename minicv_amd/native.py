@@ -33,6 +33,11 @@ class Camera(C.Structure):
     _fields_ = [("location", V3d), ("forward", V3d), ("up", V3d), ("right", V3d), ("focal", V2d)]
 
 
+class Ray3d(C.Structure):
+    """mcvRay3d: Aardvark's Ray3d (origin, direction), 48 bytes."""
+    _fields_ = [("origin", V3d), ("direction", V3d)]
+
+
 class RecoverPoseConfig(C.Structure):
     """MiniCVNative.cpp:39-46 / OpenCV.fs:16-36."""
     _fields_ = [("FocalLength", C.c_double), ("PrincipalPoint", V2d), ("Probability", C.c_double),
@@ -93,6 +98,9 @@ BATCH_PNP_WIDTH = 64       # poses (lanes) per workgroup of that sweep (kernels.
 BATCH_PNP_HYP_CAP = 1 << 18  # hypotheses per round of cvSolvePnPRansacBatch (ransac_batch_host.cpp)
 MATCH_BATCH_ROWS_HAMMING = 64   # query rows per workgroup of the batched matcher (kernels.h)
 MATCH_BATCH_ROWS_L2 = 128
+MAX_TRACK_LEN = 4096            # rays per track of the triangulation exports (MCV_MAX_TRACK_LEN)
+TRI_SHORT_MAX = 16              # longer tracks take the workgroup-per-track kernel (kernels.h kTriShortMax)
+SIN_MIN_ANGLE = float.fromhex("0x1.1de58c9f7dc27p-5")   # hyp_rays.h kSinMinAngle
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
 NORM_L2 = 4         # OpenCV numbering; uint8 + L2 = the exact int8 matcher (byte SIFT)
@@ -146,6 +154,8 @@ SIGNATURES = {
     "cvMatchL2U8Multi": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cvFindScaledPose": (_I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvFindScaledPoseCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "cvIntersectRays": (_I, [_P, _P, _I, _P, _P]),
+    "cvTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mcvGetLastError": (C.c_char_p, []),
     "mcvDeviceCount": (_I, []),
     "mcvVersion": (C.c_char_p, []),
@@ -172,6 +182,7 @@ SIGNATURES = {
     "mcvMatchL2Device": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mcvMatchL2U8Device": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mcvFindScaledPoseDevice": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "mcvTriangulateTracksDevice": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mcvProfileEnable": (None, [_I]),
     "mcvProfileReset": (None, []),
     "mcvProfileRead": (_I, [C.c_char_p, _P]),
@@ -218,6 +229,9 @@ SIGNATURES = {
     "mcvTestAffineSweep": (_I, [_P, _I, _P, _I, _F, _I, _P]),
     "mcvHostAffineRefine": (_I, [_I, _P, _I, _P, _P]),
     "mcvHostScaledCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "mcvHostIntersectRays": (_I, [_P, _P, _I, _P, _P]),
+    "mcvHostTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "mcvTestTriangulateStats": (_I, [_P]),
     "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),

@@ -261,3 +261,43 @@ def affine_problem(n: int, seed: int, outlier_frac: float = 0.5, sigma: float = 
     out = rng.random(n) < outlier_frac
     dst[out] = rng.uniform(-extent, 2 * extent, size=(int(out.sum()), 2))
     return src, dst, ~out, A.copy()
+
+
+def track_problem(T: int, seed: int = 11, lengths=(2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12), n_cameras: int = 32,
+                  sigma: float = 0.0, wrong_frac: float = 0.0, dup_frac: float = 0.0, radius: float = 10.0,
+                  focal=(3.0, 3.0)):
+    """Multi-view tracks for Ray.intersection / cvTriangulateTracks: n_cameras lookAt cameras
+    (Camera.fs:93-104) on a ring of the given radius around a point cloud in [-1.5, 1.5]^3, all looking
+    at the origin. Track t has lengths[t % len(lengths)] observations of its point, from cameras
+    (start + k step) mod n_cameras (distinct while the track is no longer than n_cameras);
+    observations = project1 + N(0, sigma); a wrong_frac share is replaced by U[-1.5, 1.5]^2 (some
+    outside the image); a dup_frac share of the later observations of a track repeats the one before
+    it (camera and coordinates: an equal ray).
+    -> (cameras[n, 14] in mcvCamera order, cameraIdx[n] i32, obs[n, 2], offsets[T + 1] i32, truth[T, 3])"""
+    from . import camera as CM
+    rng = np.random.default_rng(seed)
+    ang = 2.0 * np.pi * np.arange(n_cameras) / n_cameras
+    cams = CM.cameras_array([CM.lookAt([radius * np.cos(a), radius * np.sin(a), 0.15 * radius * np.sin(3.0 * a)],
+                                       [0.0, 0.0, 0.0], [0.0, 0.0, 1.0], focal) for a in ang])
+    lens = np.asarray(lengths, np.int64).reshape(-1)
+    R = lens[np.arange(T) % lens.size] if T else np.zeros(0, np.int64)
+    offsets = np.zeros(T + 1, np.int32)
+    np.cumsum(R, out=offsets[1:])
+    n = int(offsets[-1])
+    truth = rng.uniform(-1.5, 1.5, size=(T, 3))
+    track = np.repeat(np.arange(T), R)
+    k = np.arange(n) - np.repeat(offsets[:-1].astype(np.int64), R)
+    coprime = np.array([s for s in range(1, max(n_cameras, 2)) if np.gcd(s, n_cameras) == 1] or [1])
+    start, step = rng.integers(0, n_cameras, size=T), coprime[rng.integers(0, coprime.size, size=T)]
+    idx = ((start[track] + k * step[track]) % n_cameras).astype(np.int32)
+    c = cams[idx]
+    o = truth[track] - c[:, 0:3]
+    pz = np.einsum("ij,ij->i", o, c[:, 3:6])
+    obs = np.stack([c[:, 12] * np.einsum("ij,ij->i", o, c[:, 9:12]) / pz,
+                    c[:, 13] * np.einsum("ij,ij->i", o, c[:, 6:9]) / pz], axis=1)
+    obs = obs + rng.normal(0, sigma, size=obs.shape) if sigma > 0 else obs
+    wrong = rng.random(n) < wrong_frac
+    obs[wrong] = rng.uniform(-1.5, 1.5, size=(int(wrong.sum()), 2))
+    for i in np.nonzero((rng.random(n) < dup_frac) & (k > 0))[0]:   # in order: a run of repeats copies its head
+        idx[i], obs[i] = idx[i - 1], obs[i - 1]
+    return cams, idx, np.ascontiguousarray(obs), offsets, truth

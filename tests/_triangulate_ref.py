@@ -1,0 +1,324 @@
+"""Pure-Python reference of track triangulation and the cases both triangulation test files share.
+
+ref_intersection restates Ray.intersection (src/MiniCV/Utilities.fs:100-165) with Python floats and
+math.sqrt, every sum written term by term in the managed evaluation order (no np.sum / np.dot / @:
+their order is not the contract), and counts how often each rejection branch is taken. The order of
+the deduplicated rays, which F# leaves to its hash set, is the input order of the kept rays.
+"""
+import functools
+import math
+from collections import Counter
+
+import numpy as np
+
+from minicv_amd import camera as CM
+from minicv_amd import native as N
+from minicv_amd import synthetic as S
+
+K_SIN = float.fromhex("0x1.1de58c9f7dc27p-5")
+TWO_DEG = math.radians(2.0)
+NAN = float("nan")
+
+
+def _div(a, b):
+    """IEEE a / b (Python raises on a zero divisor)."""
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0.0:
+            return NAN
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def ref_unproject(cam, ox, oy):
+    """Camera.unproject1 (Camera.fs:85-91); cam = 14 floats in mcvCamera order."""
+    loc, fw, up, rt, fx, fy = cam[0:3], cam[3:6], cam[6:9], cam[9:12], cam[12], cam[13]
+    a, b = _div(ox, fx), _div(oy, fy)
+    d = [a * rt[k] + b * up[k] + fw[k] for k in range(3)]
+    l = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    if l == 0.0:
+        return (loc[0], loc[1], loc[2], 0.0, 0.0, 0.0)
+    r = _div(1.0, l)
+    return (loc[0], loc[1], loc[2], d[0] * r, d[1] * r, d[2] * r)
+
+
+def ref_pair(p, q, counters):
+    """One pair of intersections' (Utilities.fs:118-152) -> midpoint or None."""
+    cx = p[4] * q[5] - p[5] * q[4]
+    cy = p[5] * q[3] - p[3] * q[5]
+    cz = p[3] * q[4] - p[4] * q[3]
+    ln = math.sqrt(cx * cx + cy * cy + cz * cz)
+    if not ln > K_SIN:
+        counters["angle"] += 1
+        return None
+    a0, a1, a2 = p[0] - q[0], p[1] - q[1], p[2] - q[2]
+    udotv = p[3] * q[3] + p[4] * q[4] + p[5] * q[5]
+    au = a0 * p[3] + a1 * p[4] + a2 * p[5]
+    av = a0 * q[3] + a1 * q[4] + a2 * q[5]
+    t1 = _div(au * udotv - av, udotv * udotv - 1.0)
+    t0 = t1 * udotv - au
+    if not (t0 > 0.0 and t1 > 0.0):
+        counters["behind"] += 1
+        return None
+    pt = [0.5 * ((p[k] + p[3 + k] * t0) + (q[k] + q[3 + k] * t1)) for k in range(3)]
+    if any(v != v or v in (math.inf, -math.inf) for v in pt):
+        counters["nonfinite"] += 1
+        return None
+    if ln <= 1.0 and abs(math.asin(ln) - TWO_DEG) < 1e-6:
+        counters["accepted_near_threshold"] += 1
+    return pt
+
+
+def ref_intersection(rays, counters=None):
+    """Ray.intersection (Utilities.fs:159-165) of one track: rays = sequence of 6-tuples.
+    -> (point or None, number of midpoints)."""
+    counters = Counter() if counters is None else counters
+    kept = []
+    for r in rays:
+        r = tuple(float(v) for v in r)
+        if any(all(a == b for a, b in zip(r, k)) for k in kept):
+            counters["duplicate"] += 1
+        else:
+            kept.append(r)
+    c, s = 0, [0.0, 0.0, 0.0]
+    for i in range(len(kept)):
+        for j in range(i + 1, len(kept)):
+            pt = ref_pair(kept[i], kept[j], counters)
+            if pt is None:
+                continue
+            c += 1
+            s = [s[0] + pt[0], s[1] + pt[1], s[2] + pt[2]]
+    if c == 0:
+        return None, 0
+    return [s[0] / float(c), s[1] / float(c), s[2] / float(c)], c
+
+
+def ref_stats(cams, idx, obs, point):
+    """avgReprojectionError's form (CameraPose.fs:77-92) with Camera.project1 (Camera.fs:72-83)."""
+    total, vis = 0.0, 0
+    for ci, (ox, oy) in zip(idx, obs):
+        cam = cams[ci]
+        o = [point[k] - cam[k] for k in range(3)]
+        p0 = o[0] * cam[9] + o[1] * cam[10] + o[2] * cam[11]
+        p1 = o[0] * cam[6] + o[1] * cam[7] + o[2] * cam[8]
+        p2 = o[0] * cam[3] + o[1] * cam[4] + o[2] * cam[5]
+        cx, cy = _div(cam[12] * p0, p2), _div(cam[13] * p1, p2)
+        dx, dy = cx - ox, cy - oy
+        if p2 >= 0.0 and cx >= -1.0 and cy >= -1.0 and cx <= 1.0 and cy <= 1.0:
+            total = total + (dx * dx + dy * dy)
+            vis += 1
+    return (math.inf if vis == 0 else total / float(vis)), vis
+
+
+class Problem:
+    """A triangulation call in camera form plus its rays (ref_unproject) and the reference's answer."""
+
+    def __init__(self, cams, idx, obs, offsets):
+        self.cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 14)
+        self.idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        self.obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+        self.offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        self.T = self.offsets.size - 1
+        cl = self.cams.tolist()
+        self.rays = np.array([ref_unproject(cl[c], ox, oy) for c, (ox, oy) in zip(self.idx.tolist(), self.obs.tolist())],
+                             np.float64).reshape(-1, 6)
+        self.counters = Counter()
+        rl, ol, il, off = self.rays.tolist(), self.obs.tolist(), self.idx.tolist(), self.offsets.tolist()
+        self.points = np.full((self.T, 3), np.nan)
+        self.counts = np.zeros(self.T, np.int32)
+        self.cost = np.full(self.T, np.inf)
+        self.visible = np.zeros(self.T, np.int32)
+        for t in range(self.T):
+            a, b = off[t], off[t + 1]
+            pt, c = ref_intersection(rl[a:b], self.counters)
+            self.counts[t] = c
+            if pt is not None:
+                self.points[t] = pt
+            self.cost[t], self.visible[t] = ref_stats(cl, il[a:b], ol[a:b], self.points[t].tolist())
+
+    def lengths(self):
+        return np.diff(self.offsets)
+
+    def enough_points(self):
+        """At least half of the tracks with two or more rays have a point (reference only)."""
+        multi = self.lengths() >= 2
+        return int((self.counts[multi] > 0).sum()) * 2 >= int(multi.sum())
+
+
+def join(*parts):
+    """Concatenate (cams, idx, obs, offsets[, truth]) problems into one call."""
+    cams, idx, obs, offs, base, nobs = [], [], [], [np.zeros(1, np.int64)], 0, 0
+    for p in parts:
+        c, i, o, f = p[0], p[1], p[2], p[3]
+        cams.append(np.asarray(c, np.float64).reshape(-1, 14))
+        idx.append(np.asarray(i, np.int64) + base)
+        obs.append(np.asarray(o, np.float64).reshape(-1, 2))
+        offs.append(np.asarray(f, np.int64)[1:] + nobs)
+        base += cams[-1].shape[0]
+        nobs += obs[-1].shape[0]
+    return np.concatenate(cams), np.concatenate(idx), np.concatenate(obs), np.concatenate(offs)
+
+
+def ray_tracks(tracks):
+    """Tracks given as lists of (origin, direction): one camera per ray (location = origin, forward =
+    direction, observation (0, 0)), so unproject1 returns the ray up to the rounding of normalize."""
+    cams, offs = [], [0]
+    for tr in tracks:
+        for o, d in tr:
+            d = np.asarray(d, np.float64)
+            h = np.array([1.0, 0.0, 0.0]) if abs(d[0]) < 0.9 * np.linalg.norm(d) else np.array([0.0, 1.0, 0.0])
+            r = np.cross(d, h)
+            r /= np.linalg.norm(r)
+            u = np.cross(r, d / np.linalg.norm(d))
+            cams.append(np.concatenate([np.asarray(o, np.float64), d, u, r, [1.0, 1.0]]))
+        offs.append(len(cams))
+    n = len(cams)
+    return np.array(cams).reshape(-1, 14), np.arange(n), np.zeros((n, 2)), np.array(offs)
+
+
+def _dir(az, el=0.0):
+    return np.array([math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el)])
+
+
+def _good(T, seed, lengths=(2, 3, 4, 5, 7), **kw):
+    return S.track_problem(T, seed, lengths=lengths, **kw)
+
+
+def _duplicates():
+    cams, idx, obs, off, _ = S.track_problem(6, 21, lengths=(5, 5, 5, 5, 40, 4), n_cameras=64)
+    idx, obs = idx.copy(), obs.copy()
+
+    def dup(t, dst, src):
+        idx[off[t] + dst], obs[off[t] + dst] = idx[off[t] + src], obs[off[t] + src]
+    dup(0, 1, 0)                      # the first ray again, adjacent
+    dup(1, 4, 0)                      # the first ray again, last
+    dup(2, 3, 2)                      # adjacent in the middle
+    for k in range(1, 5):             # a track that is all duplicates: no pair
+        dup(3, k, 0)
+    for k in (1, 17, 18, 39):         # a long track (workgroup kernel): repeats of ray 0, adjacent and last
+        dup(4, k, 0)
+    dup(4, 30, 29)
+    return join((cams, idx, obs, off), _good(8, 22))
+
+
+def _angle_threshold():
+    rng = np.random.default_rng(31)
+    tracks = []
+    for k in range(48):               # two rays meeting at the origin under 2 deg +- 1e-9 rad
+        ang = TWO_DEG + rng.uniform(-1e-9, 1e-9)
+        az = rng.uniform(0, 2 * math.pi)
+        u, v = _dir(az), _dir(az + ang)
+        tracks.append([(-7.0 * u, u), (-9.0 * v, v)])
+    tracks.append([((0.0, 0.0, 0.0), _dir(0.3)), ((0.0, 1.0, 0.0), _dir(0.3))])            # parallel
+    tracks.append([((1.0, 2.0, 3.0), _dir(0.1)), ((1.0, 2.0, 3.0), _dir(0.9)),
+                   ((1.0, 2.0, 3.0), _dir(2.0, 0.4))])                                      # one shared origin
+    return join(ray_tracks(tracks), _good(60, 32))
+
+
+def _behind():
+    tracks = []
+    for k in range(6):                # the second ray points away from the crossing: t <= 0
+        u, v = _dir(0.2 + k), _dir(1.3 + k)
+        tracks.append([(-5.0 * u, u), (-6.0 * v, -v), (-4.0 * _dir(2.5 + k), _dir(2.5 + k))])
+    return join(ray_tracks(tracks), _good(10, 41))
+
+
+def _nonfinite():
+    s, c = math.sin(0.3), math.cos(0.3)
+    tracks = [[((1.7e308, 0.0, 0.0), (s, c, 0.0)), ((1.7e308, 1e300, 0.0), (s, -c, 0.0))],
+              [((0.0, -1.7e308, 0.0), (c, -s, 0.0)), ((1e300, -1.7e308, 0.0), (-c, -s, 0.0)),
+               ((5e299, -1.7e308, -5e299), (0.0, -s, c))]]
+    return join(ray_tracks(tracks), _good(6, 51))
+
+
+def _stats():
+    tracks = []
+    for k in range(5):                # the third camera looks away from the point: behind it in project1
+        u, v, w = _dir(0.4 + k), _dir(1.9 + k), _dir(3.1 + k, 0.5)
+        tracks.append([(-5.0 * u, u), (-6.0 * v, v), (4.0 * w, w)])
+    return join(S.track_problem(40, 61, lengths=(3, 5, 8, 12, 20), sigma=2e-3, wrong_frac=0.15, dup_frac=0.1),
+                ray_tracks(tracks))
+
+
+CUT = N.TRI_SHORT_MAX
+MIXED = (2, 3, 5, 9, 12, CUT + 1, 4, 20, 1, 7)
+
+CASES = {
+    "empty_and_minimal": lambda: S.track_problem(12, 1, lengths=(0, 1, 3, 0, 6, 1)),
+    "all_tracks_empty": lambda: S.track_problem(70, 2, lengths=(0,)),
+    **{f"wave_edges_T{T}": (lambda T=T: S.track_problem(T, 3 + T, lengths=MIXED)) for T in (1, 63, 64, 65, 257)},
+    "length_cutoff": lambda: S.track_problem(9, 4, lengths=(CUT - 1, CUT, CUT + 1)),
+    **{f"length_R{R}": (lambda R=R: S.track_problem(2, 5 + R, lengths=(R, 3), n_cameras=160)) for R in (63, 64, 65, 130)},
+    "length_R600": lambda: S.track_problem(2, 6, lengths=(600, 2), n_cameras=640),
+    "duplicates": _duplicates,
+    "angle_threshold": _angle_threshold,
+    "rays_behind_origin": _behind,
+    "nonfinite_midpoints": _nonfinite,
+    "statistics": _stats,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def problem(name) -> Problem:
+    """The case and its reference answer, computed once and shared (treat as read-only)."""
+    return Problem(*CASES[name]()[:4])
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def assert_same(got, ref, what):
+    """Bit for bit, NaN payloads and zero signs included."""
+    gp, gc = got[0], got[1]
+    assert np.array_equal(gc, ref.counts), f"{what}: pair counts differ"
+    assert np.array_equal(bits(gp), bits(ref.points)), f"{what}: points differ"
+    if len(got) > 2 and got[2] is not None:
+        assert np.array_equal(bits(got[2]), bits(ref.cost)), f"{what}: cost differs"
+    if len(got) > 3 and got[3] is not None:
+        assert np.array_equal(got[3], ref.visible), f"{what}: visible differs"
+
+
+def host_rays(p: Problem):
+    pts, cnt = np.full((max(p.T, 1), 3), 7.0), np.full(max(p.T, 1), -7, np.int32)
+    rays = p.rays if p.rays.size else np.zeros((1, 6))
+    k = N.lib().mcvHostIntersectRays(rays.ctypes.data, p.offsets.ctypes.data, p.T, pts.ctypes.data, cnt.ctypes.data)
+    return k, pts[:p.T], cnt[:p.T]
+
+
+def host_tracks(p: Problem, stats=True):
+    T = max(p.T, 1)
+    pts, cnt, cost, vis = np.full((T, 3), 7.0), np.full(T, -7, np.int32), np.full(T, 7.0), np.full(T, -7, np.int32)
+    idx = p.idx if p.idx.size else np.zeros(1, np.int32)
+    obs = p.obs if p.obs.size else np.zeros((1, 2))
+    k = N.lib().mcvHostTriangulateTracks(p.cams.ctypes.data, p.cams.shape[0], idx.ctypes.data, obs.ctypes.data,
+                                         p.offsets.ctypes.data, p.T, pts.ctypes.data, cnt.ctypes.data,
+                                         cost.ctypes.data if stats else None, vis.ctypes.data if stats else None)
+    return k, pts[:p.T], cnt[:p.T], cost[:p.T], vis[:p.T]
+
+
+def sentinels(T):
+    return np.full((T, 3), 7.0), np.full(T, -7, np.int32), np.full(T, 7.0), np.full(T, -7, np.int32)
+
+
+def call_export(name, p, offsets=None, idx=None, null=None, stats=True):
+    """One of the three camera-form / ray-form exports on host arrays with sentinel outputs."""
+    off = p.offsets if offsets is None else np.ascontiguousarray(offsets, np.int32)
+    idx = p.idx if idx is None else np.ascontiguousarray(idx, np.int32)
+    T = off.size - 1
+    pts, cnt, cost, vis = sentinels(max(T, 1))
+    rays, obs = (p.rays if p.rays.size else np.zeros((1, 6))), (p.obs if p.obs.size else np.zeros((1, 2)))
+    idx = idx if idx.size else np.zeros(1, np.int32)
+    a = {"rays": rays.ctypes.data, "cams": p.cams.ctypes.data, "idx": idx.ctypes.data, "obs": obs.ctypes.data,
+         "off": off.ctypes.data, "pts": pts.ctypes.data, "cnt": cnt.ctypes.data,
+         "cost": cost.ctypes.data if stats else None, "vis": vis.ctypes.data if stats else None}
+    if null:
+        a[null] = None
+    L = N.lib()
+    if name in ("cvIntersectRays", "mcvHostIntersectRays"):
+        k = getattr(L, name)(a["rays"], a["off"], T, a["pts"], a["cnt"])
+    else:
+        k = getattr(L, name)(a["cams"], p.cams.shape[0], a["idx"], a["obs"], a["off"], T, a["pts"], a["cnt"],
+                             a["cost"], a["vis"])
+    untouched = np.all(pts == 7.0) and np.all(cnt == -7) and np.all(cost == 7.0) and np.all(vis == -7)
+    return k, untouched, (pts, cnt, cost, vis)
