@@ -514,6 +514,31 @@ MCV_API int cvTriangulateTracks(const mcvCamera* cameras, int nCameras, const in
                                 const mcvV2d* observations, const int* offsets, int T, mcvV3d* points,
                                 int* pairCounts, double* cost, int* visible);
 
+/* Batched CameraPose.findScaled: P independent cvFindScaledPose problems in one call, each bit-identical
+ * to its own single call; the launches, copies and the one synchronisation do not grow with P (DESIGN
+ * §7j). The observation sets are a CSR: offsets[S + 1] ints, offsets[0] == 0, non-decreasing, over the
+ * offsets[S] rows of worldPoints / observations. Problem p is (srcCams[p], rotations[p], translations[p])
+ * over set setIdx[p]; a null setIdx means set p and needs S == P. Several problems may share a set (the
+ * candidate poses of one pair do): it is uploaded and packed once.
+ * Per problem: costs[p] / scales[p] = cvFindScaledPose's *outCost / *outScale (+inf and 0.0 for an empty
+ * set and when no candidate has a finite cost), evaluated[p] (may be null) = its return value.
+ * Returns the number of problems with a finite cost; P == 0 returns 0. Returns -1 with a message and
+ * writes nothing on a null required pointer, a negative P or S, offsets that do not start at 0 or that
+ * decrease, a setIdx entry outside [0, S), offsets[S] or the candidates of the call (2 x the rows of
+ * every problem's set, summed) over 2^28, or when no HIP device is visible. Every argument check runs
+ * before the device is touched. */
+MCV_API int cvFindScaledPoseBatch(const mcvCamera* srcCams, const mcvM33d* rotations, const mcvV3d* translations,
+                                  const int* setIdx, int P,
+                                  const mcvV3d* worldPoints, const mcvV2d* observations, const int* offsets, int S,
+                                  double* costs, double* scales, int* evaluated);
+/* Per-candidate scales and costs of cvFindScaledPoseBatch (test / analysis helper): problem after
+ * problem in cvFindScaledPoseCosts' layout, problem p's 2 N_p entries starting at 2 x the sum of N_q
+ * over q < p (N_p = the rows of p's set). Same inputs and checks. Returns the sum of N_p, -1 on failure. */
+MCV_API int cvFindScaledPoseBatchCosts(const mcvCamera* srcCams, const mcvM33d* rotations,
+                                       const mcvV3d* translations, const int* setIdx, int P,
+                                       const mcvV3d* worldPoints, const mcvV2d* observations, const int* offsets,
+                                       int S, double* scales, double* costs);
+
 /* ------------------------------------------------------------------------------------------
  * (3) Device-level API: device pointers, caller's stream (hipStream_t as void*), current device.
  *     Points on device are packed fp32 correspondences float4 {x, y, x', y'} (16 B each).
@@ -919,6 +944,17 @@ MCV_API int mcvHostTriangulateTracks(const mcvCamera* cameras, int nCameras, con
  * call that reached the device: stats8 = {kernel launches, stream synchronisations, host<->device
  * copies, memsets, short tracks (at most 16 rays), long tracks, 0, 0}. Returns 0. */
 MCV_API int mcvTestTriangulateStats(long long* stats8);
+/* Host twin of cvFindScaledPoseBatch: the same arguments, checks, outputs and return value, computed
+ * problem after problem by the host-compiled code behind mcvHostScaledCosts. No GPU. */
+MCV_API int mcvHostFindScaledPoseBatch(const mcvCamera* srcCams, const mcvM33d* rotations,
+                                       const mcvV3d* translations, const int* setIdx, int P,
+                                       const mcvV3d* worldPoints, const mcvV2d* observations, const int* offsets,
+                                       int S, double* costs, double* scales, int* evaluated);
+/* Counters of the calling thread's last cvFindScaledPoseBatch / cvFindScaledPoseBatchCosts call that
+ * reached the device: stats8 = {kernel launches, stream synchronisations, host<->device copies, memsets,
+ * problems on the device (those over a non-empty set), candidate tiles (blocks of 64 candidates of the
+ * sweep), 0, 0}. Returns 0. */
+MCV_API int mcvTestScaledBatchStats(long long* stats8);
 
 #ifdef __cplusplus
 }

@@ -10,9 +10,9 @@ from .native import RansacConfig, NativeError
 from .opencv import RansacParams, findHomography, findFundamentalMat, matchHamming, matchL2, matchL2U8, \
     recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch
 from . import camera
-from .camera import Camera, CameraPose, findScaled, triangulateTracks
+from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks
 
 __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomography", "findFundamentalMat",
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
            "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch", "camera", "Camera", "CameraPose", "findScaled",
-           "triangulateTracks"]
+           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts"]

@@ -151,6 +151,71 @@ def findScaledCosts(srcCam: Camera, world: np.ndarray, obs: np.ndarray, pose: Ca
     return sc, co
 
 
+def _scaled_batch_args(srcCams, sets, poses, setIdx):
+    """The arrays of cvFindScaledPoseBatch: cameras (P, 14), rotations (P, 9), translations (P, 3),
+    setIdx (P,) or None, world (R, 3), obs (R, 2), offsets (S + 1,)."""
+    cams = cameras_array(list(srcCams))
+    poses = list(poses)
+    P = len(poses)
+    if cams.shape[0] != P:
+        raise ValueError("srcCams and poses differ in length")
+    rots = np.array([np.asarray(p.Rotation, np.float64).reshape(9) for p in poses], np.float64).reshape(P, 9)
+    trans = np.array([_v3(p.Translation) for p in poses], np.float64).reshape(P, 3)
+    split = [_split_observations(s) for s in sets]
+    off = np.zeros(len(split) + 1, np.int32)
+    off[1:] = np.cumsum([w.shape[0] for w, _ in split])
+    world = np.concatenate([w for w, _ in split] + [np.empty((0, 3))])
+    obs = np.concatenate([o for _, o in split] + [np.empty((0, 2))])
+    idx = None if setIdx is None else np.ascontiguousarray(setIdx, np.int32).reshape(-1)
+    if idx is not None and idx.shape[0] != P:
+        raise ValueError("setIdx and poses differ in length")
+    return cams, rots, trans, idx, np.ascontiguousarray(world), np.ascontiguousarray(obs), off
+
+
+def findScaledBatch(inlierThreshold: float, srcCams, sets, poses, setIdx=None):
+    """cvFindScaledPoseBatch: findScaled for P problems in one call -> [(cost, scaled pose)] equal to
+    [findScaled(inlierThreshold, srcCams[p], sets[setIdx[p]], poses[p]) for p in range(P)].
+
+    sets: the observation sets, each a sequence of (V3d, V2d) pairs or a (world[n,3], obs[n,2]) tuple;
+    setIdx[p] names problem p's set (None: set p, one set per problem). Several problems may share a
+    set. inlierThreshold is unused, as in findScaled. Raises NativeError when the native call fails."""
+    cams, rots, trans, idx, world, obs, off = _scaled_batch_args(srcCams, sets, poses, setIdx)
+    poses = list(poses)
+    P = len(poses)
+    if P == 0:
+        return []
+    cost, s = np.empty(P), np.empty(P)
+    k = N.lib().cvFindScaledPoseBatch(cams.ctypes.data, rots.ctypes.data, trans.ctypes.data,
+                                      None if idx is None else idx.ctypes.data, P,
+                                      _nonnull(world, (1, 3)).ctypes.data, _nonnull(obs, (1, 2)).ctypes.data,
+                                      off.ctypes.data, off.size - 1, cost.ctypes.data, s.ctypes.data, None)
+    N.check(k >= 0, "cvFindScaledPoseBatch")
+    sizes = np.diff(off)[np.arange(P) if idx is None else idx]
+    return [(float(cost[p]), scale(float(s[p]), poses[p]) if sizes[p] > 0 else CameraPose())   # CameraPose.fs:42
+            for p in range(P)]
+
+
+def findScaledBatchCosts(srcCams, sets, poses, setIdx=None):
+    """cvFindScaledPoseBatchCosts: per problem (scales[2n], costs[2n]) as findScaledCosts gives them."""
+    cams, rots, trans, idx, world, obs, off = _scaled_batch_args(srcCams, sets, poses, setIdx)
+    P = rots.shape[0]
+    if P == 0:
+        return []
+    which = np.arange(P) if idx is None else idx
+    if which.size and (which.min() < 0 or which.max() >= off.size - 1):
+        raise ValueError("a problem's set is outside the sets given")
+    sizes = np.diff(off)[which]
+    total = 2 * int(sizes.sum())
+    sc, co = np.empty(max(total, 1)), np.empty(max(total, 1))
+    k = N.lib().cvFindScaledPoseBatchCosts(cams.ctypes.data, rots.ctypes.data, trans.ctypes.data,
+                                           None if idx is None else idx.ctypes.data, P,
+                                           _nonnull(world, (1, 3)).ctypes.data, _nonnull(obs, (1, 2)).ctypes.data,
+                                           off.ctypes.data, off.size - 1, sc.ctypes.data, co.ctypes.data)
+    N.check(k >= 0, "cvFindScaledPoseBatchCosts")
+    ends = 2 * np.concatenate([[0], np.cumsum(sizes)])
+    return [(sc[ends[p]:ends[p + 1]].copy(), co[ends[p]:ends[p + 1]].copy()) for p in range(P)]
+
+
 def cameras_array(cameras) -> np.ndarray:
     """Cameras as (n, 14) float64 rows in mcvCamera's field order (location, forward, up, right, focal)."""
     if isinstance(cameras, np.ndarray):

@@ -555,6 +555,22 @@ struct ScaledSetup;
 void launch_scaled(const ScaledSetup& S, const double* d_w3, const double* d_o2, int N, double* d_soa,
                    double* d_scales, uint8_t* d_used, double* d_costs, long long* d_out, hipStream_t s);
 
+// ---- batched CameraPose.findScaled (scaled_batch.hip; the index spaces: scaled_batch_index.h). d_soa: 5
+// streams of R rows (all sets' rows, set after set); d_setups / d_probs: one per problem; d_blockProb: the
+// work list, the problem of each of the nBlocks blocks of 64 candidates; d_scales / d_costs: every problem's
+// 2 N candidates at its candOff, d_used: its N observations at candOff / 2. One launch each.
+struct ScaledBatchProb;
+void launch_scaled_batch_pack(const double* d_w3, const double* d_o2, int R, double* d_soa, hipStream_t s);
+void launch_scaled_batch_candidates(const ScaledSetup* d_setups, const ScaledBatchProb* d_probs,
+                                    const int* d_blockProb, int nBlocks, const double* d_soa, int R,
+                                    double* d_scales, uint8_t* d_used, hipStream_t s);
+void launch_scaled_batch_costs(const ScaledSetup* d_setups, const ScaledBatchProb* d_probs, const int* d_blockProb,
+                               int nBlocks, const double* d_soa, int R, const double* d_scales,
+                               const uint8_t* d_used, double* d_costs, hipStream_t s);
+// d_res: cost[P], scale[P] (doubles), evaluated[P] (64-bit integers) — every problem, the empty ones included
+void launch_scaled_batch_best(const ScaledBatchProb* d_probs, int P, const double* d_costs, const double* d_scales,
+                              const uint8_t* d_used, double* d_res, hipStream_t s);
+
 // ---- Ray.intersection over many tracks (triangulate.hip)
 static const int kTriShortMax = 16;   // tracks of at most this many rays: one lane each; longer: one workgroup each
 // d_ctr: kTriCtrs counters, zeroed by the caller before the launches below.

@@ -156,6 +156,8 @@ SIGNATURES = {
     "cvFindScaledPoseCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "cvIntersectRays": (_I, [_P, _P, _I, _P, _P]),
     "cvTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "cvFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "cvFindScaledPoseBatchCosts": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "mcvGetLastError": (C.c_char_p, []),
     "mcvDeviceCount": (_I, []),
     "mcvVersion": (C.c_char_p, []),
@@ -232,6 +234,8 @@ SIGNATURES = {
     "mcvHostIntersectRays": (_I, [_P, _P, _I, _P, _P]),
     "mcvHostTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mcvTestTriangulateStats": (_I, [_P]),
+    "mcvHostFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "mcvTestScaledBatchStats": (_I, [_P]),
     "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),
