@@ -322,6 +322,39 @@ MCV_API int cvSolvePnPRansacBatch(const mcvV2d* imgPoints, const mcvV3d* worldPo
                                   const mcvM33d* K, const double* distortionCoeffs, const RansacConfig* cfg,
                                   mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask, int* counts);
 
+/* B independent cvRefinePnPLM / cvRefinePnPVVS calls in one: the refinement step of solvePnPInternal
+ * (OpenCV.fs:1006-1013) for many cameras. Problem p owns rows [offsets[p], offsets[p+1]) as in
+ * cvSolvePnPRansacBatch. refineKind: 0 = LM (cvRefinePnPLM), 1 = VVS (cvRefinePnPVVS). tVecs / rVecs [B]: in
+ * the start pose, out the refined one. mask: uint8[offsets[B]] or NULL (all points); any non-zero byte selects
+ * the row. distortionCoeffs: 4 per problem or NULL. refined: uint8[B] or NULL.
+ * With n_p the selected rows of problem p: where the single call would refine (n_p >= 3, fx and fy finite and
+ * non-zero), rVecs[p] / tVecs[p] come out as the bits cvRefinePnPLM / cvRefinePnPVVS write for the selected
+ * rows gathered in index order (the arrays OpenCV.fs:1006-1007 builds) with K[p], problem p's coefficients and
+ * the given start pose, and refined[p] = 1. Otherwise the pose is left untouched bit for bit, refined[p] = 0
+ * and mcvGetLastError() names the first such problem's index and the single call's message.
+ * The kernel launches, stream synchronisations and copies of a call do not grow with B: one pack, one compact
+ * and one gather launch (neither with a NULL mask), then per lockstep step (at most 21 for LM, 20 for VVS) two
+ * launches and one synchronisation.
+ * Returns the number of problems refined (0 for B == 0), -1 on a bad argument (a null imgPoints, worldPoints,
+ * offsets, K, tVecs or rVecs, a negative B, offsets[0] != 0, decreasing offsets, a problem over the family's
+ * limit of 65535 x 512 rows, a refineKind other than 0 / 1) or a device failure; every argument check runs
+ * before the device is touched and before any output is written. */
+MCV_API int cvRefinePnPBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int* offsets, int B,
+                             const mcvM33d* K, const double* distortionCoeffs, const uint8_t* mask, int refineKind,
+                             mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* refined);
+
+/* solvePnPRansacWithRefine (OpenCV.fs:1051) for many cameras: cvSolvePnPRansacBatch's arguments and contract,
+ * then cvRefinePnPBatch(refineKind) of every problem with a pose on the mask the first step returned. Every
+ * output equals the two calls in sequence; mask and counts stay the RANSAC inliers; a problem without a pose
+ * stays a zero pose and is not refined. The points are uploaded and packed once, and the refine reads the
+ * packed points and the mask where the RANSAC rounds left them on the device. Refuses what
+ * cvSolvePnPRansacBatch refuses and a refineKind other than 0 / 1, before the device is touched.
+ * Returns the number of problems with a pose, -1 on a bad argument or a device failure. */
+MCV_API int cvSolvePnPRansacRefineBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int* offsets,
+                                        int B, const mcvM33d* K, const double* distortionCoeffs,
+                                        const RansacConfig* cfg, int refineKind, mcvV3d* tVecs, mcvV3d* rVecs,
+                                        uint8_t* mask, int* counts);
+
 /* Device-resident match -> RANSAC hand-off. Inputs are the reference's
  * DetectorResult (MiniCVNative.h:23-29: KeyPoint2d[PointCount] + row-major descriptors,
  * DescriptorElementType 0 = uint8 -> Hamming, 5 = float32 -> L2). Matching a -> b (knn 2), then
@@ -905,6 +938,19 @@ MCV_API int mcvTestBatchSweepE(const double* pts4d, const int* offsets, int B, c
  * (R row-major, then t). counts[k] = points of pose k's problem with pnp_error <= thr2. Returns 1, 0 on failure. */
 MCV_API int mcvTestBatchSweepPnp(const float* pts8, const int* offsets, int B, const double* cam8 /* 8 per problem */,
                                  const double* poses12, const int* poseOffsets, float thr2, int* counts);
+/* The index arithmetic of cvRefinePnPBatch, as the export computes it (no device): counts[B] = the selected rows
+ * of every problem (mask NULL: all of its rows; any non-zero byte selects), compOff[B + 1] = their exclusive
+ * prefix sum, problem p's place in the compact array the reductions run over. Returns the largest count, -1
+ * on a null offsets / counts / compOff, a negative B or bad offsets. mcvTestBatchStats reports
+ * cvRefinePnPBatch and cvSolvePnPRansacRefineBatch like cvSolvePnPRansacBatch: [3] the lockstep steps of the
+ * call (the RANSAC tail's and the refine's together for the fused call), [9] the copies. */
+MCV_API int mcvHostRefinePnPBatchLayout(const int* offsets, int B, const uint8_t* mask, int* counts, int* compOff);
+/* Device self-test: cvRefinePnPLM (refineKind 0) / cvRefinePnPVVS (1) with a byte mask applied in place: the
+ * reductions skip the unselected rows of the whole array (the order of the RANSAC tail's LM) instead of running
+ * over gathered rows. cvRefinePnPBatch's tests tell the two orders apart with it. Returns 1, 0 on failure. */
+MCV_API int mcvTestRefinePnPMasked(const mcvV2d* imgPoints, const mcvV3d* worldPoints, int N, const mcvM33d* K,
+                                   const double* distortionCoeffs, const uint8_t* mask, int refineKind, mcvV3d* tVec,
+                                   mcvV3d* rVec);
 /* The index arithmetic of cvMatchFeaturesBatch, as the export computes it (no device). featureCounts[nImages],
  * imagePairs[2 B]; norm picks the kernel form (MCV_NORM_L2: int8 matrix cores, else XOR / popcount).
  * Directed problem d < B is pair d (query image first); with crossCheck, d in [B, 2B) is pair d - B reversed.

@@ -8,11 +8,13 @@ workloads.
 from . import native
 from .native import RansacConfig, NativeError
 from .opencv import RansacParams, findHomography, findFundamentalMat, matchHamming, matchL2, matchL2U8, \
-    recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch
+    recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch, \
+    refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch
 from . import camera
 from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks
 
 __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomography", "findFundamentalMat",
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
-           "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch", "camera", "Camera", "CameraPose", "findScaled",
+           "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch",
+           "refinePnPBatch", "solvePnPRansacWithRefine", "solvePnPRansacWithRefineBatch", "camera", "Camera", "CameraPose", "findScaled",
            "triangulateTracks", "findScaledBatch", "findScaledBatchCosts"]

@@ -458,7 +458,7 @@ struct BatchPnpFin {    // one winner of the mask: pose best[pose], camera cams 
     int ptOff, N;
     int pose, cam;
 };
-struct BatchPnpLmJob {  // one job of a batched LM reduction (OpPnpLM's constants)
+struct BatchPnpLmJob {  // one job of a batched LM / VVS reduction (the constants of OpPnpLM; OpPnpVVS reads no dR)
     int ptOff, N;
     double cam[8], R[9], t[3], dR[27];
 };
@@ -481,9 +481,18 @@ void launch_batch_pnp_fetch(const BatchPnpFetch* d_fetch, int nFetch, const void
 // d_mask: the segmented mask; d_count[f] += inliers (zeroed by the caller)
 void launch_batch_pnp_mask(const void* d_pts, const BatchPnpFin* d_fin, int nFin, int maxN, const double* d_cams,
                            const void* d_best, float thr2, uint8_t* d_mask, int* d_count, hipStream_t s);
-// pnp_reduce_lm (wantJ) for every job: d_part = nJobs x reduce_blocks(maxN) x 28, d_out = nJobs x 28. Returns 2.
-int launch_pnp_batch_reduce_lm(const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs, int nJobs,
-                               int maxN, double* d_part, double* d_out, hipStream_t s);
+// pnp_reduce_lm (wantJ), or with vvs pnp_reduce_vvs (the job's cam, R, t; dR unread), for every job:
+// d_part = nJobs x reduce_blocks(maxN) x 28, d_out = nJobs x 28. d_mask: the segmented mask, or nullptr: every
+// row of a job counts (the batched refinement's gathered rows). Returns 2.
+int launch_pnp_batch_reduce(bool vvs, const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs,
+                            int nJobs, int maxN, double* d_part, double* d_out, hipStream_t s);
+// The gather of the batched refinement: mcv_mask_compact's job form over the B problems
+// (d_jobs[p].ptOff / .N = problem p's rows; d_idx segmented like the mask, d_count one int per problem), then
+// d_out[g] = the g-th selected PnpPoint row of the call, g < total = d_compOff[B] as the host counted it;
+// d_rowOff / d_compOff: B + 1 ints each. Returns the kernels launched (2; 0 when nothing is selected).
+int launch_pnp_batch_gather(const void* d_pts, const uint8_t* d_mask, const BatchPnpEpnpJob* d_jobs, int B,
+                            const int* d_rowOff, const int* d_compOff, int total, int* d_idx, int* d_count,
+                            void* d_out, hipStream_t s);
 // The inlier EPnP's device steps for every job (grid y = job). compact + prep: d_idx / d_pw / d_us are segmented
 // like the mask (idx + ptOff, pw + 3 ptOff, us + 2 ptOff), d_count one int per job. Returns 2.
 int launch_pnp_batch_epnp_prep(const void* d_pts, const uint8_t* d_mask, const BatchPnpEpnpJob* d_jobs, int nJobs,

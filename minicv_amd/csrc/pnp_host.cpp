@@ -28,15 +28,7 @@
 namespace mcv {
 
 // ---- rotation algebra (host) --------------------------------------------------------------------
-static void skew(const double* v, double* S) {
-    S[0] = 0; S[1] = -v[2]; S[2] = v[1];
-    S[3] = v[2]; S[4] = 0; S[5] = -v[0];
-    S[6] = -v[1]; S[7] = v[0]; S[8] = 0;
-}
-static void mul33(const double* A, const double* B, double* C) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
+// skew, mul33: pnp_refine.h (the exponential map of PnpVvsStepper uses them too)
 
 // Rodrigues r -> R (row-major) and dR/dr_j (dR + 9 j), Gallego & Yezzi (2015):
 //   dR/dr_j = (r_j [r]x + [r x ((I - R) e_j)]x) R / |r|^2;  [e_j]x for |r| -> 0.
@@ -191,45 +183,17 @@ void pnp_lm(Plan& P, const void* d_pts, int N, const uint8_t* d_mask, double* rv
 // Virtual visual servoing (solvePnPRefineVVS restated): v = -lambda (L^T L)^+ L^T e on the
 // normalised image plane, cMo <- exp(v)^-1 cMo, 20 iterations or |v| < FLT_EPSILON.
 void pnp_vvs(Plan& P, const void* d_pts, int N, double* rvec, double* t, int maxIters, double lambda, hipStream_t s) {
-    double R[9];
-    rodrigues(rvec, R, nullptr);
-    for (int it = 0; it < maxIters; ++it) {
+    // the iteration is PnpVvsStepper (pnp_refine.h), which the batched refinement runs in lockstep
+    PnpVvsStepper st;
+    st.begin(rvec, t, maxIters, lambda);
+    while (!st.finished()) {
         double buf[28];
         reduce_to_host(P, s, 28, buf, [&](double* part, double* red) {
-            pnp_reduce_vvs(d_pts, N, nullptr, P.pnpCam, R, t, part, red, s);
+            pnp_reduce_vvs(d_pts, N, nullptr, P.pnpCam, st.R, st.t, part, red, s);
         });
-        double A[36], g[6], v[6];
-        int o = 0;
-        for (int j = 0; j < 6; ++j)
-            for (int k = j; k < 6; ++k) { A[6 * j + k] = buf[o]; A[6 * k + j] = buf[o]; ++o; }
-        for (int j = 0; j < 6; ++j) g[j] = buf[21 + j];
-        eig_solve(A, 6, g, v);
-        double vn = 0;
-        for (int k = 0; k < 6; ++k) { v[k] = -lambda * v[k]; vn += v[k] * v[k]; }
-        // T = exp(v): rotation Rodrigues(w), translation V u
-        const double* u = v;
-        const double* w = v + 3;
-        double Rw[9], S[9], S2[9], V[9];
-        rodrigues(w, Rw, nullptr);
-        skew(w, S);
-        mul33(S, S, S2);
-        const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
-        const double a = th < 1e-8 ? 0.5 : (1 - std::cos(th)) / th2;
-        const double b = th < 1e-8 ? 1.0 / 6.0 : (th - std::sin(th)) / (th2 * th);
-        for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0 ? 1.0 : 0.0) + a * S[k] + b * S2[k];
-        double tt[3];
-        for (int i = 0; i < 3; ++i) tt[i] = V[3 * i] * u[0] + V[3 * i + 1] * u[1] + V[3 * i + 2] * u[2];
-        // cMo <- T^-1 cMo: R' = Rw^T R, t' = Rw^T (t - tt)
-        double Rn[9], tn[3];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) Rn[3 * i + j] = Rw[i] * R[j] + Rw[3 + i] * R[3 + j] + Rw[6 + i] * R[6 + j];
-        for (int i = 0; i < 3; ++i)
-            tn[i] = Rw[i] * (t[0] - tt[0]) + Rw[3 + i] * (t[1] - tt[1]) + Rw[6 + i] * (t[2] - tt[2]);
-        std::memcpy(R, Rn, sizeof(R));
-        std::memcpy(t, tn, sizeof(tn));
-        if (std::sqrt(vn) < FLT_EPSILON) break;
+        st.feed(buf);
     }
-    rodrigues_inv(R, rvec);
+    st.result(rvec, t);
 }
 
 // EPnP (epnp.h, OpenCV compute_pose) over n points already on the device as double world points
@@ -619,6 +583,43 @@ static void refine_common(const mcvV2d* img, const mcvV3d* world, int N, const m
     else pnp_lm(P, P.ptsd.p, N, nullptr, r, t, 20, s);
     rVec->X = r[0]; rVec->Y = r[1]; rVec->Z = r[2];
     tVec->X = t[0]; tVec->Y = t[1]; tVec->Z = t[2];
+}
+
+// Test hook: refine_common with a byte mask applied in place (the reductions skip the unselected rows of the
+// whole array, as the RANSAC tail's LM does) instead of on gathered rows. The sums run in another order than
+// cvRefinePnPBatch's, which gathers first; its tests use this to tell the two apart. Returns 1, 0 on failure.
+extern "C" MCV_API int mcvTestRefinePnPMasked(const mcvV2d* img, const mcvV3d* world, int N, const mcvM33d* K,
+                                              const double* dist, const uint8_t* mask, int refineKind, mcvV3d* tVec,
+                                              mcvV3d* rVec) {
+    MCV_GUARD(0, {
+        if (!img || !world || !K || !mask || !tVec || !rVec || N < 3 || (refineKind != 0 && refineKind != 1))
+            fail("mcvTestRefinePnPMasked: bad argument");
+        require_device();
+        Plan& P = thread_plan(MCV_MODEL_PNP);
+        hipStream_t s = P.own_stream();
+        set_camera(P, K->M, dist);
+        P.reserve(N, 1);
+        pnp_pack(P, img, world, N, P.ptsd.p, s);
+        MCV_HIP(hipMemcpyAsync(P.mask.p, mask, (size_t)N, hipMemcpyHostToDevice, s));
+        double r[3] = {rVec->X, rVec->Y, rVec->Z}, t[3] = {tVec->X, tVec->Y, tVec->Z};
+        if (refineKind == 0) {
+            pnp_lm(P, P.ptsd.p, N, P.mask.p, r, t, 20, s);
+        } else {
+            PnpVvsStepper st;
+            st.begin(r, t, 20, 1.0);
+            while (!st.finished()) {
+                double buf[28];
+                reduce_to_host(P, s, 28, buf, [&](double* part, double* red) {
+                    pnp_reduce_vvs(P.ptsd.p, N, P.mask.p, P.pnpCam, st.R, st.t, part, red, s);
+                });
+                st.feed(buf);
+            }
+            st.result(r, t);
+        }
+        rVec->X = r[0]; rVec->Y = r[1]; rVec->Z = r[2];
+        tVec->X = t[0]; tVec->Y = t[1]; tVec->Z = t[2];
+        return 1;
+    })
 }
 
 extern "C" MCV_API int mcvHostSqpnp(const double* img, const double* world, int N, const double* cam8, double* R9,

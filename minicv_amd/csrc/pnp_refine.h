@@ -1,7 +1,7 @@
 // pnp_refine.h — the host arithmetic of solvePnPRansac's final solve, once, for the single call
-// (pnp_host.cpp) and the batched call (ransac_batch_pnp_host.cpp): the Levenberg-Marquardt controller of
-// pnp_lm as a stepper, and the O(1) algebra between the inlier EPnP's device passes. Both callers feed the
-// same sums (the single call's reductions and the batch forms of the same kernels), so a problem of a batch
+// (pnp_host.cpp) and the batched calls (ransac_batch_pnp_host.cpp): the Levenberg-Marquardt controller of
+// pnp_lm and the iteration of pnp_vvs as steppers, and the O(1) algebra between the inlier EPnP's device
+// passes. Both callers feed the same sums (the single call's reductions and the batch forms of the same kernels), so a problem of a batch
 // runs the same body on the same values as its single call.
 #pragma once
 
@@ -18,6 +18,16 @@ namespace mcv {
 
 void rodrigues(const double* r, double* R, double* dR);   // pnp_host.cpp
 void rodrigues_inv(const double* R, double* r);
+
+inline void skew(const double* v, double* S) {
+    S[0] = 0; S[1] = -v[2]; S[2] = v[1];
+    S[3] = v[2]; S[4] = 0; S[5] = -v[0];
+    S[6] = -v[1]; S[7] = v[0]; S[8] = 0;
+}
+inline void mul33(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+}
 
 // Levenberg-Marquardt on (rvec, t): damping A + lambda diag(A), lambda from 1e-3 (x10 on rejection, /10 on
 // acceptance), at most maxIters accepted-or-rejected steps, stop when the step is below FLT_EPSILON relative
@@ -89,6 +99,63 @@ private:
             dn = std::max(dn, std::fabs(d[k]));
             pn = std::max(pn, std::fabs(p[k]));
         }
+    }
+};
+
+// Virtual visual servoing (pnp_vvs's loop body): the pose is kept as (R, t); every step takes the 28 sums of
+// OpPnpVVS at it (L^T L upper triangle, L^T e, |e|^2), solves v = -lambda (L^T L)^+ L^T e and applies
+// cMo <- exp(v)^-1 cMo. At most maxIters steps; the |v| < FLT_EPSILON test comes after the update.
+// R / t are the point whose sums the caller computes; result() converts R back once.
+struct PnpVvsStepper {
+    double R[9], t[3];
+    double lambda = 1.0;
+    int it = 0, maxIters = 0;
+    bool done = false;
+
+    void begin(const double* rvec, const double* t0, int iters, double lam) {
+        rodrigues(rvec, R, nullptr);
+        for (int k = 0; k < 3; ++k) t[k] = t0[k];
+        lambda = lam;
+        it = 0; maxIters = iters;
+        done = it >= maxIters;
+    }
+    bool finished() const { return done; }
+    void feed(const double* buf) {
+        double A[36], g[6], v[6];
+        int o = 0;
+        for (int j = 0; j < 6; ++j)
+            for (int k = j; k < 6; ++k) { A[6 * j + k] = buf[o]; A[6 * k + j] = buf[o]; ++o; }
+        for (int j = 0; j < 6; ++j) g[j] = buf[21 + j];
+        eig_solve(A, 6, g, v);
+        double vn = 0;
+        for (int k = 0; k < 6; ++k) { v[k] = -lambda * v[k]; vn += v[k] * v[k]; }
+        // T = exp(v): rotation Rodrigues(w), translation V u
+        const double* u = v;
+        const double* w = v + 3;
+        double Rw[9], S[9], S2[9], V[9];
+        rodrigues(w, Rw, nullptr);
+        skew(w, S);
+        mul33(S, S, S2);
+        const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
+        const double a = th < 1e-8 ? 0.5 : (1 - std::cos(th)) / th2;
+        const double b = th < 1e-8 ? 1.0 / 6.0 : (th - std::sin(th)) / (th2 * th);
+        for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0 ? 1.0 : 0.0) + a * S[k] + b * S2[k];
+        double tt[3];
+        for (int i = 0; i < 3; ++i) tt[i] = V[3 * i] * u[0] + V[3 * i + 1] * u[1] + V[3 * i + 2] * u[2];
+        // cMo <- T^-1 cMo: R' = Rw^T R, t' = Rw^T (t - tt)
+        double Rn[9], tn[3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rn[3 * i + j] = Rw[i] * R[j] + Rw[3 + i] * R[3 + j] + Rw[6 + i] * R[6 + j];
+        for (int i = 0; i < 3; ++i)
+            tn[i] = Rw[i] * (t[0] - tt[0]) + Rw[3 + i] * (t[1] - tt[1]) + Rw[6 + i] * (t[2] - tt[2]);
+        std::memcpy(R, Rn, sizeof(R));
+        std::memcpy(t, tn, sizeof(tn));
+        ++it;
+        if (std::sqrt(vn) < FLT_EPSILON || it >= maxIters) done = true;
+    }
+    void result(double* rvec, double* tout) const {
+        rodrigues_inv(R, rvec);
+        for (int k = 0; k < 3; ++k) tout[k] = t[k];
     }
 };
 

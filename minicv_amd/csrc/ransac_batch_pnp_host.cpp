@@ -1,5 +1,6 @@
 // ransac_batch_pnp_host.cpp — cvSolvePnPRansacBatch: B independent cvSolvePnPRansacCfg problems in one call
-// whose kernel launches, stream synchronisations and copies do not grow with B.
+// whose kernel launches, stream synchronisations and copies do not grow with B, and the
+// batched refinement behind it (cvRefinePnPBatch, cvSolvePnPRansacRefineBatch: §7k).
 //
 //   pack:     the raw image and world points in one copy, mcv_pnp_pack over all of them in one launch, one
 //             table of cameras (8 doubles per problem)
@@ -16,6 +17,12 @@
 // call's own function, so each problem returns the single call's bits. Problems with exactly the sample
 // size take the single export's direct solve, one by one.
 //
+// cvRefinePnPBatch / cvSolvePnPRansacRefineBatch: the refinement step of solvePnPInternal for
+// B cameras. The rows are packed as above, every problem's selected rows are gathered into one compact array
+// (mcv_mask_compact's job form + mcv_pnp_batch_gather: 2 launches, none without a mask), and the steppers of
+// pnp_lm / pnp_vvs run in lockstep over the gathered rows, unmasked: the single call's sums on gathered arrays.
+// The fused call runs it behind the rounds on the packed rows and the mask they left on the device.
+//
 // One round (B problems, every one on the device and with a winner), counted by BatchStats:
 //   AP3P, NO_REFINE   launches 4 (pack, generate, sweep, mask) + 1 fetch = 5, synchronisations 2
 //   EPnP kinds        generate is 5 kernels: 9 launches before the refine; + compact, prep and 6 passes = 17
@@ -27,6 +34,7 @@
 #include "kernels.h"
 #include "hyp_pnp.h"
 #include "pnp_refine.h"
+#include "pnp_refine_batch_index.h"
 #include "plan.h"
 
 #include <array>
@@ -47,9 +55,9 @@ struct BatchPnpWs {
     int device = 0;
     hipStream_t stream = nullptr;
     DevBuf<double> raw, cams, scratch, lmPart, lmOut, pw, us, part;
-    DevBuf<float> pts;
+    DevBuf<float> pts, comp;
     DevBuf<uint8_t> models, best, mask;
-    DevBuf<int> table, counts, cnt, idx, ecount;
+    DevBuf<int> table, counts, cnt, idx, ecount, tab;
     DevBuf<BatchPnpDesc> desc;
     DevBuf<BatchPnpFetch> fetch;
     DevBuf<BatchPnpFin> fin;
@@ -57,7 +65,7 @@ struct BatchPnpWs {
     DevBuf<BatchPnpEpnpJob> eJobs;
     PinnedBuf<double> h_raw, h_cams, h_lmOut, h_part;
     PinnedBuf<uint8_t> h_best, h_mask;
-    PinnedBuf<int> h_table, h_counts, h_cnt, h_ecount;
+    PinnedBuf<int> h_table, h_counts, h_cnt, h_ecount, h_tab;
     PinnedBuf<BatchPnpDesc> h_desc;
     PinnedBuf<BatchPnpFetch> h_fetch;
     PinnedBuf<BatchPnpFin> h_fin;
@@ -107,14 +115,33 @@ struct Winner {     // a device problem with a pose
     bool ok;
 };
 
-// pnp_lm(.., 20) of every winner in lockstep.
-void batch_pnp_lm(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cams, hipStream_t s) {
+// The two refinements as the lockstep driver sees them: begin at a pose, fill a job's pose constants.
+void stepper_begin(PnpLmStepper& st, const double* r, const double* t) { st.begin(r, t, 20); }
+void stepper_begin(PnpVvsStepper& st, const double* r, const double* t) { st.begin(r, t, 20, 1.0); }
+void stepper_job(const PnpLmStepper& st, BatchPnpLmJob& J) {
+    const double* q = st.request();
+    rodrigues(q, J.R, J.dR);
+    for (int k = 0; k < 3; ++k) J.t[k] = q[3 + k];
+}
+void stepper_job(const PnpVvsStepper& st, BatchPnpLmJob& J) {
+    std::memcpy(J.R, st.R, sizeof(J.R));
+    std::memcpy(J.t, st.t, sizeof(J.t));
+    std::memset(J.dR, 0, sizeof(J.dR));   // OpPnpVVS reads none
+}
+
+// pnp_lm(.., 20) / pnp_vvs(.., 20, 1) of every job in lockstep: job j reduces over the rows
+// [ptOff, ptOff + N) of d_pts under d_mask (nullptr: all of them) with the camera h_cams + 8 d. A step is one
+// copy of the table of the jobs still running up, one batched reduction (2 launches), one copy of their 28
+// sums down and one synchronisation.
+template <class Stepper>
+void batch_pnp_lockstep(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cams, const void* d_pts,
+                        const uint8_t* d_mask, bool vvs, hipStream_t s) {
     if (jobs.empty()) return;
     BatchStats& stats = batch_stats();
-    std::vector<PnpLmStepper> st(jobs.size());
+    std::vector<Stepper> st(jobs.size());
     int maxN = 0;
     for (size_t j = 0; j < jobs.size(); ++j) {
-        st[j].begin(jobs[j]->r, jobs[j]->t, 20);
+        stepper_begin(st[j], jobs[j]->r, jobs[j]->t);
         maxN = std::max(maxN, jobs[j]->N);
     }
     const size_t per = (size_t)batch_reduce_blocks(maxN);
@@ -129,26 +156,149 @@ void batch_pnp_lm(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cam
         for (size_t j = 0; j < jobs.size(); ++j)
             if (!st[j].finished()) {
                 BatchPnpLmJob& J = W.h_lmJobs.p[who.size()];
-                const double* q = st[j].request();
                 J.ptOff = jobs[j]->ptOff;
                 J.N = jobs[j]->N;
                 std::memcpy(J.cam, h_cams + 8 * jobs[j]->d, sizeof(J.cam));
-                rodrigues(q, J.R, J.dR);
-                for (int k = 0; k < 3; ++k) J.t[k] = q[3 + k];
+                stepper_job(st[j], J);
                 actMaxN = std::max(actMaxN, J.N);
                 who.push_back(j);
             }
         if (who.empty()) break;
         const size_t n = who.size();
         pnp_copy(W.lmJobs.p, W.h_lmJobs.p, n * sizeof(BatchPnpLmJob), hipMemcpyHostToDevice, s);
-        stats.launches += launch_pnp_batch_reduce_lm(W.pts.p, W.mask.p, W.lmJobs.p, (int)n, actMaxN, W.lmPart.p,
-                                                     W.lmOut.p, s);
+        stats.launches += launch_pnp_batch_reduce(vvs, d_pts, d_mask, W.lmJobs.p, (int)n, actMaxN, W.lmPart.p,
+                                                  W.lmOut.p, s);
         pnp_copy(W.h_lmOut.p, W.lmOut.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, s);
         pnp_sync(s);
         ++stats.lmRounds;
         for (size_t k = 0; k < n; ++k) st[who[k]].feed(W.h_lmOut.p + 28 * k);
     }
     for (size_t j = 0; j < jobs.size(); ++j) st[j].result(jobs[j]->r, jobs[j]->t);
+}
+
+// The RANSAC batch's ITERATIVE tail: LM masked in place over every winner's rows.
+void batch_pnp_lm(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cams, hipStream_t s) {
+    batch_pnp_lockstep<PnpLmStepper>(W, jobs, h_cams, W.pts.p, W.mask.p, false, s);
+}
+
+// ---- the batched refinement (cvRefinePnPBatch, cvSolvePnPRansacRefineBatch) ----------
+const char* const kRefineSingle = "cvRefinePnP";   // the single exports' prefix of their messages
+
+// One copy of the raw points up and one launch of the pack over all of them: W.pts = every problem's rows.
+void refine_pack(BatchPnpWs& W, const mcvV2d* img, const mcvV3d* world, int total, hipStream_t s) {
+    BatchStats& stats = batch_stats();
+    auto t0 = std::chrono::steady_clock::now();
+    W.h_raw.ensure((size_t)total * 5);
+    W.raw.ensure((size_t)total * 5);
+    W.pts.ensure((size_t)total * 8);
+    std::memcpy(W.h_raw.p, img, (size_t)total * sizeof(mcvV2d));
+    std::memcpy(W.h_raw.p + 2 * (size_t)total, world, (size_t)total * sizeof(mcvV3d));
+    stats.packUs += us_since(t0);
+    pnp_copy(W.raw.p, W.h_raw.p, (size_t)total * 5 * sizeof(double), hipMemcpyHostToDevice, s);
+    launch_pnp_pack(W.raw.p, W.raw.p + 2 * (size_t)total, total, W.pts.p, s);
+    ++stats.launches;
+}
+
+// The host half of a refine: every problem's selected rows and place in the compact array, why a problem does
+// not run, and the table of those that do (pnp_refine_batch_index.h). run (may be null): the problems asked
+// for; a problem asked for that cannot run is reported through failed(p, the single call's message).
+struct RefinePlan {
+    std::vector<int> counts, compOff, reason;
+    std::vector<RefineBatchJob> jobs;
+    int largest = 0;
+    bool gathered = false;
+};
+template <class Failed>
+void refine_plan(const int* offsets, int B, const mcvM33d* K, const uint8_t* h_mask, const uint8_t* run, Failed failed,
+                 RefinePlan& R) {
+    R.gathered = h_mask != nullptr;
+    R.counts.assign((size_t)B, 0);
+    R.compOff.assign((size_t)B + 1, 0);
+    R.reason.assign((size_t)B, kRefineTooFew);
+    refine_batch_layout(offsets, B, h_mask, R.counts.data(), R.compOff.data());
+    for (int p = 0; p < B; ++p) {
+        if (run && !run[p]) continue;   // not asked for: no job, no message
+        R.reason[p] = refine_batch_reason(R.counts[p], camera_ok(K[p]));
+        char buf[160];
+        if (R.reason[p] == kRefineTooFew) {
+            snprintf(buf, sizeof(buf), "%s: need at least %d correspondences (N=%d)", kRefineSingle, kRefineMinRows,
+                     R.counts[p]);
+            failed(p, buf);
+        } else if (R.reason[p] == kRefineBadCamera) {
+            failed(p, "camera matrix needs finite non-zero fx, fy");
+        }
+    }
+    R.jobs.resize((size_t)B);
+    const int n = refine_batch_jobs(offsets, B, R.counts.data(), R.compOff.data(), R.reason.data(), R.gathered,
+                                    R.jobs.data(), &R.largest);
+    R.jobs.resize((size_t)n);
+}
+
+// The device half, for a call whose packed rows sit in W.pts and, with a mask, whose mask sits in W.mask with
+// the bytes the plan counted: every job refines (rVecs[p], tVecs[p]) in place over its selected rows, gathered
+// in index order (compact + gather, one launch each; without a mask it reduces over its own rows), as
+// cvRefinePnPLM / cvRefinePnPVVS on those rows. Returns the problems refined.
+int refine_on_device(BatchPnpWs& W, const RefinePlan& R, const int* offsets, int B, const mcvM33d* K,
+                     const double* dist, int refineKind, mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* refined,
+                     hipStream_t s) {
+    BatchStats& stats = batch_stats();
+    const std::vector<RefineBatchJob>& tab = R.jobs;
+    const std::vector<int>& compOff = R.compOff;
+    const bool gathered = R.gathered;
+    const int nJobs = (int)tab.size();
+    if (nJobs == 0) return 0;
+    const int total = offsets[B], selected = compOff[B];
+    const void* d_pts = W.pts.p;
+    if (gathered) {
+        // every problem's selected rows into one compact array: mcv_mask_compact's job form, then one lane per
+        // output row. The host counted the rows itself, so nothing is read back.
+        W.eJobs.ensure((size_t)B);
+        W.h_eJobs.ensure((size_t)B);
+        W.ecount.ensure((size_t)B);
+        W.idx.ensure((size_t)total);
+        W.comp.ensure((size_t)selected * 8);
+        W.tab.ensure(2 * ((size_t)B + 1));
+        W.h_tab.ensure(2 * ((size_t)B + 1));
+        std::memset(W.h_eJobs.p, 0, (size_t)B * sizeof(BatchPnpEpnpJob));
+        for (int p = 0; p < B; ++p) {
+            W.h_eJobs.p[p].ptOff = offsets[p];
+            W.h_eJobs.p[p].N = offsets[p + 1] - offsets[p];
+        }
+        std::memcpy(W.h_tab.p, offsets, ((size_t)B + 1) * sizeof(int));
+        std::memcpy(W.h_tab.p + B + 1, compOff.data(), ((size_t)B + 1) * sizeof(int));
+        pnp_copy(W.eJobs.p, W.h_eJobs.p, (size_t)B * sizeof(BatchPnpEpnpJob), hipMemcpyHostToDevice, s);
+        pnp_copy(W.tab.p, W.h_tab.p, 2 * ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice, s);
+        stats.launches += launch_pnp_batch_gather(W.pts.p, W.mask.p, W.eJobs.p, B, W.tab.p, W.tab.p + B + 1, selected,
+                                                  W.idx.p, W.ecount.p, W.comp.p, s);
+        d_pts = W.comp.p;
+    }
+    std::vector<double> cams((size_t)nJobs * 8);
+    std::vector<Winner> win((size_t)nJobs);
+    std::vector<Winner*> jobs((size_t)nJobs);
+    for (int j = 0; j < nJobs; ++j) {
+        const int p = tab[(size_t)j].prob;
+        double* c = cams.data() + 8 * (size_t)j;
+        c[0] = K[p].M[0]; c[1] = K[p].M[4]; c[2] = K[p].M[2]; c[3] = K[p].M[5];
+        for (int k = 0; k < 4; ++k) c[4 + k] = dist ? dist[4 * (size_t)p + k] : 0.0;
+        Winner& w = win[(size_t)j];
+        w = Winner{};
+        w.d = (size_t)j;
+        w.p = p;
+        w.ptOff = tab[(size_t)j].ptOff;
+        w.N = tab[(size_t)j].N;
+        w.r[0] = rVecs[p].X; w.r[1] = rVecs[p].Y; w.r[2] = rVecs[p].Z;
+        w.t[0] = tVecs[p].X; w.t[1] = tVecs[p].Y; w.t[2] = tVecs[p].Z;
+        w.ok = true;
+        jobs[(size_t)j] = &w;
+    }
+    if (refineKind == 1) batch_pnp_lockstep<PnpVvsStepper>(W, jobs, cams.data(), d_pts, nullptr, true, s);
+    else batch_pnp_lockstep<PnpLmStepper>(W, jobs, cams.data(), d_pts, nullptr, false, s);
+    for (const Winner& w : win) {
+        rVecs[w.p].X = w.r[0]; rVecs[w.p].Y = w.r[1]; rVecs[w.p].Z = w.r[2];
+        tVecs[w.p].X = w.t[0]; tVecs[w.p].Y = w.t[1]; tVecs[w.p].Z = w.t[2];
+        if (refined) refined[w.p] = 1;
+    }
+    return nJobs;
 }
 
 // epnp_inliers of every winner at once: compact + prep + the passes with grid y = the job, the single call's
@@ -273,7 +423,7 @@ void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_c
 
 int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int* offsets, int B, const mcvM33d* K,
               const double* dist, const RansacConfig& cfg, const RansacConfig* cfgp, mcvV3d* tVecs, mcvV3d* rVecs,
-              uint8_t* mask, int* counts) {
+              uint8_t* mask, int* counts, int refineKind = -1) {
     BatchStats& stats = batch_stats();
     stats = BatchStats();
     stats.problems = B;
@@ -296,6 +446,8 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
         if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
     };
     int ok = 0;
+    int directPoses = 0;         // poses of the single export's direct solve: their masks never reach the device
+    bool maskOnDevice = false;   // W.mask holds the returned mask of every device problem
 
     BatchLayout L;
     batch_layout(offsets, B, m, cfg.maxIters, batch_cap_pnp(), L);
@@ -324,6 +476,7 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
                 counts[p] = c;
                 for (int k = 0; k < c; ++k) mask[o + idxBuf[(size_t)k]] = 1;
                 ++ok;
+                ++directPoses;
             } else {
                 const char* e = mcvGetLastError();
                 failed(p, e && *e ? e : "the direct solve found no pose");
@@ -514,8 +667,12 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
             // runs EPnP on the inliers
             if (pnp_kind(cfg.pnpKind) == 0) batch_pnp_lm(W, jobs, W.h_cams.p, s);
             else batch_pnp_epnp(W, jobs, W.h_cams.p, world, total, failed, s);
+            maskOnDevice = true;
             for (const Winner& w : win) {
-                if (!w.ok) continue;
+                if (!w.ok) {   // its device mask slice is not the (zero) one the call returns
+                    maskOnDevice = false;
+                    continue;
+                }
                 rVecs[w.p].X = w.r[0]; rVecs[w.p].Y = w.r[1]; rVecs[w.p].Z = w.r[2];
                 tVecs[w.p].X = w.t[0]; tVecs[w.p].Y = w.t[1]; tVecs[w.p].Z = w.t[2];
                 counts[w.p] = w.count;
@@ -523,6 +680,26 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
                 ++ok;
             }
         }
+    }
+    if (refineKind >= 0 && ok > 0) {
+        // cvRefinePnPBatch on the returned mask, for every problem with a pose: the packed rows and the mask are
+        // read where the rounds left them on the device. Only what never got there is sent now: the points
+        // when no problem ran on the device, the mask when a direct solve or a failed inlier solve made the
+        // returned one differ from the device's.
+        BatchPnpWs& W = thread_batch_pnp_ws();
+        hipStream_t s = W.stream;
+        if (!D) refine_pack(W, img, world, total, s);
+        if (!maskOnDevice || directPoses > 0) {
+            W.mask.ensure((size_t)total);
+            W.h_mask.ensure((size_t)total);
+            std::memcpy(W.h_mask.p, mask, (size_t)total);
+            pnp_copy(W.mask.p, W.h_mask.p, (size_t)total, hipMemcpyHostToDevice, s);
+        }
+        std::vector<uint8_t> run((size_t)B);
+        for (int p = 0; p < B; ++p) run[(size_t)p] = counts[p] > 0 ? 1 : 0;
+        RefinePlan R;
+        refine_plan(offsets, B, K, mask, run.data(), failed, R);
+        refine_on_device(W, R, offsets, B, K, dist, refineKind, tVecs, rVecs, nullptr, s);
     }
     if (firstFail >= 0) {
         // a problem that failed returns a zero pose, count and mask slice; the first one is named
@@ -541,32 +718,131 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
 
 using namespace mcv;
 
+// The argument checks cvSolvePnPRansacBatch and cvSolvePnPRansacRefineBatch share; returns the configuration.
+static RansacConfig pnp_batch_check(const char* who, const mcvV2d* imgPoints, const mcvV3d* worldPoints,
+                                    const int* offsets, int B, const mcvM33d* K, const RansacConfig* cfgp,
+                                    mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask, int* counts) {
+    if (!imgPoints || !worldPoints || !offsets || !K || !tVecs || !rVecs || !mask || !counts)
+        fail("%s: null argument (imgPoints, worldPoints, offsets, K, tVecs, rVecs, mask and counts are required)", who);
+    if (B < 0) fail("%s: negative B (%d)", who, B);
+    if (offsets[0] != 0) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
+    for (int p = 0; p < B; ++p)
+        if (offsets[p + 1] < offsets[p])
+            fail("%s: offsets decrease at problem %d (%d -> %d)", who, p, offsets[p], offsets[p + 1]);
+    const RansacConfig cfg = cfgp ? *cfgp : pnp_config(100, 8.0f, 0.99, 0);
+    check_flags(cfg, who);
+    if (cfg.method != MCV_METHOD_RANSAC) fail("%s: unsupported method %d (only MCV_METHOD_RANSAC)", who, cfg.method);
+    if (cfg.flags & MCV_FLAG_FUSED_ERROR) fail("%s: unsupported flag MCV_FLAG_FUSED_ERROR", who);
+    if (cfg.flags & MCV_FLAG_FAST_MINIMAL) fail("%s: unsupported flag MCV_FLAG_FAST_MINIMAL", who);
+    if (cfg.deviceCount > 1) fail("%s: unsupported deviceCount %d (one GPU per call)", who, cfg.deviceCount);
+    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);
+    for (int p = 0; p < B; ++p)
+        if (offsets[p + 1] - offsets[p] > 65535 * kBatchPnpTile)
+            fail("%s: problem %d has more than %d correspondences", who, p, 65535 * kBatchPnpTile);
+    return cfg;
+}
+
 extern "C" MCV_API int cvSolvePnPRansacBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int* offsets,
                                              int B, const mcvM33d* K, const double* distortionCoeffs,
                                              const RansacConfig* cfgp, mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask,
                                              int* counts) {
     MCV_GUARD(-1, {
         const char* who = "cvSolvePnPRansacBatch";
-        if (!imgPoints || !worldPoints || !offsets || !K || !tVecs || !rVecs || !mask || !counts)
-            fail("%s: null argument (imgPoints, worldPoints, offsets, K, tVecs, rVecs, mask and counts are required)",
-                 who);
-        if (B < 0) fail("%s: negative B (%d)", who, B);
-        if (offsets[0] != 0) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
-        for (int p = 0; p < B; ++p)
-            if (offsets[p + 1] < offsets[p])
-                fail("%s: offsets decrease at problem %d (%d -> %d)", who, p, offsets[p], offsets[p + 1]);
-        const RansacConfig cfg = cfgp ? *cfgp : pnp_config(100, 8.0f, 0.99, 0);
-        check_flags(cfg, who);
-        if (cfg.method != MCV_METHOD_RANSAC) fail("%s: unsupported method %d (only MCV_METHOD_RANSAC)", who, cfg.method);
-        if (cfg.flags & MCV_FLAG_FUSED_ERROR) fail("%s: unsupported flag MCV_FLAG_FUSED_ERROR", who);
-        if (cfg.flags & MCV_FLAG_FAST_MINIMAL) fail("%s: unsupported flag MCV_FLAG_FAST_MINIMAL", who);
-        if (cfg.deviceCount > 1) fail("%s: unsupported deviceCount %d (one GPU per call)", who, cfg.deviceCount);
-        if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);
-        for (int p = 0; p < B; ++p)
-            if (offsets[p + 1] - offsets[p] > 65535 * kBatchPnpTile)
-                fail("%s: problem %d has more than %d correspondences", who, p, 65535 * kBatchPnpTile);
+        const RansacConfig cfg = pnp_batch_check(who, imgPoints, worldPoints, offsets, B, K, cfgp, tVecs, rVecs, mask,
+                                                 counts);
         return pnp_batch(who, imgPoints, worldPoints, offsets, B, K, distortionCoeffs, cfg, cfgp, tVecs, rVecs, mask,
                          counts);
+    })
+}
+
+extern "C" MCV_API int cvSolvePnPRansacRefineBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints,
+                                                   const int* offsets, int B, const mcvM33d* K,
+                                                   const double* distortionCoeffs, const RansacConfig* cfgp,
+                                                   int refineKind, mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask,
+                                                   int* counts) {
+    MCV_GUARD(-1, {
+        const char* who = "cvSolvePnPRansacRefineBatch";
+        const RansacConfig cfg = pnp_batch_check(who, imgPoints, worldPoints, offsets, B, K, cfgp, tVecs, rVecs, mask,
+                                                 counts);
+        if (refineKind != 0 && refineKind != 1)
+            fail("%s: unsupported refineKind %d (0 = LM, 1 = VVS)", who, refineKind);
+        return pnp_batch(who, imgPoints, worldPoints, offsets, B, K, distortionCoeffs, cfg, cfgp, tVecs, rVecs, mask,
+                         counts, refineKind);
+    })
+}
+
+extern "C" MCV_API int cvRefinePnPBatch(const mcvV2d* imgPoints, const mcvV3d* worldPoints, const int* offsets, int B,
+                                        const mcvM33d* K, const double* distortionCoeffs, const uint8_t* mask,
+                                        int refineKind, mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* refined) {
+    MCV_GUARD(-1, {
+        const char* who = "cvRefinePnPBatch";
+        if (!imgPoints || !worldPoints || !offsets || !K || !tVecs || !rVecs)
+            fail("%s: null argument (imgPoints, worldPoints, offsets, K, tVecs and rVecs are required)", who);
+        if (B < 0) fail("%s: negative B (%d)", who, B);
+        int where = 0;
+        const int bad = refine_batch_check_offsets(offsets, B, &where);
+        if (bad == 1) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
+        if (bad == 2)
+            fail("%s: offsets decrease at problem %d (%d -> %d)", who, where, offsets[where], offsets[where + 1]);
+        where = refine_batch_check_sizes(offsets, B, 65535 * kBatchPnpTile);
+        if (where >= 0) fail("%s: problem %d has more than %d correspondences", who, where, 65535 * kBatchPnpTile);
+        if (refineKind != 0 && refineKind != 1)
+            fail("%s: unsupported refineKind %d (0 = LM, 1 = VVS)", who, refineKind);
+        BatchStats& stats = batch_stats();
+        stats = BatchStats();
+        stats.problems = B;
+        if (B == 0) return 0;
+        int firstFail = -1;
+        std::string firstMsg;
+        auto failed = [&](int p, const std::string& msg) {
+            if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
+        };
+        RefinePlan R;
+        refine_plan(offsets, B, K, mask, nullptr, failed, R);
+        // a call in which no problem can run needs no device, as the single call that refuses its N
+        if (!R.jobs.empty()) require_device();
+        if (refined) std::memset(refined, 0, (size_t)B);
+        int ok = 0;
+        if (!R.jobs.empty()) {
+            BatchPnpWs& W = thread_batch_pnp_ws();
+            hipStream_t s = W.stream;
+            const int total = offsets[B];
+            refine_pack(W, imgPoints, worldPoints, total, s);
+            if (mask) {
+                W.mask.ensure((size_t)total);
+                W.h_mask.ensure((size_t)total);
+                std::memcpy(W.h_mask.p, mask, (size_t)total);
+                pnp_copy(W.mask.p, W.h_mask.p, (size_t)total, hipMemcpyHostToDevice, s);
+            }
+            ok = refine_on_device(W, R, offsets, B, K, distortionCoeffs, refineKind, tVecs, rVecs, refined, s);
+        }
+        if (firstFail >= 0) {
+            // a problem that was not refined keeps its pose; the first one is named
+            char buf[400];
+            snprintf(buf, sizeof(buf), "%s: problem %d: %s", who, firstFail, firstMsg.c_str());
+            set_last_error(buf);
+        } else {
+            clear_last_error();
+        }
+        return ok;
+    })
+}
+
+// The index arithmetic of cvRefinePnPBatch as the export computes it (no device): counts[B] the selected rows
+// of every problem, compOff[B + 1] their place in the compact array. Returns the largest count, -1 on a bad
+// argument.
+extern "C" MCV_API int mcvHostRefinePnPBatchLayout(const int* offsets, int B, const uint8_t* mask, int* counts,
+                                                   int* compOff) {
+    MCV_GUARD(-1, {
+        const char* who = "mcvHostRefinePnPBatchLayout";
+        if (!offsets || !counts || !compOff) fail("%s: null argument", who);
+        if (B < 0) fail("%s: negative B (%d)", who, B);
+        int where = 0;
+        const int bad = refine_batch_check_offsets(offsets, B, &where);
+        if (bad == 1) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
+        if (bad == 2)
+            fail("%s: offsets decrease at problem %d (%d -> %d)", who, where, offsets[where], offsets[where + 1]);
+        return refine_batch_layout(offsets, B, mask, counts, compOff);
     })
 }
 

@@ -18,6 +18,8 @@
 //   BATCH forms          cvSolvePnPRansacBatch: the generate kernels, mcv_mask_compact,
 //                        mcv_epnp_prep_f32, mcv_epnp_pass and the LM reduction over many problems at once,
 //                        compiled from the same bodies; their launchers are at the end of the file.
+//                        cvRefinePnPBatch adds the VVS reduction in that form and
+//                        mcv_pnp_batch_gather (every problem's selected rows into one compact array).
 #include "mcv_common.h"
 #include "hyp_pnp.h"
 #include "pnp_pk.h"
@@ -25,6 +27,7 @@
 #include "reduce.h"
 #include "kernels.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace mcv {
 
@@ -1136,26 +1139,32 @@ int launch_pnp_batch_generate(const void* d_pts, const BatchPnpDesc* d_desc, int
     return 5;
 }
 
-// pnp_reduce_lm's two stages for many jobs at once (ransac_batch.hip's pattern): job r's partials are those of
-// reduce_blocks(N_r) blocks strided by its own grid, summed in block order by reduce_final's loop.
-__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_pass(const PnpPoint* __restrict__ pts,
-                                                                               const uint8_t* __restrict__ mask,
-                                                                               const BatchPnpLmJob* __restrict__ jobs,
-                                                                               int blocksPer,
-                                                                               double* __restrict__ partials) {
+// pnp_reduce_lm's / pnp_reduce_vvs's two stages for many jobs at once (ransac_batch.hip's pattern): job r's
+// partials are those of reduce_blocks(N_r) blocks strided by its own grid, summed in block order by
+// reduce_final's loop, so its 28 sums are the bits of run_reduce<28>(N_r, op). kVvs picks OpPnpVVS (the job's
+// cam, R, t) over OpPnpLM (with dR, wantJ). mask: the segmented mask, or nullptr (every row of the job counts:
+// the batched refinement reduces over gathered rows).
+template <bool kVvs>
+__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_pass(const PnpPoint* __restrict__ pts,
+                                                                            const uint8_t* __restrict__ mask,
+                                                                            const BatchPnpLmJob* __restrict__ jobs,
+                                                                            int blocksPer,
+                                                                            double* __restrict__ partials) {
     const int r = blockIdx.x / blocksPer, b = blockIdx.x % blocksPer;
     const BatchPnpLmJob& J = jobs[r];
     const int N = J.N;
     const int nb = reduce_blocks(N);
     if (b >= nb) return;   // uniform over the workgroup
-    OpPnpLM op;
+    typename std::conditional<kVvs, OpPnpVVS, OpPnpLM>::type op;
     op.pts = pts + J.ptOff;
-    op.mask = mask + J.ptOff;
+    op.mask = mask ? mask + J.ptOff : nullptr;
     op.c = to_cam(J.cam);
     for (int k = 0; k < 9; ++k) op.R[k] = J.R[k];
     for (int k = 0; k < 3; ++k) op.t[k] = J.t[k];
-    for (int k = 0; k < 27; ++k) op.dR[k] = J.dR[k];
-    op.wantJ = true;
+    if constexpr (!kVvs) {
+        for (int k = 0; k < 27; ++k) op.dR[k] = J.dR[k];
+        op.wantJ = true;
+    }
     double acc[28];
 #pragma unroll
     for (int v = 0; v < 28; ++v) acc[v] = 0;
@@ -1163,10 +1172,10 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_pass(c
     block_sum<28>(acc, partials + ((size_t)r * blocksPer + b) * 28);
 }
 
-__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_final(const BatchPnpLmJob* __restrict__ jobs,
-                                                                                int blocksPer,
-                                                                                const double* __restrict__ partials,
-                                                                                double* __restrict__ out) {
+__global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_final(const BatchPnpLmJob* __restrict__ jobs,
+                                                                             int blocksPer,
+                                                                             const double* __restrict__ partials,
+                                                                             double* __restrict__ out) {
     const int r = blockIdx.x;
     const int nb = reduce_blocks(jobs[r].N);
     const double* part = partials + (size_t)r * blocksPer * 28;
@@ -1180,13 +1189,54 @@ __global__ __launch_bounds__(kReduceThreads) void mcv_pnp_batch_reduce_lm_final(
     block_sum<28>(acc, out + (size_t)r * 28);
 }
 
-int launch_pnp_batch_reduce_lm(const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs, int nJobs,
-                               int maxN, double* d_part, double* d_out, hipStream_t s) {
+int launch_pnp_batch_reduce(bool vvs, const void* d_pts, const uint8_t* d_mask, const BatchPnpLmJob* d_jobs,
+                            int nJobs, int maxN, double* d_part, double* d_out, hipStream_t s) {
     const int per = reduce_blocks(maxN);
-    hipLaunchKernelGGL(mcv_pnp_batch_reduce_lm_pass, dim3((unsigned)per * nJobs), dim3(kReduceThreads), 0, s,
-                       (const PnpPoint*)d_pts, d_mask, d_jobs, per, d_part);
-    hipLaunchKernelGGL(mcv_pnp_batch_reduce_lm_final, dim3(nJobs), dim3(kReduceThreads), 0, s, d_jobs, per,
+    const dim3 grid((unsigned)per * nJobs), block(kReduceThreads);
+    if (vvs)
+        hipLaunchKernelGGL(mcv_pnp_batch_reduce_pass<true>, grid, block, 0, s, (const PnpPoint*)d_pts, d_mask, d_jobs,
+                           per, d_part);
+    else
+        hipLaunchKernelGGL(mcv_pnp_batch_reduce_pass<false>, grid, block, 0, s, (const PnpPoint*)d_pts, d_mask, d_jobs,
+                           per, d_part);
+    hipLaunchKernelGGL(mcv_pnp_batch_reduce_final, dim3(nJobs), dim3(kReduceThreads), 0, s, d_jobs, per,
                        (const double*)d_part, d_out);
+    return 2;
+}
+
+// The gather of the batched refinement: out[g] = the g-th selected row of the call. Lane g finds its problem
+// in compOff (B + 1 increasing offsets, compOff[0] = 0, compOff[B] = total: the last p with compOff[p] <= g;
+// problems without selected rows own no g) and copies row idx[rowOff[p] + (g - compOff[p])] of that problem,
+// idx being mcv_mask_compact's per-problem list. One lane per output row of all problems: a small problem
+// beside a large one idles nothing.
+__global__ __launch_bounds__(256) void mcv_pnp_batch_gather(const PnpPoint* __restrict__ pts,
+                                                            const int* __restrict__ idx,
+                                                            const int* __restrict__ rowOff,
+                                                            const int* __restrict__ compOff, int B, int total,
+                                                            PnpPoint* __restrict__ out) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= total) return;
+    int lo = 0, hi = B;   // compOff[lo] <= g < compOff[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (compOff[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const int row = rowOff[lo];
+    const int i = idx[row + (g - compOff[lo])];
+    const float4* src = reinterpret_cast<const float4*>(pts + row + i);
+    float4* dst = reinterpret_cast<float4*>(out + g);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
+int launch_pnp_batch_gather(const void* d_pts, const uint8_t* d_mask, const BatchPnpEpnpJob* d_jobs, int B,
+                            const int* d_rowOff, const int* d_compOff, int total, int* d_idx, int* d_count,
+                            void* d_out, hipStream_t s) {
+    if (B <= 0 || total <= 0) return 0;
+    hipLaunchKernelGGL(mcv_mask_compact, dim3(B), dim3(1024), 0, s, d_mask, 0, d_idx, d_count, d_jobs);
+    hipLaunchKernelGGL(mcv_pnp_batch_gather, dim3((total + 255) / 256), dim3(256), 0, s, (const PnpPoint*)d_pts,
+                       (const int*)d_idx, d_rowOff, d_compOff, B, total, (PnpPoint*)d_out);
     return 2;
 }
 

@@ -140,6 +140,8 @@ SIGNATURES = {
     "cvRecoverPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvSolvePnPRansacCfg": (_I, [_P, _P, _I, M33d, _P, _P, _P, _P, _P, _P]),
     "cvSolvePnPRansacBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cvRefinePnPBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "cvSolvePnPRansacRefineBatch": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvMatchFeatures": (_I, [_P, _P, _P, _P, _P, _I]),
     "cvMatchAndFindModel": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "cvMatchFeaturesNorm": (_I, [_P, _P, _P, _I, _P, _P, _I]),
@@ -242,6 +244,8 @@ SIGNATURES = {
     "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),
     "mcvTestBatchSweepE": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "mcvTestBatchSweepPnp": (_I, [_P, _P, _I, _P, _P, _P, _F, _P]),
+    "mcvHostRefinePnPBatchLayout": (_I, [_P, _I, _P, _P, _P]),
+    "mcvTestRefinePnPMasked": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "mcvHostMatchBatchLayout": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I]),
     "mcvTestMatchBatchStats": (_I, [_P]),
     "mcvTestMatchBatchKnn": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),

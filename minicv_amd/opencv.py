@@ -410,27 +410,8 @@ def solvePnPRansacBatch(imgs, worlds, Ks, dists=None, kind: str = "AP3P", params
     (False, zeros, zeros, empty) and N.last_error() names the first such problem. params None: the native
     defaults (100 iterations, 8 px, 0.99, OpenCV's sample stream). Raises NativeError when the whole call is
     refused."""
-    if len(imgs) != len(worlds):
-        raise ValueError("imgs/worlds length mismatch")
-    B = len(imgs)
-    pi = [_v2d(x) for x in imgs]
-    pw = [_v3d(x) for x in worlds]
-    for x, y in zip(pi, pw):
-        if x.shape[0] != y.shape[0]:
-            raise ValueError("img/world length mismatch")
-    offsets = np.zeros(B + 1, dtype=np.int32)
-    offsets[1:] = np.cumsum([x.shape[0] for x in pi])
+    B, offsets, img, world, K, d = _pnp_batch_args(imgs, worlds, Ks, dists)
     total = int(offsets[B])
-    img = np.ascontiguousarray(np.concatenate(pi, axis=0)) if total else np.zeros((1, 2))
-    world = np.ascontiguousarray(np.concatenate(pw, axis=0)) if total else np.zeros((1, 3))
-    K = np.ascontiguousarray(np.asarray(Ks, dtype=np.float64).reshape(-1, 9)) if B else np.zeros((1, 9))
-    if B and K.shape[0] != B:
-        raise ValueError("Ks must have one camera matrix per problem")
-    d = None
-    if dists is not None:
-        d = np.ascontiguousarray(np.asarray(dists, dtype=np.float64).reshape(-1, 4)) if B else np.zeros((1, 4))
-        if B and d.shape[0] != B:
-            raise ValueError("dists must have one row of 4 coefficients per problem")
     cfg = None
     if params is not None or kind != "Iterative":
         cfg = params.to_c() if params is not None else _pnp_default_cfg()
@@ -486,6 +467,104 @@ def refinePnPLM(img, world, K, dist, rvec, tvec):
 def refinePnPVVS(img, world, K, dist, rvec, tvec):
     """cvRefinePnPVVS -> (rvec, tvec)."""
     return _refine(N.lib().cvRefinePnPVVS, img, world, K, dist, rvec, tvec)
+
+
+REFINE_KIND = {"LM": 0, "VVS": 1}
+
+
+def solvePnPRansacWithRefine(img, world, K, dist=None, kind: str = "AP3P", refine: str = "LM", iterations: int = 100,
+                             reproj_error: float = 8.0, confidence: float = 0.99,
+                             params: RansacParams | None = None):
+    """solvePnPRansacWithRefine (OpenCV.fs:1051, solvePnPInternal with `ransac` and `refinement`): solvePnPRansac,
+    then the inliers gathered in index order (OpenCV.fs:1006-1007), then refinePnPLM / refinePnPVVS on them from
+    the RANSAC pose. -> (ok, rvec, tvec, inlier indices); without a pose nothing is refined."""
+    fn = {"LM": refinePnPLM, "VVS": refinePnPVVS}[refine]
+    ok, r, t, inl = solvePnPRansac(img, world, K, dist, kind, iterations, reproj_error, confidence, params)
+    if not ok:
+        return ok, r, t, inl
+    r, t = fn(_v2d(img)[inl], _v3d(world)[inl], K, dist, r, t)
+    return ok, r, t, inl
+
+
+def _pnp_batch_args(imgs, worlds, Ks, dists):
+    """The segmented arrays of a PnP batch call -> (B, offsets, img, world, K, d or None)."""
+    if len(imgs) != len(worlds):
+        raise ValueError("imgs/worlds length mismatch")
+    B = len(imgs)
+    pi = [_v2d(x) for x in imgs]
+    pw = [_v3d(x) for x in worlds]
+    for x, y in zip(pi, pw):
+        if x.shape[0] != y.shape[0]:
+            raise ValueError("img/world length mismatch")
+    offsets = np.zeros(B + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([x.shape[0] for x in pi])
+    total = int(offsets[B])
+    img = np.ascontiguousarray(np.concatenate(pi, axis=0)) if total else np.zeros((1, 2))
+    world = np.ascontiguousarray(np.concatenate(pw, axis=0)) if total else np.zeros((1, 3))
+    K = np.ascontiguousarray(np.asarray(Ks, dtype=np.float64).reshape(-1, 9)) if B else np.zeros((1, 9))
+    if B and K.shape[0] != B:
+        raise ValueError("Ks must have one camera matrix per problem")
+    d = None
+    if dists is not None:
+        d = np.ascontiguousarray(np.asarray(dists, dtype=np.float64).reshape(-1, 4)) if B else np.zeros((1, 4))
+        if B and d.shape[0] != B:
+            raise ValueError("dists must have one row of 4 coefficients per problem")
+    return B, offsets, img, world, K, d
+
+
+def refinePnPBatch(imgs, worlds, Ks, dists, rvecs, tvecs, kind: str = "LM", masks=None):
+    """cvRefinePnPBatch: refinePnPLM / refinePnPVVS (kind "LM" / "VVS") of B problems in one call. imgs / worlds /
+    Ks / dists as in solvePnPRansacBatch; rvecs / tvecs: B start poses; masks: None (all points) or B arrays of
+    N_p bytes, non-zero = the row takes part (the rows are gathered in index order).
+    -> a list of (refined, rvec, tvec): where refined, the pose of the single call on the selected rows; else
+    the start pose, and N.last_error() names the first such problem. Raises NativeError when the whole call is
+    refused."""
+    B, offsets, img, world, K, d = _pnp_batch_args(imgs, worlds, Ks, dists)
+    total = int(offsets[B])
+    rs = np.zeros((max(B, 1), 3), dtype=np.float64)
+    ts = np.zeros((max(B, 1), 3), dtype=np.float64)
+    if B:
+        rs[:B] = np.asarray(rvecs, dtype=np.float64).reshape(-1, 3)
+        ts[:B] = np.asarray(tvecs, dtype=np.float64).reshape(-1, 3)
+    m = None
+    if masks is not None:
+        if len(masks) != B:
+            raise ValueError("masks must have one array per problem")
+        ms = [np.ascontiguousarray(np.asarray(x)).astype(np.uint8).reshape(-1) for x in masks]
+        for p, x in enumerate(ms):
+            if x.shape[0] != offsets[p + 1] - offsets[p]:
+                raise ValueError("a mask must have one byte per correspondence of its problem")
+        m = np.ascontiguousarray(np.concatenate(ms)) if total else np.zeros(1, dtype=np.uint8)
+    refined = np.zeros(max(B, 1), dtype=np.uint8)
+    ret = N.lib().cvRefinePnPBatch(img.ctypes.data, world.ctypes.data, offsets.ctypes.data, B, K.ctypes.data,
+                                   d.ctypes.data if d is not None else None, m.ctypes.data if m is not None else None,
+                                   REFINE_KIND[kind], ts.ctypes.data, rs.ctypes.data, refined.ctypes.data)
+    N.check(ret >= 0, "cvRefinePnPBatch")
+    return [(bool(refined[p]), rs[p].copy(), ts[p].copy()) for p in range(B)]
+
+
+def solvePnPRansacWithRefineBatch(imgs, worlds, Ks, dists=None, kind: str = "AP3P", refine: str = "LM",
+                                  params: RansacParams | None = None):
+    """cvSolvePnPRansacRefineBatch: solvePnPRansacWithRefine of B problems in one call (solvePnPRansacBatch, then
+    refinePnPBatch on its masks, the points uploaded once). -> a list of (ok, rvec, tvec, inlier indices) per
+    problem; a problem without a pose gives (False, zeros, zeros, empty) and is not refined."""
+    B, offsets, img, world, K, d = _pnp_batch_args(imgs, worlds, Ks, dists)
+    total = int(offsets[B])
+    cfg = None
+    if params is not None or kind != "Iterative":
+        cfg = params.to_c() if params is not None else _pnp_default_cfg()
+        cfg.pnpKind = SOLVER_KIND[kind]
+    ts = np.zeros((max(B, 1), 3), dtype=np.float64)
+    rs = np.zeros((max(B, 1), 3), dtype=np.float64)
+    counts = np.zeros(max(B, 1), dtype=np.int32)
+    ms = np.zeros(max(total, 1), dtype=np.uint8)
+    ret = N.lib().cvSolvePnPRansacRefineBatch(img.ctypes.data, world.ctypes.data, offsets.ctypes.data, B,
+                                              K.ctypes.data, d.ctypes.data if d is not None else None,
+                                              N.C.addressof(cfg) if cfg is not None else None, REFINE_KIND[refine],
+                                              ts.ctypes.data, rs.ctypes.data, ms.ctypes.data, counts.ctypes.data)
+    N.check(ret >= 0, "cvSolvePnPRansacRefineBatch")
+    return [(bool(counts[p] > 0), rs[p].copy(), ts[p].copy(),
+             np.flatnonzero(ms[offsets[p]:offsets[p + 1]]).astype(np.int32)) for p in range(B)]
 
 
 def solveAp3p(img, world, K):
