@@ -547,6 +547,38 @@ MCV_API int cvTriangulateTracks(const mcvCamera* cameras, int nCameras, const in
                                 const mcvV2d* observations, const int* offsets, int T, mcvV3d* points,
                                 int* pairCounts, double* cost, int* visible);
 
+/* Track building — the step between cvMatchFeaturesBatch and cvTriangulateTracks: pairwise matches
+ * (a CSR over image pairs) to tracks (a CSR of (camera, feature) over tracks), on the GPU.
+ * Inputs, host arrays in cvMatchFeaturesBatch's conventions: featureCounts[nImages] (each >= 0),
+ * imagePairs[2 B], pairs[2 offsets[B]] and offsets[B + 1] (offsets[0] == 0, non-decreasing) as
+ * cvMatchFeaturesBatch writes them, mask[offsets[B]] (nullable: cvMatchAndFindModelBatch's inlier
+ * bytes; null keeps every match, a non-zero byte keeps its match), minLength >= 2.
+ *   nodes: feature f of image i is node base[i] + f, base = the exclusive prefix sum of featureCounts;
+ *   edges: kept match k of problem p over images (i, j) = imagePairs[2p], imagePairs[2p + 1] joins
+ *     (i, pairs[2k]) and (j, pairs[2k + 1]); duplicates are harmless, i == j is legal, a self-loop
+ *     touches its node and joins nothing;
+ *   components: the connected components over the nodes touched by at least one kept edge.
+ * A component is dropped, and counted once, by the first rule that applies: oversize (more than
+ * MCV_MAX_TRACK_LEN nodes), conflicts (two different nodes of one image), short (fewer than minLength
+ * nodes). The others are the tracks, ordered by their smallest node, the observations of a track by
+ * node (that is by image). The order of the problems and of the matches changes no output bit.
+ * Writes trackOffsets[T + 1], cameraIdx[nObs] and featureIdx[nObs] (cameraIdx and trackOffsets go to
+ * cvTriangulateTracks as they are; the caller gathers its observation coordinates with featureIdx),
+ * and the optional trackOfFeature[base[nImages]] (the track of every node, -1 for a node in none) and
+ * dropped[3] (oversize, conflicts, short). trackOffsets has room for maxTracks + 1 ints, cameraIdx and
+ * featureIdx for maxObs; maxObs >= min(2 offsets[B], base[nImages]) and maxTracks >= maxObs / 2 are
+ * always enough. Returns T (0 is a valid result, as is B == 0). Returns -1 with a message and writes
+ * nothing to any output on a null required pointer, a negative nImages, B, maxTracks, maxObs or
+ * feature count, offsets that do not start at 0 or that decrease, an image index outside [0, nImages),
+ * a feature index outside its image (masked-out matches included), minLength < 2, more than 2^30
+ * nodes or matches, a result that does not fit maxTracks / maxObs, or when no HIP device is visible.
+ * Every argument check runs on the host before the device is touched; the outputs are written only
+ * after the whole result is known. */
+MCV_API int cvBuildTracks(const int* featureCounts, int nImages, const int* imagePairs, int B,
+                          const int* pairs, const int* offsets, const uint8_t* mask, int minLength,
+                          int* trackOffsets, int maxTracks, int* cameraIdx, int* featureIdx, int maxObs,
+                          int* trackOfFeature, long long* dropped);
+
 /* Batched CameraPose.findScaled: P independent cvFindScaledPose problems in one call, each bit-identical
  * to its own single call; the launches, copies and the one synchronisation do not grow with P (DESIGN
  * §7j). The observation sets are a CSR: offsets[S + 1] ints, offsets[0] == 0, non-decreasing, over the
@@ -1001,6 +1033,17 @@ MCV_API int mcvHostFindScaledPoseBatch(const mcvCamera* srcCams, const mcvM33d* 
  * problems on the device (those over a non-empty set), candidate tiles (blocks of 64 candidates of the
  * sweep), 0, 0}. Returns 0. */
 MCV_API int mcvTestScaledBatchStats(long long* stats8);
+/* Host twin of cvBuildTracks: the same arguments, checks, outputs and return value, computed by a
+ * sequential union-find (union by smaller id). No GPU. */
+MCV_API int mcvHostBuildTracks(const int* featureCounts, int nImages, const int* imagePairs, int B,
+                               const int* pairs, const int* offsets, const uint8_t* mask, int minLength,
+                               int* trackOffsets, int maxTracks, int* cameraIdx, int* featureIdx, int maxObs,
+                               int* trackOfFeature, long long* dropped);
+/* Counters of the calling thread's last cvBuildTracks call that passed its checks: stats8 = {kernel
+ * launches, stream synchronisations, host<->device copies, memsets, candidate components (those that
+ * were sorted), of them the long ones (more than 32 nodes: one workgroup each), kept matches, 0}; all
+ * are 0 for a call without a kept match, which launches nothing. Returns 0. */
+MCV_API int mcvTestTracksStats(long long* stats8);
 
 #ifdef __cplusplus
 }

@@ -11,10 +11,11 @@ from .opencv import RansacParams, findHomography, findFundamentalMat, matchHammi
     recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch, \
     refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch
 from . import camera
-from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks
+from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks, \
+    buildTracks, trackObservations
 
 __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomography", "findFundamentalMat",
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
            "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch",
            "refinePnPBatch", "solvePnPRansacWithRefine", "solvePnPRansacWithRefineBatch", "camera", "Camera", "CameraPose", "findScaled",
-           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts"]
+           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts", "buildTracks", "trackObservations"]

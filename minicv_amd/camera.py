@@ -291,3 +291,57 @@ def triangulateTracks(cameras, cameraIdx, obs, offsets, stats: bool = False):
                                     _nonnull(vis, 1).ctypes.data if stats else None)
     N.check(k >= 0, "cvTriangulateTracks")
     return (pts, cnt, cost, vis) if stats else (pts, cnt)
+
+
+def _build_tracks(export: str, featureCounts, imagePairs, pairs, offsets, mask=None, minLength: int = 2):
+    counts = np.ascontiguousarray(featureCounts, np.int32).reshape(-1)
+    ip = np.ascontiguousarray(imagePairs, np.int32).reshape(-1, 2)
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    off = _offsets(offsets)
+    B = off.size - 1
+    if ip.shape[0] != B:
+        raise ValueError("imagePairs needs one row per problem")
+    if pr.shape[0] < off[-1]:
+        raise ValueError("pairs is shorter than offsets[B]")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask).reshape(-1).astype(np.uint8, copy=False)
+        if mask.shape[0] < off[-1]:
+            raise ValueError("mask is shorter than offsets[B]")
+    nodes = int(np.maximum(counts, 0).astype(np.int64).sum())
+    maxObs = max(min(2 * max(int(off[-1]), 0), nodes), 0)   # the capacities that are always enough
+    maxTracks = maxObs // 2
+    toff, cam, feat = np.empty(maxTracks + 1, np.int32), np.empty(maxObs, np.int32), np.empty(maxObs, np.int32)
+    tof, dropped = np.empty(nodes, np.int32), np.zeros(3, np.int64)
+    T = getattr(N.lib(), export)(_nonnull(counts, 1).ctypes.data, counts.size, _nonnull(ip, (1, 2)).ctypes.data, B,
+                                 _nonnull(pr, (1, 2)).ctypes.data, off.ctypes.data,
+                                 None if mask is None else _nonnull(mask, 1).ctypes.data, int(minLength),
+                                 toff.ctypes.data, maxTracks, _nonnull(cam, 1).ctypes.data,
+                                 _nonnull(feat, 1).ctypes.data, maxObs, _nonnull(tof, 1).ctypes.data,
+                                 dropped.ctypes.data)
+    N.check(T >= 0, export)
+    n = int(toff[T])
+    return toff[:T + 1].copy(), cam[:n].copy(), feat[:n].copy(), tof, dropped
+
+
+def buildTracks(featureCounts, imagePairs, pairs, offsets, mask=None, minLength: int = 2):
+    """cvBuildTracks: the connected components of the match graph as tracks. featureCounts[nImages];
+    imagePairs[B, 2], pairs[n, 2] and offsets[B + 1] as matchFeaturesBatch returns them; mask[n]
+    (optional: matchAndFindModelBatch's inlier bytes). Components over MAX_TRACK_LEN nodes, with two
+    features of one image, or under minLength nodes are dropped.
+    -> (trackOffsets[T + 1], cameraIdx[nObs], featureIdx[nObs], trackOfFeature[sum(featureCounts)],
+    dropped[3] = oversize, conflicts, short). trackOffsets and cameraIdx are triangulateTracks' CSR."""
+    return _build_tracks("cvBuildTracks", featureCounts, imagePairs, pairs, offsets, mask, minLength)
+
+
+def trackObservations(pointsPerImage, cameraIdx, featureIdx) -> np.ndarray:
+    """The (nObs, 2) float64 observations of a track CSR: pointsPerImage[cameraIdx[k]][featureIdx[k]], so
+    that triangulateTracks(cameras, cameraIdx, trackObservations(...), trackOffsets) is one line away."""
+    cam = np.ascontiguousarray(cameraIdx, np.int64).reshape(-1)
+    feat = np.ascontiguousarray(featureIdx, np.int64).reshape(-1)
+    if cam.shape != feat.shape:
+        raise ValueError("cameraIdx and featureIdx differ in length")
+    obs = np.empty((cam.size, 2), np.float64)
+    for i in np.unique(cam):
+        sel = cam == i
+        obs[sel] = np.asarray(pointsPerImage[int(i)], np.float64).reshape(-1, 2)[feat[sel]]
+    return obs

@@ -599,4 +599,36 @@ void launch_tri_intersect(const double* d_rays, const int* d_offsets, int T, dou
 void launch_tri_stats(const double* d_cameras, const int* d_cameraIdx, const double* d_obs, const int* d_offsets,
                       int T, const double* d_points, double* d_cost, int* d_visible, hipStream_t s);
 
+// ---- track building: pairwise matches -> track CSR (tracks.hip)
+static const int kTrkShortMax = 32;   // components of at most this many nodes: one lane each; longer: one workgroup each
+// d_ctr: kTrkCtrs 64-bit words, zeroed by the caller before launch_build_tracks.
+//   [0] oversize, [1] conflicts, [2] short, [3] fail word (a bounded loop gave up),
+//   [4] candidates << 32 | their nodes, [5] tracks << 32 | observations, [6] long candidates queued
+static const int kTrkCtrs = 8;
+static const int kTrkScanItems = 2048;   // nodes per block of the two scans
+struct TrkDevice {
+    const int* edges;        // 2 nEdges node ids
+    long long nEdges;
+    const int* base;         // nImages + 1
+    int nImages, nNodes, minLength;
+    int* parent;             // nNodes each: parent, size, cursor, trk
+    int* size;
+    int* cursor;
+    int* trk;
+    uint8_t* touched;        // nNodes
+    unsigned long long* blockSums;   // ceil(nNodes / kTrkScanItems) + 1
+    int slotCap;             // min(2 nEdges, nNodes): the nodes a call can touch
+    int* slots;              // slotCap
+    int* candList;           // slotCap / 2 + 1
+    int* longList;           // slotCap / kTrkShortMax + 1
+    int* trackOffsets;       // slotCap / 2 + 1
+    int* cameraIdx;          // slotCap
+    int* featureIdx;         // slotCap
+    int* trackOfFeature;     // nNodes, or null
+    unsigned long long* ctr;
+};
+static const int kTrkLaunches = 13;
+// All launches of a call (kTrkLaunches of them, whatever the sizes); the results stay on the device.
+void launch_build_tracks(const TrkDevice& D, hipStream_t s);
+
 }  // namespace mcv

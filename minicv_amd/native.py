@@ -100,6 +100,8 @@ MATCH_BATCH_ROWS_HAMMING = 64   # query rows per workgroup of the batched matche
 MATCH_BATCH_ROWS_L2 = 128
 MAX_TRACK_LEN = 4096            # rays per track of the triangulation exports (MCV_MAX_TRACK_LEN)
 TRI_SHORT_MAX = 16              # longer tracks take the workgroup-per-track kernel (kernels.h kTriShortMax)
+TRK_SHORT_MAX = 32              # larger components are sorted by a workgroup each (kernels.h kTrkShortMax)
+TRK_LAUNCHES = 13               # kernel launches of a cvBuildTracks call (kernels.h kTrkLaunches)
 SIN_MIN_ANGLE = float.fromhex("0x1.1de58c9f7dc27p-5")   # hyp_rays.h kSinMinAngle
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
@@ -158,6 +160,7 @@ SIGNATURES = {
     "cvFindScaledPoseCosts": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "cvIntersectRays": (_I, [_P, _P, _I, _P, _P]),
     "cvTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "cvBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
     "cvFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "cvFindScaledPoseBatchCosts": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "mcvGetLastError": (C.c_char_p, []),
@@ -238,6 +241,8 @@ SIGNATURES = {
     "mcvTestTriangulateStats": (_I, [_P]),
     "mcvHostFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "mcvTestScaledBatchStats": (_I, [_P]),
+    "mcvHostBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "mcvTestTracksStats": (_I, [_P]),
     "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),

@@ -1,0 +1,265 @@
+"""Track building: an independent pure-Python reference (a dict-based union-find, sets and sorts; no
+union-by-smaller-id, no counting sort, nothing of tracks_ref.h's structure), the case list shared by
+tests/test_tracks.py and tests/test_gpu_tracks.py, and the ctypes call with sentinel-filled outputs.
+Every case's reference answer is computed once and never modified."""
+import functools
+from collections import defaultdict
+
+import numpy as np
+
+from minicv_amd import native as N
+
+MAX_LEN = 4096
+SENTINEL = -77
+RANDOM_SEED = 11   # the random scene: see random_scene()
+
+
+class Case:
+    """One call's inputs, from a list of problems (i, j, [(a, b), ...], mask bytes or None)."""
+
+    def __init__(self, counts, problems, minLength=2, use_mask=None):
+        self.counts = np.ascontiguousarray(counts, np.int32)
+        self.problems = [(int(i), int(j), [tuple(map(int, m)) for m in ms],
+                          None if mk is None else [int(b) for b in mk]) for i, j, ms, mk in problems]
+        self.minLength = minLength
+        self.use_mask = any(p[3] is not None for p in self.problems) if use_mask is None else use_mask
+        self.imagePairs = np.array([[p[0], p[1]] for p in self.problems], np.int32).reshape(-1, 2)
+        self.pairs = np.array([m for p in self.problems for m in p[2]], np.int32).reshape(-1, 2)
+        self.offsets = np.concatenate([[0], np.cumsum([len(p[2]) for p in self.problems])]).astype(np.int32)
+        self.mask = (np.array([b for p in self.problems for b in (p[3] if p[3] is not None else [1] * len(p[2]))],
+                              np.uint8) if self.use_mask else None)
+        self.nodes = int(self.counts.sum())
+
+    def permuted(self, seed):
+        """The same graph with the problems, and the matches of each problem with their mask bytes, reordered."""
+        rng = np.random.default_rng(seed)
+        probs = []
+        for q in rng.permutation(len(self.problems)):
+            i, j, ms, mk = self.problems[q]
+            o = rng.permutation(len(ms))
+            probs.append((i, j, [ms[k] for k in o], None if mk is None else [mk[k] for k in o]))
+        return Case(self.counts, probs, self.minLength, self.use_mask)
+
+
+class Result:
+    def __init__(self, T, trackOffsets, cameraIdx, featureIdx, trackOfFeature, dropped):
+        self.T, self.trackOffsets, self.cameraIdx, self.featureIdx = T, trackOffsets, cameraIdx, featureIdx
+        self.trackOfFeature, self.dropped = trackOfFeature, dropped
+
+
+def reference(case) -> Result:
+    """The definition, read off the issue: components of the kept edges over the touched nodes, each
+    dropped by the first rule that applies (oversize, conflict, short), the others ordered by their
+    smallest node, their nodes ascending."""
+    base = np.concatenate([[0], np.cumsum(case.counts.astype(np.int64))])
+    up = {}
+
+    def root(x):
+        path = []
+        while up.setdefault(x, x) != x:
+            path.append(x)
+            x = up[x]
+        for y in path:
+            up[y] = x
+        return x
+
+    for i, j, ms, mk in case.problems:
+        for k, (a, b) in enumerate(ms):
+            if case.use_mask and mk is not None and not mk[k]:
+                continue
+            ra, rb = root(int(base[i]) + a), root(int(base[j]) + b)
+            if ra != rb:
+                up[ra] = rb   # whichever: the order of the roots plays no part in the definition
+    comps = defaultdict(list)
+    for x in list(up):
+        comps[root(x)].append(x)
+    toff, cam, feat = [0], [], []
+    tof = np.full(case.nodes, -1, np.int32)
+    dropped = [0, 0, 0]
+    for nodes in sorted((sorted(c) for c in comps.values()), key=lambda c: c[0]):
+        images = [int(np.searchsorted(base, g, side="right")) - 1 for g in nodes]
+        if len(nodes) > MAX_LEN:
+            dropped[0] += 1
+        elif len(set(images)) < len(nodes):
+            dropped[1] += 1
+        elif len(nodes) < case.minLength:
+            dropped[2] += 1
+        else:
+            for g, i in zip(nodes, images):
+                tof[g] = len(toff) - 1
+                cam.append(i)
+                feat.append(g - int(base[i]))
+            toff.append(len(cam))
+    return Result(len(toff) - 1, np.array(toff, np.int32), np.array(cam, np.int32), np.array(feat, np.int32), tof,
+                  np.array(dropped, np.int64))
+
+
+# ---- the shared cases
+
+def path(L, order="ascending", minLength=2):
+    """One feature in each of L images, image k matched to image k + 1."""
+    ks = list(range(L - 1))
+    if order == "descending":
+        ks = ks[::-1]
+    elif order == "shuffled":
+        ks = [int(k) for k in np.random.default_rng(L).permutation(L - 1)]
+    return Case([1] * L, [(k, k + 1, [(0, 0)], None) for k in ks], minLength)
+
+
+def random_scene(seed=RANDOM_SEED):
+    """64 images of 500 features, 200 image pairs, matches from shared 3-D point ids (1500 points, each
+    image sees 500 of them in a shuffled feature order), 5 % of the matches wrong (a random feature of the
+    second image), 10 % masked out, minLength 3. Seed 11: the reference counts are pinned by
+    tests/test_tracks.py::test_random_scene_has_every_drop_class."""
+    rng = np.random.default_rng(seed)
+    nImg, nFeat, nPts, nPairs = 64, 500, 1500, 200
+    seen = [rng.permutation(nPts)[:nFeat] for _ in range(nImg)]   # seen[i][f] = the point of feature f
+    slot = []
+    for s in seen:
+        m = np.full(nPts, -1)
+        m[s] = np.arange(nFeat)
+        slot.append(m)
+    chosen = set()
+    while len(chosen) < nPairs:
+        i, j = (int(v) for v in rng.integers(0, nImg, 2))
+        if i != j:
+            chosen.add((min(i, j), max(i, j)))
+    probs = []
+    for i, j in sorted(chosen):
+        shared = np.nonzero((slot[i] >= 0) & (slot[j] >= 0))[0]
+        ms = []
+        for p in shared:
+            b = int(slot[j][p])
+            if rng.random() < 0.05:
+                b = int(rng.integers(0, nFeat))
+            ms.append((int(slot[i][p]), b))
+        probs.append((i, j, ms, [int(rng.random() >= 0.10) for _ in ms]))
+    return Case([nFeat] * nImg, probs, minLength=3)
+
+
+def _lengths_scene(minLength):
+    """Paths of 2, 3, 4, 5 and 6 images side by side: feature k of the first k + 2 images."""
+    probs = [(i, i + 1, [(k, k) for k in range(5) if i + 1 < k + 2], None) for i in range(5)]
+    return Case([5] * 6, probs, minLength)
+
+
+def _zigzag(n):
+    """Two images: A.f0 - B.f0 - A.f1 - B.f1 - ...: one component of 2 n nodes over 2 images."""
+    ms = [(k, k) for k in range(n)] + [(k + 1, k) for k in range(n - 1)]
+    return Case([n, n], [(0, 1, ms, None)])
+
+
+def _long_conflict():
+    """A path through 50 images (a long component, within nImages) with a second feature of image 20."""
+    probs = [(k, k + 1, [(0, 0)], None) for k in range(49)] + [(30, 20, [(0, 1)], None)]
+    return Case([2] * 50, probs)
+
+
+PATH_LENGTHS = list(range(2, 41)) + [63, 64, 65, 130, 600, 4096, 4097]
+
+CASES = {
+    "B0": lambda: Case([3, 4], []),
+    "no_images": lambda: Case([], []),
+    "empty_problems": lambda: Case([3, 3, 3], [(0, 1, [], None), (1, 2, [], None), (0, 2, [], None)]),
+    "empty_problems_around_one": lambda: Case([3, 0, 3], [(0, 1, [], None), (2, 0, [(1, 2)], None), (1, 1, [], None)]),
+    "all_masked": lambda: Case([3, 3], [(0, 1, [(0, 0), (1, 1)], [0, 0]), (1, 0, [(2, 2)], [0])]),
+    "one_edge": lambda: Case([2, 2], [(0, 1, [(1, 0)], None)]),
+    **{f"path_L{L}": (lambda L=L: path(L)) for L in PATH_LENGTHS},
+    **{f"path_L600_{o}": (lambda o=o: path(600, o)) for o in ("descending", "shuffled")},
+    "path_L4096_descending": lambda: path(4096, "descending"),
+    "star": lambda: Case([1] * 51, [(0, k, [(0, 0)], None) for k in range(1, 51)]),
+    "star_inward": lambda: Case([2] * 9, [(k, 8, [(1, 1)], None) for k in range(8)]),
+    "joined_by_the_last_edge": lambda: Case([1] * 8, [(0, 1, [(0, 0)], None), (1, 2, [(0, 0)], None),
+                                                     (4, 5, [(0, 0)], None), (5, 6, [(0, 0)], None),
+                                                     (7, 6, [(0, 0)], None), (6, 2, [(0, 0)], None)]),
+    "duplicate_edges": lambda: Case([2, 2, 2], [(0, 1, [(0, 1), (0, 1), (1, 0)], None), (1, 0, [(1, 0)], None),
+                                                (1, 2, [(1, 1), (1, 1)], None)]),
+    "same_image_and_self_loop": lambda: Case([5, 3], [(0, 0, [(1, 1), (2, 3)], None), (0, 1, [(4, 0)], None)]),
+    "self_loop_on_a_track": lambda: Case([2, 2], [(0, 0, [(0, 0)], None), (0, 1, [(0, 1)], None)]),
+    "conflict_through_a_third_image": lambda: Case([2, 1, 2, 1], [(0, 1, [(0, 0)], None), (1, 0, [(0, 1)], None),
+                                                                 (2, 3, [(1, 0)], None)]),
+    "zigzag_over_two_images": lambda: _zigzag(7),
+    "zigzag_long": lambda: _zigzag(40),
+    "long_conflict": _long_conflict,
+    **{f"min_length_{m}": (lambda m=m: _lengths_scene(m)) for m in (2, 3, 5)},
+    **{f"wave_edge_{n}": (lambda n=n: Case([n - 32, 32], [(0, 1, [(k, k) for k in range(min(n - 32, 32))], None)]))
+       for n in (63, 64, 65)},
+    "masked_half": lambda: Case([6, 6], [(0, 1, [(k, k) for k in range(6)], [1, 0, 1, 0, 2, 255])]),
+    "random_scene": random_scene,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def case(name) -> Case:
+    return CASES[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name) -> Result:
+    return reference(case(name))
+
+
+# ---- the native call
+
+def capacities(c):
+    """The capacities the header documents as always enough."""
+    maxObs = min(2 * int(c.offsets[-1]), c.nodes)
+    return maxObs // 2, maxObs
+
+
+def run(export, c, maxTracks=None, maxObs=None, want_tof=True, want_dropped=True, null=(), **override):
+    """-> (return value, Result over the sentinel-filled buffers trimmed to the result, untouched).
+    override replaces a scalar or an input array (counts, imagePairs, pairs, offsets, mask, nImages, B,
+    minLength); null names pointers to pass as NULL."""
+    mt, mo = capacities(c)
+    maxTracks = mt if maxTracks is None else maxTracks
+    maxObs = mo if maxObs is None else maxObs
+    a = {"counts": c.counts, "imagePairs": c.imagePairs, "pairs": c.pairs, "offsets": c.offsets, "mask": c.mask}
+    for k in list(override):
+        if k in a:
+            a[k] = override.pop(k)
+    a = {k: (None if v is None else np.ascontiguousarray(v, np.uint8 if k == "mask" else np.int32)) for k, v in a.items()}
+    nImages = override.pop("nImages", a["counts"].size)
+    B = override.pop("B", a["offsets"].size - 1)
+    minLength = override.pop("minLength", c.minLength)
+    assert not override, override
+    nodes = int(np.maximum(a["counts"], 0).astype(np.int64).sum())
+    if nodes > 1 << 26:
+        nodes = 0   # a call that is refused for its size: no buffer of that size is made for it
+    out = {"trackOffsets": np.full(max(maxTracks, 0) + 1, SENTINEL, np.int32),
+           "cameraIdx": np.full(max(maxObs, 0) + 1, SENTINEL, np.int32),
+           "featureIdx": np.full(max(maxObs, 0) + 1, SENTINEL, np.int32),
+           "trackOfFeature": np.full(nodes + 1, SENTINEL, np.int32),
+           "dropped": np.full(3, SENTINEL, np.int64)}
+
+    def ptr(name, arr, optional=False):
+        if name in null or arr is None or optional:
+            return None
+        return (arr if arr.size else np.zeros(2, arr.dtype)).ctypes.data
+    keep = [a[k] if a[k] is None or a[k].size else np.zeros(2, a[k].dtype) for k in a]   # alive during the call
+    T = getattr(N.lib(), export)(ptr("counts", keep[0]), nImages, ptr("imagePairs", keep[1]), B, ptr("pairs", keep[2]),
+                                 ptr("offsets", keep[3]), ptr("mask", keep[4]), minLength,
+                                 ptr("trackOffsets", out["trackOffsets"]), maxTracks,
+                                 ptr("cameraIdx", out["cameraIdx"]), ptr("featureIdx", out["featureIdx"]), maxObs,
+                                 ptr("trackOfFeature", out["trackOfFeature"], not want_tof),
+                                 ptr("dropped", out["dropped"], not want_dropped))
+    untouched = all(np.all(v == SENTINEL) for v in out.values())
+    if T < 0:
+        return T, None, untouched
+    n = int(out["trackOffsets"][T])
+    # nothing beyond the result is written
+    assert np.all(out["trackOffsets"][T + 1:] == SENTINEL) and np.all(out["cameraIdx"][n:] == SENTINEL)
+    assert np.all(out["featureIdx"][n:] == SENTINEL) and out["trackOfFeature"][nodes] == SENTINEL
+    return T, Result(T, out["trackOffsets"][:T + 1], out["cameraIdx"][:n], out["featureIdx"][:n],
+                     out["trackOfFeature"][:nodes], out["dropped"]), untouched
+
+
+def assert_same(got: Result, want: Result, what, tof=True, dropped=True):
+    assert got.T == want.T, (what, got.T, want.T)
+    for f in ("trackOffsets", "cameraIdx", "featureIdx") + (("trackOfFeature",) if tof else ()) + \
+            (("dropped",) if dropped else ()):
+        assert np.array_equal(getattr(got, f), getattr(want, f)), (what, f)
+    if not tof:
+        assert np.all(got.trackOfFeature == SENTINEL), what
+    if not dropped:
+        assert np.all(got.dropped == SENTINEL), what
