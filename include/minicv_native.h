@@ -579,6 +579,41 @@ MCV_API int cvBuildTracks(const int* featureCounts, int nImages, const int* imag
                           int* trackOffsets, int maxTracks, int* cameraIdx, int* featureIdx, int maxObs,
                           int* trackOfFeature, long long* dropped);
 
+/* Bundle adjustment — the refinement after cvTriangulateTracks: Levenberg-Marquardt over the cameras
+ * (rotation and location; the focal lengths stay) and the track points, minimising the reprojection
+ * error of the whole scene on the GPU. Inputs in the layouts the pipeline hands out: the
+ * mcvCamera array, cvBuildTracks' trackOffsets / cameraIdx CSR, the observations, the points of
+ * cvTriangulateTracks, fixedCameras[nCameras] (nullable: a non-zero byte keeps that camera constant).
+ *   residual: r = focal * pc.xy / pc.z - observation with pc = R (X - c), R = rows (right, up, forward);
+ *     project1's [-1, 1] window is not applied;
+ *   used set, fixed at the input parameters: an observation is used when its point is finite, pc.z > 0
+ *     and r is finite; a track with fewer than two used observations is excluded and its point comes
+ *     back bit for bit (the NaN points of cvTriangulateTracks included); a fixed camera and a camera
+ *     without a used observation come back bit for bit;
+ *   loss: squared error, or Huber with huberDelta > 0 (cost = the sum of rho over the used observations);
+ *   step: the reduced camera system by matrix-free preconditioned conjugate gradients, damping
+ *     d + lambda clamp(d, 1e-6, 1e32), lambda / 10 after an accepted and 10 lambda after a rejected trial.
+ * summary->termination: 1 accepted decrease <= functionTolerance x cost, 2 maxIterations reached,
+ * 3 cost == 0, 4 lambda over 1e12, 5 nothing to do. All arithmetic is fp64 in one defined order: the
+ * outputs equal mcvHostBundleAdjust's bit for bit.
+ * Returns the LM iterations run (trials, accepted or rejected; 0 is valid). Returns -1 with a message
+ * and writes no output on a null required pointer, a negative count, bad offsets, a track over
+ * MCV_MAX_TRACK_LEN, a camera index outside [0, nCameras), more than 2^26 observations, a non-finite
+ * camera, a configuration value that is not positive and finite where one is needed, or when no HIP
+ * device is visible. Every check runs on the host before the device is touched. */
+typedef struct { int maxIterations;      /* LM iterations, default 50 */
+                 int maxCgIterations;    /* per linear solve, default 64 */
+                 double cgTolerance;     /* stop when r.z <= tol^2 * r0.z0, default 0.1 */
+                 double initialLambda;   /* default 1e-3 */
+                 double functionTolerance; /* default 1e-6 */
+                 double huberDelta;      /* <= 0: plain squared error */ } mcvBaConfig;
+typedef struct { double initialCost, finalCost; int iterations, accepted, rejected, cgIterations,
+                 usedObservations, usedTracks, termination; } mcvBaSummary;
+MCV_API int cvBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras /*nullable*/,
+                           const int* cameraIdx, const mcvV2d* observations, const int* offsets, int T,
+                           const mcvV3d* points, const mcvBaConfig* cfg /*nullable = defaults*/,
+                           mcvCamera* outCameras, mcvV3d* outPoints, mcvBaSummary* summary /*nullable*/);
+
 /* Batched CameraPose.findScaled: P independent cvFindScaledPose problems in one call, each bit-identical
  * to its own single call; the launches, copies and the one synchronisation do not grow with P (DESIGN
  * §7j). The observation sets are a CSR: offsets[S + 1] ints, offsets[0] == 0, non-decreasing, over the
@@ -1044,6 +1079,30 @@ MCV_API int mcvHostBuildTracks(const int* featureCounts, int nImages, const int*
  * were sorted), of them the long ones (more than 32 nodes: one workgroup each), kept matches, 0}; all
  * are 0 for a call without a kept match, which launches nothing. Returns 0. */
 MCV_API int mcvTestTracksStats(long long* stats8);
+/* Host twin of cvBundleAdjust: the same arguments, checks, outputs, summary and return value, computed
+ * sequentially by the host-compiled kernel arithmetic (ba_terms.h) in the kernels' summation orders. No GPU. */
+MCV_API int mcvHostBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                                const int* cameraIdx, const mcvV2d* observations, const int* offsets, int T,
+                                const mcvV3d* points, const mcvBaConfig* cfg, mcvCamera* outCameras,
+                                mcvV3d* outPoints, mcvBaSummary* summary);
+/* The twin's linearisation at the given parameters: used[n], and per observation A[12] (2x6 row-major over
+ * (omega, dc); zero for a camera that stays constant), B[6] (2x3), r[2] (all three scaled by sqrt(w)) and
+ * w; zeros for an unused observation. Returns the number of used observations, -1 on failure. */
+MCV_API int mcvHostBaLinearize(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                               const int* cameraIdx, const mcvV2d* observations, const int* offsets, int T,
+                               const mcvV3d* points, const mcvBaConfig* cfg, uint8_t* used, double* A, double* B,
+                               double* r, double* w);
+/* The twin's first step at damping lambda: dCameras[6 nCameras] (omega, dc; zero for a constant camera)
+ * and dPoints[3 T] (zero for an excluded track). Returns the PCG iterations, -1 on failure (a failed solve
+ * included). */
+MCV_API int mcvHostBaStep(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                          const int* cameraIdx, const mcvV2d* observations, const int* offsets, int T,
+                          const mcvV3d* points, const mcvBaConfig* cfg, double lambda, double* dCameras,
+                          double* dPoints);
+/* Counters of the calling thread's last cvBundleAdjust call that reached the device: stats8 = {kernel
+ * launches, stream synchronisations, host<->device copies, memsets, linearisations, trials (LM
+ * iterations), chunks of 8 PCG iterations, segments of the camera lists}. Returns 0. */
+MCV_API int mcvTestBundleAdjustStats(long long* stats8);
 
 #ifdef __cplusplus
 }

@@ -345,3 +345,38 @@ def trackObservations(pointsPerImage, cameraIdx, featureIdx) -> np.ndarray:
         sel = cam == i
         obs[sel] = np.asarray(pointsPerImage[int(i)], np.float64).reshape(-1, 2)[feat[sel]]
     return obs
+
+
+def _bundle_adjust(export: str, cameras, cameraIdx, obs, offsets, points, fixed=None, cfg=None):
+    cams = cameras_array(cameras)
+    idx = np.ascontiguousarray(cameraIdx, np.int32).reshape(-1)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+    off = _offsets(offsets)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    T = off.size - 1
+    if idx.shape[0] != obs.shape[0]:
+        raise ValueError("cameraIdx and obs differ in length")
+    if pts.shape[0] != T:
+        raise ValueError("points needs one row per track")
+    if fixed is not None:
+        fixed = (np.asarray(fixed).reshape(-1) != 0).astype(np.uint8)
+        if fixed.shape[0] != cams.shape[0]:
+            raise ValueError("fixed needs one entry per camera")
+    outC, outP, sm = np.empty_like(cams), np.empty_like(pts), N.BaSummary()
+    k = getattr(N.lib(), export)(_nonnull(cams, (1, 14)).ctypes.data, cams.shape[0],
+                                 None if fixed is None else _nonnull(fixed, 1).ctypes.data,
+                                 _nonnull(idx, 1).ctypes.data, _nonnull(obs, (1, 2)).ctypes.data, off.ctypes.data, T,
+                                 _nonnull(pts, (1, 3)).ctypes.data, None if cfg is None else C.addressof(cfg),
+                                 _nonnull(outC, (1, 14)).ctypes.data, _nonnull(outP, (1, 3)).ctypes.data,
+                                 C.addressof(sm))
+    N.check(k >= 0, export)
+    return outC, outP, sm.as_dict()
+
+
+def bundleAdjust(cameras, cameraIdx, obs, offsets, points, fixed=None, cfg=None):
+    """cvBundleAdjust: Levenberg-Marquardt over the cameras (rotation and location) and the track points.
+    cameras: Camera records or (n, 14) rows; cameraIdx[n], obs[n, 2], offsets[T + 1] (buildTracks' CSR and
+    trackObservations' rows); points[T, 3] (triangulateTracks' points, NaN rows included); fixed[nCameras]
+    (optional: true keeps that camera constant); cfg: a native.BaConfig (None = the library's defaults).
+    -> (cameras[n, 14], points[T, 3], summary dict of mcvBaSummary's fields)."""
+    return _bundle_adjust("cvBundleAdjust", cameras, cameraIdx, obs, offsets, points, fixed, cfg)

@@ -631,4 +631,48 @@ static const int kTrkLaunches = 13;
 // All launches of a call (kTrkLaunches of them, whatever the sizes); the results stay on the device.
 void launch_build_tracks(const TrkDevice& D, hipStream_t s);
 
+// ---- bundle adjustment (bundle_adjust.hip)
+// The record of one PCG solve, on the device: read back once per chunk of kBaCgChunk iterations.
+struct BaCgState {
+    double rz, rz0;
+    int iter, done, failed, pad;
+};
+// Cost and flag of one evaluation of the parameters, read back once per trial.
+struct BaCostRecord {
+    double cost;
+    int badz, pad;
+};
+// d_ctr: [0] long tracks queued, [1] used observations, [2] used tracks, [3] a factorisation of the
+// current solve failed, [4] a used observation has pc.z <= 0 in the cost being evaluated
+static const int kBaCtrs = 8;
+struct BaDevice {
+    int nCameras, T, n, nSeg;
+    const int *offsets, *cameraIdx, *obsTrack, *camObs, *segCam, *segStart, *segEnd, *camSegPtr;
+    const double* obs;          // 2 n
+    const uint8_t* fixed;       // nCameras
+    double *cams, *pts;         // the current parameters: 14 nCameras, 3 T
+    double *cams2, *pts2;       // the trial copy
+    uint8_t *used, *trackUsed, *active;   // n, T, nCameras
+    double* E;                  // kBaEntry n: A, B, r of every used observation
+    double *U, *g, *L, *b;      // per camera: 21, 6, 21, 6
+    double *x, *r, *z, *p, *q, *pq;   // per camera: 6 each, pq 1
+    double *V, *h, *Vinv, *t, *y;     // per point: 6, 3, 6, 3, 3
+    double* part;               // 27 per segment: the segments' partial sums of the pass in flight
+    int* longList;              // T
+    unsigned int* ctr;
+    BaCgState* cg;
+    BaCostRecord* rec;
+    double lambda, delta, tol2;
+    int maxCg;
+};
+// launches of each stage, whatever the sizes
+static const int kBaLaunchesSetup = 3, kBaLaunchesCost = 2, kBaLaunchesLinearize = 4, kBaLaunchesSystem = 4,
+                 kBaLaunchesCgIter = 5, kBaLaunchesTrial = 3 + kBaLaunchesCost;
+void launch_ba_setup(const BaDevice& D, hipStream_t s);       // the used set, the long-track queue, the active cameras
+void launch_ba_cost(const BaDevice& D, const double* d_cams, const double* d_pts, hipStream_t s);   // -> D.rec
+void launch_ba_linearize(const BaDevice& D, hipStream_t s);   // E, V, h, U, g at D.cams / D.pts
+void launch_ba_system(const BaDevice& D, hipStream_t s);      // Vinv, t, L, b at D.lambda and the PCG start
+void launch_ba_cg_iteration(const BaDevice& D, hipStream_t s);
+void launch_ba_trial(const BaDevice& D, hipStream_t s);       // cams2 / pts2 from x, and their cost -> D.rec
+
 }  // namespace mcv

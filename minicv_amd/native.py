@@ -38,6 +38,31 @@ class Ray3d(C.Structure):
     _fields_ = [("origin", V3d), ("direction", V3d)]
 
 
+class BaConfig(C.Structure):
+    """mcvBaConfig; BaConfig.default() holds the library's defaults."""
+    _fields_ = [("maxIterations", C.c_int), ("maxCgIterations", C.c_int), ("cgTolerance", C.c_double),
+                ("initialLambda", C.c_double), ("functionTolerance", C.c_double), ("huberDelta", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw) -> "BaConfig":
+        c = cls(50, 64, 0.1, 1e-3, 1e-6, 0.0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"BaConfig has no field {k}")
+            setattr(c, k, v)
+        return c
+
+
+class BaSummary(C.Structure):
+    """mcvBaSummary."""
+    _fields_ = [("initialCost", C.c_double), ("finalCost", C.c_double), ("iterations", C.c_int),
+                ("accepted", C.c_int), ("rejected", C.c_int), ("cgIterations", C.c_int),
+                ("usedObservations", C.c_int), ("usedTracks", C.c_int), ("termination", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RecoverPoseConfig(C.Structure):
     """MiniCVNative.cpp:39-46 / OpenCV.fs:16-36."""
     _fields_ = [("FocalLength", C.c_double), ("PrincipalPoint", V2d), ("Probability", C.c_double),
@@ -102,6 +127,12 @@ MAX_TRACK_LEN = 4096            # rays per track of the triangulation exports (M
 TRI_SHORT_MAX = 16              # longer tracks take the workgroup-per-track kernel (kernels.h kTriShortMax)
 TRK_SHORT_MAX = 32              # larger components are sorted by a workgroup each (kernels.h kTrkShortMax)
 TRK_LAUNCHES = 13               # kernel launches of a cvBuildTracks call (kernels.h kTrkLaunches)
+BA_SEG = 1024                   # entries per segment of a camera's list in cvBundleAdjust (ba_terms.h kBaSeg)
+BA_SHORT_MAX = 64               # longer tracks take the wave-per-track kernels (ba_terms.h kBaShortMax)
+BA_CG_CHUNK = 8                 # PCG iterations between two reads of the solve's record (ba_terms.h kBaCgChunk)
+# kernel launches of cvBundleAdjust's stages (kernels.h kBaLaunches*): the call's total is
+# SETUP + COST + LINEARIZE x linearisations + (SYSTEM + TRIAL) x trials + CG_ITER x BA_CG_CHUNK x chunks
+BA_LAUNCHES = {"setup": 3, "cost": 2, "linearize": 4, "system": 4, "cg_iter": 5, "trial": 5}
 SIN_MIN_ANGLE = float.fromhex("0x1.1de58c9f7dc27p-5")   # hyp_rays.h kSinMinAngle
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
@@ -161,6 +192,7 @@ SIGNATURES = {
     "cvIntersectRays": (_I, [_P, _P, _I, _P, _P]),
     "cvTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "cvBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "cvFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "cvFindScaledPoseBatchCosts": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "mcvGetLastError": (C.c_char_p, []),
@@ -243,6 +275,10 @@ SIGNATURES = {
     "mcvTestScaledBatchStats": (_I, [_P]),
     "mcvHostBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
     "mcvTestTracksStats": (_I, [_P]),
+    "mcvHostBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "mcvHostBaLinearize": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),
+    "mcvTestBundleAdjustStats": (_I, [_P]),
     "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),
