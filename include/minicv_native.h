@@ -949,6 +949,30 @@ MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* cand8, const 
  * left to fp64 (all of them with the prefilter off); lanes without a model are not counted. A staged evaluate
  * counts only after the first call of this hook (the counters cost atomics). Not thread-safe: tests only. */
 MCV_API int mcvTestHCellPre(int mode, long long* stats);
+/* The homography generate's certified one-row pass 2. Where an evaluate hands out only the chunk's key (op-by-op
+ * error, eigen solver), pass 2 of the split generate replays one row of V from the rotation log in reverse, bounds
+ * its distance to the row of the exact replay, and keeps the fp32 model only where that bound proves it to be the
+ * exact path's, bit for bit; every other lane runs the exact pass 2. Models, statuses, keys and finalize results
+ * are the same either way. mode 0: automatic (chunks of at least 2^14 hypotheses), 1: wherever it applies, 2:
+ * never, 3: as 1 with the bound multiplied by 2^40, so that no lane is decided and every one takes the fallback;
+ * any other mode leaves the setting. Returns the previous mode, -1 on error. stats (may be NULL; 2 values), for the
+ * calling thread's last homography generate (read after its stream was synchronised): [0] lanes decided, [1] lanes
+ * left to the exact pass or the log-overflow kernel; both 0 where the pass did not run. Not thread-safe: tests only. */
+MCV_API int mcvTestHGenRow(int mode, long long* stats);
+/* Device self-test: the split generate alone on host float4 points, hypotheses [hypBegin, hypBegin + hypCount).
+ * table (may be NULL): a sample table, 4 indices per hypothesis from hypothesis 0 (no subset check), instead of
+ * the seeded stream. row 0: the exact pass 2; 1: the certified one-row pass; 2: that with the bound times 2^40.
+ * models8[8 hypCount] and counts[hypCount] receive the fp32 models and the statuses as the generate leaves them;
+ * stats as for mcvTestHGenRow. Honours mcvTestEigLogCap. Returns 1, 0 on failure. */
+MCV_API int mcvTestHGenerate(const float* pts4, int N, uint64_t seed, const int* table, int64_t hypBegin, int hypCount,
+                             int row, float* models8, int* counts, long long* stats);
+/* Host twin of the one-row pass beside the exact solve, arguments as above (errHuge: the bound times 2^40). Per
+ * hypothesis: modelsFwd8 / statusFwd = the exact path's fp32 model and status; decided = 1 where the one-row pass
+ * certifies its model, then in modelsRow8; err = its bound on |y - v|_inf (the reverse row against the forward
+ * replay's row of the same log) and dev = that distance as measured. Returns 1, 0 on failure. */
+MCV_API int mcvHostHGenRow(const float* pts4, int N, uint64_t seed, const int* table, int64_t hypBegin, int hypCount,
+                           int errHuge, float* modelsRow8, float* modelsFwd8, int* statusFwd, int* decided,
+                           double* err, double* dev);
 /* The prefilter's verdict on caller-supplied data, arguments as for mcvTestHCellBound (B is not read).
  * verdicts[k * cells + c] for model k and cell c: 0 not certified, 1 certified, 2 undecided; an empty cell is
  * undecided or not certified, never certified. Returns 1, 0 on failure. */

@@ -349,6 +349,100 @@ MCV_HD bool h_model_f(const double* H, HModelF* mf) {
     return ok;
 }
 
+// The certified twin of h_from_eig + h_model_f (the split generate's one-row pass, DESIGN.md §7 "Certified
+// one-row replay", lemma 2). Input: y with |y[i] - H0[i]| <= err, H0 the eigenvector row the exact path holds. It
+// runs h_from_eig's operations on y in h_from_eig's order and carries, for every intermediate value, a
+// bound b on the distance between the value computed here (v) and the value the exact path computes at
+// the same place. One rounded operation z = fl(x o y), with D a bound on the distance of the two exact
+// results: |z - z'| <= D (1 + u) + 2u |z'| (1 + 2u) + 2^-1073 (u = 2^-53; no overflow, checked: `ok`
+// needs |v| + b < 2^1000 everywhere). The bound arithmetic rounds upward: 4u |v| stands for the 2u term
+// and the sum is multiplied by 1 + 2^-50, which covers its own (at most five) roundings; 2^-1060 covers
+// the underflow terms.
+struct HEb {
+    double v, b;
+};
+static constexpr double kEbUp = 1.0 + 0x1p-50, kEbDn = 1.0 - 0x1p-50, kEb4u = 0x1p-51, kEbTiny = 0x1p-1060;
+MCV_HD HEb eb_close(double v, double d, bool& ok) {
+    HEb z{v, (d + kEb4u * __builtin_fabs(v)) * kEbUp + kEbTiny};
+    ok = ok && (__builtin_fabs(z.v) + z.b < 0x1p1000);   // false for a NaN too
+    return z;
+}
+// a: the same number on both paths (a normalisation constant)
+MCV_HD HEb eb_mulc(double a, const HEb& x, bool& ok) { return eb_close(a * x.v, __builtin_fabs(a) * x.b, ok); }
+MCV_HD HEb eb_add(const HEb& x, const HEb& y, bool& ok) { return eb_close(x.v + y.v, x.b + y.b, ok); }
+MCV_HD HEb eb_mul(const HEb& x, const HEb& y, bool& ok) {
+    return eb_close(x.v * y.v, (__builtin_fabs(x.v) * y.b + __builtin_fabs(y.v) * x.b) + x.b * y.b, ok);
+}
+// 1 / x: both paths' x lie in |x.v| +- x.b, which must keep away from 0
+MCV_HD HEb eb_rcp(const HEb& x, bool& ok) {
+    const double m = (__builtin_fabs(x.v) - x.b) * kEbDn;
+    ok = ok && (m > 0);
+    return eb_close(1. / x.v, x.b / ((__builtin_fabs(x.v) * m) * kEbDn), ok);
+}
+// C = A B in mat3_mul's order; A (left = true) or B is the exact constant matrix
+template <bool LEFT>
+MCV_HD void eb_mat3_mul(const double* K, const HEb* X, HEb* C, bool& ok) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 3; ++i)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 3; ++j) {
+            HEb p[3];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 3; ++k)
+                p[k] = LEFT ? eb_mulc(K[3 * i + k], X[3 * k + j], ok) : eb_mulc(K[3 * k + j], X[3 * i + k], ok);
+            C[3 * i + j] = eb_add(eb_add(p[0], p[1], ok), p[2], ok);
+        }
+}
+
+// True = decided: *mf is, bit for bit, the model h_from_eig + h_model_f give on the exact H0, and both
+// return true there (status 1): every H[i] of the exact path lies in a finite enclosure, and each of the
+// eight enclosures lies strictly inside the set of doubles that round to one float, a normal one with
+// 2^-100 <= |f| <= 2^100. False = undecided (anything else: a NaN, err not below 2^-20, H22 not
+// separated from 0, an enclosure that reaches a rounding boundary, a model the exact path may reject):
+// the caller runs the exact path.
+MCV_HD bool h_model_f_cert(const double (&y)[9], double err, const double (&nm)[8], HModelF* mf) {
+    const double cmx = nm[0], cmy = nm[1], smx = nm[2], smy = nm[3], cMx = nm[4], cMy = nm[5], sMx = nm[6],
+                 sMy = nm[7];
+    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    bool ok = err < 0x1p-20;
+    HEb H0[9], T[9], R[9];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 9; ++i) {
+        H0[i] = HEb{y[i], err};
+        ok = ok && (__builtin_fabs(y[i]) < 0x1p100);
+    }
+    eb_mat3_mul<true>(invHnorm, H0, T, ok);
+    eb_mat3_mul<false>(Hnorm2, T, R, ok);
+    const HEb s = eb_rcp(R[8], ok);
+    (void)eb_mul(R[8], s, ok);   // H[8]: finite on the exact path
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 8; ++i) {
+        const HEb h = eb_mul(R[i], s, ok);
+        const float f = (float)h.v;
+        const uint32_t fb = __builtin_bit_cast(uint32_t, f);
+        const double af = __builtin_fabs((double)f);
+        // the neighbours of f in magnitude and the two midpoints (exact: 25 significant bits)
+        const double dn = __builtin_fabs((double)__builtin_bit_cast(float, fb - 1u));
+        const double up = __builtin_fabs((double)__builtin_bit_cast(float, fb + 1u));
+        const double lo = 0.5 * (af + dn), hi = 0.5 * (af + up), av = __builtin_fabs(h.v);
+        // av - lo and hi - av are exact (Sterbenz: lo <= av <= hi, hi <= 2 lo)
+        ok = ok && (af >= 0x1p-100 && af <= 0x1p100) && (av - lo > h.b) && (hi - av > h.b);
+        mf->h[i] = f;
+    }
+    return ok;
+}
+
 // One hypothesis: returns 1 (model written), kStatusNoModel, or kStatusNoSample.
 // pts4: N packed {x, y, x', y'}. idx_out (optional) receives the accepted sample.
 template <class WS>

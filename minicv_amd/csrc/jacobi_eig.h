@@ -530,4 +530,61 @@ MCV_HD void eig9_replay(WS& v, const EigRot* log, int64_t logStride, int nrot) {
     eig9_replay_cols<9, 4>(v, 0, log, logStride, nrot);
 }
 
+// One row of V from the log, applied last to first: y = e_r, then for t = nrot .. 1 the components
+// (k_t, l_t) of y rotate as y_k' = y_k c + y_l s, y_l' = -y_k s + y_l c (y^T <- y^T G_t, G_t the matrix
+// eig9_replay_cols multiplies V by from the left: in real arithmetic y = e_r^T G_n ... G_1, row r of V).
+// 6 flops and two 8-byte slots per rotation against the forward replay's 54 and 18. The two products
+// round differently, so y only nominates: *err bounds |y - v|_inf, v the row the forward replay computes
+// from the same log ("Certified one-row replay", lemma 1; u = 2^-53):
+//   q_t = max(1, fl-chain of (c^2 + s^2 + 1) / 2 * (1 + 2^-48))   >= sqrt(c^2 + s^2) (1 + 5u), stored c, s
+//   E  <- fl(fl(E q_t) + 3u S_t),  S_t = |fl(y_k c)| + |fl(y_l s)| + |fl(y_k s)| + |fl(y_l c)|   (reverse side)
+//   P  <- fl(P q_t);  F = 3u n P                                                             (forward side)
+//   err = 2 (E + F) (1 + 2^-48)
+// The inflation of q_t pays for every rounding of the bound's own arithmetic (the lemma counts them).
+// A NaN anywhere makes err NaN, which no caller accepts. `ntop` >= nrot: the rows are visited from
+// ntop - 1 down and those from nrot up skipped, so the lanes of a wave that share ntop read the same
+// log row at every step (a contiguous kilobyte) whatever their own counts. D loads in flight.
+static constexpr double kEigRowQ = 0.5 * (1.0 + 0x1p-48), kEigRow3u = 3 * 0x1p-53;
+template <int D, class WS>
+MCV_HD void eig9_replay_row_rev(const EigRot* log, int64_t logStride, int nrot, int ntop, int r, WS& y, double* err) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 9; ++i) y[i] = (i == r) ? 1.0 : 0.0;
+    double E = 0.0, P = 1.0;
+    EigRot q[D];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int u = 0; u < D; ++u) {
+        const int t = ntop - 1 - u;
+        q[u] = (t >= 0 && t < nrot) ? log[(int64_t)t * logStride] : EigRot{0.0, 0.0};
+    }
+    for (int t0 = ntop - 1; t0 >= 0; t0 -= D) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int u = 0; u < D; ++u) {
+            const EigRot e = q[u];
+            const int t = t0 - u, tn = t - D;
+            if (tn >= 0 && tn < nrot) q[u] = log[(int64_t)tn * logStride];
+            if (t >= 0 && t < nrot) {
+                int k, l;
+                const double c = eig_rot_c(e.c, k, l), s = e.s;
+                const double a = y[k], b = y[l];
+                const double p1 = a * c, p2 = b * s, p3 = a * s, p4 = b * c;
+                y[k] = p1 + p2;
+                y[l] = p4 - p3;
+                const double S = ((__builtin_fabs(p1) + __builtin_fabs(p2)) + __builtin_fabs(p3)) + __builtin_fabs(p4);
+                double qt = ((c * c + s * s) + 1.0) * kEigRowQ;
+                qt = qt < 1.0 ? 1.0 : qt;
+                E = E * qt + S * kEigRow3u;
+                P = P * qt;
+            }
+        }
+    }
+    const double F = ((double)nrot * P) * kEigRow3u;
+    *err = ((E + F) * 2.0) * (1.0 + 0x1p-48);
+}
+
 }  // namespace mcv

@@ -28,8 +28,19 @@ void launch_h_mask_one(const float* d_pts4, int N, const HOneOut* d_one, float t
 // d_scratch (h_gen_scratch_bytes(hypCount) bytes): the split eigen generate's rotation log, samples
 // and overflow list (ransac_h_gen.hip); nullptr runs the one-pass solve.
 void launch_h_generate(const float* d_pts4, int N, Sampler smp, int64_t hypBegin, int hypCount, void* d_models,
-                       double* d_h64, int* d_counts, hipStream_t s, bool fast, void* d_scratch = nullptr);
+                       double* d_h64, int* d_counts, hipStream_t s, bool fast, void* d_scratch = nullptr,
+                       bool certifiedRow = false);
 size_t h_gen_scratch_bytes(int hypCount);
+// certifiedRow (split generate only): pass 2 as the certified one-row replay (mcv_h_gen_r) with the exact
+// pass 2 on the lanes it leaves undecided. Same fp32 models and statuses, bit for bit; d_h64 is written only
+// for the undecided and the overflow lanes. While the scratch still holds the call's log (a call of one piece:
+// h_gen_row_log_kept, and no generate since), launch_h_gen_v_one replays hypothesis `local` of the call
+// exactly: its fp32 model and d_h64[9 local ..] as the switch-off generate writes them.
+bool h_gen_row_log_kept(int hypCount);
+void launch_h_gen_v_one(const float* d_pts4, int hypCount, int local, void* d_scratch, void* d_models, double* d_h64,
+                        hipStream_t s);
+const int* h_gen_row_stats(const void* d_scratch, int hypCount);   // device: {decided, undecided} lanes of the call
+void h_gen_row_err_scale(bool huge);   // mcvTestHGenRow: err times 2^40 (no lane decided)
 void launch_h_verify(const float* d_pts4, int N, const void* d_models, int* d_counts, int hypCount, float thr2,
                      bool fused, const float* d_bbox, hipStream_t s);
 void launch_bbox(const float* d_pts4, int N, float* d_bbox, hipStream_t s);

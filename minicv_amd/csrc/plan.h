@@ -68,6 +68,10 @@ struct Plan {
     DevBuf<double> h64;       // homography: each hypothesis' fp64 model (finalize takes the winner's);
                               // affine / similarity: the generate's fp64 models (6 per hypothesis)
     DevBuf<uint8_t> hgen;     // homography: the split eigen generate's scratch (rotation log of one piece)
+    bool hrowLast = false;    // the last homography generate ran the certified one-row pass 2: h64 holds only the
+                              // undecided lanes' models
+    bool hrowLogKept = false; // ... and hgen still holds that chunk's log, samples and meta words (one piece)
+    int hrowCount = 0;        // the last homography generate's hypotheses (the layout of hgen)
     DevBuf<float> pairs;      // paired point layout of the packed sweeps (homography 8, PnP 12 floats per 2)
     DevBuf<char> hrec;        // homography matrix-core sweep: the bf16 point records (h_rec_bytes(N): 24 B per point)
     DevBuf<unsigned long long> hmfmaStats;   // its undecided rows / overflowed / out-of-domain waves of the last sweep (kHMfmaStats)
@@ -213,7 +217,7 @@ void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, 
 
 // homography family (ransac_h_*.hip / ransac_h_host.cpp)
 void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
+                      int* d_counts, hipStream_t s, bool certifiedRow = false);
 // keyOnly: nobody reads d_counts beyond the best-key reduction, so the sweep may run in self-pruning stages
 void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                       int* d_counts, bool keyOnly, hipStream_t s);

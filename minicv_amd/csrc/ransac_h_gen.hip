@@ -4,6 +4,8 @@
 //
 //   mcv_h_generate          the one-pass solve (and the MCV_FLAG_FAST_MINIMAL elimination)
 //   mcv_h_gen_aw / _v / _ovf  the default: the eigen-solve split in two passes over a rotation log
+//   mcv_h_gen_r             the certified one-row pass 2 (key-only evaluates): the reverse replay of one row
+//                           nominates the fp32 model, mcv_h_gen_v_list solves the lanes it cannot certify
 //   mcv_h_one               one hypothesis in full (the finalize path's winner re-solve)
 //
 // Built with -ffp-contract=off (see hyp_homography.h): every model is the host twin's, bit for bit.
@@ -121,19 +123,15 @@ __global__ __launch_bounds__(L) void mcv_h_gen_aw(const float* __restrict__ pts4
     meta[j] = nrot | (r << 16);
 }
 
-// Pass 2: G lanes per hypothesis (9 / G columns of V each; G = 1 or 3), Q hypotheses per block.
-template <int G, int Q, int D, bool TR = false>
-__global__ __launch_bounds__(G * Q) void mcv_h_gen_v(const float* __restrict__ pts4, int count, int base,
-                                                     const int4* __restrict__ sidx, const int* __restrict__ meta,
-                                                     const EigRot* __restrict__ log, int logStride,
-                                                     HModelF* __restrict__ models, double* __restrict__ h64,
-                                                     int* __restrict__ counts) {
+// Pass 2 for piece lane j with meta word m, run by the G lanes of its group (every lane of the block calls it:
+// it holds a barrier): V from the log, row r -> the models of hypothesis base + j. CNT = false: no status written
+// (finalize's winner: the counts buffer holds the sweep's counts by then).
+template <int G, int D, bool TR, bool CNT>
+__device__ __forceinline__ void h_gen_v_lane(const float* __restrict__ pts4, int j, int m, int g, EigWsLane v, int base,
+                                             const int4* __restrict__ sidx, const EigRot* __restrict__ log,
+                                             int logStride, HModelF* __restrict__ models, double* __restrict__ h64,
+                                             int* __restrict__ counts) {
     constexpr int C = 9 / G;
-    const int h = threadIdx.x / G, g = threadIdx.x - h * G;   // hypothesis of the block, column group
-    const int j = blockIdx.x * Q + h;
-    __shared__ double lds[kEigVWs * Q];
-    EigWsLane v{lds + h * kEigVWs};
-    const int m = j < count ? meta[j] : kMetaDone;
     if (m >= 0) {
 #pragma unroll
         for (int i = 0; i < 9; ++i)
@@ -162,10 +160,106 @@ __global__ __launch_bounds__(G * Q) void mcv_h_gen_v(const float* __restrict__ p
     if (h_from_eig(H0, nm, H) && h_model_f(H, &mf)) {
         models[i] = mf;
         for (int k = 0; k < 9; ++k) h64[9 * (int64_t)i + k] = H[k];
-        counts[i] = 0;
+        if constexpr (CNT) counts[i] = 0;
     } else {
-        h_store_none(models, counts, i, kStatusNoModel);
+        if constexpr (CNT) h_store_none(models, counts, i, kStatusNoModel);
     }
+}
+
+// Pass 2: G lanes per hypothesis (9 / G columns of V each; G = 1 or 3), Q hypotheses per block.
+template <int G, int Q, int D, bool TR = false>
+__global__ __launch_bounds__(G * Q) void mcv_h_gen_v(const float* __restrict__ pts4, int count, int base,
+                                                     const int4* __restrict__ sidx, const int* __restrict__ meta,
+                                                     const EigRot* __restrict__ log, int logStride,
+                                                     HModelF* __restrict__ models, double* __restrict__ h64,
+                                                     int* __restrict__ counts) {
+    const int h = threadIdx.x / G, g = threadIdx.x - h * G;   // hypothesis of the block, column group
+    const int j = blockIdx.x * Q + h;
+    __shared__ double lds[kEigVWs * Q];
+    EigWsLane v{lds + h * kEigVWs};
+    const int m = j < count ? meta[j] : kMetaDone;
+    h_gen_v_lane<G, D, TR, true>(pts4, j, m, g, v, base, sidx, log, logStride, models, h64, counts);
+}
+
+// Pass 2 for the one-row pass's undecided lanes: a fixed grid strides over list[1 .. list[0]], the piece-local
+// lanes to solve (list == nullptr: the one lane `single`, finalize's winner, with CNT = false).
+template <int G, int Q, int D, bool CNT, bool TR = false>
+__global__ __launch_bounds__(G * Q) void mcv_h_gen_v_list(const float* __restrict__ pts4, int count, int base,
+                                                          const int4* __restrict__ sidx, const int* __restrict__ meta,
+                                                          const EigRot* __restrict__ log, int logStride,
+                                                          HModelF* __restrict__ models, double* __restrict__ h64,
+                                                          int* __restrict__ counts, const int* __restrict__ list,
+                                                          int single) {
+    const int h = threadIdx.x / G, g = threadIdx.x - h * G;
+    __shared__ double lds[kEigVWs * Q];
+    EigWsLane v{lds + h * kEigVWs};
+    const int n = list ? min(list[0], count) : 1;
+    for (int e0 = blockIdx.x * Q; e0 < n; e0 += gridDim.x * Q) {   // the same trips for every lane of the block
+        const int e = e0 + h;
+        const int j = e < n ? (list ? list[1 + e] : single) : -1;
+        const int m = (j >= 0 && j < count) ? meta[j] : kMetaDone;
+        h_gen_v_lane<G, D, TR, CNT>(pts4, j, m, g, v, base, sidx, log, logStride, models, h64, counts);
+        if constexpr (G > 1) __syncthreads();   // the slices are rewritten by the next trip
+    }
+}
+
+// The certified one-row pass 2 (jacobi_eig.h eig9_replay_row_rev, hyp_homography.h h_model_f_cert): lane per
+// hypothesis, one wave per block, y in a 9-double LDS slice (odd stride). The wave walks the log rows from
+// its largest rotation count down, so every step reads one contiguous row. A decided lane writes its fp32
+// model and status 0 (no h64: finalize replays the winner); an undecided one appends its piece-local index
+// to und[1 ..] (und[0] = the length; one atomic per wave) for mcv_h_gen_v_list. Lanes pass 1 finished
+// (meta < 0: status written, or handed to mcv_h_gen_ovf) are skipped. stats[0 / 1] += decided / undecided
+// lanes, the overflow lanes among the latter. errScale multiplies err (mcvTestHGenRow: 2^40 leaves no lane
+// decided).
+static constexpr int kHGenRD = 8;
+__global__ __launch_bounds__(64) void mcv_h_gen_r(const float* __restrict__ pts4, int count, int base,
+                                                  const int4* __restrict__ sidx, const int* __restrict__ meta,
+                                                  const EigRot* __restrict__ log, int logStride,
+                                                  HModelF* __restrict__ models, int* __restrict__ counts,
+                                                  int* __restrict__ und, int* __restrict__ stats, double errScale) {
+    __shared__ double lds[9 * 64];
+    const int lane = threadIdx.x;
+    const int j = blockIdx.x * 64 + lane;
+    const int m = j < count ? meta[j] : kMetaDone;
+    const int nrot = m >= 0 ? (m & 0xffff) : 0;
+    int ntop = nrot;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ntop = max(ntop, __shfl_xor(ntop, o));
+    EigWsLane ys{lds + lane * 9};
+    double err = 0;
+    eig9_replay_row_rev<kHGenRD>(log + j, logStride, nrot, ntop, m >= 0 ? (m >> 16) : 0, ys, &err);
+    bool dec = false;
+    if (m >= 0) {
+        double y[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) y[k] = ys[k];
+        const int4 id = sidx[j];
+        const int ix[4] = {id.x, id.y, id.z, id.w};
+        float sx[4], sy[4], dx[4], dy[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 q = reinterpret_cast<const float4*>(pts4)[ix[k]];
+            sx[k] = q.x; sy[k] = q.y; dx[k] = q.z; dy[k] = q.w;
+        }
+        double nm[8];
+        HModelF mf;
+        (void)h_norm4(sx, sy, dx, dy, nm);   // pass 1 accepted this sample: the same values again
+        dec = h_model_f_cert(y, err * errScale, nm, &mf);
+        if (dec) {
+            models[base + j] = mf;
+            counts[base + j] = 0;
+        }
+    }
+    const bool un = m >= 0 && !dec;
+    const uint64_t bu = __ballot(un), bd = __ballot(dec), bo = __ballot(m == kMetaOverflow);
+    int at = 0;
+    if (lane == 0) {
+        if (bu) at = atomicAdd(und, (int)__popcll(bu));
+        if (bd) atomicAdd(stats, (int)__popcll(bd));
+        if (bu | bo) atomicAdd(stats + 1, (int)__popcll(bu) + (int)__popcll(bo));
+    }
+    at = __shfl(at, 0);
+    if (un) und[1 + at + (int)__popcll(bu & ((1ull << lane) - 1ull))] = j;
 }
 
 template <int L>
@@ -213,14 +307,41 @@ __global__ void mcv_h_one(const float* __restrict__ pts4, int N, Sampler smp, in
 static constexpr int kHGenMaxPiece = 1 << 20;
 static int h_gen_piece(int hypCount) { return std::min(hypCount, kHGenMaxPiece); }
 
-size_t h_gen_scratch_bytes(int hypCount) {
+// The scratch of the split generate: one piece's rotation log, samples and meta words, the overflow list of
+// the whole call, and the one-row pass's undecided list (one piece) with its two counters.
+struct HGenScratch {
+    EigRot* log;
+    int4* sidx;
+    int *meta, *ovf, *und, *stats;
+    size_t bytes;
+};
+static HGenScratch h_gen_layout(void* d_scratch, int hypCount) {
     const size_t piece = (size_t)h_gen_piece(hypCount);
-    return piece * kEigLogCap * sizeof(EigRot) + piece * (sizeof(int4) + sizeof(int)) +
-           ((size_t)hypCount + 1) * sizeof(int);
+    const size_t oSidx = piece * kEigLogCap * sizeof(EigRot), oMeta = oSidx + piece * sizeof(int4);
+    const size_t oOvf = oMeta + piece * sizeof(int), oUnd = oOvf + ((size_t)hypCount + 1) * sizeof(int);
+    const size_t oStats = oUnd + (piece + 1) * sizeof(int);
+    HGenScratch L{};
+    L.bytes = oStats + 2 * sizeof(int);
+    if (!d_scratch) return L;   // the size alone
+    char* b = (char*)d_scratch;
+    L.log = (EigRot*)b;
+    L.sidx = (int4*)(b + oSidx);
+    L.meta = (int*)(b + oMeta);
+    L.ovf = (int*)(b + oOvf);
+    L.und = (int*)(b + oUnd);
+    L.stats = (int*)(b + oStats);
+    return L;
 }
 
+size_t h_gen_scratch_bytes(int hypCount) { return h_gen_layout(nullptr, hypCount).bytes; }
+
+// mcvTestHGenRow's second switch: err times 2^40, so that no lane is decided (tests drive the fallback)
+static double g_hrow_err_scale = 1.0;
+void h_gen_row_err_scale(bool huge) { g_hrow_err_scale = huge ? 0x1p40 : 1.0; }
+static constexpr int kHGenVListBlocks = 1024;
+
 void launch_h_generate(const float* d_pts4, int N, Sampler smp, int64_t hypBegin, int hypCount, void* d_models,
-                       double* d_h64, int* d_counts, hipStream_t s, bool fast, void* d_scratch) {
+                       double* d_h64, int* d_counts, hipStream_t s, bool fast, void* d_scratch, bool certifiedRow) {
     if (fast) {
         hipLaunchKernelGGL(mcv_h_generate<true>, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_pts4, N, smp, hypBegin,
                            hypCount, (HModelF*)d_models, d_h64, d_counts);
@@ -233,26 +354,43 @@ void launch_h_generate(const float* d_pts4, int N, Sampler smp, int64_t hypBegin
         return;
     }
     const int piece = h_gen_piece(hypCount);
-    char* b = (char*)d_scratch;
-    EigRot* log = (EigRot*)b;
-    b += (size_t)piece * kEigLogCap * sizeof(EigRot);
-    int4* sidx = (int4*)b;
-    b += (size_t)piece * sizeof(int4);
-    int* meta = (int*)b;
-    b += (size_t)piece * sizeof(int);
-    int* ovf = (int*)b;
-    (void)hipMemsetAsync(ovf, 0, sizeof(int), s);   // errors surface at the caller's hipGetLastError
+    const HGenScratch L = h_gen_layout(d_scratch, hypCount);
+    (void)hipMemsetAsync(L.ovf, 0, sizeof(int), s);   // errors surface at the caller's hipGetLastError
+    if (certifiedRow) (void)hipMemsetAsync(L.stats, 0, 2 * sizeof(int), s);
     for (int base = 0; base < hypCount; base += piece) {
         const int cnt = std::min(piece, hypCount - base);
         hipLaunchKernelGGL(mcv_h_gen_aw<kHGenAwLanes>, dim3((cnt + kHGenAwLanes - 1) / kHGenAwLanes),
-                           dim3(kHGenAwLanes), 0, s, d_pts4, N, smp, hypBegin, cnt, (HModelF*)d_models, d_counts, sidx,
-                           meta, log, piece, ovf, base, g_eig_log_cap);
-        hipLaunchKernelGGL((mcv_h_gen_v<kHGenVG, kHGenVQ, kHGenVD>), dim3((cnt + kHGenVQ - 1) / kHGenVQ),
-                           dim3(kHGenVG * kHGenVQ), 0, s, d_pts4, cnt, base, sidx, meta, log, piece, (HModelF*)d_models,
-                           d_h64, d_counts);
+                           dim3(kHGenAwLanes), 0, s, d_pts4, N, smp, hypBegin, cnt, (HModelF*)d_models, d_counts,
+                           L.sidx, L.meta, L.log, piece, L.ovf, base, g_eig_log_cap);
+        if (certifiedRow) {
+            (void)hipMemsetAsync(L.und, 0, sizeof(int), s);
+            hipLaunchKernelGGL(mcv_h_gen_r, dim3((cnt + 63) / 64), dim3(64), 0, s, d_pts4, cnt, base, L.sidx, L.meta,
+                               L.log, piece, (HModelF*)d_models, d_counts, L.und, L.stats, g_hrow_err_scale);
+            hipLaunchKernelGGL((mcv_h_gen_v_list<kHGenVG, kHGenVQ, kHGenVD, true>), dim3(kHGenVListBlocks),
+                               dim3(kHGenVG * kHGenVQ), 0, s, d_pts4, cnt, base, L.sidx, L.meta, L.log, piece,
+                               (HModelF*)d_models, d_h64, d_counts, L.und, -1);
+        } else {
+            hipLaunchKernelGGL((mcv_h_gen_v<kHGenVG, kHGenVQ, kHGenVD>), dim3((cnt + kHGenVQ - 1) / kHGenVQ),
+                               dim3(kHGenVG * kHGenVQ), 0, s, d_pts4, cnt, base, L.sidx, L.meta, L.log, piece,
+                               (HModelF*)d_models, d_h64, d_counts);
+        }
     }
     hipLaunchKernelGGL(mcv_h_gen_ovf<kEigLanes>, dim3(kHGenOvfBlocks), dim3(kEigLanes), 0, s, d_pts4, N, smp, hypBegin,
-                       ovf, (HModelF*)d_models, d_h64, d_counts);
+                       L.ovf, (HModelF*)d_models, d_h64, d_counts);
+}
+
+bool h_gen_row_log_kept(int hypCount) { return hypCount <= h_gen_piece(hypCount); }
+
+void launch_h_gen_v_one(const float* d_pts4, int hypCount, int local, void* d_scratch, void* d_models, double* d_h64,
+                        hipStream_t s) {
+    const HGenScratch L = h_gen_layout(d_scratch, hypCount);
+    hipLaunchKernelGGL((mcv_h_gen_v_list<kHGenVG, kHGenVQ, kHGenVD, false>), dim3(1), dim3(kHGenVG * kHGenVQ), 0, s,
+                       d_pts4, hypCount, 0, L.sidx, L.meta, L.log, h_gen_piece(hypCount), (HModelF*)d_models, d_h64,
+                       nullptr, nullptr, local);
+}
+
+const int* h_gen_row_stats(const void* d_scratch, int hypCount) {
+    return h_gen_layout(const_cast<void*>(d_scratch), hypCount).stats;
 }
 
 void launch_h_one(const float* d_pts4, int N, Sampler smp, int64_t hyp, HOneOut* d_out, hipStream_t s, bool fast) {

@@ -8,7 +8,7 @@
 // Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
 // [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
 // Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHCellRel,
-// mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma).
+// mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma, mcvTestHGenRow, mcvTestHGenerate, mcvHostHGenRow).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -43,6 +43,11 @@ static bool g_hcell_pre_count = false;   // staged evaluates count only once the
 // mcvTestHStage0Slots: the slots stage 0 sweeps where the bound runs: 0 the rule (kernels.h), else that many
 static int g_hstage0_slots = 0;
 static thread_local Plan* t_hcell_pre_plan = nullptr;
+// mcvTestHGenRow: the generate's certified one-row pass 2: 0 automatic (key-only op-by-op evaluates of the eigen
+// solver from kHRowMinHyps hypotheses), 1 wherever it applies, 2 never, 3 as 1 with err times 2^40
+static int g_hrow_mode = 0;
+static const int kHRowMinHyps = 1 << 14;   // below, pass 2 is a few microseconds either way and the launches count
+static thread_local Plan* t_hrow_plan = nullptr;
 static thread_local long long t_hcell_pre_last[2] = {0, 0};
 // mcvTestHMfma: the certified homography sweep's form (kHForm*), and where the calling thread's last
 // such sweep left its stats: a plan's device counters, or the values a sweep outside a plan reported
@@ -59,6 +64,7 @@ void h_plan_forget(const Plan* P) {
     if (t_hstage_plan == P) t_hstage_plan = nullptr;
     if (t_hmfma_plan == P) t_hmfma_plan = nullptr;
     if (t_hcell_pre_plan == P) t_hcell_pre_plan = nullptr;
+    if (t_hrow_plan == P) t_hrow_plan = nullptr;
 }
 
 // The host half of HomographyEstimatorCallback::runKernel on a refit record (kernels.h kRefit*): the single
@@ -114,12 +120,19 @@ void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipS
 
 // One chunk of hypotheses: models, statuses, and P.last = this chunk (the winner's models can come straight
 // from its buffers: h_finalize). Shared by the RANSAC evaluate below and lmeds_search.
+// certifiedRow: the one-row pass 2 (kernels.h). P.h64 then holds only some of the chunk's models; its one reader,
+// h_finalize's cached branch, replays the winner from the log the plan still holds (P.hrowLogKept) first.
 void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
+                      int* d_counts, hipStream_t s, bool certifiedRow) {
     const Sampler smp = P.sampler(cfg);
+    certifiedRow = certifiedRow && !fast_minimal(cfg);
     if (!fast_minimal(cfg)) P.hgen.ensure(h_gen_scratch_bytes(hypCount));
     launch_h_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, P.h64.p, d_counts, s, fast_minimal(cfg),
-                      fast_minimal(cfg) ? nullptr : P.hgen.p);
+                      fast_minimal(cfg) ? nullptr : P.hgen.p, certifiedRow);
+    P.hrowLast = certifiedRow;
+    P.hrowLogKept = certifiedRow && h_gen_row_log_kept(hypCount);
+    P.hrowCount = hypCount;
+    t_hrow_plan = &P;
     mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
 }
 
@@ -140,7 +153,11 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     }
     {
         ProfScope pg("h_generate", s);
-        h_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+        // the certified one-row pass 2 where only the key leaves the evaluate (the staged sweep's own condition)
+        const bool row = keyOnly && !fused && !fast_minimal(cfg) && g_hrow_mode != 2 &&
+                         (g_hrow_mode != 0 || hypCount >= kHRowMinHyps);
+        if (row) h_gen_row_err_scale(g_hrow_mode == 3);
+        h_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s, row);
     }
     // Staging decision. The certified sweep may run in self-pruning stages only where nobody reads
     // the per-hypothesis counts: the caller gets the key alone. The key stays exact. B is the full
@@ -261,8 +278,13 @@ int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
     // winner re-solve -> mask from the device-side record -> one read-back of both
     HOneOut* d_one = (HOneOut*)P.one.p;
     const Sampler smp = P.sampler(cfg);
-    const bool cached = P.last.covers(hyp, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20);
+    bool cached = P.last.covers(hyp, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20);
+    // a chunk of the one-row pass 2 holds the winner's fp64 model only after its exact replay from the chunk's
+    // log; where the log is gone (a chunk of more than one piece), the single-lane solve as for a winner outside
+    if (cached && P.hrowLast && !P.hrowLogKept) cached = false;
     if (cached) {
+        if (P.hrowLast)
+            launch_h_gen_v_one(d_pts, P.hrowCount, (int)(hyp - P.last.begin), P.hgen.p, P.models.p, P.h64.p, s);
         // the winner's fp64 and fp32 models straight from the last chunk's buffers (the same code
         // produced them) instead of a single-lane eigen re-solve (~0.4 ms); a winner has status 1
         const int64_t local = hyp - P.last.begin;
@@ -588,6 +610,119 @@ extern "C" MCV_API int mcvTestHCellPre(int mode, long long* stats) {
             stats[1] = (long long)v[1];
         }
         return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the generate's certified one-row pass 2 and the lane figures of the
+// calling thread's last homography generate (read after its stream was synchronised).
+extern "C" MCV_API int mcvTestHGenRow(int mode, long long* stats) {
+    MCV_GUARD(-1, {
+        const int prev = g_hrow_mode;
+        if (mode >= 0 && mode <= 3) g_hrow_mode = mode;
+        if (stats) {
+            int v[2] = {0, 0};
+            const Plan* P = t_hrow_plan;
+            if (P && P->hrowLast)
+                MCV_HIP(hipMemcpy(v, h_gen_row_stats(P->hgen.p, P->hrowCount), sizeof(v), hipMemcpyDeviceToHost));
+            stats[0] = v[0];
+            stats[1] = v[1];
+        }
+        return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the split generate alone on host points, exact or one-row pass 2.
+extern "C" MCV_API int mcvTestHGenerate(const float* pts4, int N, uint64_t seed, const int* table, int64_t hypBegin,
+                                        int hypCount, int row, float* models8, int* counts, long long* stats) {
+    MCV_GUARD(0, {
+        if (!pts4 || !models8 || !counts) fail("mcvTestHGenerate: null argument");
+        if (N < 4 || hypBegin < 0 || hypCount <= 0 || row < 0 || row > 2) fail("mcvTestHGenerate: bad arguments");
+        require_device();
+        DevBuf<float> p;
+        DevBuf<uint8_t> m, scratch;
+        DevBuf<double> h64;
+        DevBuf<int> c, tab;
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)hypCount * sizeof(HModelF));
+        h64.ensure((size_t)hypCount * 9);
+        c.ensure((size_t)hypCount);
+        scratch.ensure(h_gen_scratch_bytes(hypCount));
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        if (table) {
+            tab.ensure((size_t)(hypBegin + hypCount) * 4);
+            MCV_HIP(hipMemcpy(tab.p, table, (size_t)(hypBegin + hypCount) * 16, hipMemcpyHostToDevice));
+        }
+        // every slot must be written by the generate: a byte pattern no model or status has
+        MCV_HIP(hipMemset(m.p, 0xA5, (size_t)hypCount * sizeof(HModelF)));
+        MCV_HIP(hipMemset(c.p, 0xA5, (size_t)hypCount * sizeof(int)));
+        h_gen_row_err_scale(row == 2);
+        launch_h_generate(p.p, N, Sampler{seed, table ? tab.p : nullptr}, hypBegin, hypCount, m.p, h64.p, c.p, 0, false,
+                          scratch.p, row != 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        h_gen_row_err_scale(false);
+        MCV_HIP(hipMemcpy(models8, m.p, (size_t)hypCount * sizeof(HModelF), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(counts, c.p, (size_t)hypCount * sizeof(int), hipMemcpyDeviceToHost));
+        if (stats) {
+            int v[2] = {0, 0};
+            if (row) MCV_HIP(hipMemcpy(v, h_gen_row_stats(scratch.p, hypCount), sizeof(v), hipMemcpyDeviceToHost));
+            stats[0] = v[0];
+            stats[1] = v[1];
+        }
+        return 1;
+    })
+}
+
+// Host twin (declared in minicv_native.h): the one-row pass 2 beside the exact solve, hypothesis by hypothesis.
+extern "C" MCV_API int mcvHostHGenRow(const float* pts4, int N, uint64_t seed, const int* table, int64_t hypBegin,
+                                      int hypCount, int errHuge, float* modelsRow8, float* modelsFwd8, int* statusFwd,
+                                      int* decided, double* err, double* dev) {
+    MCV_GUARD(0, {
+        if (!pts4 || !modelsRow8 || !modelsFwd8 || !statusFwd || !decided || !err || !dev)
+            fail("mcvHostHGenRow: null argument");
+        if (N < 4 || hypBegin < 0 || hypCount <= 0) fail("mcvHostHGenRow: bad arguments");
+        const Sampler smp{seed, table};
+        std::vector<EigRot> log(192);
+        for (int64_t q = 0; q < hypCount; ++q) {
+            const uint64_t hyp = (uint64_t)(hypBegin + q);
+            // the exact path: the one-pass solve (the split generate's models are its bits)
+            double H[9];
+            HModelF mf;
+            EigWsLocal ws;
+            for (int k = 0; k < 8; ++k) mf.h[k] = 0;
+            statusFwd[q] = h_hypothesis(pts4, N, smp, hyp, H, &mf, nullptr, ws);
+            for (int k = 0; k < 8; ++k) modelsFwd8[8 * q + k] = statusFwd[q] == 1 ? mf.h[k] : 0.f;
+            decided[q] = 0;
+            err[q] = dev[q] = 0;
+            for (int k = 0; k < 8; ++k) modelsRow8[8 * q + k] = 0.f;
+            // pass 1 as mcv_h_gen_aw runs it: the logged solve on the upper triangle and W
+            float sx[4], sy[4], dx[4], dy[4];
+            int idx[4];
+            double nm[8];
+            double aw[kEigWs];   // the host form of the logged solve still sends its skipped pairs to the junk slot
+            aw[kEigJunk] = 0.0;
+            EigWsLane wl{aw};
+            if (!h_sample(pts4, N, smp, hyp, sx, sy, dx, dy, idx)) continue;
+            if (!h_norm4(sx, sy, dx, dy, nm) || !h_ltl4(sx, sy, dx, dy, nm, wl)) continue;
+            double w[9];
+            int nrot = 0;
+            const int r = eig9_jacobi<EigWsLane, true>(wl, w, 8, &nrot, log.data(), 1, (int)log.size());
+            if (nrot < 0) continue;   // log overflow: the one-pass kernel's lane, undecided
+            double y[9], e = 0;
+            EigWsLane yl{y};
+            eig9_replay_row_rev<8>(log.data(), 1, nrot, nrot, r, yl, &e);
+            double V[81];
+            EigWsLane vl{V};
+            eig9_replay(vl, log.data(), 1, nrot);
+            for (int k = 0; k < 9; ++k) dev[q] = std::max(dev[q], std::fabs(y[k] - V[9 * r + k]));
+            err[q] = e;
+            HModelF mr;
+            const double (&yr)[9] = y;
+            decided[q] = h_model_f_cert(yr, errHuge ? e * 0x1p40 : e, nm, &mr) ? 1 : 0;
+            if (decided[q])
+                for (int k = 0; k < 8; ++k) modelsRow8[8 * q + k] = mr.h[k];
+        }
+        return 1;
     })
 }
 

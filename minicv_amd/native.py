@@ -261,6 +261,9 @@ SIGNATURES = {
     "mcvTestHCellBound": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcvTestHCellRel": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mcvTestHCellPre": (_I, [_I, _P]),
+    "mcvTestHGenRow": (_I, [_I, _P]),
+    "mcvTestHGenerate": (_I, [_P, _I, _U64, _P, _I64, _I, _I, _P, _P, _P]),
+    "mcvHostHGenRow": (_I, [_P, _I, _U64, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcvTestHStage0Slots": (_I, [_I]),
     "mcvTestHCellPreVerdicts": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
