@@ -988,6 +988,18 @@ MCV_API int mcvTestHCellPreVerdicts(const float* pts4, int N, const float* cand8
  * (2^21 slots). Returns D, -1 on a bad argument. */
 MCV_API int mcvHostBatchLayout(const int* offsets, int B, int m, int maxIters, long long cap, long long* desc4,
                                long long* info4);
+/* The plan of one hypothesis round of the RANSAC batches (cvFindModelBatch, the essential and the PnP batches), as
+ * their shared round driver computes it (no device). Device problem d has the points [ptOff[d], ptOff[d] + N[d]),
+ * the sampler rows from rowOff[d] (NULL: 0) and the replay state niters[d] / stopped[d]; active[nActive]: the
+ * ascending device indices still in the search. The round holds the hypotheses [begin, begin + size) of every
+ * active problem that is not stopped and has niters > begin; they are compacted in order. desc6[6 j ..] of entry
+ * j: point offset, N, hypBegin = begin, hypCount = min(niters - begin, size), slot offset = j * stride (stride =
+ * the round's largest hypCount), row offset; activeOut[j]: its device index (both with room for nActive entries);
+ * info2 = {n, stride}. Returns n, -1 on a null array, nActive outside [0, D], begin outside [0, 2^31), size
+ * outside [1, 2^31) or an active list that is not ascending within [0, D). */
+MCV_API int mcvHostBatchRound(const int* ptOff, const int* N, const long long* rowOff, const long long* niters,
+                              const int* stopped, int D, const int* active, int nActive, long long begin,
+                              long long size, long long* desc6, int* activeOut, long long* info2);
 /* The slot cap of cvFindModelBatch's rounds (cap <= 0: back to the default). Returns the previous cap.
  * Not thread-safe: tests only. */
 MCV_API long long mcvTestBatchCap(long long cap);
@@ -995,7 +1007,9 @@ MCV_API long long mcvTestBatchCap(long long cap);
  * [2] hypothesis rounds, [3] Levenberg-Marquardt rounds, [4] problems routed through the single export,
  * [5] B (the launches and synchronisations of routed problems are the single export's and not counted),
  * [6] host microseconds spent converting the points to float4, [7] host microseconds spent drawing
- * OpenCV's sample tables (MCV_FLAG_CV_SAMPLER; 0 with the Philox sampler). Returns 1. */
+ * OpenCV's sample tables (MCV_FLAG_CV_SAMPLER; 0 with the Philox sampler), [8] the problems summed over the
+ * hypothesis rounds they ran in, [9] the host <-> device copies enqueued (memsets are not counted; every RANSAC
+ * batch family counts [8] and [9] the same way). Returns 1. */
 MCV_API int mcvTestBatchStats(long long* stats16);
 /* Device self-test: the batched inlier sweep (mcv_batch_sweep) on caller-supplied models. pts4: the
  * segmented float4 points, problem p owning [offsets[p], offsets[p+1]); its models are
@@ -1021,8 +1035,7 @@ MCV_API int mcvTestBatchSweepE(const double* pts4d, const int* offsets, int B, c
 /* cvSolvePnPRansacBatch shares the hooks above as well: its layout is mcvHostBatchLayout with m = 4 (P3P /
  * AP3P) or 5 (the other kinds) and its own default cap of 2^18 hypotheses per round; mcvTestBatchCap overrides
  * it like the essential cap; mcvTestBatchStats reports [3] the lockstep LM steps (at most 21), [6] the host
- * microseconds staging the raw points and cameras, [8] as for the essential batches and [9] the host <->
- * device copies enqueued.
+ * microseconds staging the raw points and cameras, [8] and [9] as above.
  * Device self-test: the batched PnP sweep (mcv_batch_pnp_sweep) on caller-supplied poses. pts8: the segmented
  * PnpPoint rows (8 floats: X, Y, Z, u, v, 3 pad), problem p owning [offsets[p], offsets[p+1]); cam8: 8 doubles
  * per problem (fx, fy, cx, cy, k1, k2, p1, p2); its poses are [poseOffsets[p], poseOffsets[p+1]) of poses12

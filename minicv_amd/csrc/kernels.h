@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "epnp.h"
+#include "ransac_batch_index.h"
 
 namespace mcv {
 
@@ -360,12 +361,7 @@ void launch_error_rank(int model, const float* d_pts4, int N, const void* d_mode
 // ---- batched 2-D model RANSAC (ransac_batch.hip): B problems of one family per launch. All problems'
 // float4 points sit in one segmented buffer; the tables below name each problem's share of it.
 static const int kBatchTile = 1024;          // points staged in LDS per trip of the batched sweep (16 KiB)
-struct BatchDesc {      // one problem of a hypothesis round
-    int ptOff, N;            // its points: [ptOff, ptOff + N) of the segmented buffer
-    int hypBegin, hypCount;  // its hypotheses of this round
-    int64_t slotOff;         // its first slot in the round's model / count buffers
-    int64_t rowOff;          // its first row of the sampler table (MCV_FLAG_CV_SAMPLER)
-};
+// BatchDesc, one problem of a hypothesis round: ransac_batch_index.h
 struct BatchFin {       // one problem with a winner
     int ptOff, N;
     int64_t rowOff;

@@ -17,11 +17,11 @@
 #include "mcv_runtime.h"
 #include "kernels.h"
 #include "plan.h"
+#include "batch_host.h"
 
 #include <algorithm>
 #include <climits>
 #include <cstring>
-#include <memory>
 #include <numeric>
 #include <vector>
 
@@ -99,36 +99,15 @@ void mb_layout(const int* counts, int nImages, const int* imagePairs, int B, boo
     }
 }
 
-struct MbWs {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct MbWs : DeviceWs {
     DevBuf<uint8_t> raw, rows, keep;
     DevBuf<int> norms, tables, idx, idx2, di1, di2, cnt, off, pairs, offsets;
     DevBuf<float> df1, df2, dist;
     PinnedBuf<uint8_t> h_raw;
     PinnedBuf<int> h_tables, h_offsets;
-    ~MbWs() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
-MbWs& thread_mb_ws() {
-    int dev = 0;
-    MCV_HIP(hipGetDevice(&dev));
-    thread_local std::vector<std::unique_ptr<MbWs>> all;
-    for (auto& w : all)
-        if (w->device == dev) return *w;
-    all.emplace_back(new MbWs());
-    all.back()->device = dev;
-    MCV_HIP(hipStreamCreateWithFlags(&all.back()->stream, hipStreamNonBlocking));
-    return *all.back();
-}
-
-void mb_sync(hipStream_t s) {
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipStreamSynchronize(s));
-    ++t_mb_stats.syncs;
-}
+void mb_sync(hipStream_t s) { counted_sync(s, t_mb_stats.syncs); }
 
 int padded_width(bool ham, int dim) {
     if (ham) return dim <= 32 ? 32 : 64;
@@ -271,7 +250,7 @@ int match_features_batch(const char* who, const DetectorResult* images, int nIma
               L);
     if (L.totalQ == 0) return 0;
     require_device();
-    MbWs& W = thread_mb_ws();
+    MbWs& W = thread_device_ws<MbWs>();
     hipStream_t s = W.stream;
     const MbTables T = mb_knn(W, L, nImages, counts.data(), [&](int i) { return images[i].Descriptors; }, dim, ham, s);
     const int totalQ = L.totalQ, nb = (totalQ + 255) / 256;
@@ -443,7 +422,7 @@ extern "C" MCV_API int mcvTestMatchBatchKnn(const uint8_t* rows, const int* feat
         mb_layout(featureCounts, nImages, directedPairs, D, false, ham ? kMatchBatchRowsHamming : kMatchBatchRowsL2, L);
         if (L.totalOut == 0) return 0;
         require_device();
-        MbWs& W = thread_mb_ws();
+        MbWs& W = thread_device_ws<MbWs>();
         hipStream_t s = W.stream;
         mb_knn(W, L, nImages, featureCounts, [&](int i) { return rows + first[(size_t)i] * dim; }, dim, ham, s);
         const size_t n = (size_t)L.totalOut;

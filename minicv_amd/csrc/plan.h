@@ -6,6 +6,7 @@
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "mcv_common.h"
+#include "ransac_batch_index.h"
 #include <stdint.h>
 #include <vector>
 
@@ -275,26 +276,16 @@ void e_check(const RansacConfig& cfg, const char* who);
 int e_kind(const RansacConfig& cfg);   // f_error's kind of the Sampson error (fused 0, op-by-op 1)
 extern const double kCheiralityDist;   // recoverPose's distanceThresh for the focal/pp overload
 
-// ---- batch calls (ransac_batch_host.cpp: cvFindModelBatch; ransac_batch_e_host.cpp: the essential batches)
+// ---- the RANSAC batch calls (ransac_batch_host.cpp: cvFindModelBatch; ransac_batch_e_host.cpp: the essential
+// batches; ransac_batch_pnp_host.cpp: the PnP batches). Their layout and round plan: ransac_batch_index.h; the
+// round driver and the host helpers they share: batch_host.h.
 struct BatchStats {
     long long launches = 0, syncs = 0, rounds = 0, lmRounds = 0, single = 0, problems = 0;
     long long packUs = 0, tableUs = 0;   // host time: point conversion, OpenCV sample tables
-    long long problemRounds = 0;         // essential batches: problems summed over the rounds they ran in
-    long long copies = 0;                // PnP batch: host <-> device copies enqueued
+    long long problemRounds = 0;         // problems summed over the hypothesis rounds they ran in
+    long long copies = 0;                // host <-> device copies enqueued (every family; memsets are not counted)
 };
 BatchStats& batch_stats();   // the calling thread's last batch call (mcvTestBatchStats)
-// The index arithmetic of a batch call (mcvHostBatchLayout exposes it). Problems with more points than
-// the sample size m go to the device; they are numbered in order (device index d).
-//   point offset  offsets[p] (point units; nothing is padded)
-//   slot offset   d * per, 64-bit: problem d's first slot of a round in which every device problem runs
-//   row offset    d * iters: its first row of the sampler table
-//   per           hypotheses per problem per round = clamp(cap / D, 1, iters); rounds = ceil(iters / per)
-struct BatchLayout {
-    std::vector<int> dev;             // device problems
-    std::vector<int64_t> slotOff, rowOff;   // per problem (-1: not on the device)
-    int64_t iters = 1, per = 1, rounds = 0;
-};
-void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L);
 // Throws what cvFindModelBatch refuses a (model, cfg) for, with its message; no device needed.
 void batch_check_config(int model, const RansacConfig* cfg);
 int64_t batch_cap_essential();   // hypotheses a round of the essential batches may hold (mcvTestBatchCap)

@@ -1,5 +1,5 @@
 // pnp_refine_batch_index.h — the index arithmetic of the batched PnP refinement (cvRefinePnPBatch,
-// cvSolvePnPRansacRefineBatch): the checks of the offsets, each problem's selected rows, its
+// cvSolvePnPRansacRefineBatch): the check of the problem sizes, each problem's selected rows, its
 // place in the compact (gathered) point array, the refusal reasons and the table of the problems that run.
 // Plain C++ without the HIP runtime: the exports (ransac_batch_pnp_host.cpp), the layout hook
 // (mcvHostRefinePnPBatchLayout) and the stand-alone sanitizer program (tests/asan/pnp_refine_batch_asan_main.cpp)
@@ -13,21 +13,18 @@
 //            reduces over its problem's compact rows, or over its rows when the call has no mask
 #pragma once
 
+#include "ransac_batch_index.h"   // batch_check_offsets: the one check of the offsets
+
 #include <cstdint>
 
 namespace mcv {
 
 static const int kRefineMinRows = 3;   // cvRefinePnPLM / cvRefinePnPVVS refuse fewer
 
-// 0: fine; 1: offsets[0] != 0; 2: offsets[*where + 1] < offsets[*where]
+// The check of the offsets under this header's name: batch_check_offsets itself (0 fine, 1 offsets[0] != 0,
+// 2 offsets[*where + 1] < offsets[*where]).
 inline int refine_batch_check_offsets(const int* offsets, int B, int* where) {
-    if (offsets[0] != 0) return 1;
-    for (int p = 0; p < B; ++p)
-        if (offsets[p + 1] < offsets[p]) {
-            *where = p;
-            return 2;
-        }
-    return 0;
+    return batch_check_offsets(offsets, B, where);
 }
 
 // The first problem with more than `limit` rows, or -1.

@@ -2,9 +2,9 @@
 // (homography, 8-point fundamental, affine, similarity) in one call whose kernel launches and stream
 // synchronisations do not grow with B.
 //
-//   all points -> one segmented float4 buffer, one H2D copy (+ one for OpenCV's sample tables)
-//   rounds:   batched generate + batched sweep over every problem still searching, one copy of the
-//             counts back, the single call's sequential replay per problem on the host
+//   all points -> one segmented float4 buffer, one H2D copy (+ one for OpenCV's sample tables: one block of
+//             rows per problem, because checkSubset makes them depend on the points)
+//   rounds:   batch_host.h's driver over the batched generate + the batched sweep
 //   finalize: every winner re-solved, masked and counted in two launches, one copy back
 //   refine:   the B Levenberg-Marquardt solvers in lockstep (lm_solver.h's LmStepper, the controller the
 //             single call loops over): each step is one batched reduction over the problems still
@@ -13,32 +13,25 @@
 //             call's own functions (LmStepper, h_refit_from_record, a_to_params / a_from_params), so
 //             every problem returns the single call's bits.
 // Problems with exactly the sample size take the single export's direct solve (routed through it).
-#include "minicv_native.h"
-#include "mcv_runtime.h"
 #include "kernels.h"
 #include "linalg.h"
 #include "mcv_common.h"
 #include "hyp_homography.h"
 #include "hyp_affine.h"
 #include "lm_solver.h"
-#include "plan.h"
+#include "batch_host.h"
 
 #include <cmath>
 #include <cfloat>
+#include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
-#include <memory>
 #include <algorithm>
-#include <chrono>
 
 namespace mcv {
 
-// Slots (problem x hypothesis) one round may hold. 2^21 slots are 151 MB of fundamental models (72 B),
-// 64 MB of homography models, 8 MB of counts: B = 1024 problems of the default 2000 iterations fit one
-// round. Above it every round gives each problem cap / problems hypotheses (at least one).
-static const int64_t kBatchSlotCap = (int64_t)1 << 21;
-static int64_t g_batch_cap = kBatchSlotCap;   // mcvTestBatchCap
+static int64_t g_batch_cap = kBatchSlotCap;   // a round's slots (ransac_batch_index.h); mcvTestBatchCap
 // The essential batches count hypotheses, not slots: one costs 2292 B of five-point stage, 720 B of dense
 // models and 80 B of counts and slot indices, ~3.1 KB, so 2^18 of them are 0.8 GB (B = 256 problems of the
 // default 1000 iterations fit one round).
@@ -51,32 +44,10 @@ int64_t batch_cap_essential() { return g_batch_cap == kBatchSlotCap ? kBatchHypC
 static const int64_t kBatchHypCapPnp = (int64_t)1 << 18;
 int64_t batch_cap_pnp() { return g_batch_cap == kBatchSlotCap ? kBatchHypCapPnp : g_batch_cap; }
 
-static long long us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-}
 static thread_local BatchStats t_stats;
 BatchStats& batch_stats() { return t_stats; }
 
-void batch_layout(const int* offsets, int B, int m, int maxIters, int64_t cap, BatchLayout& L) {
-    L.dev.clear();
-    L.slotOff.assign((size_t)B, -1);
-    L.rowOff.assign((size_t)B, -1);
-    L.iters = std::max(maxIters, 1);
-    for (int p = 0; p < B; ++p)
-        if (offsets[p + 1] - offsets[p] > m) L.dev.push_back(p);
-    const int64_t D = (int64_t)L.dev.size();
-    if (cap < 1) cap = kBatchSlotCap;
-    L.per = D ? std::min(std::max<int64_t>(cap / D, 1), L.iters) : L.iters;
-    L.rounds = D ? (L.iters + L.per - 1) / L.per : 0;
-    for (int64_t d = 0; d < D; ++d) {
-        L.slotOff[(size_t)L.dev[(size_t)d]] = d * L.per;
-        L.rowOff[(size_t)L.dev[(size_t)d]] = d * L.iters;
-    }
-}
-
-struct BatchWs {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct BatchWs : DeviceWs {
     DevBuf<float> pts;
     DevBuf<int> table, counts, cnt;
     DevBuf<uint8_t> models, mask;
@@ -93,67 +64,31 @@ struct BatchWs {
     PinnedBuf<BatchRed> h_red;
     PinnedBuf<BatchOne> h_one;
     PinnedBuf<double> h_par, h_out, h_rec;
-    ~BatchWs() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-
-static BatchWs& thread_batch_ws() {
-    int dev = 0;
-    MCV_HIP(hipGetDevice(&dev));
-    thread_local std::vector<std::unique_ptr<BatchWs>> all;
-    for (auto& w : all)
-        if (w->device == dev) return *w;
-    all.emplace_back(new BatchWs());
-    all.back()->device = dev;
-    MCV_HIP(hipStreamCreateWithFlags(&all.back()->stream, hipStreamNonBlocking));
-    return *all.back();
-}
-
-static void batch_sync(hipStream_t s) {
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipStreamSynchronize(s));
-    ++t_stats.syncs;
-}
 
 static const char* batch_model_name(int model) {
     return model == MCV_MODEL_HOMOGRAPHY ? "homography" : model == MCV_MODEL_FUNDAMENTAL ? "fundamental"
            : model == MCV_MODEL_AFFINE   ? "affine" : "similarity";
 }
 
+// What a (model, cfg) is refused for; returns the configuration. NULL cfg: the single exports' defaults.
+static RansacConfig batch_config(int model, const RansacConfig* cfgp) {
+    if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
+        fail("cvFindModelBatch: unsupported model %d (homography, fundamental, affine, similarity)", model);
+    RansacConfig cfg = config_or_default(cfgp);
+    if (!cfgp && model != MCV_MODEL_HOMOGRAPHY) cfg.confidence = 0.99;
+    check_batch_config("cvFindModelBatch", cfg, true);
+    return cfg;
+}
+void batch_check_config(int model, const RansacConfig* cfgp) { (void)batch_config(model, cfgp); }
+
 // Everything a call can be refused for without touching the device.
 static RansacConfig batch_check(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
                                 const RansacConfig* cfgp, const mcvM33d* models, const int* counts) {
     if (!a || !b || !offsets || !models || !counts)
         fail("cvFindModelBatch: null argument (a, b, offsets, models and counts are required)");
-    if (B < 0) fail("cvFindModelBatch: negative B (%d)", B);
-    if (offsets[0] != 0) fail("cvFindModelBatch: offsets[0] must be 0 (is %d)", offsets[0]);
-    for (int p = 0; p < B; ++p)
-        if (offsets[p + 1] < offsets[p])
-            fail("cvFindModelBatch: offsets decrease at problem %d (%d -> %d)", p, offsets[p], offsets[p + 1]);
-    if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
-        fail("cvFindModelBatch: unsupported model %d (homography, fundamental, affine, similarity)", model);
-    RansacConfig cfg = config_or_default(cfgp);
-    if (!cfgp && model != MCV_MODEL_HOMOGRAPHY) cfg.confidence = 0.99;   // the single exports' NULL defaults
-    check_flags(cfg, "cvFindModelBatch");
-    if (cfg.method != MCV_METHOD_RANSAC)
-        fail("cvFindModelBatch: unsupported method %d (only MCV_METHOD_RANSAC; LSQ and LMedS have no batch form)",
-             cfg.method);
-    if (cfg.flags & MCV_FLAG_FUSED_ERROR) fail("cvFindModelBatch: unsupported flag MCV_FLAG_FUSED_ERROR");
-    if (cfg.flags & MCV_FLAG_FAST_MINIMAL) fail("cvFindModelBatch: unsupported flag MCV_FLAG_FAST_MINIMAL");
-    if (cfg.flags & MCV_FLAG_SEVEN_POINT) fail("cvFindModelBatch: unsupported flag MCV_FLAG_SEVEN_POINT");
-    if (cfg.deviceCount > 1) fail("cvFindModelBatch: unsupported deviceCount %d (one GPU per call)", cfg.deviceCount);
-    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("cvFindModelBatch: confidence must be in (0,1)");
-    return cfg;
-}
-
-// batch_check's configuration part alone (model, cfg), for callers that build the points themselves.
-void batch_check_config(int model, const RansacConfig* cfgp) {
-    static const int off0[1] = {0};
-    const mcvV2d v{};
-    mcvM33d m;
-    int c = 0;
-    (void)batch_check(model, &v, &v, off0, 0, cfgp, &m, &c);
+    check_batch_offsets("cvFindModelBatch", offsets, B);
+    return batch_config(model, cfgp);
 }
 
 // The single export on one slice (N == sample size: its direct solve). Returns its count.
@@ -179,7 +114,7 @@ static void upload_red(BatchWs& W, const std::vector<const RefineJob*>& act, hip
     W.red.ensure(n);
     W.h_red.ensure(n);
     for (size_t k = 0; k < n; ++k) W.h_red.p[k] = BatchRed{act[k]->ptOff, act[k]->N};
-    MCV_HIP(hipMemcpyAsync(W.red.p, W.h_red.p, n * sizeof(BatchRed), hipMemcpyHostToDevice, s));
+    batch_copy(W.red.p, W.h_red.p, n * sizeof(BatchRed), hipMemcpyHostToDevice, s);
 }
 
 // LMSolver(refine callback, 10) of every job in lockstep: per step one batched reduction over the jobs
@@ -212,10 +147,10 @@ static void batch_lm(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hipStre
             const double* x = st[who[k]].request();
             for (int i = 0; i < 8; ++i) W.h_par.p[8 * k + i] = i < LX ? x[i] : 0.0;
         }
-        MCV_HIP(hipMemcpyAsync(W.par.p, W.h_par.p, n * 8 * sizeof(double), hipMemcpyHostToDevice, s));
+        batch_copy(W.par.p, W.h_par.p, n * 8 * sizeof(double), hipMemcpyHostToDevice, s);
         t_stats.launches += launch_batch_reduce_lm(LX, W.pts.p, W.mask.p, W.red.p, (int)n, maxN, W.par.p, W.part.p,
                                                    W.out.p, s);
-        MCV_HIP(hipMemcpyAsync(W.h_out.p, W.out.p, n * 45 * sizeof(double), hipMemcpyDeviceToHost, s));
+        batch_copy(W.h_out.p, W.out.p, n * 45 * sizeof(double), hipMemcpyDeviceToHost, s);
         batch_sync(s);
         ++t_stats.lmRounds;
         for (size_t k = 0; k < n; ++k) st[who[k]].feed(W.h_out.p + 45 * k);
@@ -238,7 +173,7 @@ static void batch_h_refit(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hi
     W.h_rec.ensure(n * kRefitDoubles);
     W.part.ensure(n * (size_t)batch_reduce_blocks(maxN) * 45);
     t_stats.launches += launch_batch_refit_chain(W.pts.p, W.mask.p, W.red.p, (int)n, maxN, W.part.p, W.rec.p, s);
-    MCV_HIP(hipMemcpyAsync(W.h_rec.p, W.rec.p, n * kRefitDoubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    batch_copy(W.h_rec.p, W.rec.p, n * kRefitDoubles * sizeof(double), hipMemcpyDeviceToHost, s);
     batch_sync(s);
     for (size_t k = 0; k < n; ++k) {
         double Hr[9];
@@ -247,11 +182,30 @@ static void batch_h_refit(BatchWs& W, std::vector<RefineJob>& jobs, int maxN, hi
     }
 }
 
+// cvFindModelBatch's part of a hypothesis round (batch_host.h's batch_rounds): one model per hypothesis, one
+// confidence for all problems; a winner is re-solved from its index, so a new best needs no fetch.
+struct Rounds2d {
+    BatchWs& W;
+    int model, errKind;
+    uint64_t seed;
+    const int* d_table;
+    float thr2;
+    double conf;
+    static constexpr int slots = 1;
+    BatchDesc& desc(size_t j, int) { return W.h_desc.p[j]; }
+    void launch(const std::vector<int>&, BatchRound R, hipStream_t s) {
+        launch_batch_generate(model, W.pts.p, W.desc.p, R.n, R.stride, seed, d_table, W.models.p, W.counts.p, s);
+        launch_batch_sweep(model, errKind, W.pts.p, W.desc.p, R.n, R.stride, W.models.p, W.counts.p, thr2, s);
+        batch_stats().launches += 2;
+    }
+    double confidence(int) const { return conf; }
+    void best_changed(const std::vector<BestChange>&, hipStream_t) {}
+};
+
 static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const int* offsets, int B,
                             const RansacConfig* cfgp, mcvM33d* models, uint8_t* mask, int* counts) {
     const RansacConfig cfg = batch_check(model, a, b, offsets, B, cfgp, models, counts);
-    t_stats = BatchStats();
-    t_stats.problems = B;
+    batch_stats_begin(B);
     if (B == 0) return 0;
     const int total = offsets[B];
     std::memset(models, 0, (size_t)B * sizeof(mcvM33d));
@@ -264,11 +218,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
     const double t = effective_threshold(cfg);
     const float thr2 = (float)(t * t);
     const int errKind = model == MCV_MODEL_FUNDAMENTAL ? f_error_kind(cfg) : 0;
-    int firstFail = -1;
-    std::string firstMsg;
-    auto failed = [&](int p, const std::string& msg) {
-        if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
-    };
+    BatchFailures fails;
     int ok = 0;
 
     BatchLayout L;
@@ -279,13 +229,13 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
         char buf[160];
         if (N < m) {
             snprintf(buf, sizeof(buf), "need at least %d correspondences (N=%d)", m, N);
-            failed(p, buf);
+            fails.note(p, buf);
         } else if (N == m) {
             const int c = batch_single(model, a + offsets[p], b + offsets[p], N, cfgp, models[p].M,
                                        mask ? mask + offsets[p] : nullptr);
             if (c > 0) { counts[p] = c; ++ok; }
             else {
-                failed(p, mcvGetLastError());
+                fails.note(p, mcvGetLastError());
                 std::memset(models[p].M, 0, sizeof(mcvM33d));
                 if (mask) std::memset(mask + offsets[p], 0, (size_t)N);
             }
@@ -293,7 +243,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
     }
     const size_t D = L.dev.size();
     if (D) {
-        BatchWs& W = thread_batch_ws();
+        BatchWs& W = thread_device_ws<BatchWs>();
         hipStream_t s = W.stream;
         // ---- points: one conversion pass (OpenCV's convertTo(CV_32F)), one copy
         W.h_pts.ensure((size_t)total * 4);
@@ -301,7 +251,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
         auto t0 = std::chrono::steady_clock::now();
         pack_float4(a, b, total, W.h_pts.p);
         t_stats.packUs = us_since(t0);
-        MCV_HIP(hipMemcpyAsync(W.pts.p, W.h_pts.p, (size_t)total * 16, hipMemcpyHostToDevice, s));
+        batch_copy(W.pts.p, W.h_pts.p, (size_t)total * 16, hipMemcpyHostToDevice, s);
         // ---- OpenCV's sample stream: one cv::RNG((uint64)-1) stream per problem, as each single call draws
         const int* d_table = nullptr;
         if (cv_sampler(cfg)) {
@@ -317,59 +267,22 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
                 std::memcpy(W.h_table.p + d * rowInts, rows.data(), rowInts * sizeof(int));
             }
             t_stats.tableUs = us_since(t0);
-            MCV_HIP(hipMemcpyAsync(W.table.p, W.h_table.p, D * rowInts * sizeof(int), hipMemcpyHostToDevice, s));
+            batch_copy(W.table.p, W.h_table.p, D * rowInts * sizeof(int), hipMemcpyHostToDevice, s);
             d_table = W.table.p;
         }
         // ---- hypothesis rounds
-        std::vector<mcvReplayState> st(D);
-        for (auto& x : st) mcvReplayInit(&x, cfg.maxIters);
-        std::vector<size_t> active(D);
-        for (size_t d = 0; d < D; ++d) active[d] = d;
+        std::vector<BatchProblem> prob(D);
+        for (size_t d = 0; d < D; ++d) {
+            const int p = L.dev[d];
+            prob[d] = BatchProblem{offsets[p], offsets[p + 1] - offsets[p], L.rowOff[(size_t)p]};
+        }
         const size_t slotsMax = D * (size_t)L.per;
         W.models.ensure(slotsMax * batch_model_bytes(model));
         W.counts.ensure(slotsMax);
         W.h_counts.ensure(slotsMax);
-        W.desc.ensure(D);
-        W.h_desc.ensure(D);
-        for (int64_t begin = 0; !active.empty(); begin += L.per) {
-            // a round holds the hypotheses [begin, begin + per) of every problem still searching; the
-            // problems are compacted, so problem j of the round owns slots [j per, j per + count)
-            std::vector<size_t> run;
-            int maxHyp = 0;
-            for (size_t d : active) {
-                const int64_t left = (int64_t)st[d].niters - begin;
-                if (st[d].stopped || left <= 0) continue;
-                const int p = L.dev[d];
-                BatchDesc& X = W.h_desc.p[run.size()];
-                X.ptOff = offsets[p];
-                X.N = offsets[p + 1] - offsets[p];
-                X.hypBegin = (int)begin;
-                X.hypCount = (int)std::min<int64_t>(left, L.per);
-                X.slotOff = (int64_t)run.size() * L.per;
-                X.rowOff = L.rowOff[(size_t)p];
-                maxHyp = std::max(maxHyp, X.hypCount);
-                run.push_back(d);
-            }
-            active.swap(run);
-            if (active.empty()) break;
-            const size_t n = active.size();
-            MCV_HIP(hipMemcpyAsync(W.desc.p, W.h_desc.p, n * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
-            launch_batch_generate(model, W.pts.p, W.desc.p, (int)n, maxHyp, cfg.seed, d_table, W.models.p, W.counts.p,
-                                  s);
-            launch_batch_sweep(model, errKind, W.pts.p, W.desc.p, (int)n, maxHyp, W.models.p, W.counts.p, thr2, s);
-            t_stats.launches += 2;
-            MCV_HIP(hipMemcpyAsync(W.h_counts.p, W.counts.p, n * (size_t)L.per * sizeof(int), hipMemcpyDeviceToHost,
-                                   s));
-            batch_sync(s);
-            ++t_stats.rounds;
-            for (size_t j = 0; j < n; ++j) {
-                const size_t d = active[j];
-                const BatchDesc& X = W.h_desc.p[j];
-                mcvReplayChunk(&st[d], W.h_counts.p + j * (size_t)L.per, begin, X.hypCount, X.N, m, cfg.confidence,
-                               fixed ? 1 : 0);
-                if (begin + X.hypCount >= st[d].niters) st[d].stopped = 1;
-            }
-        }
+        Rounds2d F{W, model, errKind, cfg.seed, d_table, thr2, cfg.confidence};
+        std::vector<mcvReplayState> st;
+        batch_rounds(F, prob, st, cfg.maxIters, L.per, L.per, m, fixed, s);
         // ---- winners: re-solve, mask and count, all in two launches
         std::vector<size_t> win;
         int maxN = 0;
@@ -380,7 +293,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
             if (st[d].bestIndex < 0) {
                 char buf[160];
                 snprintf(buf, sizeof(buf), "RANSAC found no model with >= %d inliers", m);
-                failed(p, buf);
+                fails.note(p, buf);
                 continue;
             }
             BatchFin& F = W.h_fin.p[win.size()];
@@ -399,15 +312,15 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
             W.h_cnt.ensure(n);
             W.mask.ensure((size_t)total);
             W.h_mask.ensure((size_t)total);
-            MCV_HIP(hipMemcpyAsync(W.fin.p, W.h_fin.p, n * sizeof(BatchFin), hipMemcpyHostToDevice, s));
+            batch_copy(W.fin.p, W.h_fin.p, n * sizeof(BatchFin), hipMemcpyHostToDevice, s);
             MCV_HIP(hipMemsetAsync(W.cnt.p, 0, n * sizeof(int), s));
             MCV_HIP(hipMemsetAsync(W.mask.p, 0, (size_t)total, s));
             launch_batch_one(model, W.pts.p, W.fin.p, (int)n, cfg.seed, d_table, W.one.p, s);
             launch_batch_mask(model, errKind, W.pts.p, W.fin.p, (int)n, maxN, W.one.p, thr2, W.mask.p, W.cnt.p, s);
             t_stats.launches += 2;
-            MCV_HIP(hipMemcpyAsync(W.h_one.p, W.one.p, n * sizeof(BatchOne), hipMemcpyDeviceToHost, s));
-            MCV_HIP(hipMemcpyAsync(W.h_cnt.p, W.cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
-            MCV_HIP(hipMemcpyAsync(W.h_mask.p, W.mask.p, (size_t)total, hipMemcpyDeviceToHost, s));
+            batch_copy(W.h_one.p, W.one.p, n * sizeof(BatchOne), hipMemcpyDeviceToHost, s);
+            batch_copy(W.h_cnt.p, W.cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
+            batch_copy(W.h_mask.p, W.mask.p, (size_t)total, hipMemcpyDeviceToHost, s);
             batch_sync(s);
             std::vector<RefineJob> jobs;
             int jobMaxN = 0;
@@ -419,12 +332,12 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
                     char buf[160];
                     snprintf(buf, sizeof(buf), "winning hypothesis %lld has no model (status %d)", (long long)F.hyp,
                              o.status);
-                    failed(p, buf);
+                    fails.note(p, buf);
                     continue;
                 }
                 const int c = W.h_cnt.p[k];
                 if (c <= 0) {   // cannot happen for a replay winner (its sweep count was >= m): fail closed
-                    failed(p, "the winning model has no inliers");
+                    fails.note(p, "the winning model has no inliers");
                     continue;
                 }
                 counts[p] = c;
@@ -456,15 +369,8 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
             }
         }
     }
-    if (firstFail >= 0) {
-        // a problem that failed returns a zero model, count and mask slice; the first one is named
-        char buf[400];
-        snprintf(buf, sizeof(buf), "cvFindModelBatch (%s): problem %d: %s", batch_model_name(model), firstFail,
-                 firstMsg.c_str());
-        set_last_error(buf);
-    } else {
-        clear_last_error();
-    }
+    // a problem that failed returns a zero model, count and mask slice; the first one is named
+    fails.report((std::string("cvFindModelBatch (") + batch_model_name(model) + ")").c_str());
     return ok;
 }
 
@@ -497,6 +403,43 @@ extern "C" MCV_API int mcvHostBatchLayout(const int* offsets, int B, int m, int 
     })
 }
 
+extern "C" MCV_API int mcvHostBatchRound(const int* ptOff, const int* N, const long long* rowOff,
+                                         const long long* niters, const int* stopped, int D, const int* active,
+                                         int nActive, long long begin, long long size, long long* desc6,
+                                         int* activeOut, long long* info2) {
+    MCV_GUARD(-1, {
+        const char* who = "mcvHostBatchRound";
+        if (!info2 || D < 0 || nActive < 0 || nActive > D || (D > 0 && (!ptOff || !N || !niters || !stopped)) ||
+            (nActive > 0 && (!active || !desc6 || !activeOut)))
+            fail("%s: bad argument", who);
+        if (begin < 0 || begin > INT_MAX || size < 1 || size > INT_MAX)
+            fail("%s: begin %lld or size %lld outside [0, 2^31) / [1, 2^31)", who, begin, size);
+        for (int k = 0; k < nActive; ++k)
+            if (active[k] < 0 || active[k] >= D || (k > 0 && active[k] <= active[k - 1]))
+                fail("%s: active[%d] = %d is not an ascending index below D = %d", who, k, active[k], D);
+        struct State { int64_t niters; int stopped; };
+        std::vector<BatchProblem> prob((size_t)D);
+        std::vector<State> st((size_t)D);
+        for (int d = 0; d < D; ++d) {
+            prob[(size_t)d] = BatchProblem{ptOff[d], N[d], rowOff ? rowOff[d] : 0};
+            st[(size_t)d] = State{niters[d], stopped[d]};
+        }
+        std::vector<int> act(active, active + nActive);
+        std::vector<BatchDesc> desc((size_t)nActive);
+        const BatchRound R = batch_round(prob.data(), st.data(), act, begin, size,
+                                         [&](size_t j, int) -> BatchDesc& { return desc[j]; });
+        for (int j = 0; j < R.n; ++j) {
+            const BatchDesc& X = desc[(size_t)j];
+            const long long row[6] = {X.ptOff, X.N, X.hypBegin, X.hypCount, X.slotOff, X.rowOff};
+            std::memcpy(desc6 + 6 * j, row, sizeof(row));
+            activeOut[j] = act[(size_t)j];
+        }
+        info2[0] = R.n;
+        info2[1] = R.stride;
+        return R.n;
+    })
+}
+
 extern "C" MCV_API long long mcvTestBatchCap(long long cap) {
     const long long prev = g_batch_cap;
     g_batch_cap = cap > 0 ? cap : kBatchSlotCap;
@@ -505,17 +448,10 @@ extern "C" MCV_API long long mcvTestBatchCap(long long cap) {
 
 extern "C" MCV_API int mcvTestBatchStats(long long* stats16) {
     if (!stats16) return 0;
-    for (int i = 0; i < 16; ++i) stats16[i] = 0;
-    stats16[0] = t_stats.launches;
-    stats16[1] = t_stats.syncs;
-    stats16[2] = t_stats.rounds;
-    stats16[3] = t_stats.lmRounds;
-    stats16[4] = t_stats.single;
-    stats16[5] = t_stats.problems;
-    stats16[6] = t_stats.packUs;
-    stats16[7] = t_stats.tableUs;
-    stats16[8] = t_stats.problemRounds;
-    stats16[9] = t_stats.copies;
+    const BatchStats& S = t_stats;
+    const long long v[16] = {S.launches, S.syncs,  S.rounds,  S.lmRounds,      S.single,
+                             S.problems, S.packUs, S.tableUs, S.problemRounds, S.copies};
+    std::memcpy(stats16, v, sizeof(v));
     return 1;
 }
 

@@ -4,24 +4,20 @@
 //
 //   pack:     the raw image and world points in one copy, mcv_pnp_pack over all of them in one launch, one
 //             table of cameras (8 doubles per problem)
-//   rounds:   the single call's generate in its batch form (AP3P: one kernel; EPnP: the five split stages) +
-//             the batched sweep over every problem still searching, one copy of the counts back, the single
-//             call's sequential replay per problem on the host (mcvReplayChunk); the problems whose best
-//             changed get that pose copied out of the round's buffer before the next round reuses it
+//   rounds:   batch_host.h's driver over the single call's generate in its batch form (AP3P: one kernel; EPnP:
+//             the five split stages) + the batched sweep; a changed best pose is copied out of the round's buffer
 //   finalize: every winner masked and counted in one launch, one copy back
-//   refine:   kind 0: the winners' Levenberg-Marquardt solvers in lockstep (PnpLmStepper, the controller
-//             pnp_lm loops over), one batched reduction and one read-back per step, at most 21 steps;
-//             other kinds: EPnP on the inliers for all winners at once, the four read-backs of the single
-//             call once each, EpnpHostSolve's algebra per job between them
-// Every device step is the batch form of the single call's kernel (same body) and every host step the single
-// call's own function, so each problem returns the single call's bits. Problems with exactly the sample
-// size take the single export's direct solve, one by one.
+//   refine:   kind 0: the winners' LM solvers in lockstep (PnpLmStepper), one batched reduction and one read-back
+//             per step, at most 21 steps; other kinds: EPnP on the inliers for all winners at once, the four
+//             read-backs of the single call once each, EpnpHostSolve's algebra per job between them
+// Every device step is the batch form of the single call's kernel and every host step the single call's own
+// function, so each problem returns the single call's bits. Problems with exactly the sample size take the
+// single export's direct solve, one by one.
 //
-// cvRefinePnPBatch / cvSolvePnPRansacRefineBatch: the refinement step of solvePnPInternal for
-// B cameras. The rows are packed as above, every problem's selected rows are gathered into one compact array
-// (mcv_mask_compact's job form + mcv_pnp_batch_gather: 2 launches, none without a mask), and the steppers of
-// pnp_lm / pnp_vvs run in lockstep over the gathered rows, unmasked: the single call's sums on gathered arrays.
-// The fused call runs it behind the rounds on the packed rows and the mask they left on the device.
+// cvRefinePnPBatch / cvSolvePnPRansacRefineBatch: the rows are packed as above, every problem's selected rows
+// are gathered into one compact array (2 launches, none without a mask), and the steppers of pnp_lm / pnp_vvs
+// run in lockstep over the gathered rows, unmasked. The fused call runs it behind the rounds on the packed rows
+// and the mask they left on the device.
 //
 // One round (B problems, every one on the device and with a winner), counted by BatchStats:
 //   AP3P, NO_REFINE   launches 4 (pack, generate, sweep, mask) + 1 fetch = 5, synchronisations 2
@@ -29,31 +25,24 @@
 //                     with 4 more synchronisations (6 in all)
 //   kind 0            9 + 2 per LM step, one synchronisation per step (at most 21)
 // each further round adds the generate, the sweep, a fetch and one synchronisation.
-#include "minicv_native.h"
-#include "mcv_runtime.h"
 #include "kernels.h"
 #include "hyp_pnp.h"
 #include "pnp_refine.h"
 #include "pnp_refine_batch_index.h"
-#include "plan.h"
+#include "batch_host.h"
 
 #include <array>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
-#include <memory>
 #include <algorithm>
-#include <chrono>
 
 namespace mcv {
 
 namespace {
 
-struct BatchPnpWs {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct BatchPnpWs : DeviceWs {
     DevBuf<double> raw, cams, scratch, lmPart, lmOut, pw, us, part;
     DevBuf<float> pts, comp;
     DevBuf<uint8_t> models, best, mask;
@@ -71,49 +60,40 @@ struct BatchPnpWs {
     PinnedBuf<BatchPnpFin> h_fin;
     PinnedBuf<BatchPnpLmJob> h_lmJobs;
     PinnedBuf<BatchPnpEpnpJob> h_eJobs;
-    ~BatchPnpWs() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-
-BatchPnpWs& thread_batch_pnp_ws() {
-    int dev = 0;
-    MCV_HIP(hipGetDevice(&dev));
-    thread_local std::vector<std::unique_ptr<BatchPnpWs>> all;
-    for (auto& w : all)
-        if (w->device == dev) return *w;
-    all.emplace_back(new BatchPnpWs());
-    all.back()->device = dev;
-    MCV_HIP(hipStreamCreateWithFlags(&all.back()->stream, hipStreamNonBlocking));
-    return *all.back();
-}
-
-long long us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-}
-
-void pnp_sync(hipStream_t s) {
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipStreamSynchronize(s));
-    ++batch_stats().syncs;
-}
-void pnp_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-    ++batch_stats().copies;
-}
 
 bool camera_ok(const mcvM33d& K) {
     const double fx = K.M[0], fy = K.M[4];
     return fx != 0 && fy != 0 && std::isfinite(fx) && std::isfinite(fy);
 }
 
+// A problem's row of the camera table: fx, fy, cx, cy, then its four distortion coefficients (dist: 4 per
+// problem, or null).
+void camera_fill(const mcvM33d* K, const double* dist, int p, double* c) {
+    c[0] = K[p].M[0]; c[1] = K[p].M[4]; c[2] = K[p].M[2]; c[3] = K[p].M[5];
+    for (int k = 0; k < 4; ++k) c[4 + k] = dist ? dist[4 * (size_t)p + k] : 0.0;
+}
+
 struct Winner {     // a device problem with a pose
     size_t d;       // device index
     int p;          // problem
-    int ptOff, N, count;
-    double r[3], t[3];
-    bool ok;
+    int ptOff, N;
+    int count = 0;
+    double r[3] = {0, 0, 0}, t[3] = {0, 0, 0};
+    bool ok = true;
 };
+// The host mask of a call to the device (one copy).
+void mask_upload(BatchPnpWs& W, const uint8_t* mask, int total, hipStream_t s) {
+    W.mask.ensure((size_t)total);
+    W.h_mask.ensure((size_t)total);
+    std::memcpy(W.h_mask.p, mask, (size_t)total);
+    batch_copy(W.mask.p, W.h_mask.p, (size_t)total, hipMemcpyHostToDevice, s);
+}
+
+void winner_store(const Winner& w, mcvV3d* rVecs, mcvV3d* tVecs) {
+    rVecs[w.p] = mcvV3d{w.r[0], w.r[1], w.r[2]};
+    tVecs[w.p] = mcvV3d{w.t[0], w.t[1], w.t[2]};
+}
 
 // The two refinements as the lockstep driver sees them: begin at a pose, fill a job's pose constants.
 void stepper_begin(PnpLmStepper& st, const double* r, const double* t) { st.begin(r, t, 20); }
@@ -165,20 +145,15 @@ void batch_pnp_lockstep(BatchPnpWs& W, std::vector<Winner*>& jobs, const double*
             }
         if (who.empty()) break;
         const size_t n = who.size();
-        pnp_copy(W.lmJobs.p, W.h_lmJobs.p, n * sizeof(BatchPnpLmJob), hipMemcpyHostToDevice, s);
+        batch_copy(W.lmJobs.p, W.h_lmJobs.p, n * sizeof(BatchPnpLmJob), hipMemcpyHostToDevice, s);
         stats.launches += launch_pnp_batch_reduce(vvs, d_pts, d_mask, W.lmJobs.p, (int)n, actMaxN, W.lmPart.p,
                                                   W.lmOut.p, s);
-        pnp_copy(W.h_lmOut.p, W.lmOut.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, s);
-        pnp_sync(s);
+        batch_copy(W.h_lmOut.p, W.lmOut.p, n * 28 * sizeof(double), hipMemcpyDeviceToHost, s);
+        batch_sync(s);
         ++stats.lmRounds;
         for (size_t k = 0; k < n; ++k) st[who[k]].feed(W.h_lmOut.p + 28 * k);
     }
     for (size_t j = 0; j < jobs.size(); ++j) st[j].result(jobs[j]->r, jobs[j]->t);
-}
-
-// The RANSAC batch's ITERATIVE tail: LM masked in place over every winner's rows.
-void batch_pnp_lm(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cams, hipStream_t s) {
-    batch_pnp_lockstep<PnpLmStepper>(W, jobs, h_cams, W.pts.p, W.mask.p, false, s);
 }
 
 // ---- the batched refinement (cvRefinePnPBatch, cvSolvePnPRansacRefineBatch) ----------
@@ -194,23 +169,22 @@ void refine_pack(BatchPnpWs& W, const mcvV2d* img, const mcvV3d* world, int tota
     std::memcpy(W.h_raw.p, img, (size_t)total * sizeof(mcvV2d));
     std::memcpy(W.h_raw.p + 2 * (size_t)total, world, (size_t)total * sizeof(mcvV3d));
     stats.packUs += us_since(t0);
-    pnp_copy(W.raw.p, W.h_raw.p, (size_t)total * 5 * sizeof(double), hipMemcpyHostToDevice, s);
+    batch_copy(W.raw.p, W.h_raw.p, (size_t)total * 5 * sizeof(double), hipMemcpyHostToDevice, s);
     launch_pnp_pack(W.raw.p, W.raw.p + 2 * (size_t)total, total, W.pts.p, s);
     ++stats.launches;
 }
 
 // The host half of a refine: every problem's selected rows and place in the compact array, why a problem does
 // not run, and the table of those that do (pnp_refine_batch_index.h). run (may be null): the problems asked
-// for; a problem asked for that cannot run is reported through failed(p, the single call's message).
+// for; a problem asked for that cannot run is noted in fails with the single call's message.
 struct RefinePlan {
     std::vector<int> counts, compOff, reason;
     std::vector<RefineBatchJob> jobs;
     int largest = 0;
     bool gathered = false;
 };
-template <class Failed>
-void refine_plan(const int* offsets, int B, const mcvM33d* K, const uint8_t* h_mask, const uint8_t* run, Failed failed,
-                 RefinePlan& R) {
+void refine_plan(const int* offsets, int B, const mcvM33d* K, const uint8_t* h_mask, const uint8_t* run,
+                 BatchFailures& fails, RefinePlan& R) {
     R.gathered = h_mask != nullptr;
     R.counts.assign((size_t)B, 0);
     R.compOff.assign((size_t)B + 1, 0);
@@ -223,9 +197,9 @@ void refine_plan(const int* offsets, int B, const mcvM33d* K, const uint8_t* h_m
         if (R.reason[p] == kRefineTooFew) {
             snprintf(buf, sizeof(buf), "%s: need at least %d correspondences (N=%d)", kRefineSingle, kRefineMinRows,
                      R.counts[p]);
-            failed(p, buf);
+            fails.note(p, buf);
         } else if (R.reason[p] == kRefineBadCamera) {
-            failed(p, "camera matrix needs finite non-zero fx, fy");
+            fails.note(p, "camera matrix needs finite non-zero fx, fy");
         }
     }
     R.jobs.resize((size_t)B);
@@ -266,8 +240,8 @@ int refine_on_device(BatchPnpWs& W, const RefinePlan& R, const int* offsets, int
         }
         std::memcpy(W.h_tab.p, offsets, ((size_t)B + 1) * sizeof(int));
         std::memcpy(W.h_tab.p + B + 1, compOff.data(), ((size_t)B + 1) * sizeof(int));
-        pnp_copy(W.eJobs.p, W.h_eJobs.p, (size_t)B * sizeof(BatchPnpEpnpJob), hipMemcpyHostToDevice, s);
-        pnp_copy(W.tab.p, W.h_tab.p, 2 * ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice, s);
+        batch_copy(W.eJobs.p, W.h_eJobs.p, (size_t)B * sizeof(BatchPnpEpnpJob), hipMemcpyHostToDevice, s);
+        batch_copy(W.tab.p, W.h_tab.p, 2 * ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice, s);
         stats.launches += launch_pnp_batch_gather(W.pts.p, W.mask.p, W.eJobs.p, B, W.tab.p, W.tab.p + B + 1, selected,
                                                   W.idx.p, W.ecount.p, W.comp.p, s);
         d_pts = W.comp.p;
@@ -277,25 +251,17 @@ int refine_on_device(BatchPnpWs& W, const RefinePlan& R, const int* offsets, int
     std::vector<Winner*> jobs((size_t)nJobs);
     for (int j = 0; j < nJobs; ++j) {
         const int p = tab[(size_t)j].prob;
-        double* c = cams.data() + 8 * (size_t)j;
-        c[0] = K[p].M[0]; c[1] = K[p].M[4]; c[2] = K[p].M[2]; c[3] = K[p].M[5];
-        for (int k = 0; k < 4; ++k) c[4 + k] = dist ? dist[4 * (size_t)p + k] : 0.0;
+        camera_fill(K, dist, p, cams.data() + 8 * (size_t)j);
         Winner& w = win[(size_t)j];
-        w = Winner{};
-        w.d = (size_t)j;
-        w.p = p;
-        w.ptOff = tab[(size_t)j].ptOff;
-        w.N = tab[(size_t)j].N;
-        w.r[0] = rVecs[p].X; w.r[1] = rVecs[p].Y; w.r[2] = rVecs[p].Z;
-        w.t[0] = tVecs[p].X; w.t[1] = tVecs[p].Y; w.t[2] = tVecs[p].Z;
-        w.ok = true;
+        w = Winner{(size_t)j, p, tab[(size_t)j].ptOff, tab[(size_t)j].N};
+        std::memcpy(w.r, &rVecs[p], sizeof(w.r));   // mcvV3d: three doubles
+        std::memcpy(w.t, &tVecs[p], sizeof(w.t));
         jobs[(size_t)j] = &w;
     }
     if (refineKind == 1) batch_pnp_lockstep<PnpVvsStepper>(W, jobs, cams.data(), d_pts, nullptr, true, s);
     else batch_pnp_lockstep<PnpLmStepper>(W, jobs, cams.data(), d_pts, nullptr, false, s);
     for (const Winner& w : win) {
-        rVecs[w.p].X = w.r[0]; rVecs[w.p].Y = w.r[1]; rVecs[w.p].Z = w.r[2];
-        tVecs[w.p].X = w.t[0]; tVecs[w.p].Y = w.t[1]; tVecs[w.p].Z = w.t[2];
+        winner_store(w, rVecs, tVecs);
         if (refined) refined[w.p] = 1;
     }
     return nJobs;
@@ -304,9 +270,8 @@ int refine_on_device(BatchPnpWs& W, const RefinePlan& R, const int* offsets, int
 // epnp_inliers of every winner at once: compact + prep + the passes with grid y = the job, the single call's
 // four read-backs once each. world: the caller's points (a job's first inlier as pw holds it: the double of
 // its float coordinates). A job whose inlier count is below 4 fails, as epnp_inliers does.
-template <class Failed>
 void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_cams, const mcvV3d* world, int total,
-                    Failed failed, hipStream_t s) {
+                    BatchFailures& fails, hipStream_t s) {
     if (jobs.empty()) return;
     BatchStats& stats = batch_stats();
     const size_t n = jobs.size();
@@ -343,14 +308,14 @@ void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_c
     }
     W.part.ensure((size_t)partTotal);
     W.h_part.ensure((size_t)partTotal);
-    auto upload = [&]() { pnp_copy(W.eJobs.p, W.h_eJobs.p, n * sizeof(BatchPnpEpnpJob), hipMemcpyHostToDevice, s); };
+    auto upload = [&]() { batch_copy(W.eJobs.p, W.h_eJobs.p, n * sizeof(BatchPnpEpnpJob), hipMemcpyHostToDevice, s); };
     auto pass = [&](int mode, int nacc, int region, int prev) {
         stats.launches += launch_pnp_batch_epnp_pass(mode, W.eJobs.p, (int)n, maxNblk, W.ecount.p, W.pw.p, W.us.p, nacc,
                                                      region, prev, W.part.p, s);
     };
     auto fetch = [&]() {
-        pnp_copy(W.h_part.p, W.part.p, (size_t)partTotal * sizeof(double), hipMemcpyDeviceToHost, s);
-        pnp_sync(s);
+        batch_copy(W.h_part.p, W.part.p, (size_t)partTotal * sizeof(double), hipMemcpyDeviceToHost, s);
+        batch_sync(s);
     };
     // ---- {count, SumPw, Pw0}
     upload();
@@ -358,7 +323,7 @@ void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_c
                                                  W.pw.p, W.us.p, s);
     pass(kEpnpPassSumPw, 3, 0, -1);
     pass(kEpnpPassPw0, 6, 1, 0);
-    pnp_copy(W.h_ecount.p, W.ecount.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
+    batch_copy(W.h_ecount.p, W.ecount.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
     fetch();
     std::vector<EpnpHostSolve> H(n);
     std::vector<int> nblk(n, 0);
@@ -370,7 +335,7 @@ void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_c
         if (c < 4) {
             char buf[120];
             snprintf(buf, sizeof(buf), "EPnP needs at least 4 points (n=%d)", c);
-            failed(jobs[j]->p, buf);
+            fails.note(jobs[j]->p, buf);
             jobs[j]->ok = false;
             live[j] = 0;
             J.n = 0;
@@ -421,12 +386,57 @@ void batch_pnp_epnp(BatchPnpWs& W, std::vector<Winner*>& jobs, const double* h_c
     }
 }
 
+// The PnP batch's part of a hypothesis round (batch_host.h's batch_rounds): one pose per hypothesis, one
+// confidence for all problems, each descriptor with its camera.
+struct RoundsPnp {
+    BatchPnpWs& W;
+    bool epnp;
+    uint64_t seed;
+    const int* d_table;
+    float thr2;
+    double conf;
+    static constexpr int slots = 1;
+    BatchDesc& desc(size_t j, int d) {   // entry j with its camera: cams + 8 d
+        W.h_desc.p[j].cam = d;
+        W.h_desc.p[j].pad = 0;
+        return W.h_desc.p[j].d;
+    }
+    void launch(const std::vector<int>&, BatchRound R, hipStream_t s) {
+        BatchStats& stats = batch_stats();
+        const size_t n = (size_t)R.n, cols = n * (size_t)R.stride;
+        int maxN = 0;
+        for (size_t j = 0; j < n; ++j) maxN = std::max(maxN, W.h_desc.p[j].d.N);
+        W.models.ensure(cols * sizeof(PnpPose));
+        W.counts.ensure(cols);
+        W.h_counts.ensure(cols);
+        if (epnp) W.scratch.ensure(cols * (size_t)kEpnpSplitDoubles);
+        {
+            ProfScope pg("batch_pnp_generate", s);
+            stats.launches += launch_pnp_batch_generate(W.pts.p, W.desc.p, R.n, R.stride, W.cams.p, seed, d_table, epnp,
+                                                        W.models.p, W.counts.p, W.scratch.p, s);
+        }
+        {
+            ProfScope ps("batch_pnp_sweep", s);
+            launch_batch_pnp_sweep(W.pts.p, W.desc.p, R.n, R.stride, maxN, W.cams.p, W.models.p, W.counts.p, thr2, s);
+        }
+        ++stats.launches;
+    }
+    double confidence(int) const { return conf; }
+    void best_changed(const std::vector<BestChange>& ch, hipStream_t s) {
+        for (size_t k = 0; k < ch.size(); ++k)
+            W.h_fetch.p[k] = BatchPnpFetch{W.h_desc.p[ch[k].j].d.slotOff + ch[k].slot, ch[k].d, 0};
+        // in stream order before the next round's generate reuses the pose buffer; the next round rewrites
+        // h_fetch only after its own synchronisation
+        batch_copy(W.fetch.p, W.h_fetch.p, ch.size() * sizeof(BatchPnpFetch), hipMemcpyHostToDevice, s);
+        launch_batch_pnp_fetch(W.fetch.p, (int)ch.size(), W.models.p, W.best.p, s);
+        ++batch_stats().launches;
+    }
+};
+
 int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int* offsets, int B, const mcvM33d* K,
               const double* dist, const RansacConfig& cfg, const RansacConfig* cfgp, mcvV3d* tVecs, mcvV3d* rVecs,
               uint8_t* mask, int* counts, int refineKind = -1) {
-    BatchStats& stats = batch_stats();
-    stats = BatchStats();
-    stats.problems = B;
+    BatchStats& stats = batch_stats_begin(B);
     if (B == 0) return 0;
     const int total = offsets[B];
     std::memset(tVecs, 0, (size_t)B * sizeof(mcvV3d));
@@ -440,11 +450,7 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
     const bool fixed = (cfg.flags & MCV_FLAG_FIXED_ITERS) != 0;
     const bool refine = !(cfg.flags & MCV_FLAG_NO_REFINE);
     const float thr2 = (float)(cfg.threshold * cfg.threshold);
-    int firstFail = -1;
-    std::string firstMsg;
-    auto failed = [&](int p, const std::string& msg) {
-        if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
-    };
+    BatchFailures fails;
     int ok = 0;
     int directPoses = 0;         // poses of the single export's direct solve: their masks never reach the device
     bool maskOnDevice = false;   // W.mask holds the returned mask of every device problem
@@ -458,9 +464,9 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
         char buf[200];
         if (N < 4) {
             snprintf(buf, sizeof(buf), "need at least 4 correspondences (N=%d)", N);
-            failed(p, buf);
+            fails.note(p, buf);
         } else if (!camera_ok(K[p])) {
-            failed(p, "camera matrix needs finite non-zero fx, fy");
+            fails.note(p, "camera matrix needs finite non-zero fx, fy");
         } else if (N <= m) {
             // npoints == model_points (and N == 4 with a 5-point kind): the single export's direct solve
             ++stats.single;
@@ -479,7 +485,7 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
                 ++directPoses;
             } else {
                 const char* e = mcvGetLastError();
-                failed(p, e && *e ? e : "the direct solve found no pose");
+                fails.note(p, e && *e ? e : "the direct solve found no pose");
             }
         } else {
             dev.push_back(p);
@@ -487,131 +493,32 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
     }
     const size_t D = dev.size();
     if (D) {
-        BatchPnpWs& W = thread_batch_pnp_ws();
+        BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
         hipStream_t s = W.stream;
-        // ---- points: the raw image and world points in one copy, packed to PnpPoint rows by one launch
-        auto t0 = std::chrono::steady_clock::now();
-        W.h_raw.ensure((size_t)total * 5);
-        W.raw.ensure((size_t)total * 5);
-        W.pts.ensure((size_t)total * 8);
-        std::memcpy(W.h_raw.p, img, (size_t)total * sizeof(mcvV2d));
-        std::memcpy(W.h_raw.p + 2 * (size_t)total, world, (size_t)total * sizeof(mcvV3d));
+        // ---- points: refine_pack; the table of cameras in one more copy
+        refine_pack(W, img, world, total, s);
+        const auto t0 = std::chrono::steady_clock::now();
         W.h_cams.ensure(D * 8);
         W.cams.ensure(D * 8);
+        std::vector<BatchProblem> prob(D);
         for (size_t d = 0; d < D; ++d) {
             const int p = dev[d];
-            double* c = W.h_cams.p + 8 * d;
-            c[0] = K[p].M[0]; c[1] = K[p].M[4]; c[2] = K[p].M[2]; c[3] = K[p].M[5];
-            for (int k = 0; k < 4; ++k) c[4 + k] = dist ? dist[4 * (size_t)p + k] : 0.0;
+            camera_fill(K, dist, p, W.h_cams.p + 8 * d);
+            prob[d] = BatchProblem{offsets[p], offsets[p + 1] - offsets[p], 0};
         }
-        stats.packUs = us_since(t0);
-        pnp_copy(W.raw.p, W.h_raw.p, (size_t)total * 5 * sizeof(double), hipMemcpyHostToDevice, s);
-        pnp_copy(W.cams.p, W.h_cams.p, D * 8 * sizeof(double), hipMemcpyHostToDevice, s);
-        launch_pnp_pack(W.raw.p, W.raw.p + 2 * (size_t)total, total, W.pts.p, s);
-        ++stats.launches;
-        // ---- OpenCV's sample stream: one cv::RNG((uint64)-1) stream per problem, as each single call draws.
-        // PnPRansacCallback has no checkSubset, so the rows depend on N and the sample size alone: one table
-        // per distinct N of the call.
-        const int* d_table = nullptr;
-        std::vector<int64_t> rowOff(D, 0);
-        if (cv_sampler(cfg)) {
-            t0 = std::chrono::steady_clock::now();
-            const size_t rowInts = (size_t)L.iters * m;
-            std::map<int, int64_t> byN;
-            std::vector<int> rows, all;
-            for (size_t d = 0; d < D; ++d) {
-                const int N = offsets[dev[d] + 1] - offsets[dev[d]];
-                auto it = byN.find(N);
-                if (it == byN.end()) {
-                    cv_table_build(MCV_MODEL_PNP, cfg, nullptr, N, L.iters, rows);
-                    it = byN.emplace(N, (int64_t)byN.size() * L.iters).first;
-                    all.insert(all.end(), rows.begin(), rows.begin() + (ptrdiff_t)rowInts);
-                }
-                rowOff[d] = it->second;
-            }
-            W.h_table.ensure(all.size());
-            W.table.ensure(all.size());
-            std::memcpy(W.h_table.p, all.data(), all.size() * sizeof(int));
-            stats.tableUs = us_since(t0);
-            pnp_copy(W.table.p, W.h_table.p, all.size() * sizeof(int), hipMemcpyHostToDevice, s);
-            d_table = W.table.p;
-        }
+        stats.packUs += us_since(t0);
+        batch_copy(W.cams.p, W.h_cams.p, D * 8 * sizeof(double), hipMemcpyHostToDevice, s);
+        // ---- OpenCV's sample stream (PnPRansacCallback has no checkSubset: one table per distinct N)
+        const int* d_table = cv_tables_by_n(MCV_MODEL_PNP, cfg, prob, L.iters, m, W.h_table, W.table, s);
         // ---- hypothesis rounds
-        std::vector<mcvReplayState> st(D);
-        for (auto& x : st) mcvReplayInit(&x, cfg.maxIters);
-        std::vector<size_t> active(D);
-        for (size_t d = 0; d < D; ++d) active[d] = d;
-        W.desc.ensure(D);
-        W.h_desc.ensure(D);
         W.fetch.ensure(D);
         W.h_fetch.ensure(D);
         W.best.ensure(D * sizeof(PnpPose));
         W.h_best.ensure(D * sizeof(PnpPose));
         MCV_HIP(hipMemsetAsync(W.best.p, 0, D * sizeof(PnpPose), s));
-        for (int64_t begin = 0; !active.empty(); begin += L.per) {
-            // a round holds the hypotheses [begin, begin + per) of every problem still searching; the problems
-            // are compacted, so problem j of the round owns the slots [j stride, j stride + count)
-            std::vector<size_t> run;
-            int stride = 0, maxN = 0;
-            for (size_t d : active) {
-                const int64_t left = (int64_t)st[d].niters - begin;
-                if (st[d].stopped || left <= 0) continue;
-                const int p = dev[d];
-                BatchPnpDesc& X = W.h_desc.p[run.size()];
-                X.d.ptOff = offsets[p];
-                X.d.N = offsets[p + 1] - offsets[p];
-                X.d.hypBegin = (int)begin;
-                X.d.hypCount = (int)std::min<int64_t>(left, L.per);
-                X.d.rowOff = rowOff[d];
-                X.cam = (int)d;
-                X.pad = 0;
-                stride = std::max(stride, X.d.hypCount);
-                maxN = std::max(maxN, X.d.N);
-                run.push_back(d);
-            }
-            active.swap(run);
-            if (active.empty()) break;
-            const size_t n = active.size();
-            const size_t cols = n * (size_t)stride;
-            for (size_t j = 0; j < n; ++j) W.h_desc.p[j].d.slotOff = (int64_t)j * stride;
-            W.models.ensure(cols * sizeof(PnpPose));
-            W.counts.ensure(cols);
-            W.h_counts.ensure(cols);
-            if (epnp) W.scratch.ensure(cols * (size_t)kEpnpSplitDoubles);
-            pnp_copy(W.desc.p, W.h_desc.p, n * sizeof(BatchPnpDesc), hipMemcpyHostToDevice, s);
-            {
-                ProfScope pg("batch_pnp_generate", s);
-                stats.launches += launch_pnp_batch_generate(W.pts.p, W.desc.p, (int)n, stride, W.cams.p, cfg.seed,
-                                                            d_table, epnp, W.models.p, W.counts.p, W.scratch.p, s);
-            }
-            {
-                ProfScope ps("batch_pnp_sweep", s);
-                launch_batch_pnp_sweep(W.pts.p, W.desc.p, (int)n, stride, maxN, W.cams.p, W.models.p, W.counts.p, thr2,
-                                       s);
-            }
-            ++stats.launches;
-            pnp_copy(W.h_counts.p, W.counts.p, cols * sizeof(int), hipMemcpyDeviceToHost, s);
-            pnp_sync(s);
-            ++stats.rounds;
-            stats.problemRounds += (long long)n;
-            size_t nFetch = 0;
-            for (size_t j = 0; j < n; ++j) {
-                const size_t d = active[j];
-                const BatchDesc& X = W.h_desc.p[j].d;
-                const int64_t before = st[d].bestIndex;
-                mcvReplayChunk(&st[d], W.h_counts.p + X.slotOff, begin, X.hypCount, X.N, m, cfg.confidence,
-                               fixed ? 1 : 0);
-                if (begin + X.hypCount >= st[d].niters) st[d].stopped = 1;
-                if (st[d].bestIndex != before)
-                    W.h_fetch.p[nFetch++] = BatchPnpFetch{X.slotOff + (st[d].bestIndex - begin), (int)d, 0};
-            }
-            if (nFetch) {   // in stream order before the next round's generate reuses the pose buffer
-                pnp_copy(W.fetch.p, W.h_fetch.p, nFetch * sizeof(BatchPnpFetch), hipMemcpyHostToDevice, s);
-                launch_batch_pnp_fetch(W.fetch.p, (int)nFetch, W.models.p, W.best.p, s);
-                ++stats.launches;
-                // the next round rewrites h_fetch only after its own synchronisation
-            }
-        }
+        RoundsPnp F{W, epnp, cfg.seed, d_table, thr2, cfg.confidence};
+        std::vector<mcvReplayState> st;
+        batch_rounds(F, prob, st, cfg.maxIters, L.per, L.per, m, fixed, s);
         // ---- winners: mask and count, all in one launch
         std::vector<Winner> win;
         int winMaxN = 0;
@@ -620,15 +527,10 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
         for (size_t d = 0; d < D; ++d) {
             const int p = dev[d];
             if (st[d].bestIndex < 0) {
-                failed(p, "RANSAC found no pose with >= 4 inliers");
+                fails.note(p, "RANSAC found no pose with >= 4 inliers");
                 continue;
             }
-            Winner w{};
-            w.d = d;
-            w.p = p;
-            w.ptOff = offsets[p];
-            w.N = offsets[p + 1] - offsets[p];
-            w.ok = true;
+            const Winner w{d, p, offsets[p], offsets[p + 1] - offsets[p]};
             W.h_fin.p[win.size()] = BatchPnpFin{w.ptOff, w.N, (int)d, (int)d};
             winMaxN = std::max(winMaxN, w.N);
             win.push_back(w);
@@ -639,21 +541,21 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
             W.h_cnt.ensure(n);
             W.mask.ensure((size_t)total);
             W.h_mask.ensure((size_t)total);
-            pnp_copy(W.fin.p, W.h_fin.p, n * sizeof(BatchPnpFin), hipMemcpyHostToDevice, s);
+            batch_copy(W.fin.p, W.h_fin.p, n * sizeof(BatchPnpFin), hipMemcpyHostToDevice, s);
             MCV_HIP(hipMemsetAsync(W.cnt.p, 0, n * sizeof(int), s));
             MCV_HIP(hipMemsetAsync(W.mask.p, 0, (size_t)total, s));
             launch_batch_pnp_mask(W.pts.p, W.fin.p, (int)n, winMaxN, W.cams.p, W.best.p, thr2, W.mask.p, W.cnt.p, s);
             ++stats.launches;
-            pnp_copy(W.h_best.p, W.best.p, D * sizeof(PnpPose), hipMemcpyDeviceToHost, s);
-            pnp_copy(W.h_cnt.p, W.cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
-            pnp_copy(W.h_mask.p, W.mask.p, (size_t)total, hipMemcpyDeviceToHost, s);
-            pnp_sync(s);
+            batch_copy(W.h_best.p, W.best.p, D * sizeof(PnpPose), hipMemcpyDeviceToHost, s);
+            batch_copy(W.h_cnt.p, W.cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
+            batch_copy(W.h_mask.p, W.mask.p, (size_t)total, hipMemcpyDeviceToHost, s);
+            batch_sync(s);
             std::vector<Winner*> jobs;
             for (size_t k = 0; k < n; ++k) {
                 Winner& w = win[k];
                 w.count = W.h_cnt.p[k];
                 if (w.count <= 0) {   // cannot happen for a replay winner (its sweep count was >= m): fail closed
-                    failed(w.p, "the winning pose has no inliers");
+                    fails.note(w.p, "the winning pose has no inliers");
                     w.ok = false;
                     continue;
                 }
@@ -663,18 +565,18 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
                 for (int k3 = 0; k3 < 3; ++k3) w.t[k3] = pose.t[k3];
                 if (refine) jobs.push_back(&w);
             }
-            // solvePnPRansac's tail (p_finalize): ITERATIVE refines the RANSAC pose with LM, every other kind
-            // runs EPnP on the inliers
-            if (pnp_kind(cfg.pnpKind) == 0) batch_pnp_lm(W, jobs, W.h_cams.p, s);
-            else batch_pnp_epnp(W, jobs, W.h_cams.p, world, total, failed, s);
+            // solvePnPRansac's tail (p_finalize): ITERATIVE refines the RANSAC pose with LM, masked in place over
+            // every winner's rows; every other kind runs EPnP on the inliers
+            if (pnp_kind(cfg.pnpKind) == 0)
+                batch_pnp_lockstep<PnpLmStepper>(W, jobs, W.h_cams.p, W.pts.p, W.mask.p, false, s);
+            else batch_pnp_epnp(W, jobs, W.h_cams.p, world, total, fails, s);
             maskOnDevice = true;
             for (const Winner& w : win) {
                 if (!w.ok) {   // its device mask slice is not the (zero) one the call returns
                     maskOnDevice = false;
                     continue;
                 }
-                rVecs[w.p].X = w.r[0]; rVecs[w.p].Y = w.r[1]; rVecs[w.p].Z = w.r[2];
-                tVecs[w.p].X = w.t[0]; tVecs[w.p].Y = w.t[1]; tVecs[w.p].Z = w.t[2];
+                winner_store(w, rVecs, tVecs);
                 counts[w.p] = w.count;
                 std::memcpy(mask + w.ptOff, W.h_mask.p + w.ptOff, (size_t)w.N);
                 ++ok;
@@ -686,29 +588,17 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
         // read where the rounds left them on the device. Only what never got there is sent now: the points
         // when no problem ran on the device, the mask when a direct solve or a failed inlier solve made the
         // returned one differ from the device's.
-        BatchPnpWs& W = thread_batch_pnp_ws();
+        BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
         hipStream_t s = W.stream;
         if (!D) refine_pack(W, img, world, total, s);
-        if (!maskOnDevice || directPoses > 0) {
-            W.mask.ensure((size_t)total);
-            W.h_mask.ensure((size_t)total);
-            std::memcpy(W.h_mask.p, mask, (size_t)total);
-            pnp_copy(W.mask.p, W.h_mask.p, (size_t)total, hipMemcpyHostToDevice, s);
-        }
+        if (!maskOnDevice || directPoses > 0) mask_upload(W, mask, total, s);
         std::vector<uint8_t> run((size_t)B);
         for (int p = 0; p < B; ++p) run[(size_t)p] = counts[p] > 0 ? 1 : 0;
         RefinePlan R;
-        refine_plan(offsets, B, K, mask, run.data(), failed, R);
+        refine_plan(offsets, B, K, mask, run.data(), fails, R);
         refine_on_device(W, R, offsets, B, K, dist, refineKind, tVecs, rVecs, nullptr, s);
     }
-    if (firstFail >= 0) {
-        // a problem that failed returns a zero pose, count and mask slice; the first one is named
-        char buf[400];
-        snprintf(buf, sizeof(buf), "%s: problem %d: %s", who, firstFail, firstMsg.c_str());
-        set_last_error(buf);
-    } else {
-        clear_last_error();
-    }
+    fails.report(who);   // a problem that failed returns a zero pose, count and mask slice; the first one is named
     return ok;
 }
 
@@ -718,27 +608,22 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
 
 using namespace mcv;
 
+// The kernels' grids take at most 65535 tiles of a problem's rows.
+static void pnp_check_sizes(const char* who, const int* offsets, int B) {
+    const int where = refine_batch_check_sizes(offsets, B, 65535 * kBatchPnpTile);
+    if (where >= 0) fail("%s: problem %d has more than %d correspondences", who, where, 65535 * kBatchPnpTile);
+}
+
 // The argument checks cvSolvePnPRansacBatch and cvSolvePnPRansacRefineBatch share; returns the configuration.
 static RansacConfig pnp_batch_check(const char* who, const mcvV2d* imgPoints, const mcvV3d* worldPoints,
                                     const int* offsets, int B, const mcvM33d* K, const RansacConfig* cfgp,
                                     mcvV3d* tVecs, mcvV3d* rVecs, uint8_t* mask, int* counts) {
     if (!imgPoints || !worldPoints || !offsets || !K || !tVecs || !rVecs || !mask || !counts)
         fail("%s: null argument (imgPoints, worldPoints, offsets, K, tVecs, rVecs, mask and counts are required)", who);
-    if (B < 0) fail("%s: negative B (%d)", who, B);
-    if (offsets[0] != 0) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
-    for (int p = 0; p < B; ++p)
-        if (offsets[p + 1] < offsets[p])
-            fail("%s: offsets decrease at problem %d (%d -> %d)", who, p, offsets[p], offsets[p + 1]);
+    check_batch_offsets(who, offsets, B);
     const RansacConfig cfg = cfgp ? *cfgp : pnp_config(100, 8.0f, 0.99, 0);
-    check_flags(cfg, who);
-    if (cfg.method != MCV_METHOD_RANSAC) fail("%s: unsupported method %d (only MCV_METHOD_RANSAC)", who, cfg.method);
-    if (cfg.flags & MCV_FLAG_FUSED_ERROR) fail("%s: unsupported flag MCV_FLAG_FUSED_ERROR", who);
-    if (cfg.flags & MCV_FLAG_FAST_MINIMAL) fail("%s: unsupported flag MCV_FLAG_FAST_MINIMAL", who);
-    if (cfg.deviceCount > 1) fail("%s: unsupported deviceCount %d (one GPU per call)", who, cfg.deviceCount);
-    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);
-    for (int p = 0; p < B; ++p)
-        if (offsets[p + 1] - offsets[p] > 65535 * kBatchPnpTile)
-            fail("%s: problem %d has more than %d correspondences", who, p, 65535 * kBatchPnpTile);
+    check_batch_config(who, cfg);
+    pnp_check_sizes(who, offsets, B);
     return cfg;
 }
 
@@ -778,52 +663,28 @@ extern "C" MCV_API int cvRefinePnPBatch(const mcvV2d* imgPoints, const mcvV3d* w
         const char* who = "cvRefinePnPBatch";
         if (!imgPoints || !worldPoints || !offsets || !K || !tVecs || !rVecs)
             fail("%s: null argument (imgPoints, worldPoints, offsets, K, tVecs and rVecs are required)", who);
-        if (B < 0) fail("%s: negative B (%d)", who, B);
-        int where = 0;
-        const int bad = refine_batch_check_offsets(offsets, B, &where);
-        if (bad == 1) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
-        if (bad == 2)
-            fail("%s: offsets decrease at problem %d (%d -> %d)", who, where, offsets[where], offsets[where + 1]);
-        where = refine_batch_check_sizes(offsets, B, 65535 * kBatchPnpTile);
-        if (where >= 0) fail("%s: problem %d has more than %d correspondences", who, where, 65535 * kBatchPnpTile);
+        check_batch_offsets(who, offsets, B);
+        pnp_check_sizes(who, offsets, B);
         if (refineKind != 0 && refineKind != 1)
             fail("%s: unsupported refineKind %d (0 = LM, 1 = VVS)", who, refineKind);
-        BatchStats& stats = batch_stats();
-        stats = BatchStats();
-        stats.problems = B;
+        batch_stats_begin(B);
         if (B == 0) return 0;
-        int firstFail = -1;
-        std::string firstMsg;
-        auto failed = [&](int p, const std::string& msg) {
-            if (firstFail < 0 || p < firstFail) { firstFail = p; firstMsg = msg; }
-        };
+        BatchFailures fails;
         RefinePlan R;
-        refine_plan(offsets, B, K, mask, nullptr, failed, R);
+        refine_plan(offsets, B, K, mask, nullptr, fails, R);
         // a call in which no problem can run needs no device, as the single call that refuses its N
         if (!R.jobs.empty()) require_device();
         if (refined) std::memset(refined, 0, (size_t)B);
         int ok = 0;
         if (!R.jobs.empty()) {
-            BatchPnpWs& W = thread_batch_pnp_ws();
+            BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
             hipStream_t s = W.stream;
             const int total = offsets[B];
             refine_pack(W, imgPoints, worldPoints, total, s);
-            if (mask) {
-                W.mask.ensure((size_t)total);
-                W.h_mask.ensure((size_t)total);
-                std::memcpy(W.h_mask.p, mask, (size_t)total);
-                pnp_copy(W.mask.p, W.h_mask.p, (size_t)total, hipMemcpyHostToDevice, s);
-            }
+            if (mask) mask_upload(W, mask, total, s);
             ok = refine_on_device(W, R, offsets, B, K, distortionCoeffs, refineKind, tVecs, rVecs, refined, s);
         }
-        if (firstFail >= 0) {
-            // a problem that was not refined keeps its pose; the first one is named
-            char buf[400];
-            snprintf(buf, sizeof(buf), "%s: problem %d: %s", who, firstFail, firstMsg.c_str());
-            set_last_error(buf);
-        } else {
-            clear_last_error();
-        }
+        fails.report(who);   // a problem that was not refined keeps its pose; the first one is named
         return ok;
     })
 }
@@ -836,12 +697,7 @@ extern "C" MCV_API int mcvHostRefinePnPBatchLayout(const int* offsets, int B, co
     MCV_GUARD(-1, {
         const char* who = "mcvHostRefinePnPBatchLayout";
         if (!offsets || !counts || !compOff) fail("%s: null argument", who);
-        if (B < 0) fail("%s: negative B (%d)", who, B);
-        int where = 0;
-        const int bad = refine_batch_check_offsets(offsets, B, &where);
-        if (bad == 1) fail("%s: offsets[0] must be 0 (is %d)", who, offsets[0]);
-        if (bad == 2)
-            fail("%s: offsets decrease at problem %d (%d -> %d)", who, where, offsets[where], offsets[where + 1]);
+        check_batch_offsets(who, offsets, B);
         return refine_batch_layout(offsets, B, mask, counts, compOff);
     })
 }

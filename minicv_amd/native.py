@@ -283,6 +283,7 @@ SIGNATURES = {
     "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),
     "mcvTestBundleAdjustStats": (_I, [_P]),
     "mcvHostBatchLayout": (_I, [_P, _I, _I, _I, C.c_longlong, _P, _P]),
+    "mcvHostBatchRound": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "mcvTestBatchCap": (C.c_longlong, [C.c_longlong]),
     "mcvTestBatchStats": (_I, [_P]),
     "mcvTestBatchSweep": (_I, [_I, _P, _P, _I, _P, _P, _F, _I, _P]),

@@ -1,7 +1,11 @@
 """CPU tests of cvFindModelBatch (B independent RANSAC problems in one call): every argument check runs
 before the device is touched, and the index arithmetic of a call (mcvHostBatchLayout: the descriptor
-table, 64-bit slot offsets, the rounds under the slot cap) is checked against its definition."""
+table, 64-bit slot offsets, the rounds under the slot cap) and the plan of a hypothesis round
+(mcvHostBatchRound: which problems run, their counts, the compact stride) are checked against their definitions,
+the plan also under sanitizers in a program of its own."""
 import ctypes as C
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -194,3 +198,128 @@ def test_batch_cap_hook_round_trip(native):
     finally:
         L.mcvTestBatchCap(prev)
     assert prev == 1 << 21
+
+
+# ---- the plan of a hypothesis round ------------------------------------------------------------------
+SIZES3 = np.array([30, 7, 64], dtype=np.int32)            # three device problems
+PT3 = np.array([0, 30, 37], dtype=np.int32)
+ROW3 = np.array([0, 10, 20], dtype=np.int64)
+
+
+def _round(pt_off, n, row_off, niters, stopped, active, begin, size):
+    """mcvHostBatchRound on numpy arrays: (the round's device indices, its descriptors, stride)."""
+    D, nA = len(n), len(active)
+    niters = np.ascontiguousarray(niters, dtype=np.int64)
+    stopped = np.ascontiguousarray(stopped, dtype=np.int32)
+    active = np.ascontiguousarray(active, dtype=np.int32)
+    desc = np.full((max(nA, 1), 6), -7, dtype=np.int64)
+    out = np.full(max(nA, 1), -7, dtype=np.int32)
+    info = np.full(2, -7, dtype=np.int64)
+    k = N.lib().mcvHostBatchRound(pt_off.ctypes.data, n.ctypes.data, row_off.ctypes.data, niters.ctypes.data,
+                                  stopped.ctypes.data, D, active.ctypes.data, nA, begin, size, desc.ctypes.data,
+                                  out.ctypes.data, info.ctypes.data)
+    assert k >= 0, N.last_error()
+    assert info[0] == k and (desc[k:] == -7).all() and (out[k:] == -7).all()   # nothing past the round is written
+    return out[:k].tolist(), desc[:k], int(info[1])
+
+
+def _expected_round(pt_off, n, row_off, niters, stopped, active, begin, size):
+    """The definition, in numpy."""
+    a = np.asarray(active, dtype=np.int64)
+    niters, stopped = np.asarray(niters, dtype=np.int64), np.asarray(stopped)
+    keep = a[(stopped[a] == 0) & (niters[a] - begin > 0)]
+    cnt = np.minimum(niters[keep] - begin, size)
+    stride = int(cnt.max()) if len(keep) else 0
+    desc = np.stack([pt_off[keep], n[keep], np.full(len(keep), begin), cnt, np.arange(len(keep)) * stride,
+                     row_off[keep]], axis=1).astype(np.int64).reshape(len(keep), 6)
+    return keep.tolist(), desc, stride
+
+
+def _walk(pt_off, n, row_off, niters, stopped, sizes, after_round=None):
+    """Rounds of the given sizes from begin = 0 on, the active list carried along as the driver does; returns
+    every round's hypothesis counts. after_round(r, niters, stopped) plays the replay's part."""
+    niters, stopped = np.array(niters, dtype=np.int64), np.array(stopped, dtype=np.int32)
+    active, begin, seen = list(range(len(n))), 0, []
+    for r, size in enumerate(sizes):
+        got = _round(pt_off, n, row_off, niters, stopped, active, begin, size)
+        exp = _expected_round(pt_off, n, row_off, niters, stopped, active, begin, size)
+        assert got[0] == exp[0] and got[2] == exp[2]
+        np.testing.assert_array_equal(got[1], exp[1])
+        assert got[2] == (int(got[1][:, 3].max()) if got[0] else 0)      # the stride is the largest count
+        seen.append(got[1][:, 3].tolist())
+        active, begin = got[0], begin + size
+        if after_round:
+            after_round(r, niters, stopped)
+    return seen, active
+
+
+def test_round_plan_splits_the_budget(native):
+    seen, active = _walk(PT3, SIZES3, ROW3, [10] * 3, [0] * 3, [4, 4, 4, 4])
+    assert seen == [[4] * 3, [4] * 3, [2] * 3, []] and active == []
+
+
+def test_round_plan_follows_a_lowered_budget(native):
+    def lower(r, niters, stopped):
+        if r == 0:
+            niters[1] = 5
+    seen, active = _walk(PT3, SIZES3, ROW3, [10] * 3, [0] * 3, [4, 4, 4], lower)
+    assert seen == [[4, 4, 4], [4, 1, 4], [2, 2]] and active == [0, 2]
+
+
+def test_round_plan_drops_a_stopped_problem(native):
+    seen, active = _walk(PT3, SIZES3, ROW3, [10] * 3, [0, 1, 0], [4, 4])
+    assert seen == [[4, 4], [4, 4]] and active == [0, 2]
+    ids, desc, stride = _round(PT3, SIZES3, ROW3, [10] * 3, [0, 1, 0], [0, 1, 2], 0, 4)
+    assert desc[:, 0].tolist() == [0, 37] and desc[:, 4].tolist() == [0, 4] and desc[:, 5].tolist() == [0, 20]
+
+
+def test_round_plan_smaller_first_round(native):
+    seen, active = _walk(PT3, SIZES3, ROW3, [10] * 3, [0] * 3, [2, 4, 4, 4])
+    assert seen == [[2] * 3, [4] * 3, [4] * 3, []]
+
+
+def test_round_plan_single_problem_and_all_stopped(native):
+    one = (PT3[:1], SIZES3[:1], ROW3[:1])
+    seen, _ = _walk(*one, [10], [0], [4, 4, 4, 4])
+    assert seen == [[4], [4], [2], []]
+    ids, desc, stride = _round(PT3, SIZES3, ROW3, [10] * 3, [1] * 3, [0, 1, 2], 0, 4)
+    assert ids == [] and len(desc) == 0 and stride == 0
+    ids, desc, stride = _round(PT3, SIZES3, ROW3, [10] * 3, [0] * 3, [], 0, 4)
+    assert ids == [] and stride == 0
+
+
+def test_round_plan_refuses_bad_arguments(native):
+    L = N.lib()
+    nit, stp = np.full(3, 10, dtype=np.int64), np.zeros(3, dtype=np.int32)
+    act = np.arange(3, dtype=np.int32)
+    desc, out, info = np.zeros((3, 6), dtype=np.int64), np.zeros(3, dtype=np.int32), np.zeros(2, dtype=np.int64)
+
+    def call(pt=PT3, n=SIZES3, niters=nit, stopped=stp, D=3, active=act, nA=3, begin=0, size=4, desc=desc, out=out,
+             info=info):
+        p = lambda a: None if a is None else a.ctypes.data
+        return L.mcvHostBatchRound(p(pt), p(n), p(ROW3), p(niters), p(stopped), D, p(active), nA, begin, size, p(desc),
+                                   p(out), p(info))
+
+    assert call() == 3
+    for null in ("pt", "n", "niters", "stopped", "active", "desc", "out", "info"):
+        assert call(**{null: None}) == -1 and "mcvHostBatchRound" in native.last_error()
+    for bad in (dict(D=-1), dict(nA=-1), dict(nA=4), dict(begin=-1), dict(begin=1 << 31), dict(size=0),
+                dict(size=1 << 31)):
+        assert call(**bad) == -1
+    for lst in ([0, 2, 1], [0, 1, 1], [0, 1, 3], [-1, 0, 1]):
+        assert call(active=np.array(lst, dtype=np.int32)) == -1 and "ascending" in native.last_error()
+
+
+def test_index_code_under_sanitizers(tmp_path):
+    """tests/asan/ransac_batch_index_asan_main.cpp: a stand-alone program (its own main, nothing preloaded,
+    nothing loaded into Python) over ransac_batch_index.h, built with -fsanitize=address,undefined."""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = tmp_path / "ransac_batch_index_asan"
+    src = N.ROOT / "tests" / "asan" / "ransac_batch_index_asan_main.cpp"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{N.ROOT / 'minicv_amd' / 'csrc'}", str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ransac_batch_index_asan ok" in r.stdout and "ERROR" not in r.stderr
