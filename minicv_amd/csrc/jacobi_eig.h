@@ -19,7 +19,8 @@
 // dependent (k, l) indexing would otherwise put the matrices in scratch. On the host (twins, the
 // single-lane winner kernels) it is a private array (EigWsLocal). Both run the same code and round
 // identically (-ffp-contract=off; division and sqrt are IEEE on both sides).
-// indR / indC are kept in registers as 4-bit fields of one 32-bit word each. The rotation's five
+// indR / indC are kept in registers: 4-bit fields of one 32-bit word each in the generic loop, byte
+// offsets in two 64-bit words in the device's lane-slice loop (eig9_rotations_lane). The rotation's five
 // quotients run gfx950's refined-reciprocal division inside its exact domain (eig_rotation).
 #pragma once
 
@@ -94,9 +95,17 @@ struct EigWsLane {
 // with the two at i = k, l sent to a junk slot, whose (0, 0) rotated to (+0, +0) and never won a
 // rescan: the same result with 12 more fp64 operations, 4 more LDS accesses and two more rescan steps
 // per rotation). The host / generic path keeps the 9-pair branch-free form.
+// Word 7 holds what the lane-slice loop derives from (k, l), so that the pivot's slot alone (the row
+// index) names them: k << 4 | l, and for the loop's byte trackers (eig9_rotations_lane) the shift of
+// column k's byte (column l's when k = 0), the shift of row l's byte (row k's when l = 8) and
+// eig_row_off(l).
 struct EigPairLut {
     uint32_t w[36][8];
 };
+// Byte offset of A(r, r + 1) in the packed upper triangle: 8 (r (15 - r) / 2 - 1 + r + 1) - 8 r. Row r's
+// element A(r, c) lies at eig_row_off(r) + 8 (c - 1), column c's element A(r, c) at 8 (c - 1) +
+// eig_row_off(r); at most 224, one byte.
+constexpr uint32_t eig_row_off(int r) { return (uint32_t)(4 * r * (15 - r)); }
 constexpr EigPairLut eig_make_pair_lut7() {
     EigPairLut t{};
     for (int k = 0; k < 9; ++k)
@@ -109,6 +118,8 @@ constexpr EigPairLut eig_make_pair_lut7() {
                 const int e1 = i < l ? ((i * (15 - i)) >> 1) - 1 + l : ((l * (15 - l)) >> 1) - 1 + i;
                 t.w[row][j++] = (uint32_t)(8 * e0) | ((uint32_t)(8 * e1) << 16);
             }
+            const uint32_t shCk = 8u * (uint32_t)(k == 0 ? l - 1 : k - 1), shRl = 8u * (uint32_t)(l == 8 ? k : l);
+            t.w[row][7] = (uint32_t)((k << 4) | l) | (shCk << 8) | (shRl << 16) | (eig_row_off(l) << 24);
         }
     return t;
 }
@@ -172,6 +183,210 @@ MCV_HD void eig_pick(double& v, int& kl, double v2, int kl2) {
     kl = t ? kl2 : kl;
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// The rotation loop of eig9_jacobi on a lane slice in LDS (EigWsLane): the same pivots, operations and
+// stored values as the generic loop, with the bookkeeping cut down to what a lane has to issue.
+//
+// Trackers. indR / indC are one byte per row 0..7 (tr) and per column 1..8 (tc) of two 64-bit words,
+// and hold the byte offset of the tracked element inside its row / column: 8 (c - 1) for
+// indR[i] = c, eig_row_off(r) for indC[i] = r. A candidate's LDS address is then one add of a byte
+// field to a loop-invariant base (rb[i] = slice + eig_row_off(i), cb[i] = slice + 8 (i - 1)), with no
+// multiply. The pivot tree carries that address beside the value; the pivot's slot is the row of
+// kEigPairLut7, whose word 7 gives k, l and the tracker shifts (one table load, whose address is
+// taken once before the loop).
+//
+// Rescans. A tracker's result is the first index of the largest magnitude in its range if that is
+// above zero, and the range's start otherwise, over values none of which is a signalling NaN (they
+// are sums of products), a NaN never winning and never raising the running value: `mag < |x|` is
+// false for a NaN x, and the generic loop's running value starts at 0 and only takes winners.
+//   column trackers (range j < k or j < l - 1, a prefix of the 7 pairs): a forward scan with the
+//     running magnitude f = max(f, |x|) over all pairs (maxNum drops a NaN x, as the select did;
+//     what it adds past the range is never compared in range) and the unchanged compare f < |x|;
+//   row trackers (range j >= k or j >= l - 1, a suffix): a backward scan from j = 6, b = max(b, |x|)
+//     started at the smallest subnormal, the pair winning when |x| >= b. Every in-range holder of
+//     the range's maximum M wins when visited (b <= M there), nothing smaller that comes before all
+//     of them does (b >= M by then), so the last winner is the first holder of M; with M = 0 nothing
+//     wins (0 >= 2^-1074 is false), and a NaN neither wins nor moves b.
+// Either way a step is a compare, a max, a mask `and` and one select of the carried address, against
+// two compares and three selects with the signed running value. A tracker carries the LDS address of
+// its winner (the pair addresses are there already) and starts at its range's start; the byte to
+// store is that address minus the row's / column's base. The two inserts that have no slot (column
+// k = 0, row l = 8) are sent to the byte the other insert of the same word rewrites right after.
+typedef __attribute__((address_space(3))) double EigLdsF64;
+typedef uint32_t EigU4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) const EigU4 EigGlobalU4;
+__device__ __forceinline__ double eig_lds_ld(uint32_t a) { return *reinterpret_cast<const EigLdsF64*>(a); }
+__device__ __forceinline__ void eig_lds_st(uint32_t a, double v) { *reinterpret_cast<EigLdsF64*>(a) = v; }
+// max(m, |x|) as the one instruction it is (maxNum: a NaN x leaves m; m is never a NaN here). Through the
+// generic fmax the compiler re-quiets the running value before every step, one more instruction each.
+__device__ __forceinline__ double eig_max_abs(double m, double x) {
+    double r;
+    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(x));
+    return r;
+}
+__device__ __forceinline__ uint32_t eig_byte(uint64_t x, int i) { return (uint32_t)(x >> (8 * i)) & 0xffu; }
+__device__ __forceinline__ uint64_t eig_set_byte(uint64_t x, uint32_t sh, uint32_t v) {   // v < 256
+    return (x & ~((uint64_t)0xff << sh)) | ((uint64_t)v << sh);
+}
+
+// A pivot candidate (value, LDS address) and the first maximum by magnitude of candidates I .. I + N - 1 in
+// scan order as a pairwise tree: the later one wins only when strictly greater (eig_pick).
+struct EigCand {
+    double v;
+    uint32_t a;
+};
+__device__ __forceinline__ EigCand eig_first(EigCand x, EigCand y) {
+    const bool t = __builtin_fabs(x.v) < __builtin_fabs(y.v);
+    return EigCand{t ? y.v : x.v, t ? y.a : x.a};
+}
+template <int I, int N, class F>
+__device__ __forceinline__ EigCand eig_first_tree(F& cand) {
+    if constexpr (N == 1) return cand(I);
+    else return eig_first(eig_first_tree<I, N / 2>(cand), eig_first_tree<I + N / 2, N / 2>(cand));
+}
+
+template <bool LOG>
+__device__ __forceinline__ int eig9_rotations_lane(EigWsLane& ws, bool& logOk, EigRot* log, int logStride,
+                                                   int logCap) {
+    constexpr int n = 9, P7 = n - 2;
+    const uint32_t lb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)(char*)ws.p;
+    uint64_t tr = 0, tc = 0;
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+        if (k < n - 1) {
+            uint32_t m = 8 * k;
+            double mv = __builtin_fabs(ws[eig_tri(k, k + 1)]);
+#pragma unroll
+            for (int i = k + 2; i < n; ++i) {
+                const double val = __builtin_fabs(ws[eig_tri(k, i)]);
+                if (mv < val) mv = val, m = 8 * (i - 1);
+            }
+            tr |= (uint64_t)m << (8 * k);
+        }
+        if (k > 0) {
+            uint32_t m = eig_row_off(0);
+            double mv = __builtin_fabs(ws[eig_tri(0, k)]);
+#pragma unroll
+            for (int i = 1; i < k; ++i) {
+                const double val = __builtin_fabs(ws[eig_tri(i, k)]);
+                if (mv < val) mv = val, m = eig_row_off(i);
+            }
+            tc |= (uint64_t)m << (8 * (k - 1));
+        }
+    }
+    uint32_t rb[n - 1], cb[n - 1];
+#pragma unroll
+    for (int i = 0; i < n - 1; ++i) {
+        rb[i] = lb + eig_row_off(i);
+        cb[i] = lb + 8 * i;   // column i + 1
+    }
+    // the table's address in a scalar pair for the whole loop (as a constant it is rebuilt on every trip)
+    uint64_t lut = (uint64_t)(uintptr_t)&kEigPairLut7;
+    asm volatile("" : "+s"(lut));
+    int it = 0;
+    for (; it < n * n * 30; ++it) {
+        // pivot: the first maximum over the 16 candidates in OpenCV's scan order (rows 0..7, then columns
+        // 1..8), as a pairwise tree (first wins on ties), the element's address carried along
+        // (each candidate's full address sits in a register, opaque to the compiler: with the constant part
+        // visible it carries the candidate's position instead and rebuilds the address from it with a
+        // chain of compares and selects)
+        auto cand = [&](int i) {
+            uint32_t a = i < 8 ? rb[i & 7] + eig_byte(tr, i & 7) : cb[i & 7] + eig_byte(tc, i & 7);
+            asm("" : "+v"(a));
+            return EigCand{eig_lds_ld(a), a};
+        };
+        const EigCand piv = eig_first_tree<0, 16>(cand);
+        const double p = piv.v;   // = A(k, l)
+        const uint32_t pa = piv.a;
+        if (__builtin_fabs(p) <= kDblEpsilon) break;
+        const EigGlobalU4* lr = reinterpret_cast<const EigGlobalU4*>(lut + ((pa - lb) << 2));   // 32 B per row
+        const EigU4 q0 = lr[0], q1 = lr[1];
+        const uint32_t qw[P7] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z};
+        const uint32_t kl = q1.w & 0xffu, k = kl >> 4, l = kl & 15u;
+        const uint32_t shCk = (q1.w >> 8) & 0xffu, shRl = (q1.w >> 16) & 0xffu, shRk = k << 3, shCl = (l << 3) - 8;
+        const uint32_t wka = lb + 8 * kEigW + shRk, wla = lb + 8 * kEigW + (l << 3);
+        // every operand of the rotation is read before anything is written back
+        const double wk = eig_lds_ld(wka), wl = eig_lds_ld(wla);
+        uint32_t a0[P7], a1[P7];
+        double x0[P7], x1[P7], wa[n], wb[n];
+#pragma unroll
+        for (int j = 0; j < P7; ++j) {
+            a0[j] = lb + (qw[j] & 0xffffu);
+            a1[j] = lb + (qw[j] >> 16);
+            x0[j] = eig_lds_ld(a0[j]);
+            x1[j] = eig_lds_ld(a1[j]);
+        }
+        const uint32_t vka = lb + 8 * kEigV + 72 * k, vla = lb + 8 * kEigV + 72 * l;
+        if constexpr (!LOG) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) {
+                wa[i] = eig_lds_ld(vka + 8 * i);
+                wb[i] = eig_lds_ld(vla + 8 * i);
+            }
+        }
+        const double y = (wl - wk) * 0.5;
+        double c, s, t;
+        eig_rotation(p, y, c, s, t);
+        if constexpr (LOG) {
+            if (it >= logCap || !eig_rot_c_ok(c)) {
+                logOk = false;
+                break;
+            }
+            EigRot e;
+            const uint64_t cb64 = (__builtin_bit_cast(uint64_t, c) & ((1ull << 53) - 1)) | ((uint64_t)kl << 53);
+            e.c = __builtin_bit_cast(double, cb64);   // eig_rot_pack(c, k, l)
+            e.s = s;
+            log[(int64_t)it * logStride] = e;
+        }
+        eig_lds_st(pa, 0.0);
+        eig_lds_st(wka, wk - t);
+        eig_lds_st(wla, wl + t);
+        double nk[P7], nl[P7];
+#pragma unroll
+        for (int j = 0; j < P7; ++j) {
+            nk[j] = x0[j] * c - x1[j] * s;
+            nl[j] = x0[j] * s + x1[j] * c;
+            eig_lds_st(a0[j], nk[j]);
+            eig_lds_st(a1[j], nl[j]);
+        }
+        if constexpr (!LOG) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) {
+                eig_lds_st(vka + 8 * i, wa[i] * c - wb[i] * s);
+                eig_lds_st(vla + 8 * i, wa[i] * s + wb[i] * c);
+            }
+        }
+        // the rescans over the 7 pairs in index order (i_j > k <=> j >= k, i_j > l <=> j >= l - 1); bases:
+        // row k starts at pa - 8 (l - 1), row l at the table's offset, column i at slice + 8 (i - 1)
+        const uint32_t rbk = pa - shCl, rbl = lb + (q1.w >> 24), cbk = lb + shRk - 8, cbl = lb + shCl;
+        uint32_t sRk = rbk + shRk, sCk = cbk + eig_row_off(0), sRl = rbl + (l << 3), sCl = cbl + eig_row_off(0);
+        double fk = 0.0, fl = 0.0;
+#pragma unroll
+        for (int j = 0; j < P7; ++j) {
+            const double ak = __builtin_fabs(nk[j]), al = __builtin_fabs(nl[j]);
+            sCk = ((uint32_t)j < k && fk < ak) ? a0[j] : sCk;
+            sCl = ((uint32_t)j + 1 < l && fl < al) ? a1[j] : sCl;
+            fk = eig_max_abs(fk, nk[j]);
+            fl = eig_max_abs(fl, nl[j]);
+        }
+        double bk = 0x1p-1074, bl = 0x1p-1074;
+#pragma unroll
+        for (int j = P7 - 1; j >= 0; --j) {
+            const double ak = __builtin_fabs(nk[j]), al = __builtin_fabs(nl[j]);
+            sRk = ((uint32_t)j >= k && ak >= bk) ? a0[j] : sRk;
+            sRl = ((uint32_t)j + 1 >= l && al >= bl) ? a1[j] : sRl;
+            bk = eig_max_abs(bk, nk[j]);
+            bl = eig_max_abs(bl, nl[j]);
+        }
+        tr = eig_set_byte(tr, shRl, sRl - rbl);   // l = 8 has no row: row k's byte, rewritten below
+        tr = eig_set_byte(tr, shRk, sRk - rbk);
+        tc = eig_set_byte(tc, shCk, sCk - cbk);   // k = 0 has no column: column l's byte, rewritten below
+        tc = eig_set_byte(tc, shCl, sCl - cbl);
+    }
+    return it;
+}
+#endif
+
 // cv::eigen on the 9x9 symmetric matrix whose strict upper triangle (packed) and diagonal the caller
 // stored at ws[kEigA..] and ws[kEigW..]. On return w[] holds the eigenvalues in descending order and
 // the function returns the workspace row of V (the original row index) that the sort moved to
@@ -197,98 +412,114 @@ MCV_HD int eig9_jacobi(WS& ws, double (&w)[9], int pos, int* iters = nullptr, Ei
     }
     if constexpr (!LOG) ws[junk] = 0.0;   // stays +0: the skipped pair rotates (0, 0) into (+0, +0)
     bool logOk = true;
-    uint32_t indR = 0, indC = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int k = 0; k < n; ++k) {
-        if (k < n - 1) {
-            int m = k + 1;
-            double mv = __builtin_fabs(ws[eig_tri(k, k + 1)]);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = k + 2; i < n; ++i) {
-                const double val = __builtin_fabs(ws[eig_tri(k, i)]);
-                if (mv < val) mv = val, m = i;
-            }
-            indR = eig_set_nib(indR, k, m);
-        }
-        if (k > 0) {
-            int m = 0;
-            double mv = __builtin_fabs(ws[eig_tri(0, k)]);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 1; i < k; ++i) {
-                const double val = __builtin_fabs(ws[eig_tri(i, k)]);
-                if (mv < val) mv = val, m = i;
-            }
-            indC = eig_set_nib(indC, k - 1, m);
-        }
-    }
     int it = 0;
-    for (; it < n * n * 30; ++it) {
-        // pivot (k, l): the first maximum over the 16 candidates in OpenCV's scan order (rows 0..7
-        // through indR, then columns 1..8 through indC), as a pairwise tree (first wins on ties)
-        double cv[16];
-        int ck[16];
+    // a lane slice on the device runs its own form of the loop (eig9_rotations_lane); the host and the
+    // private workspace run the generic one below
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool kLane = std::is_same<WS, EigWsLane>::value;
+#else
+    constexpr bool kLane = false;
+#endif
+    if constexpr (kLane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        it = eig9_rotations_lane<LOG>(ws, logOk, log, logStride, logCap);
+#endif
+    } else {
+        uint32_t indR = 0, indC = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-        for (int i = 0; i < n - 1; ++i) {
-            const int c = eig_nib(indR, i);
-            cv[i] = ws[eig_row_base(i) + c];
-            ck[i] = i * 16 + c;
+        for (int k = 0; k < n; ++k) {
+            if (k < n - 1) {
+                int m = k + 1;
+                double mv = __builtin_fabs(ws[eig_tri(k, k + 1)]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+                for (int i = k + 2; i < n; ++i) {
+                    const double val = __builtin_fabs(ws[eig_tri(k, i)]);
+                    if (mv < val) mv = val, m = i;
+                }
+                indR = eig_set_nib(indR, k, m);
+            }
+            if (k > 0) {
+                int m = 0;
+                double mv = __builtin_fabs(ws[eig_tri(0, k)]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+                for (int i = 1; i < k; ++i) {
+                    const double val = __builtin_fabs(ws[eig_tri(i, k)]);
+                    if (mv < val) mv = val, m = i;
+                }
+                indC = eig_set_nib(indC, k - 1, m);
+            }
         }
+        for (; it < n * n * 30; ++it) {
+            // pivot (k, l): the first maximum over the 16 candidates in OpenCV's scan order (rows 0..7
+            // through indR, then columns 1..8 through indC), as a pairwise tree (first wins on ties)
+            double cv[16];
+            int ck[16];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-        for (int i = 1; i < n; ++i) {
-            const int r = eig_nib(indC, i - 1);
-            cv[7 + i] = ws[eig_row_base(r) + i];
-            ck[7 + i] = r * 16 + i;
-        }
+            for (int i = 0; i < n - 1; ++i) {
+                const int c = eig_nib(indR, i);
+                cv[i] = ws[eig_row_base(i) + c];
+                ck[i] = i * 16 + c;
+            }
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-        for (int h = 1; h < 16; h *= 2)
+            for (int i = 1; i < n; ++i) {
+                const int r = eig_nib(indC, i - 1);
+                cv[7 + i] = ws[eig_row_base(r) + i];
+                ck[7 + i] = r * 16 + i;
+            }
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-            for (int i = 0; i < 16; i += 2 * h) eig_pick(cv[i], ck[i], cv[i + h], ck[i + h]);
-        const int k = ck[0] >> 4, l = ck[0] & 15;
-        const int ekl = eig_tri(k, l);
-        const double p = cv[0];   // = A(k, l)
-        if (__builtin_fabs(p) <= kDblEpsilon) break;
-        // every operand of the rotation is read before anything is written back (the reads do not
-        // depend on the scalar chain, so their LDS latency hides behind it): W[k], W[l], for every
-        // other i the pair (A(k|i), A(l|i)) of the upper triangle (i = k, l read and write the junk
-        // slot), and V rows k and l
-        const double wk = ws[kEigW + k], wl = ws[kEigW + l];
+            for (int h = 1; h < 16; h *= 2)
 #if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (std::is_same<WS, EigWsLane>::value) {
-            // the 7 pairs of the indices outside {k, l} (kEigPairLut7: 2 vector loads from L1)
-            constexpr int P7 = n - 2;
-            const uint4* lr = reinterpret_cast<const uint4*>(kEigPairLut7.w[ekl]);
-            const uint4 q0 = lr[0], q1 = lr[1];
-            const uint32_t qw[P7] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z};
-            char* const b = reinterpret_cast<char*>(ws.p);
-            int o0[P7], o1[P7];
-            double x0[P7], x1[P7], wa[n], wb[n];
 #pragma unroll
-            for (int j = 0; j < P7; ++j) {
-                o0[j] = (int)(qw[j] & 0xffffu);
-                o1[j] = (int)(qw[j] >> 16);
-                x0[j] = *reinterpret_cast<const double*>(b + o0[j]);
-                x1[j] = *reinterpret_cast<const double*>(b + o1[j]);
+#endif
+                for (int i = 0; i < 16; i += 2 * h) eig_pick(cv[i], ck[i], cv[i + h], ck[i + h]);
+            const int k = ck[0] >> 4, l = ck[0] & 15;
+            const int ekl = eig_tri(k, l);
+            const double p = cv[0];   // = A(k, l)
+            if (__builtin_fabs(p) <= kDblEpsilon) break;
+            // every operand of the rotation is read before anything is written back (the reads do not
+            // depend on the scalar chain, so their LDS latency hides behind it): W[k], W[l], for every
+            // other i the pair (A(k|i), A(l|i)) of the upper triangle (i = k, l read and write the junk
+            // slot), and V rows k and l
+            const double wk = ws[kEigW + k], wl = ws[kEigW + l];
+            const int rk = eig_row_base(k), rl = eig_row_base(l);
+            int e0[n], e1[n];
+            double a0[n], b0[n], va[n], vb[n];
+            {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+                for (int i = 0; i < n; ++i) {
+                    // branch-free index selection (a select of LDS addresses feeding a load is otherwise
+                    // turned into control flow around each load)
+                    const int mk = -(int)(i < k), ml = -(int)(i < l), ms = -(int)(i == k || i == l);
+                    const int x0 = ((eig_row_base(i) + k) & mk) | ((rk + i) & ~mk);
+                    const int x1 = ((eig_row_base(i) + l) & ml) | ((rl + i) & ~ml);
+                    e0[i] = (junk & ms) | (x0 & ~ms);
+                    e1[i] = (junk & ms) | (x1 & ~ms);
+                    a0[i] = ws[e0[i]];
+                    b0[i] = ws[e1[i]];
+                }
             }
             const int vk = kEigV + (k << 3) + k, vl = kEigV + (l << 3) + l;   // + 9 k, + 9 l
             if constexpr (!LOG) {
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
+#endif
                 for (int i = 0; i < n; ++i) {
-                    wa[i] = ws[vk + i];
-                    wb[i] = ws[vl + i];
+                    va[i] = ws[vk + i];
+                    vb[i] = ws[vl + i];
                 }
             }
             const double y = (wl - wk) * 0.5;
@@ -307,135 +538,51 @@ MCV_HD int eig9_jacobi(WS& ws, double (&w)[9], int pos, int* iters = nullptr, Ei
             ws[ekl] = 0;
             ws[kEigW + k] = wk - t;
             ws[kEigW + l] = wl + t;
-            double nk[P7], nl[P7];
+            // rotate rows and columns k and l; nk / nl keep the new values for the rescans (at i = k, l the
+            // junk pair (0, 0) rotates to (+0, +0): A(k, l) = 0 without a select)
+            double nk[n], nl[n];
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-            for (int j = 0; j < P7; ++j) {
-                nk[j] = x0[j] * c - x1[j] * s;
-                nl[j] = x0[j] * s + x1[j] * c;
-                *reinterpret_cast<double*>(b + o0[j]) = nk[j];
-                *reinterpret_cast<double*>(b + o1[j]) = nl[j];
+#endif
+            for (int i = 0; i < n; ++i) {
+                nk[i] = a0[i] * c - b0[i] * s;
+                nl[i] = a0[i] * s + b0[i] * c;
+                ws[e0[i]] = nk[i];
+                ws[e1[i]] = nl[i];
             }
+            // rotate eigenvectors
             if constexpr (!LOG) {
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
+#endif
                 for (int i = 0; i < n; ++i) {
-                    ws[vk + i] = wa[i] * c - wb[i] * s;
-                    ws[vl + i] = wa[i] * s + wb[i] * c;
+                    ws[vk + i] = va[i] * c - vb[i] * s;
+                    ws[vl + i] = va[i] * s + vb[i] * c;
                 }
             }
-            // the rescans over the 7 pairs in index order: i_j > k <=> j >= k, i_j > l <=> j >= l - 1;
-            // a tracker keeps the pair position j of its first maximum (-1: none beat the running 0, the
-            // start index: k + 1 for a row, 0 for a column), mapped back to i_j at the end
-            int jRk = -1, jCk = -1, jRl = -1, jCl = -1;
+            // refresh indR / indC of rows and columns k and l (first maximum by magnitude). OpenCV takes
+            // the first in-range element unconditionally; here the index starts there (k + 1 for a row,
+            // 0 for a column) with a running value of 0, which only a strictly larger |value| replaces —
+            // the same index for finite values. Values stay signed (magnitudes through the compare).
+            int mRk = k + 1, mCk = 0, mRl = l + 1, mCl = 0;
             double vRk = 0, vCk = 0, vRl = 0, vCl = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-            for (int j = 0; j < P7; ++j) {
-                const double ak = __builtin_fabs(nk[j]), al = __builtin_fabs(nl[j]);
-                const bool tRk = j >= k && __builtin_fabs(vRk) < ak, tCk = j < k && __builtin_fabs(vCk) < ak;
-                const bool tRl = j >= l - 1 && __builtin_fabs(vRl) < al, tCl = j < l - 1 && __builtin_fabs(vCl) < al;
-                vRk = tRk ? nk[j] : vRk; jRk = tRk ? j : jRk;
-                vCk = tCk ? nk[j] : vCk; jCk = tCk ? j : jCk;
-                vRl = tRl ? nl[j] : vRl; jRl = tRl ? j : jRl;
-                vCl = tCl ? nl[j] : vCl; jCl = tCl ? j : jCl;
+#endif
+            for (int i = 0; i < n; ++i) {
+                const double ak = __builtin_fabs(nk[i]), al = __builtin_fabs(nl[i]);
+                const bool tRk = i > k && __builtin_fabs(vRk) < ak, tCk = i < k && __builtin_fabs(vCk) < ak;
+                const bool tRl = i > l && __builtin_fabs(vRl) < al, tCl = i < l && __builtin_fabs(vCl) < al;
+                vRk = tRk ? nk[i] : vRk; mRk = tRk ? i : mRk;
+                vCk = tCk ? nk[i] : vCk; mCk = tCk ? i : mCk;
+                vRl = tRl ? nl[i] : vRl; mRl = tRl ? i : mRl;
+                vCl = tCl ? nl[i] : vCl; mCl = tCl ? i : mCl;
             }
-            auto orig = [&](int j) { return j + (j >= k ? 1 : 0) + (j >= l - 1 ? 1 : 0); };
-            const int mRk = jRk < 0 ? k + 1 : orig(jRk), mCk = jCk < 0 ? 0 : orig(jCk);
-            const int mRl = jRl < 0 ? l + 1 : orig(jRl), mCl = jCl < 0 ? 0 : orig(jCl);
             if (k < n - 1) indR = eig_set_nib(indR, k, mRk);
             if (k > 0) indC = eig_set_nib(indC, k - 1, mCk);
             if (l < n - 1) indR = eig_set_nib(indR, l, mRl);
             indC = eig_set_nib(indC, l - 1, mCl);   // l >= 1
-            continue;
         }
-#endif
-        const int rk = eig_row_base(k), rl = eig_row_base(l);
-        int e0[n], e1[n];
-        double a0[n], b0[n], va[n], vb[n];
-        {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 0; i < n; ++i) {
-                // branch-free index selection (a select of LDS addresses feeding a load is otherwise
-                // turned into control flow around each load)
-                const int mk = -(int)(i < k), ml = -(int)(i < l), ms = -(int)(i == k || i == l);
-                const int x0 = ((eig_row_base(i) + k) & mk) | ((rk + i) & ~mk);
-                const int x1 = ((eig_row_base(i) + l) & ml) | ((rl + i) & ~ml);
-                e0[i] = (junk & ms) | (x0 & ~ms);
-                e1[i] = (junk & ms) | (x1 & ~ms);
-                a0[i] = ws[e0[i]];
-                b0[i] = ws[e1[i]];
-            }
-        }
-        const int vk = kEigV + (k << 3) + k, vl = kEigV + (l << 3) + l;   // + 9 k, + 9 l
-        if constexpr (!LOG) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 0; i < n; ++i) {
-                va[i] = ws[vk + i];
-                vb[i] = ws[vl + i];
-            }
-        }
-        const double y = (wl - wk) * 0.5;
-        double c, s, t;
-        eig_rotation(p, y, c, s, t);
-        if constexpr (LOG) {
-            if (it >= logCap || !eig_rot_c_ok(c)) {
-                logOk = false;
-                break;
-            }
-            EigRot e;
-            e.c = eig_rot_pack(c, k, l);
-            e.s = s;
-            log[(int64_t)it * logStride] = e;
-        }
-        ws[ekl] = 0;
-        ws[kEigW + k] = wk - t;
-        ws[kEigW + l] = wl + t;
-        // rotate rows and columns k and l; nk / nl keep the new values for the rescans (at i = k, l the
-        // junk pair (0, 0) rotates to (+0, +0): A(k, l) = 0 without a select)
-        double nk[n], nl[n];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int i = 0; i < n; ++i) {
-            nk[i] = a0[i] * c - b0[i] * s;
-            nl[i] = a0[i] * s + b0[i] * c;
-            ws[e0[i]] = nk[i];
-            ws[e1[i]] = nl[i];
-        }
-        // rotate eigenvectors
-        if constexpr (!LOG) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 0; i < n; ++i) {
-                ws[vk + i] = va[i] * c - vb[i] * s;
-                ws[vl + i] = va[i] * s + vb[i] * c;
-            }
-        }
-        // refresh indR / indC of rows and columns k and l (first maximum by magnitude). OpenCV takes
-        // the first in-range element unconditionally; here the index starts there (k + 1 for a row,
-        // 0 for a column) with a running value of 0, which only a strictly larger |value| replaces —
-        // the same index for finite values. Values stay signed (magnitudes through the compare).
-        int mRk = k + 1, mCk = 0, mRl = l + 1, mCl = 0;
-        double vRk = 0, vCk = 0, vRl = 0, vCl = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int i = 0; i < n; ++i) {
-            const double ak = __builtin_fabs(nk[i]), al = __builtin_fabs(nl[i]);
-            const bool tRk = i > k && __builtin_fabs(vRk) < ak, tCk = i < k && __builtin_fabs(vCk) < ak;
-            const bool tRl = i > l && __builtin_fabs(vRl) < al, tCl = i < l && __builtin_fabs(vCl) < al;
-            vRk = tRk ? nk[i] : vRk; mRk = tRk ? i : mRk;
-            vCk = tCk ? nk[i] : vCk; mCk = tCk ? i : mCk;
-            vRl = tRl ? nl[i] : vRl; mRl = tRl ? i : mRl;
-            vCl = tCl ? nl[i] : vCl; mCl = tCl ? i : mCl;
-        }
-        if (k < n - 1) indR = eig_set_nib(indR, k, mRk);
-        if (k > 0) indC = eig_set_nib(indC, k - 1, mCk);
-        if (l < n - 1) indR = eig_set_nib(indR, l, mRl);
-        indC = eig_set_nib(indC, l - 1, mCl);   // l >= 1
     }
     if (iters) *iters = logOk ? it : -1;
     // descending selection sort, rows of V swapped along (tracked as a permutation)

@@ -68,9 +68,12 @@ __global__ __launch_bounds__(FAST ? 256 : L) void mcv_h_generate(const float* __
 static constexpr int kEigLogCap = 192;
 // the log rows pass 1 may use (mcvTestEigLogCap lowers it so the tests drive the overflow path)
 static int g_eig_log_cap = kEigLogCap;
-// 56 x 360 B = 19.7 KB: 8 blocks (two waves per SIMD) per CU. Screen (with 376-byte slices): 40 / 64 /
-// 32-lane blocks (10 / 6 / 13 per CU) 6.6 / 5.7 / 6.7 ms against 5.2 ms of generate per 2^20 at 54.
-static constexpr int kHGenAwLanes = 56;
+// 64 x 360 B = 22.5 KB: 7 blocks of one full wave per CU (7 x 23040 B of the 160 KB). Screen on the
+// trimmed rotation loop ("Fewer instructions per rotation in pass 1"; kernel ms per 2^20
+// hypotheses): 56 lanes (8 blocks of 20480 B, the former choice) 2.909, 60 lanes 3.014, 64 lanes 2.847.
+// Round 6 had screened 64 lanes only with 376-byte slices, where six blocks fit (40 / 64 / 32-lane
+// blocks, 10 / 6 / 13 per CU: 6.6 / 5.7 / 6.7 ms against 5.2 ms of generate per 2^20 at 54).
+static constexpr int kHGenAwLanes = 64;
 // pass 2: one column of V per lane (9 lanes per hypothesis, 7 hypotheses per 63-lane block), 4 log
 // loads in flight. Round-6 screen at cfg3 (generate ms per 2^20 hypotheses, pass 1 ~3.7 of it): one
 // lane per hypothesis with one load ahead 5.78, with 8 ahead 5.78; 3 lanes x 3 columns 5.16-5.17 (V
