@@ -153,27 +153,33 @@ static void launch_error_rank_k(const float* d_pts4, int N, const void* d_models
                        (const typename RankModel<MODEL>::Stored*)d_models, d_status, (uint32_t)rank, d_keys);
 }
 
+// (model, errKind) -> f(RankCase<MODEL, KIND>()): the one place that names the instantiations, for the device
+// launch and the host twin alike.
+template <int MODEL, int KIND>
+struct RankCase {
+    static const int model = MODEL, kind = KIND;
+};
+template <class F>
+static void rank_dispatch(int model, int errKind, F f) {
+    if (model == MCV_MODEL_HOMOGRAPHY)
+        return errKind ? f(RankCase<MCV_MODEL_HOMOGRAPHY, 1>()) : f(RankCase<MCV_MODEL_HOMOGRAPHY, 0>());
+    if (affine_family(model)) return errKind ? f(RankCase<MCV_MODEL_AFFINE, 1>()) : f(RankCase<MCV_MODEL_AFFINE, 0>());
+    if (model != MCV_MODEL_FUNDAMENTAL) fail("error rank: model %d has no rank kernel", model);
+    switch (errKind) {
+        case 0: f(RankCase<MCV_MODEL_FUNDAMENTAL, 0>()); break;
+        case 1: f(RankCase<MCV_MODEL_FUNDAMENTAL, 1>()); break;
+        case 2: f(RankCase<MCV_MODEL_FUNDAMENTAL, 2>()); break;
+        case 3: f(RankCase<MCV_MODEL_FUNDAMENTAL, 3>()); break;
+        default: fail("error rank: unknown error kind %d", errKind);
+    }
+}
+
 void launch_error_rank(int model, const float* d_pts4, int N, const void* d_models, const int* d_status, int nSlots,
                        int errKind, int rank, uint32_t* d_keys, hipStream_t s) {
     if (N <= 0 || nSlots <= 0 || rank < 0 || rank >= N) fail("error rank: bad sizes (N=%d, slots=%d, rank=%d)", N, nSlots, rank);
-    if (model == MCV_MODEL_HOMOGRAPHY) {
-        if (errKind) launch_error_rank_k<MCV_MODEL_HOMOGRAPHY, 1>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
-        else launch_error_rank_k<MCV_MODEL_HOMOGRAPHY, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
-        return;
-    }
-    if (affine_family(model)) {
-        if (errKind) launch_error_rank_k<MCV_MODEL_AFFINE, 1>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
-        else launch_error_rank_k<MCV_MODEL_AFFINE, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
-        return;
-    }
-    if (model != MCV_MODEL_FUNDAMENTAL) fail("error rank: model %d has no rank kernel", model);
-    switch (errKind) {
-        case 0: launch_error_rank_k<MCV_MODEL_FUNDAMENTAL, 0>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s); break;
-        case 1: launch_error_rank_k<MCV_MODEL_FUNDAMENTAL, 1>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s); break;
-        case 2: launch_error_rank_k<MCV_MODEL_FUNDAMENTAL, 2>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s); break;
-        case 3: launch_error_rank_k<MCV_MODEL_FUNDAMENTAL, 3>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s); break;
-        default: fail("error rank: unknown error kind %d", errKind);
-    }
+    rank_dispatch(model, errKind, [&](auto c) {
+        launch_error_rank_k<decltype(c)::model, decltype(c)::kind>(d_pts4, N, d_models, d_status, nSlots, rank, d_keys, s);
+    });
 }
 
 static void check_rank_args(const char* who, int model, const float* pts4, int N, const void* models, int nModels,
@@ -238,20 +244,9 @@ extern "C" MCV_API int mcvHostErrorRank(int model, const float* pts4, int N, con
                                         int errKind, int rank, float* values) {
     MCV_GUARD(0, {
         check_rank_args("mcvHostErrorRank", model, pts4, N, models, nModels, errKind, rank, values);
-        if (model == MCV_MODEL_HOMOGRAPHY) {
-            if (errKind) host_error_rank<MCV_MODEL_HOMOGRAPHY, 1>(pts4, N, models, nModels, rank, values);
-            else host_error_rank<MCV_MODEL_HOMOGRAPHY, 0>(pts4, N, models, nModels, rank, values);
-        } else if (affine_family(model)) {
-            if (errKind) host_error_rank<MCV_MODEL_AFFINE, 1>(pts4, N, models, nModels, rank, values);
-            else host_error_rank<MCV_MODEL_AFFINE, 0>(pts4, N, models, nModels, rank, values);
-        } else {
-            switch (errKind) {
-                case 0: host_error_rank<MCV_MODEL_FUNDAMENTAL, 0>(pts4, N, models, nModels, rank, values); break;
-                case 1: host_error_rank<MCV_MODEL_FUNDAMENTAL, 1>(pts4, N, models, nModels, rank, values); break;
-                case 2: host_error_rank<MCV_MODEL_FUNDAMENTAL, 2>(pts4, N, models, nModels, rank, values); break;
-                default: host_error_rank<MCV_MODEL_FUNDAMENTAL, 3>(pts4, N, models, nModels, rank, values); break;
-            }
-        }
+        rank_dispatch(model, errKind, [&](auto c) {
+            host_error_rank<decltype(c)::model, decltype(c)::kind>(pts4, N, models, nModels, rank, values);
+        });
         return 1;
     })
 }

@@ -171,8 +171,7 @@ extern "C" MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const De
         if (mcfg.model != MCV_MODEL_HOMOGRAPHY && mcfg.model != MCV_MODEL_FUNDAMENTAL && !affine_family(mcfg.model))
             fail("cvMatchAndFindModel: model %d unsupported (homography, fundamental, affine or similarity)",
                  mcfg.model);
-        RansacConfig rcfg = config_or_default(rcfgp);
-        if (!rcfgp && mcfg.model != MCV_MODEL_HOMOGRAPHY) rcfg.confidence = 0.99;
+        const RansacConfig rcfg = config_or_default(mcfg.model, rcfgp);
         if (rcfg.method != MCV_METHOD_RANSAC) fail("cvMatchAndFindModel: only RANSAC (method 8)");
         check_flags(rcfg, "cvMatchAndFindModel");
         if (!(rcfg.confidence > 0 && rcfg.confidence < 1)) fail("cvMatchAndFindModel: confidence must be in (0,1)");

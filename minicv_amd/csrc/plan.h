@@ -8,6 +8,7 @@
 #include "mcv_common.h"
 #include "ransac_batch_index.h"
 #include <stdint.h>
+#include <string.h>
 #include <vector>
 
 namespace mcv {
@@ -16,11 +17,75 @@ namespace mcv {
 static const int64_t kChunkFirst = 4096;
 static const int64_t kChunkMax = 1 << 20;
 
-size_t model_bytes(int model);   // device model bytes per hypothesis
-int model_points(int model);
-int model_points_cfg(int model, const RansacConfig& cfg);   // PnP: 5 with the EPnP kernel; F 7-point: 7
-int model_slots_cfg(int model, const RansacConfig& cfg);    // F 7-point: 3 model slots per hypothesis
-int model_slots(int model);      // model slots per hypothesis (essential: 10)
+struct Plan;
+
+// ---- the family table: one record per MCV_MODEL_*, what the shared framework (ransac_host.cpp) needs to know
+// about a model family and the family's own code behind one set of hook signatures. family_of(model) returns it.
+// The constant part is device-free and constexpr; ransac_host.cpp pins every entry with static_asserts.
+struct FamilyShape {
+    const char* name;
+    int points;           // minimal sample size (a configuration may change it: points_cfg)
+    int slots;            // model slots per hypothesis (slots_cfg)
+    int modelBytes;       // device model bytes per hypothesis
+    bool doublePoints;    // points are 32 B each (essential double4, PnP rows) in Plan::ptsd; else float4 in Plan::pts
+    bool defaultThreshold;   // thr2_of: a threshold <= 0 means 3 pixels (the 2-D families); essential / PnP: as given
+    double defaultConfidence;   // config_or_default (OpenCV's per function); essential / PnP: e_config, pnp_config
+    int h64PerHyp;        // doubles per hypothesis of Plan::h64, the generate's fp64 models (0: the family has none)
+};
+constexpr FamilyShape kFamilyShapes[] = {
+    {"homography", 4, 1, 32, false, true, 0.995, 9},   // MCV_MODEL_HOMOGRAPHY
+    {"fundamental", 8, 1, 80, false, true, 0.99, 0},   // MCV_MODEL_FUNDAMENTAL
+    {"essential", 5, 10, 720, true, false, 0.999, 0},  // MCV_MODEL_ESSENTIAL
+    {"pnp", 4, 1, 96, true, false, 0.99, 0},           // MCV_MODEL_PNP
+    {"affine", 3, 1, 24, false, true, 0.99, 6},        // MCV_MODEL_AFFINE
+    {"similarity", 2, 1, 24, false, true, 0.99, 6},    // MCV_MODEL_SIMILARITY
+};
+// The hooks. d_pts is the family's device point buffer (doublePoints tells its layout); a null hook: the family
+// has none. generate = one chunk's models, statuses and P.last (shared by the RANSAC evaluate and lmeds_search);
+// evaluate = generate + verify into d_counts (keyOnly: nobody reads d_counts beyond the best-key reduction, which
+// only the homography sweep exploits); finalize = the winner's model and mask, returns its inlier count.
+using ReserveHook = void(Plan& P);
+using GenerateHook = void(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                          int* d_counts, hipStream_t s);
+using EvaluateHook = void(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                          int* d_counts, bool keyOnly, hipStream_t s);
+using FinalizeHook = int(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+                         uint8_t* d_mask, hipStream_t s);
+using HostHypothesisHook = int(int model, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9,
+                               float* modelf9, int* sampleIdx, bool fast);
+using ConfigIntHook = int(const RansacConfig& cfg);
+// find_model_2d's family-specific parts. refuse: the refusals that depend on the configuration, the minimal-N
+// one included (null: N < points, before the configuration is read). direct: the cases solved on all points
+// without a search (count = N, mask all 1); false: not one of them.
+using EntryRefuseHook = void(const char* who, int N, const RansacConfig& cfg);
+using EntryDirectHook = bool(Plan& P, const char* who, int N, const RansacConfig& cfg, hipStream_t s, double* model9);
+struct RansacFamily : FamilyShape {
+    ReserveHook* reserve;        // further buffers of its own for P.maxN points / P.maxHyps hypotheses (essential)
+    GenerateHook* generate;
+    EvaluateHook* evaluate;
+    FinalizeHook* finalize;
+    HostHypothesisHook* host_hypothesis;
+    ConfigIntHook* points_cfg;   // null: points whatever the configuration (PnP with EPnP: 5; 7-point F: 7)
+    ConfigIntHook* slots_cfg;    // null: slots (7-point F: 3)
+    bool lsq;                    // MCV_METHOD_LSQ is one of the 2-D entry's methods (a direct case)
+    EntryRefuseHook* entry_refuse;
+    EntryDirectHook* entry_direct;
+};
+const RansacFamily& family_of(int model);   // throws on a model outside the table
+// forwards of the table
+size_t model_bytes(int model);
+int model_points(int model), model_slots(int model);
+int model_points_cfg(int model, const RansacConfig& cfg), model_slots_cfg(int model, const RansacConfig& cfg);
+size_t point_bytes(int model, int N);   // device point buffer: 16 N (float4), 32 N (E double4, PnP rows)
+
+// The minimal solver that produced a chunk's models (LastChunk::kind).
+enum ChunkSolver : int {
+    kSolverNone = -1,
+    kSolverHEigen, kSolverHElimination,     // homography: the reference's eigen solve / MCV_FLAG_FAST_MINIMAL
+    kSolverF8Exact, kSolverF8Fast,          // 8-point fundamental
+    kSolverEReference, kSolverEFast,        // five-point essential
+    kSolverAp3p, kSolverEpnp, kSolverAp3pFast,   // PnP
+};
 
 // Key of the last evaluated chunk. A winner inside it takes its model from the chunk's buffers
 // instead of a re-solve; the key names everything that produced those buffers (the hypothesis
@@ -35,12 +100,12 @@ struct LastChunk {
     const int* table = nullptr;
     const void* pts = nullptr;
     int N = 0;
-    int kind = -1;            // H: 20 eigen, 21 elimination; F: 10 / 11; E: 30 / 31; PnP: 1 EPnP, 0 AP3P
-    void set(int64_t b, int64_t c, const Sampler& smp, const void* p, int n, int k) {
+    ChunkSolver kind = kSolverNone;
+    void set(int64_t b, int64_t c, const Sampler& smp, const void* p, int n, ChunkSolver k) {
         begin = b; count = c; seed = smp.seed; table = smp.table; pts = p; N = n; kind = k;
     }
     void clear() { *this = LastChunk(); }
-    bool covers(int64_t hyp, const Sampler& smp, const void* p, int n, int k) const {
+    bool covers(int64_t hyp, const Sampler& smp, const void* p, int n, ChunkSolver k) const {
         return begin >= 0 && hyp >= begin && hyp < begin + count && seed == smp.seed && table == smp.table &&
                pts == p && N == n && kind == k;
     }
@@ -141,6 +206,54 @@ inline void mask_to_host(Plan& P, uint8_t* mask, int N, hipStream_t s) {
     MCV_HIP(hipStreamSynchronize(s));
 }
 
+// The squared inlier threshold the verify and mask kernels take. The 2-D families read a threshold <= 0 as
+// 3 pixels (effective_threshold); essential and PnP take the configuration's as given.
+double effective_threshold(const RansacConfig& cfg);
+inline float thr2_of(const Plan& P, const RansacConfig& cfg) {
+    const double t = kFamilyShapes[P.model].defaultThreshold ? effective_threshold(cfg) : cfg.threshold;
+    return (float)(t * t);
+}
+
+// The winner record (a T at d_src, by default the plan's single-hypothesis record P.one) to the host:
+// queue_one enqueues the copy, take_one reads it after the caller's next synchronisation of s (so that a
+// finalize can return the record, the count and the freshness words with one synchronisation), fetch_one
+// is the two around a synchronisation of its own, after the launch that wrote the record.
+template <class T>
+inline void queue_one(Plan& P, hipStream_t s, const void* d_src = nullptr) {
+    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_src ? d_src : P.one.p, sizeof(T), hipMemcpyDeviceToHost, s));
+}
+template <class T>
+inline T take_one(const Plan& P) {
+    T one;
+    memcpy(&one, P.h_one.p, sizeof(T));
+    return one;
+}
+template <class T>
+inline T fetch_one(Plan& P, hipStream_t s, const void* d_src = nullptr) {
+    MCV_HIP(hipGetLastError());
+    queue_one<T>(P, s, d_src);
+    MCV_HIP(hipStreamSynchronize(s));
+    return take_one<T>(P);
+}
+
+// The winner's inlier count: a mask kernel adds to P.count, zeroed before it (zero_count); queue_count
+// enqueues its copy to the host and take_count reads it after the caller's next synchronisation.
+// mask_count is the whole sequence around launch(int* d_count), with a synchronisation of its own.
+inline void zero_count(Plan& P, hipStream_t s) { MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s)); }
+inline void queue_count(Plan& P, hipStream_t s) {
+    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+}
+inline int take_count(const Plan& P) { return P.h_i.p[0]; }
+template <class F>
+inline int mask_count(Plan& P, hipStream_t s, F launch) {
+    zero_count(P, s);
+    launch(P.count.p);
+    MCV_HIP(hipGetLastError());
+    queue_count(P, s);
+    MCV_HIP(hipStreamSynchronize(s));
+    return take_count(P);
+}
+
 // Opt-in kernel timing with HIP events recorded on the launch stream (bench.py's live roofline).
 // mcvProfileEnable(n): every n-th launch of each named scope is timed (n = 1: all of them). An event
 // pair costs the stream ~3 us each way, 17 % of the 36 us cfg2 Hamming step when every launch is
@@ -173,17 +286,15 @@ inline void pack_float4(const mcvV2d* a, const mcvV2d* b, int n, float* dst) {
     }
 }
 void pack_points(Plan& P, const mcvV2d* a, const mcvV2d* b, int N, float* d_dst, hipStream_t s);
-size_t point_bytes(int model, int N);   // device point buffer: 16 N (H / F float4), 32 N (E double4, PnP)
 // Evaluate side: P.last = this chunk, and the fingerprint of its points -> P.fp[0] (async).
-void mark_chunk(Plan& P, int64_t begin, int64_t count, const Sampler& smp, const void* d_pts, int N, int kind,
-                hipStream_t s);
+void mark_chunk(Plan& P, int64_t begin, int64_t count, const Sampler& smp, const void* d_pts, int N,
+                ChunkSolver kind, hipStream_t s);
 // Finalize side, on the cached-model path: the current points' fingerprint -> P.fp[1], both to
 // P.h_fp (async; chunk_fresh reads them after the caller's next stream synchronisation).
 void queue_chunk_check(Plan& P, const void* d_pts, int N, hipStream_t s);
 inline bool chunk_fresh(const Plan& P) { return P.h_fp.p[0] == P.h_fp.p[1]; }
 // The device points' fingerprint, synchronously (CV-sampler table checks).
 uint64_t device_fingerprint(Plan& P, const void* d_pts, int N, hipStream_t s);
-double effective_threshold(const RansacConfig& cfg);
 bool cv_sampler(const RansacConfig& cfg);   // MCV_FLAG_CV_SAMPLER
 void check_flags(const RansacConfig& cfg, const char* who);   // rejects the retired bit 4
 // OpenCV's subset stream (cv_sampler.cpp): rows [0, rows) for P's model / cfg, uploaded to P.subsets.
@@ -198,7 +309,9 @@ void cv_table_prepare(Plan& P, const void* d_pts, const float* h_pts4, int N, co
                       hipStream_t s);
 bool fused_error(const RansacConfig& cfg);
 bool fast_minimal(const RansacConfig& cfg);   // MCV_FLAG_FAST_MINIMAL
-RansacConfig config_or_default(const RansacConfig* cfg);
+// *cfg, or the 2-D exports' defaults for the model (OpenCV's: threshold 3, 2000 iterations, its own sample stream,
+// the family's defaultConfidence)
+RansacConfig config_or_default(int model, const RansacConfig* cfg);
 int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, hipStream_t s,
                       const float* h_pts4 = nullptr);
 // LMedS (method 4) on device-resident H / F / affine-family points: RANSACUpdateNumIters(confidence, 0.45, m, maxIters)
@@ -213,61 +326,53 @@ int finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t
 void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                     int* d_counts, uint64_t* d_key, hipStream_t s, bool needCounts = true);
 
-// Per family: *_generate_chunk = one chunk's models, statuses and P.last (shared by the RANSAC evaluate and
-// lmeds_search); *_evaluate_chunk = generate + verify into d_counts; *_finalize = the winner's model and mask.
+// The 2-D entry (cvFindHomography, cvFindFundamentalMat, cvEstimateAffine2D, cvEstimateAffinePartial2D): the
+// refusals, pack, the family's direct cases, LMedS or RANSAC, finalize, the mask to the host. Returns the count.
+int find_model_2d(int model, const char* who, const mcvV2d* a, const mcvV2d* b, int N, const RansacConfig* cfgp,
+                  double* model9, uint8_t* mask);
 
+// ---- what the families put into the table (ransac_host.cpp: one row each) and what else other files call
 // homography family (ransac_h_*.hip / ransac_h_host.cpp)
-void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s, bool certifiedRow = false);
-// keyOnly: nobody reads d_counts beyond the best-key reduction, so the sweep may run in self-pruning stages
-void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, bool keyOnly, hipStream_t s);
-int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* H, uint8_t* d_mask,
-               hipStream_t s);
-int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
-                      int* sampleIdx, bool fast);
+GenerateHook h_generate;
+EvaluateHook h_evaluate;
+FinalizeHook h_finalize;
+HostHypothesisHook h_host_hypothesis;
+EntryDirectHook h_entry_direct;
 // runKernel's host half on one refit record (kernels.h kRefit*) -> H; false: degenerate, H is not a model
 bool h_refit_from_record(const double* r, double* H);
 void h_plan_forget(const Plan* P);   // ~Plan: drops the test hooks' references to the plan
 
 // fundamental-matrix family (ransac_f.hip / ransac_f_host.cpp)
-bool f_seven(int model, const RansacConfig& cfg);   // fundamental with MCV_FLAG_SEVEN_POINT
+GenerateHook f_generate;
+EvaluateHook f_evaluate;
+FinalizeHook f_finalize;
+HostHypothesisHook f_host_hypothesis;
+ConfigIntHook f_points_cfg, f_slots_cfg;
+EntryRefuseHook f_entry_refuse;
+EntryDirectHook f_entry_direct;
 int f_error_kind(const RansacConfig& cfg);
-void f_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-void f_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* F, uint8_t* d_mask,
-               hipStream_t s);
 int f_fit_all(Plan& P, const float* d_pts, int N, hipStream_t s, double* F);
-int f_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* F9, float* Ff9, int* sampleIdx,
-                      bool fast);
 
 // affine / similarity family (ransac_a.hip / ransac_a_host.cpp)
 inline bool affine_family(int model) { return model == MCV_MODEL_AFFINE || model == MCV_MODEL_SIMILARITY; }
-void a_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-int a_host_hypothesis(int model, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
-                      int* sampleIdx);
-int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
-               uint8_t* d_mask, hipStream_t s);
+GenerateHook a_generate;
+EvaluateHook a_evaluate;
+FinalizeHook a_finalize;
+HostHypothesisHook a_host_hypothesis;
+EntryDirectHook a_entry_direct;
 
 // PnP family (ransac_pnp.hip / pnp_host.cpp)
-void p_evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-int p_finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
-               uint8_t* d_mask, hipStream_t s);
+EvaluateHook p_evaluate;
+FinalizeHook p_finalize;
+ConfigIntHook p_points_cfg;
 bool pnp_cfg_epnp(const RansacConfig& cfg);   // minimal sets of 5 for EPnP (solverKind 0/1/3/4)
 // cvSolvePnPRansac's configuration: OpenCV's sample stream, RANSAC, the given budget / threshold / kind
 RansacConfig pnp_config(int iters, float thr, double conf, int kind);
 
 // essential-matrix family (ransac_e.hip / ransac_e_host.cpp)
-void e_evaluate_chunk(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s);
-int e_finalize(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int64_t slot, double* E,
-               uint8_t* d_mask, hipStream_t s);
+ReserveHook e_reserve;
+EvaluateHook e_evaluate;
+FinalizeHook e_finalize;   // hyp = the winning model slot
 // The essential exports' configuration: cvFindEssentialMat's (NULL: its defaults) and cvRecoverPose's; e_check
 // throws on what the family does not support (method, confidence, the retired flag bit).
 RansacConfig e_config(const RansacConfig* cfg);

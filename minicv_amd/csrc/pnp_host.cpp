@@ -23,7 +23,6 @@
 #include <cstring>
 #include <algorithm>
 #include <vector>
-#include <algorithm>
 
 namespace mcv {
 
@@ -109,7 +108,6 @@ static void pnp_pack(Plan& P, const mcvV2d* img, const mcvV3d* world, int N, voi
     MCV_HIP(hipGetLastError());
 }
 
-static bool fused_pnp(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FUSED_ERROR) != 0; }
 // MCV_FLAG_FAST_MINIMAL: AP3P hypotheses from the real-root finder instead of the reference's Ferrari quartic
 static bool fast_ap3p(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FAST_MINIMAL) != 0; }
 bool pnp_cfg_epnp(const RansacConfig& cfg) { return pnp_kind_epnp(pnp_kind(cfg.pnpKind)); }
@@ -124,40 +122,26 @@ static void pnp_generate_exact(Plan& P, const void* d_pts, int N, const Sampler&
     MCV_HIP(hipGetLastError());
 }
 
-void p_evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
-    const float thr2 = (float)(cfg.threshold * cfg.threshold);
-    const bool epnp = pnp_cfg_epnp(cfg);
+int p_points_cfg(const RansacConfig& cfg) { return pnp_cfg_epnp(cfg) ? 5 : 4; }
+static ChunkSolver pnp_solver(const RansacConfig& cfg) {
+    return pnp_cfg_epnp(cfg) ? kSolverEpnp : (fast_ap3p(cfg) ? kSolverAp3pFast : kSolverAp3p);
+}
+
+void p_evaluate(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, bool, hipStream_t s) {
     const Sampler smp = P.sampler(cfg);
     {
         ProfScope pg("pnp_generate", s);
-        pnp_generate_exact(P, d_pts, N, smp, hypBegin, hypCount, epnp, fast_ap3p(cfg), P.models.p, d_counts, s);
+        pnp_generate_exact(P, d_pts, N, smp, hypBegin, hypCount, pnp_cfg_epnp(cfg), fast_ap3p(cfg), P.models.p,
+                           d_counts, s);
     }
-    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, epnp ? 1 : (fast_ap3p(cfg) ? 2 : 0), s);
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, pnp_solver(cfg), s);
     P.bb4.ensure(4);
     P.pairs.ensure((size_t)(N + 1) * kPnpPairFloatsPerPoint);
     launch_pnp_extent(d_pts, N, P.bb4.p, P.pairs.p, s);
     ProfScope ps("pnp_verify", s);
-    launch_pnp_verify(d_pts, N, P.pnpCam, P.models.p, d_counts, hypCount, thr2, fused_pnp(cfg), P.bb4.p, P.pairs.p, s);
-}
-
-static PnpOneOut pnp_fetch_one(Plan& P, hipStream_t s) {
-    PnpOneOut one;
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, P.one.p, sizeof(PnpOneOut), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    std::memcpy(&one, P.h_one.p, sizeof(PnpOneOut));
-    return one;
-}
-
-static int pnp_mask_count(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, const double* R, const double* t,
-                          uint8_t* d_mask, hipStream_t s) {
-    const float thr2 = (float)(cfg.threshold * cfg.threshold);
-    MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-    launch_pnp_mask(d_pts, N, P.pnpCam, R, t, thr2, fused_pnp(cfg), d_mask, P.count.p, s);
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    return P.h_i.p[0];
+    launch_pnp_verify(d_pts, N, P.pnpCam, P.models.p, d_counts, hypCount, thr2_of(P, cfg), fused_error(cfg), P.bb4.p,
+                      P.pairs.p, s);
 }
 
 // Levenberg-Marquardt on (rvec, t) over the (masked) correspondences: damping A + lambda diag(A),
@@ -348,38 +332,36 @@ static void epnp_inliers(Plan& P, const void* d_pts, int N, const uint8_t* d_mas
 int p_finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
                uint8_t* d_mask, hipStream_t s) {
     PnpOneOut one;
-    const bool epnp = pnp_cfg_epnp(cfg);
     const Sampler smp = P.sampler(cfg);
     int count = 0;
-    if (P.last.covers(hyp, smp, d_pts, N, epnp ? 1 : (fast_ap3p(cfg) ? 2 : 0))) {
+    if (P.last.covers(hyp, smp, d_pts, N, pnp_solver(cfg))) {
         // the winner's pose straight from the last chunk's model buffer (the same code produced it)
         // instead of a single-lane re-solve; its mask and count from that slot too, so the pose, the
         // count and the freshness check return with one synchronisation
         const PnpPose* d_m = (const PnpPose*)P.models.p + (hyp - P.last.begin);
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, d_m, sizeof(PnpPose), hipMemcpyDeviceToHost, s));
+        queue_one<PnpPose>(P, s, d_m);
         queue_chunk_check(P, d_pts, N, s);
-        MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-        launch_pnp_mask_dev(d_pts, N, P.pnpCam, d_m, (float)(cfg.threshold * cfg.threshold), fused_pnp(cfg), d_mask,
-                            P.count.p, s);
+        zero_count(P, s);
+        launch_pnp_mask_dev(d_pts, N, P.pnpCam, d_m, thr2_of(P, cfg), fused_error(cfg), d_mask, P.count.p, s);
         MCV_HIP(hipGetLastError());
-        MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        queue_count(P, s);
         MCV_HIP(hipStreamSynchronize(s));
         if (!chunk_fresh(P)) {   // the points changed since the chunk was evaluated: re-solve
             P.last.clear();
             return p_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
         }
-        PnpPose pose;
-        std::memcpy(&pose, P.h_one.p, sizeof(PnpPose));
+        const PnpPose pose = take_one<PnpPose>(P);
         std::memcpy(one.R, pose.R, sizeof(one.R));
         std::memcpy(one.t, pose.t, sizeof(one.t));
         one.status = 1;
-        count = P.h_i.p[0];
+        count = take_count(P);
     } else {
-        launch_pnp_one(d_pts, N, P.pnpCam, smp, hyp, epnp, (PnpOneOut*)P.one.p, s, fast_ap3p(cfg));
-        MCV_HIP(hipGetLastError());
-        one = pnp_fetch_one(P, s);
+        launch_pnp_one(d_pts, N, P.pnpCam, smp, hyp, pnp_cfg_epnp(cfg), (PnpOneOut*)P.one.p, s, fast_ap3p(cfg));
+        one = fetch_one<PnpOneOut>(P, s);
         if (one.status != 1) fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
-        count = pnp_mask_count(P, d_pts, N, cfg, one.R, one.t, d_mask, s);
+        count = mask_count(P, s, [&](int* d_count) {
+            launch_pnp_mask(d_pts, N, P.pnpCam, one.R, one.t, thr2_of(P, cfg), fused_error(cfg), d_mask, d_count, s);
+        });
     }
     double r[3], t[3] = {one.t[0], one.t[1], one.t[2]};
     rodrigues_inv(one.R, r);
@@ -414,8 +396,7 @@ static PnpResult pnp_ransac(Plan& P, const mcvV2d* img, const mcvV3d* world, int
         // npoints == model_points: one solvePnP on all points (P3P for 4, here AP3P; EPnP for 5)
         if (N == 4) launch_pnp_solve4(P.ptsd.p, P.pnpCam, (PnpOneOut*)P.one.p, s, fast_ap3p(cfg));
         else launch_pnp_solve5(P.ptsd.p, P.pnpCam, (PnpOneOut*)P.one.p, s);
-        MCV_HIP(hipGetLastError());
-        PnpOneOut one = pnp_fetch_one(P, s);
+        const PnpOneOut one = fetch_one<PnpOneOut>(P, s);
         if (one.status != 1) return res;
         rodrigues_inv(one.R, res.r);
         for (int k = 0; k < 3; ++k) res.t[k] = one.t[k];
@@ -464,8 +445,7 @@ static bool pnp_ransac_export(const mcvV2d* img, const mcvV3d* world, int N, con
     rVec->X = r.r[0]; rVec->Y = r.r[1]; rVec->Z = r.r[2];
     tVec->X = r.t[0]; tVec->Y = r.t[1]; tVec->Z = r.t[2];
     std::vector<uint8_t> m(N);
-    MCV_HIP(hipMemcpyAsync(m.data(), P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
+    mask_to_host(P, m.data(), N, s);
     int c = 0;
     for (int i = 0; i < N; ++i)
         if (m[i]) {
@@ -703,11 +683,7 @@ extern "C" MCV_API int solveAp3p(mcvM33d* Rs, mcvV3d* ts, double mu0, double mv0
         P.one.ensure(sizeof(Ap3pOut));
         P.h_one.ensure(sizeof(Ap3pOut));
         launch_pnp_ap3p(in, (Ap3pOut*)P.one.p, s);
-        MCV_HIP(hipGetLastError());
-        Ap3pOut out;
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, P.one.p, sizeof(Ap3pOut), hipMemcpyDeviceToHost, s));
-        MCV_HIP(hipStreamSynchronize(s));
-        std::memcpy(&out, P.h_one.p, sizeof(Ap3pOut));
+        const Ap3pOut out = fetch_one<Ap3pOut>(P, s);
         for (int k = 0; k < out.count; ++k) {
             for (int j = 0; j < 9; ++j) Rs[k].M[j] = out.R[k][j];
             ts[k].X = out.t[k][0]; ts[k].Y = out.t[k][1]; ts[k].Z = out.t[k][2];

@@ -20,25 +20,23 @@ namespace mcv {
 
 // One chunk of hypotheses; the winner is re-solved from its sample (a closed form: nothing to cache).
 // Shared by the RANSAC evaluate below and lmeds_search.
-void a_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
+void a_generate(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, hipStream_t s) {
     P.last.clear();
-    launch_a_generate(model_points(P.model), d_pts, N, P.sampler(cfg), hypBegin, hypCount, P.models.p, P.h64.p,
-                      d_counts, s);
+    launch_a_generate(model_points(P.model), (const float*)d_pts, N, P.sampler(cfg), hypBegin, hypCount, P.models.p,
+                      P.h64.p, d_counts, s);
 }
 
-void a_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
+void a_evaluate(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, bool, hipStream_t s) {
     P.pairs.ensure((size_t)(N + 1) / 2 * 8);
-    launch_h_pair(d_pts, N, P.pairs.p, s);
+    launch_h_pair((const float*)d_pts, N, P.pairs.p, s);
     {
         ProfScope pg("a_generate", s);
-        a_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+        a_generate(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
     }
     ProfScope ps("a_verify", s);
-    launch_a_verify(P.pairs.p, N, P.models.p, d_counts, hypCount, thr2, fused_error(cfg), s);
+    launch_a_verify(P.pairs.p, N, P.models.p, d_counts, hypCount, thr2_of(P, cfg), fused_error(cfg), s);
 }
 
 // LMSolver::create(Affine2DRefineCallback / AffinePartial2DRefineCallback, 10)->run: the sums over the
@@ -79,26 +77,22 @@ static int a_lm_refine_host(const float* pts4, int N, const uint8_t* mask, doubl
 static int a_finalize_impl(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
                            uint8_t* d_mask, hipStream_t s, bool direct) {
     const int m = model_points(P.model);
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
     AOneOut* d_one = (AOneOut*)P.one.p;
     launch_a_one(m, d_pts, N, P.sampler(cfg), hyp, d_one, s, direct);
-    int count = N;
-    if (!direct) {
-        MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-        launch_a_mask_one(d_pts, N, d_one, thr2, fused_error(cfg), d_mask, P.count.p, s);
-        MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!direct) {   // the record and the count come back with one synchronisation
+        zero_count(P, s);
+        launch_a_mask_one(d_pts, N, d_one, thr2_of(P, cfg), fused_error(cfg), d_mask, P.count.p, s);
+        queue_count(P, s);
     }
     MCV_HIP(hipGetLastError());
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(AOneOut), hipMemcpyDeviceToHost, s));
+    queue_one<AOneOut>(P, s);
     MCV_HIP(hipStreamSynchronize(s));
-    AOneOut one;
-    std::memcpy(&one, P.h_one.p, sizeof(AOneOut));
+    const AOneOut one = take_one<AOneOut>(P);
     if (one.status != 1) {
         if (direct) fail("degenerate point set (no finite model from the %d correspondences)", m);
         fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
     }
-    if (!direct) count = P.h_i.p[0];
+    const int count = direct ? N : take_count(P);
     double A[6];
     for (int k = 0; k < 6; ++k) A[k] = one.A[k];
     if (!direct && !(cfg.flags & MCV_FLAG_NO_REFINE) && count > m) {
@@ -110,13 +104,20 @@ static int a_finalize_impl(Plan& P, const float* d_pts, int N, const RansacConfi
     return count;
 }
 
-int a_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+int a_finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
                uint8_t* d_mask, hipStream_t s) {
-    return a_finalize_impl(P, d_pts, N, cfg, hyp, model9, d_mask, s, false);
+    return a_finalize_impl(P, (const float*)d_pts, N, cfg, hyp, model9, d_mask, s, false);
+}
+
+// The 2-D entry's direct case: N == the sample size, one solve on all points.
+bool a_entry_direct(Plan& P, const char*, int N, const RansacConfig& cfg, hipStream_t s, double* model9) {
+    if (N != model_points(P.model)) return false;
+    a_finalize_impl(P, P.pts.p, N, cfg, 0, model9, P.mask.p, s, true);
+    return true;
 }
 
 int a_host_hypothesis(int model, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
-                      int* sampleIdx) {
+                      int* sampleIdx, bool) {
     const int m = model_points(model);
     if (N < m) fail("N < %d", m);
     AModelF mf;
@@ -131,40 +132,11 @@ int a_host_hypothesis(int model, const float* pts4, int N, uint64_t seed, int64_
     return st;
 }
 
+// The exports' 2 x 3 result: the first six of find_model_2d's nine.
 static int estimate_affine(int model, const char* who, const mcvV2d* from, const mcvV2d* to, int N,
                            const RansacConfig* cfgp, double* A6, uint8_t* mask) {
-    if (!from || !to || !A6 || N < 0) fail("%s: null argument or negative N", who);
-    if (mask) std::memset(mask, 0, (size_t)N);
-    const int m = model_points(model);
-    if (N < m) fail("%s: need at least %d correspondences (N=%d)", who, m, N);
-    RansacConfig cfg = config_or_default(cfgp);
-    if (!cfgp) cfg.confidence = 0.99;
-    check_flags(cfg, who);
-    if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LMEDS) fail("%s: unsupported method %d", who, cfg.method);
-    if (!(cfg.confidence > 0 && cfg.confidence < 1)) fail("%s: confidence must be in (0,1)", who);
-    require_device();
-    Plan& P = thread_plan(model);
-    hipStream_t s = P.own_stream();
-    P.reserve(N, 1);
-    pack_points(P, from, to, N, P.pts.p, s);
     double model9[9];
-    int count = 0;
-    if (N == m) {
-        count = a_finalize_impl(P, P.pts.p, N, cfg, 0, model9, P.mask.p, s, true);
-        if (mask) std::memset(mask, 1, (size_t)N);
-    } else {
-        RansacConfig fin = cfg;
-        int64_t best;
-        if (cfg.method == MCV_METHOD_LMEDS) {
-            best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
-        } else {
-            best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
-            if (best < 0) fail("%s: RANSAC found no model with >= %d inliers", who, m);
-        }
-        count = a_finalize(P, P.pts.p, N, fin, best, model9, P.mask.p, s);
-        if (cfg.method == MCV_METHOD_LMEDS && count < m) fail("%s: LMedS model has %d inliers (< %d)", who, count, m);
-        mask_to_host(P, mask, N, s);
-    }
+    const int count = find_model_2d(model, who, from, to, N, cfgp, A6 ? model9 : nullptr, mask);
     for (int k = 0; k < 6; ++k) A6[k] = model9[k];
     return count;
 }

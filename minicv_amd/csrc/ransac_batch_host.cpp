@@ -75,8 +75,7 @@ static const char* batch_model_name(int model) {
 static RansacConfig batch_config(int model, const RansacConfig* cfgp) {
     if (model != MCV_MODEL_HOMOGRAPHY && model != MCV_MODEL_FUNDAMENTAL && !affine_family(model))
         fail("cvFindModelBatch: unsupported model %d (homography, fundamental, affine, similarity)", model);
-    RansacConfig cfg = config_or_default(cfgp);
-    if (!cfgp && model != MCV_MODEL_HOMOGRAPHY) cfg.confidence = 0.99;
+    const RansacConfig cfg = config_or_default(model, cfgp);
     check_batch_config("cvFindModelBatch", cfg, true);
     return cfg;
 }

@@ -30,14 +30,21 @@ int e_kind(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FUSED_ERROR) 
 // constraints, Illinois real roots) instead of the reference's (fivepoint.cpp / five_point_ref.h).
 static bool e_fast(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FAST_MINIMAL) != 0; }
 
-void e_evaluate_chunk(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
-    const float thr2 = (float)(cfg.threshold * cfg.threshold);
+static ChunkSolver e_solver(const RansacConfig& cfg) { return e_fast(cfg) ? kSolverEFast : kSolverEReference; }
+
+void e_reserve(Plan& P) {
+    P.dslot.ensure((size_t)P.maxHyps * kEModelSlots);
+    P.ndense.ensure(8);
+    if (P.maxHyps >= kEStageMinHyps) P.estage.ensure((size_t)P.maxHyps * sizeof(EStage));
+}
+
+void e_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, bool, hipStream_t s) {
+    const double* d_pts = (const double*)d_ptsv;
     const Sampler smp = P.sampler(cfg);
-    const bool fast = e_fast(cfg);
     {
         ProfScope pg("e_generate", s);
-        if (fast) {   // opt-in: the Illinois replacement solver (hyp_essential.h / five_point_wave.h)
+        if (e_fast(cfg)) {   // opt-in: the Illinois replacement solver (hyp_essential.h / five_point_wave.h)
             if (hypCount >= kEStageMinHyps) P.estage.ensure((size_t)hypCount * sizeof(EStage));
             launch_e_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, P.dslot.p, P.ndense.p, d_counts,
                               hypCount >= kEStageMinHyps ? P.estage.p : nullptr, s);
@@ -47,53 +54,30 @@ void e_evaluate_chunk(Plan& P, const double* d_pts, int N, const RansacConfig& c
                                P.estage.p, s);
         }
     }
-    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast ? 31 : 30, s);
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, e_solver(cfg), s);
     P.bb4.ensure(4);
     P.pts.ensure((size_t)N * 4);
     launch_abs_bound4(d_pts, true, N, P.bb4.p, P.pts.p, s);   // fp32 copy + bounds for the prefilter
     ProfScope ps("e_verify", s);
-    launch_e_verify(d_pts, N, P.models.p, P.dslot.p, P.ndense.p, hypCount * kEModelSlots, d_counts, thr2, e_kind(cfg),
-                    s, P.pts.p, P.bb4.p);
-}
-
-static EOneOut e_one(Plan& P, const double* d_pts, int N, const Sampler& smp, int64_t hyp, bool fast,
-                     hipStream_t s) {
-    EOneOut* d_one = (EOneOut*)P.one.p;
-    if (fast) launch_e_one(d_pts, N, smp, hyp, d_one, s);
-    else launch_e5_one(d_pts, N, smp, hyp, d_one, s);
-    MCV_HIP(hipGetLastError());
-    EOneOut one;
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(EOneOut), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    std::memcpy(&one, P.h_one.p, sizeof(EOneOut));
-    return one;
-}
-
-static int e_mask_count(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, const double* E,
-                        uint8_t* d_mask, hipStream_t s) {
-    const float thr2 = (float)(cfg.threshold * cfg.threshold);
-    MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-    launch_e_mask(d_pts, N, E, thr2, e_kind(cfg), d_mask, P.count.p, s);
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    return P.h_i.p[0];
+    launch_e_verify(d_pts, N, P.models.p, P.dslot.p, P.ndense.p, hypCount * kEModelSlots, d_counts, thr2_of(P, cfg),
+                    e_kind(cfg), s, P.pts.p, P.bb4.p);
 }
 
 // Winner (model slot) -> E and its mask. OpenCV keeps the best hypothesis' model as is.
-int e_finalize(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int64_t slot, double* E,
+int e_finalize(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t slot, double* E,
                uint8_t* d_mask, hipStream_t s) {
+    const double* d_pts = (const double*)d_ptsv;
     const int64_t hyp = slot / kEModelSlots;
     const int k = (int)(slot % kEModelSlots);
     bool have = false;
     const Sampler smp = P.sampler(cfg);
-    if (P.last.covers(hyp, smp, d_pts, N, e_fast(cfg) ? 31 : 30)) {
+    if (P.last.covers(hyp, smp, d_pts, N, e_solver(cfg))) {
         const int local = (int)((hyp - P.last.begin) * kEModelSlots + k);
         int* d_found = P.ndense.p + 7;
-        uint8_t* d_out = P.one.p;
-        launch_e_fetch(P.models.p, P.dslot.p, P.ndense.p, (int)(P.last.count * kEModelSlots), local, d_out, d_found, s);
+        launch_e_fetch(P.models.p, P.dslot.p, P.ndense.p, (int)(P.last.count * kEModelSlots), local, P.one.p, d_found,
+                       s);
         MCV_HIP(hipGetLastError());
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, d_out, 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+        queue_one<mcvM33d>(P, s);   // the fetched slot's 9 doubles
         MCV_HIP(hipMemcpyAsync(P.h_i.p, d_found, sizeof(int), hipMemcpyDeviceToHost, s));
         queue_chunk_check(P, d_pts, N, s);
         MCV_HIP(hipStreamSynchronize(s));
@@ -104,11 +88,15 @@ int e_finalize(Plan& P, const double* d_pts, int N, const RansacConfig& cfg, int
         }
     }
     if (!have) {
-        const EOneOut one = e_one(P, d_pts, N, smp, hyp, e_fast(cfg), s);
+        if (e_fast(cfg)) launch_e_one(d_pts, N, smp, hyp, (EOneOut*)P.one.p, s);
+        else launch_e5_one(d_pts, N, smp, hyp, (EOneOut*)P.one.p, s);
+        const EOneOut one = fetch_one<EOneOut>(P, s);
         if (one.status <= k) fail("winning slot %lld has no model (status %d)", (long long)slot, one.status);
         for (int j = 0; j < 9; ++j) E[j] = one.E[k][j];
     }
-    return e_mask_count(P, d_pts, N, cfg, E, d_mask, s);
+    return mask_count(P, s, [&](int* d_count) {
+        launch_e_mask(d_pts, N, E, thr2_of(P, cfg), e_kind(cfg), d_mask, d_count, s);
+    });
 }
 
 // Upload the pixel pairs and normalise them on the device.
@@ -124,22 +112,14 @@ static void e_pack(Plan& P, const mcvV2d* a, const mcvV2d* b, int N, double foca
 
 // Five-point solve on the first 5 device-resident correspondences (count == modelPoints case).
 static EOneOut e_solve_first5(Plan& P, const double* d_pts, hipStream_t s) {
-    double h[20];
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_pts, 5 * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    std::memcpy(h, P.h_one.p, sizeof(h));
+    struct First5 { double h[20]; };
+    const First5 p = fetch_one<First5>(P, s, d_pts);
     EFiveIn in;
     for (int i = 0; i < 5; ++i) {
-        in.x1[i] = h[4 * i]; in.y1[i] = h[4 * i + 1]; in.x2[i] = h[4 * i + 2]; in.y2[i] = h[4 * i + 3];
+        in.x1[i] = p.h[4 * i]; in.y1[i] = p.h[4 * i + 1]; in.x2[i] = p.h[4 * i + 2]; in.y2[i] = p.h[4 * i + 3];
     }
-    EOneOut* d_one = (EOneOut*)P.one.p;
-    launch_e_fivepoint(in, d_one, s);
-    MCV_HIP(hipGetLastError());
-    EOneOut one;
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(EOneOut), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
-    std::memcpy(&one, P.h_one.p, sizeof(EOneOut));
-    return one;
+    launch_e_fivepoint(in, (EOneOut*)P.one.p, s);
+    return fetch_one<EOneOut>(P, s);
 }
 
 struct EResult {
@@ -246,10 +226,7 @@ extern "C" MCV_API int cvFindEssentialMat(const mcvV2d* a, const mcvV2d* b, cons
             if (N == 5) fail("cvFindEssentialMat: N == 5 gave %d solutions (OpenCV returns them stacked)", r.nmodels);
             fail("cvFindEssentialMat: RANSAC found no model with >= 5 inliers");
         }
-        if (mask) {
-            MCV_HIP(hipMemcpyAsync(mask, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));
-            MCV_HIP(hipStreamSynchronize(s));
-        }
+        mask_to_host(P, mask, N, s);
         for (int k = 0; k < 9; ++k) E->M[k] = r.E[k];
         return r.count;
     })
@@ -267,8 +244,7 @@ extern "C" MCV_API mcvBool cvRecoverPoses(const RecoverPoseConfig* config, const
         hipStream_t s = P.own_stream();
         const EResult r = e_find(P, pa, pb, N, config->FocalLength, config->PrincipalPoint, cfg, s);
         if (r.nmodels == 0) { set_last_error("cvRecoverPoses: no essential matrix"); return false; }
-        MCV_HIP(hipMemcpyAsync(ms, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));   // :179-183
-        MCV_HIP(hipStreamSynchronize(s));
+        mask_to_host(P, ms, N, s);   // :179-183
         if (r.count <= 0) { set_last_error("cvRecoverPoses: E is not 3x3 (several N == 5 solutions)"); return false; }
         double t[3];
         e_decompose(r.E, rMat1->M, rMat2->M, t);   // :186
@@ -289,8 +265,7 @@ extern "C" MCV_API int cvRecoverPose(const RecoverPoseConfig* config, const int 
         hipStream_t s = P.own_stream();
         const EResult r = e_find(P, pa, pb, N, config->FocalLength, config->PrincipalPoint, cfg, s);
         if (r.nmodels == 0) fail("cvRecoverPose: no essential matrix");
-        MCV_HIP(hipMemcpyAsync(ms, P.mask.p, (size_t)N, hipMemcpyDeviceToHost, s));   // :206-210
-        MCV_HIP(hipStreamSynchronize(s));
+        mask_to_host(P, ms, N, s);   // :206-210
         if (r.count <= 0) fail("cvRecoverPose: E is not 3x3 (several N == 5 solutions)");
         double t[3];
         const int good = e_recover(P, N, r.E, P.mask.p, rMat->M, t, s);   // :212
@@ -308,13 +283,8 @@ extern "C" MCV_API int cvFivePoint(const mcvV2d* pa, const mcvV2d* pb, mcvM33d* 
         P.reserve(5, 1);
         EFiveIn in;
         for (int i = 0; i < 5; ++i) { in.x1[i] = pa[i].X; in.y1[i] = pa[i].Y; in.x2[i] = pb[i].X; in.y2[i] = pb[i].Y; }
-        EOneOut* d_one = (EOneOut*)P.one.p;
-        launch_e_fivepoint(in, d_one, s);
-        MCV_HIP(hipGetLastError());
-        EOneOut one;
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(EOneOut), hipMemcpyDeviceToHost, s));
-        MCV_HIP(hipStreamSynchronize(s));
-        std::memcpy(&one, P.h_one.p, sizeof(EOneOut));
+        launch_e_fivepoint(in, (EOneOut*)P.one.p, s);
+        const EOneOut one = fetch_one<EOneOut>(P, s);
         const int n = std::max(one.status, 0);
         for (int k = 0; k < n; ++k)
             for (int j = 0; j < 9; ++j) Es[k].M[j] = one.E[k][j];

@@ -24,55 +24,53 @@ int f_error_kind(const RansacConfig& cfg) {
     return e * 2 + ((cfg.flags & MCV_FLAG_FUSED_ERROR) ? 0 : 1);
 }
 
-bool f_seven(int model, const RansacConfig& cfg) {
-    return model == MCV_MODEL_FUNDAMENTAL && (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0;
-}
+// MCV_FLAG_SEVEN_POINT: 7-point samples (OpenCV's FM_RANSAC / FM_LMEDS), up to 3 models each
+static bool f_seven(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0; }
+int f_points_cfg(const RansacConfig& cfg) { return f_seven(cfg) ? 7 : 8; }
+int f_slots_cfg(const RansacConfig& cfg) { return f_seven(cfg) ? kF7Slots : 1; }
+static ChunkSolver f_solver(const RansacConfig& cfg) { return fast_minimal(cfg) ? kSolverF8Fast : kSolverF8Exact; }
 
 // One chunk of hypotheses. 8-point: P.last = this chunk (the winner's fp64 model can come straight from
 // its buffer: f_finalize). 7-point (OpenCV FM_RANSAC): 3 model slots per hypothesis (slot keys like
 // essential), nothing cached. Shared by the RANSAC evaluate below and lmeds_search.
-void f_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
+void f_generate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, hipStream_t s) {
+    const float* d_pts = (const float*)d_ptsv;
     const Sampler smp = P.sampler(cfg);
-    if (f_seven(P.model, cfg)) {
+    if (f_seven(cfg)) {
         P.last.clear();
         launch_f7_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, d_counts, s);
         return;
     }
     launch_f_generate(d_pts, N, smp, hypBegin, hypCount, P.models.p, d_counts, s, fast_minimal(cfg));
-    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 11 : 10, s);
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, f_solver(cfg), s);
 }
 
-void f_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s) {
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
-    if (f_seven(P.model, cfg)) {
-        f_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+void f_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, bool, hipStream_t s) {
+    const float* d_pts = (const float*)d_ptsv;
+    if (f_seven(cfg)) {
+        f_generate(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
     } else {
         ProfScope pg("f_generate", s);
-        f_generate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+        f_generate(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
     }
     P.bb4.ensure(4);
     launch_abs_bound4(d_pts, false, N, P.bb4.p, nullptr, s);
     ProfScope ps("f_verify", s);
-    const int nSlots = hypCount * model_slots_cfg(P.model, cfg);
-    launch_f_verify(d_pts, N, P.models.p, d_counts, nSlots, thr2, f_error_kind(cfg), s, P.bb4.p);
+    const int nSlots = hypCount * f_slots_cfg(cfg);
+    launch_f_verify(d_pts, N, P.models.p, d_counts, nSlots, thr2_of(P, cfg), f_error_kind(cfg), s, P.bb4.p);
 }
 
-int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* F, uint8_t* d_mask,
+int f_finalize(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hyp, double* F, uint8_t* d_mask,
                hipStream_t s) {
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
-    FOneOut* d_one = (FOneOut*)P.one.p;
-    const bool fast = (cfg.flags & MCV_FLAG_FAST_MINIMAL) != 0;
+    const float* d_pts = (const float*)d_ptsv;
     FOneOut one;
     const Sampler smp = P.sampler(cfg);
-    if (!(cfg.flags & MCV_FLAG_SEVEN_POINT) && P.last.covers(hyp, smp, d_pts, N, fast ? 11 : 10)) {
+    if (!f_seven(cfg) && P.last.covers(hyp, smp, d_pts, N, f_solver(cfg))) {
         // the winner's model straight from the last chunk's buffer (the same code produced it) instead
         // of a single-lane re-solve (the eigen-solve's ~0.5 ms latency)
-        const FModelD* d_m = (const FModelD*)P.models.p + (hyp - P.last.begin);
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, d_m, sizeof(FModelD), hipMemcpyDeviceToHost, s));
+        queue_one<FModelD>(P, s, (const FModelD*)P.models.p + (hyp - P.last.begin));
         queue_chunk_check(P, d_pts, N, s);
         MCV_HIP(hipStreamSynchronize(s));
         if (!chunk_fresh(P)) {   // the points changed since the chunk was evaluated: re-solve
@@ -82,21 +80,15 @@ int f_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
         std::memcpy(one.F, P.h_one.p, sizeof(FModelD));
         one.status = 1;
     } else {
-        if (cfg.flags & MCV_FLAG_SEVEN_POINT) launch_f7_one(d_pts, N, smp, hyp, d_one, s);   // hyp = model slot
-        else launch_f_one(d_pts, N, smp, hyp, d_one, s, fast);
-        MCV_HIP(hipGetLastError());
-        MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(FOneOut), hipMemcpyDeviceToHost, s));
-        MCV_HIP(hipStreamSynchronize(s));
-        std::memcpy(&one, P.h_one.p, sizeof(FOneOut));
+        if (f_seven(cfg)) launch_f7_one(d_pts, N, smp, hyp, (FOneOut*)P.one.p, s);   // hyp = model slot
+        else launch_f_one(d_pts, N, smp, hyp, (FOneOut*)P.one.p, s, fast_minimal(cfg));
+        one = fetch_one<FOneOut>(P, s);
     }
     if (one.status != 1) fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
-    MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-    launch_f_mask(d_pts, N, one.F, thr2, f_error_kind(cfg), d_mask, P.count.p, s);
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipStreamSynchronize(s));
     for (int k = 0; k < 9; ++k) F[k] = one.F[k];
-    return P.h_i.p[0];
+    return mask_count(P, s, [&](int* d_count) {
+        launch_f_mask(d_pts, N, one.F, thr2_of(P, cfg), f_error_kind(cfg), d_mask, d_count, s);
+    });
 }
 
 // run8Point over all correspondences: GPU fp64 sums (centroids, Euclidean distances, A^T A), then the
@@ -134,14 +126,37 @@ int f_fit_all(Plan& P, const float* d_pts, int N, hipStream_t s, double* F) {
     return N;
 }
 
-int f_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* F9, float* Ff9, int* sampleIdx,
-                      bool fast) {
+int f_host_hypothesis(int, const float* pts4, int N, uint64_t seed, int64_t hyp, double* F9, float* Ff9,
+                      int* sampleIdx, bool fast) {
     if (N < 8) fail("N < 8");
     for (int k = 0; k < 9; ++k) F9[k] = 0;
     EigWsLocal ws;
     const int st = f_hypothesis(pts4, N, Sampler{seed, nullptr}, (uint64_t)hyp, F9, sampleIdx, ws, fast);
     for (int k = 0; k < 9; ++k) Ff9[k] = (float)F9[k];
     return st;
+}
+
+// The 2-D entry's refusals that depend on the configuration: the sample size is 7 or 8.
+void f_entry_refuse(const char* who, int N, const RansacConfig& cfg) {
+    if (f_seven(cfg) && cfg.method == MCV_METHOD_RANSAC && N != 7 && N < 15)
+        fail("%s: 7-point FM_RANSAC needs N >= 15 (OpenCV uses LMeDS below that: use method 4; N=%d)", who, N);
+    if (N < f_points_cfg(cfg)) fail("%s: need at least %d correspondences (N=%d)", who, f_points_cfg(cfg), N);
+}
+
+// The 2-D entry's direct cases. 7-point at N == 7: run7Point once (the first of its models). FM_8POINT (method
+// 0), and N == 8 unless it is 7-point LMedS (7-point at any N > 7 searches; the range below 15 is where
+// OpenCV itself runs LMedS): run8Point on all points.
+bool f_entry_direct(Plan& P, const char* who, int N, const RansacConfig& cfg, hipStream_t s, double* F) {
+    if (f_seven(cfg) && N == 7) {
+        launch_f7_direct(P.pts.p, (FOneOut*)P.one.p, s);
+        const FOneOut one = fetch_one<FOneOut>(P, s);
+        if (one.status <= 0) fail("%s: degenerate 7-point set", who);
+        for (int k = 0; k < 9; ++k) F[k] = one.F[k];
+        return true;
+    }
+    if (cfg.method != MCV_METHOD_LSQ && !(N == 8 && !(f_seven(cfg) && cfg.method == MCV_METHOD_LMEDS))) return false;
+    if (f_fit_all(P, P.pts.p, N, s, F) <= 0) fail("%s: degenerate point set", who);
+    return true;
 }
 
 }  // namespace mcv
@@ -151,59 +166,7 @@ using namespace mcv;
 extern "C" MCV_API int cvFindFundamentalMat(const mcvV2d* a, const mcvV2d* b, const int N, const RansacConfig* cfgp,
                                             mcvM33d* F, uint8_t* mask) {
     MCV_GUARD(0, {
-        if (!a || !b || !F || N < 0) fail("cvFindFundamentalMat: null argument or negative N");
-        if (mask) std::memset(mask, 0, (size_t)N);
-        RansacConfig cfg = config_or_default(cfgp);
-        if (!cfgp) cfg.confidence = 0.99;
-        check_flags(cfg, "cvFindFundamentalMat");
-        const bool seven = (cfg.flags & MCV_FLAG_SEVEN_POINT) != 0;
-        if (seven && cfg.method == MCV_METHOD_RANSAC && N != 7 && N < 15)
-            fail("cvFindFundamentalMat: 7-point FM_RANSAC needs N >= 15 (OpenCV uses LMeDS below that: use method 4; "
-                 "N=%d)", N);
-        if (!seven && N < 8) fail("cvFindFundamentalMat: need at least 8 correspondences (N=%d)", N);
-        if (seven && N < 7) fail("cvFindFundamentalMat: need at least 7 correspondences (N=%d)", N);
-        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
-            fail("cvFindFundamentalMat: unsupported method %d", cfg.method);
-        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
-            fail("cvFindFundamentalMat: confidence must be in (0,1)");
-        require_device();
-        Plan& P = thread_plan(MCV_MODEL_FUNDAMENTAL);
-        hipStream_t s = P.own_stream();
-        P.reserve(N, 1);
-        pack_points(P, a, b, N, P.pts.p, s);
-        double Fm[9];
-        int count = 0;
-        if (seven && N == 7) {
-            // findFundamentalMat with npoints == 7: run7Point once (the first of its models), mask all 1
-            launch_f7_direct(P.pts.p, (FOneOut*)P.one.p, s);
-            MCV_HIP(hipGetLastError());
-            FOneOut one;
-            MCV_HIP(hipMemcpyAsync(P.h_one.p, P.one.p, sizeof(FOneOut), hipMemcpyDeviceToHost, s));
-            MCV_HIP(hipStreamSynchronize(s));
-            std::memcpy(&one, P.h_one.p, sizeof(FOneOut));
-            if (one.status <= 0) fail("cvFindFundamentalMat: degenerate 7-point set");
-            for (int k = 0; k < 9; ++k) Fm[k] = one.F[k];
-            if (mask) std::memset(mask, 1, (size_t)N);
-            count = N;
-        } else if (cfg.method == MCV_METHOD_LSQ || (N == 8 && !(seven && cfg.method == MCV_METHOD_LMEDS))) {
-            count = f_fit_all(P, P.pts.p, N, s, Fm);
-            if (count <= 0) fail("cvFindFundamentalMat: degenerate point set");
-            if (mask) std::memset(mask, 1, (size_t)N);
-        } else if (cfg.method == MCV_METHOD_LMEDS) {
-            // 8-point, or 7-point at any N > 7 (the range below 15 is where OpenCV itself runs LMedS)
-            RansacConfig fin = cfg;
-            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
-            count = f_finalize(P, P.pts.p, N, fin, best, Fm, P.mask.p, s);
-            if (count < (seven ? 7 : 8)) fail("cvFindFundamentalMat: LMedS model has %d inliers (< %d)", count, seven ? 7 : 8);
-            mask_to_host(P, mask, N, s);
-        } else {
-            const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
-            if (best < 0) fail("cvFindFundamentalMat: RANSAC found no model with >= %d inliers", seven ? 7 : 8);
-            count = f_finalize(P, P.pts.p, N, cfg, best, Fm, P.mask.p, s);
-            mask_to_host(P, mask, N, s);
-        }
-        for (int k = 0; k < 9; ++k) F->M[k] = Fm[k];
-        return count;
+        return find_model_2d(MCV_MODEL_FUNDAMENTAL, "cvFindFundamentalMat", a, b, N, cfgp, F ? F->M : nullptr, mask);
     })
 }
 

@@ -2,7 +2,7 @@
 //
 // cvFindHomography (new export, conventions of cvRecoverPose, MiniCVNative.cpp:197-215):
 //   pack V2d -> float4 on device  ->  RANSAC or LMedS of the shared framework (ransac_host.cpp) over
-//   h_evaluate_chunk (generate + the certified / staged / matrix-core / packed sweep; the decisions and
+//   h_evaluate (generate + the certified / staged / matrix-core / packed sweep; the decisions and
 //   their exactness argument are in it)  ->  h_finalize: mask of the winner, refit on its inliers (runKernel:
 //   GPU reductions + 9x9 Jacobi here), 10 Levenberg-Marquardt iterations (GPU reductions + 8x8 solve here).
 // Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
@@ -118,12 +118,14 @@ void h_lm_refine(Plan& P, const float* d_pts, int N, const uint8_t* d_mask, hipS
     lm_solver_run<8>(sums, H, maxIters);   // H[0..7]; H[8] stays
 }
 
+static ChunkSolver h_solver(const RansacConfig& cfg) { return fast_minimal(cfg) ? kSolverHElimination : kSolverHEigen; }
+
 // One chunk of hypotheses: models, statuses, and P.last = this chunk (the winner's models can come straight
 // from its buffers: h_finalize). Shared by the RANSAC evaluate below and lmeds_search.
 // certifiedRow: the one-row pass 2 (kernels.h). P.h64 then holds only some of the chunk's models; its one reader,
 // h_finalize's cached branch, replays the winner from the log the plan still holds (P.hrowLogKept) first.
-void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, hipStream_t s, bool certifiedRow) {
+static void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin,
+                             int hypCount, int* d_counts, hipStream_t s, bool certifiedRow) {
     const Sampler smp = P.sampler(cfg);
     certifiedRow = certifiedRow && !fast_minimal(cfg);
     if (!fast_minimal(cfg)) P.hgen.ensure(h_gen_scratch_bytes(hypCount));
@@ -133,15 +135,19 @@ void h_generate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
     P.hrowLogKept = certifiedRow && h_gen_row_log_kept(hypCount);
     P.hrowCount = hypCount;
     t_hrow_plan = &P;
-    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20, s);
+    mark_chunk(P, hypBegin, hypCount, smp, d_pts, N, h_solver(cfg), s);
+}
+void h_generate(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, hipStream_t s) {
+    h_generate_chunk(P, (const float*)d_pts, N, cfg, hypBegin, hypCount, d_counts, s, false);
 }
 
 // Generate + verify one chunk of hypotheses. keyOnly: the caller consumes only the chunk's best key
 // (evaluate_chunk's reduction over d_counts), never the per-hypothesis counts.
-void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
-                      int* d_counts, bool keyOnly, hipStream_t s) {
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
+void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+                int* d_counts, bool keyOnly, hipStream_t s) {
+    const float* d_pts = (const float*)d_ptsv;
+    const float thr2 = thr2_of(P, cfg);
     const bool fused = fused_error(cfg);
     P.pairs.ensure((size_t)(N + 1) / 2 * 8);
     launch_h_pair(d_pts, N, P.pairs.p, s);
@@ -271,14 +277,13 @@ void h_evaluate_chunk(Plan& P, const float* d_pts, int N, const RansacConfig& cf
 }
 
 // Winner -> mask (+ refit + LM). Returns inlier count, 0 on failure. Synchronises s.
-int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* H, uint8_t* d_mask,
+int h_finalize(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hyp, double* H, uint8_t* d_mask,
                hipStream_t s) {
-    const double t = effective_threshold(cfg);
-    const float thr2 = (float)(t * t);
+    const float* d_pts = (const float*)d_ptsv;
     // winner re-solve -> mask from the device-side record -> one read-back of both
     HOneOut* d_one = (HOneOut*)P.one.p;
     const Sampler smp = P.sampler(cfg);
-    bool cached = P.last.covers(hyp, smp, d_pts, N, fast_minimal(cfg) ? 21 : 20);
+    bool cached = P.last.covers(hyp, smp, d_pts, N, h_solver(cfg));
     // a chunk of the one-row pass 2 holds the winner's fp64 model only after its exact replay from the chunk's
     // log; where the log is gone (a chunk of more than one piece), the single-lane solve as for a winner outside
     if (cached && P.hrowLast && !P.hrowLogKept) cached = false;
@@ -297,20 +302,19 @@ int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
     } else {
         launch_h_one(d_pts, N, smp, hyp, d_one, s, fast_minimal(cfg));
     }
-    MCV_HIP(hipMemsetAsync(P.count.p, 0, sizeof(int), s));
-    launch_h_mask_one(d_pts, N, d_one, thr2, fused_error(cfg), d_mask, P.count.p, s);
+    zero_count(P, s);
+    launch_h_mask_one(d_pts, N, d_one, thr2_of(P, cfg), fused_error(cfg), d_mask, P.count.p, s);
     MCV_HIP(hipGetLastError());
-    HOneOut one;
-    MCV_HIP(hipMemcpyAsync(P.h_one.p, d_one, sizeof(HOneOut), hipMemcpyDeviceToHost, s));
-    MCV_HIP(hipMemcpyAsync(P.h_i.p, P.count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    queue_one<HOneOut>(P, s);
+    queue_count(P, s);
     MCV_HIP(hipStreamSynchronize(s));
     if (cached && !chunk_fresh(P)) {   // the points changed since the chunk was evaluated: re-solve
         P.last.clear();
         return h_finalize(P, d_pts, N, cfg, hyp, H, d_mask, s);
     }
-    std::memcpy(&one, P.h_one.p, sizeof(HOneOut));
+    const HOneOut one = take_one<HOneOut>(P);
     if (one.status != 1) fail("winning hypothesis %lld has no model (status %d)", (long long)hyp, one.status);
-    const int count = P.h_i.p[0];
+    const int count = take_count(P);
     for (int k = 0; k < 9; ++k) H[k] = one.H[k];
     if (cfg.flags & MCV_FLAG_NO_REFINE) return count;
     if (N > 4 && count > 0) {
@@ -322,7 +326,7 @@ int h_finalize(Plan& P, const float* d_pts, int N, const RansacConfig& cfg, int6
     return count;
 }
 
-int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
+int h_host_hypothesis(int, const float* pts4, int N, uint64_t seed, int64_t hyp, double* model9, float* modelf9,
                       int* sampleIdx, bool fast) {
     if (N < 4) fail("N < 4");
     HModelF mf;
@@ -336,6 +340,14 @@ int h_host_hypothesis(const float* pts4, int N, uint64_t seed, int64_t hyp, doub
     return st;
 }
 
+// The 2-D entry's direct cases, least squares (method 0) and N == 4: runKernel on all points, then the refine.
+bool h_entry_direct(Plan& P, const char* who, int N, const RansacConfig& cfg, hipStream_t s, double* H) {
+    if (cfg.method != MCV_METHOD_LSQ && N != 4) return false;
+    if (!h_refit(P, P.pts.p, N, nullptr, s, H)) fail("%s: degenerate point set", who);
+    if (N > 4) h_lm_refine(P, P.pts.p, N, nullptr, s, H, 10);
+    return true;
+}
+
 }  // namespace mcv
 
 using namespace mcv;
@@ -343,42 +355,7 @@ using namespace mcv;
 extern "C" MCV_API int cvFindHomography(const mcvV2d* src, const mcvV2d* dst, const int N, const RansacConfig* cfgp,
                                         mcvM33d* H, uint8_t* mask) {
     MCV_GUARD(0, {
-        if (!src || !dst || !H || N < 0) fail("cvFindHomography: null argument or negative N");
-        if (mask) std::memset(mask, 0, (size_t)N);
-        if (N < 4) fail("cvFindHomography: need at least 4 correspondences (N=%d)", N);
-        const RansacConfig cfg = config_or_default(cfgp);
-        check_flags(cfg, "cvFindHomography");
-        if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LSQ && cfg.method != MCV_METHOD_LMEDS)
-            fail("cvFindHomography: unsupported method %d", cfg.method);
-        if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
-            fail("cvFindHomography: confidence must be in (0,1)");
-        require_device();
-        Plan& P = thread_plan(MCV_MODEL_HOMOGRAPHY);
-        hipStream_t s = P.own_stream();
-        P.reserve(N, 1);
-        pack_points(P, src, dst, N, P.pts.p, s);
-        double Hm[9];
-        int count = 0;
-        if (cfg.method == MCV_METHOD_LSQ || N == 4) {
-            if (!h_refit(P, P.pts.p, N, nullptr, s, Hm)) fail("cvFindHomography: degenerate point set");
-            if (N > 4) h_lm_refine(P, P.pts.p, N, nullptr, s, Hm, 10);
-            if (mask) std::memset(mask, 1, (size_t)N);
-            count = N;
-        } else if (cfg.method == MCV_METHOD_LMEDS) {
-            // the winner's mask comes from the existing finalize with LMedS' own threshold
-            RansacConfig fin = cfg;
-            const int64_t best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
-            count = h_finalize(P, P.pts.p, N, fin, best, Hm, P.mask.p, s);
-            if (count < 4) fail("cvFindHomography: LMedS model has %d inliers (< 4)", count);
-            mask_to_host(P, mask, N, s);
-        } else {
-            const int64_t best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
-            if (best < 0) fail("cvFindHomography: RANSAC found no model with >= 4 inliers");
-            count = h_finalize(P, P.pts.p, N, cfg, best, Hm, P.mask.p, s);
-            mask_to_host(P, mask, N, s);
-        }
-        for (int k = 0; k < 9; ++k) H->M[k] = Hm[k];
-        return count;
+        return find_model_2d(MCV_MODEL_HOMOGRAPHY, "cvFindHomography", src, dst, N, cfgp, H ? H->M : nullptr, mask);
     })
 }
 

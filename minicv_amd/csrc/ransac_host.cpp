@@ -3,7 +3,8 @@
 // devices (ransac_search: generate + verify on the GPU per chunk, counts or the best key back, replay on
 // the host), LMedS (lmeds_search) and the device-level mcvRansacEvaluate / mcvRansacFinalize.
 // What a chunk's evaluate and a winner's finalize do is each family's own (ransac_h_host.cpp,
-// ransac_f_host.cpp, ransac_a_host.cpp, ransac_e_host.cpp, pnp_host.cpp): one dispatch line each here.
+// ransac_f_host.cpp, ransac_a_host.cpp, ransac_e_host.cpp, pnp_host.cpp): one table row each (kFamilies), and
+// the 2-D exports' common entry (find_model_2d).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -91,23 +92,66 @@ namespace mcv {
 // ------------------------------------------------------------------------------------------
 // Plan
 // ------------------------------------------------------------------------------------------
+// The family table (plan.h): one row per MCV_MODEL_*. Columns: shape | reserve, generate, evaluate, finalize,
+// host_hypothesis | points_cfg, slots_cfg | lsq, entry_refuse, entry_direct.
+static const RansacFamily kFamilies[] = {
+    {kFamilyShapes[MCV_MODEL_HOMOGRAPHY], nullptr, h_generate, h_evaluate, h_finalize, h_host_hypothesis,
+     nullptr, nullptr, true, nullptr, h_entry_direct},
+    {kFamilyShapes[MCV_MODEL_FUNDAMENTAL], nullptr, f_generate, f_evaluate, f_finalize, f_host_hypothesis,
+     f_points_cfg, f_slots_cfg, true, f_entry_refuse, f_entry_direct},
+    {kFamilyShapes[MCV_MODEL_ESSENTIAL], e_reserve, nullptr, e_evaluate, e_finalize, nullptr,
+     nullptr, nullptr, false, nullptr, nullptr},
+    {kFamilyShapes[MCV_MODEL_PNP], nullptr, nullptr, p_evaluate, p_finalize, nullptr,
+     p_points_cfg, nullptr, false, nullptr, nullptr},
+    {kFamilyShapes[MCV_MODEL_AFFINE], nullptr, a_generate, a_evaluate, a_finalize, a_host_hypothesis,
+     nullptr, nullptr, false, nullptr, a_entry_direct},
+    {kFamilyShapes[MCV_MODEL_SIMILARITY], nullptr, a_generate, a_evaluate, a_finalize, a_host_hypothesis,
+     nullptr, nullptr, false, nullptr, a_entry_direct},
+};
+// a row's sample size, model slots, device model bytes and bytes per point
+constexpr bool shape_is(int model, int points, int slots, int modelBytes, int pointBytes) {
+    return kFamilyShapes[model].points == points && kFamilyShapes[model].slots == slots &&
+           kFamilyShapes[model].modelBytes == modelBytes && (kFamilyShapes[model].doublePoints ? 32 : 16) == pointBytes;
+}
+static_assert(sizeof(kFamilyShapes) / sizeof(kFamilyShapes[0]) == MCV_MODEL_SIMILARITY + 1, "one row per model");
+static_assert(shape_is(MCV_MODEL_HOMOGRAPHY, 4, 1, 32, 16), "homography row");
+static_assert(shape_is(MCV_MODEL_FUNDAMENTAL, 8, 1, 80, 16), "fundamental row");
+static_assert(shape_is(MCV_MODEL_ESSENTIAL, 5, kEModelSlots, 72 * kEModelSlots, 32), "essential row");
+static_assert(shape_is(MCV_MODEL_PNP, 4, 1, 96, 32), "PnP row");
+static_assert(shape_is(MCV_MODEL_AFFINE, 3, 1, 24, 16), "affine row");
+static_assert(shape_is(MCV_MODEL_SIMILARITY, 2, 1, 24, 16), "similarity row");
+
+const RansacFamily& family_of(int model) {
+    if (model < MCV_MODEL_HOMOGRAPHY || model > MCV_MODEL_SIMILARITY) fail("unknown model %d", model);
+    return kFamilies[model];
+}
+size_t model_bytes(int model) { return (size_t)family_of(model).modelBytes; }
+int model_slots(int model) { return family_of(model).slots; }
+int model_points(int model) { return family_of(model).points; }
+int model_slots_cfg(int model, const RansacConfig& cfg) {
+    const RansacFamily& f = family_of(model);
+    return f.slots_cfg ? f.slots_cfg(cfg) : f.slots;
+}
+int model_points_cfg(int model, const RansacConfig& cfg) {
+    const RansacFamily& f = family_of(model);
+    return f.points_cfg ? f.points_cfg(cfg) : f.points;
+}
+size_t point_bytes(int model, int N) { return (size_t)N * (family_of(model).doublePoints ? 32 : 16); }
+
 void Plan::reserve(int n, int64_t hyps) {
     if (n > maxN) maxN = n;
     if (hyps > maxHyps) maxHyps = hyps;
-    const size_t slots = (size_t)model_slots(model);
-    if (model == MCV_MODEL_ESSENTIAL || model == MCV_MODEL_PNP) {
+    const RansacFamily& f = family_of(model);
+    if (f.doublePoints) {
         ptsd.ensure((size_t)maxN * 4);
         raw.ensure((size_t)maxN * 4);
-        dslot.ensure((size_t)maxHyps * slots);
-        ndense.ensure(8);
-        if (model == MCV_MODEL_ESSENTIAL && maxHyps >= kEStageMinHyps) estage.ensure((size_t)maxHyps * sizeof(EStage));
     } else {
         pts.ensure((size_t)maxN * 4);
     }
-    models.ensure((size_t)maxHyps * model_bytes(model));
-    if (model == MCV_MODEL_HOMOGRAPHY) h64.ensure((size_t)maxHyps * 9);
-    if (affine_family(model)) h64.ensure((size_t)maxHyps * 6);
-    counts.ensure((size_t)maxHyps * slots);
+    if (f.reserve) f.reserve(*this);
+    models.ensure((size_t)maxHyps * f.modelBytes);
+    if (f.h64PerHyp) h64.ensure((size_t)maxHyps * f.h64PerHyp);
+    counts.ensure((size_t)maxHyps * f.slots);
     pkey.ensure(512);
     pfail.ensure(512);
     key.ensure(2);
@@ -117,21 +161,13 @@ void Plan::reserve(int n, int64_t hyps) {
     count.ensure(1);
     bbox.ensure(4);
     one.ensure(512);
-    h_counts.ensure((size_t)maxHyps * slots);
+    h_counts.ensure((size_t)maxHyps * f.slots);
     h_red.ensure(64);
-    if (model != MCV_MODEL_ESSENTIAL && model != MCV_MODEL_PNP) h_pack.ensure((size_t)maxN * 4);
+    if (!f.doublePoints) h_pack.ensure((size_t)maxN * 4);
     one.ensure(sizeof(EOneOut));
     h_one.ensure(sizeof(EOneOut));
     h_i.ensure(4);
 }
-
-size_t model_bytes(int model) {
-    if (model == MCV_MODEL_PNP) return 96;
-    if (affine_family(model)) return 24;
-    return model == MCV_MODEL_ESSENTIAL ? 72 * kEModelSlots : (model == MCV_MODEL_FUNDAMENTAL ? 80 : 32);
-}
-int model_slots(int model) { return model == MCV_MODEL_ESSENTIAL ? kEModelSlots : 1; }
-int model_slots_cfg(int model, const RansacConfig& cfg) { return f_seven(model, cfg) ? kF7Slots : model_slots(model); }
 
 hipStream_t Plan::own_stream() {
     if (!stream) MCV_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -157,18 +193,8 @@ Plan& thread_plan(int model, int shard) {
     return *plans.back();
 }
 
-size_t point_bytes(int model, int N) {
-    return (size_t)N * (model == MCV_MODEL_ESSENTIAL || model == MCV_MODEL_PNP ? 32 : 16);
-}
-
-// Device-resident point buffer of a plan (layout per model) and its size in bytes.
-static void* plan_points(Plan& P, int N, size_t* bytes) {
-    *bytes = point_bytes(P.model, N);
-    return P.model == MCV_MODEL_ESSENTIAL || P.model == MCV_MODEL_PNP ? (void*)P.ptsd.p : (void*)P.pts.p;
-}
-
-void mark_chunk(Plan& P, int64_t begin, int64_t count, const Sampler& smp, const void* d_pts, int N, int kind,
-                hipStream_t s) {
+void mark_chunk(Plan& P, int64_t begin, int64_t count, const Sampler& smp, const void* d_pts, int N,
+                ChunkSolver kind, hipStream_t s) {
     P.fp.ensure(2);
     P.h_fp.ensure(2);
     P.last.set(begin, count, smp, d_pts, N, kind);
@@ -201,20 +227,9 @@ bool fused_error(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FUSED_E
 bool fast_minimal(const RansacConfig& cfg) { return (cfg.flags & MCV_FLAG_FAST_MINIMAL) != 0; }
 
 // Evaluate one chunk of hypotheses on the device (generate + verify [+ best key]).
-void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
+void evaluate_chunk(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hypBegin, int hypCount,
                     int* d_counts, uint64_t* d_key, hipStream_t s, bool needCounts) {
-    const float* d_pts = (const float*)d_ptsv;
-    const bool keyOnly = d_key != nullptr && !needCounts;
-    if (P.model == MCV_MODEL_ESSENTIAL)
-        e_evaluate_chunk(P, (const double*)d_ptsv, N, cfg, hypBegin, hypCount, d_counts, s);
-    else if (P.model == MCV_MODEL_PNP)
-        p_evaluate_chunk(P, d_ptsv, N, cfg, hypBegin, hypCount, d_counts, s);
-    else if (affine_family(P.model))
-        a_evaluate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
-    else if (P.model == MCV_MODEL_HOMOGRAPHY)
-        h_evaluate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, keyOnly, s);
-    else
-        f_evaluate_chunk(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, s);
+    family_of(P.model).evaluate(P, d_pts, N, cfg, hypBegin, hypCount, d_counts, d_key != nullptr && !needCounts, s);
     // the chunk's best key and first sampler failure over all its model slots
     const int slots = model_slots_cfg(P.model, cfg);
     if (d_key)
@@ -223,25 +238,9 @@ void evaluate_chunk(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg,
     MCV_HIP(hipGetLastError());
 }
 
-int model_points(int model) {
-    if (model == MCV_MODEL_AFFINE) return 3;
-    if (model == MCV_MODEL_SIMILARITY) return 2;
-    return model == MCV_MODEL_FUNDAMENTAL ? 8 : (model == MCV_MODEL_ESSENTIAL ? 5 : 4);
-}
-// (homography and PnP with the AP3P kernel: 4)
-int model_points_cfg(int model, const RansacConfig& cfg) {
-    if (f_seven(model, cfg)) return 7;
-    return model == MCV_MODEL_PNP && pnp_cfg_epnp(cfg) ? 5 : model_points(model);
-}
-
-int finalize(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
+int finalize(Plan& P, const void* d_pts, int N, const RansacConfig& cfg, int64_t hyp, double* model9,
              uint8_t* d_mask, hipStream_t s) {
-    if (P.model == MCV_MODEL_ESSENTIAL) return e_finalize(P, (const double*)d_ptsv, N, cfg, hyp, model9, d_mask, s);
-    if (P.model == MCV_MODEL_PNP) return p_finalize(P, d_ptsv, N, cfg, hyp, model9, d_mask, s);
-    const float* d_pts = (const float*)d_ptsv;
-    if (P.model == MCV_MODEL_HOMOGRAPHY) return h_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
-    if (affine_family(P.model)) return a_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
-    return f_finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
+    return family_of(P.model).finalize(P, d_pts, N, cfg, hyp, model9, d_mask, s);
 }
 
 // Full RANSAC on device-resident points with the OpenCV sequential-replay semantics.
@@ -280,7 +279,7 @@ int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
     const int64_t tableRows = std::max(cfg.maxIters, 1);
     if (cv_sampler(cfg)) {
         std::vector<float> host;
-        if (!h_pts4 && P.model != MCV_MODEL_ESSENTIAL && P.model != MCV_MODEL_PNP) {
+        if (!h_pts4 && !family_of(P.model).doublePoints) {   // cv_table_build reads host float4 points
             host.resize((size_t)N * 4);
             MCV_HIP(hipMemcpyAsync(host.data(), d_pts, (size_t)N * 16, hipMemcpyDeviceToHost, s));
             MCV_HIP(hipStreamSynchronize(s));
@@ -291,7 +290,7 @@ int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
         cv_table_upload(P, table, m, tableRows, N, tableFp, s);
     }
     if (shards > 1) {
-        size_t bytes = 0;
+        const size_t bytes = point_bytes(P.model, N);
         MCV_HIP(hipStreamSynchronize(s));
         for (int k = 1; k < shards; ++k) {
             const int dev = (home + k) % ndev;
@@ -299,7 +298,7 @@ int64_t ransac_search(Plan& P, const void* d_pts, int N, const RansacConfig& cfg
             Plan& Pk = thread_plan(P.model, k);
             Pk.reserve(N, slotScale);
             std::memcpy(Pk.pnpCam, P.pnpCam, sizeof(P.pnpCam));
-            void* dst = plan_points(Pk, N, &bytes);
+            void* dst = family_of(P.model).doublePoints ? (void*)Pk.ptsd.p : (void*)Pk.pts.p;
             hipStream_t sk = Pk.own_stream();
             MCV_HIP(hipMemcpyPeerAsync(dst, dev, d_pts, home, bytes, sk));
             if (cv_sampler(cfg)) cv_table_upload(Pk, table, m, tableRows, N, tableFp, sk);
@@ -397,11 +396,13 @@ int64_t lmeds_search(Plan& P, const float* d_pts, int N, const RansacConfig& cfg
     const int nSlots = cnt * slots;
     P.reserve(N, (int64_t)cnt * (slots / model_slots(P.model)));
     if (cv_sampler(cfg)) cv_table_prepare(P, d_pts, h_pts4, N, cfg, niters, s);
+    // the rank kernel's error kinds are its own numbering, not a family hook: the fundamental matrix has four
+    // (f_error_kind), the other families op-by-op 0 / fused 1
     const int errKind = P.model == MCV_MODEL_FUNDAMENTAL ? f_error_kind(cfg) : (fused_error(cfg) ? 1 : 0);
     // the whole budget as one chunk, by the generate the family's RANSAC evaluate calls
-    if (P.model == MCV_MODEL_HOMOGRAPHY) h_generate_chunk(P, d_pts, N, cfg, 0, cnt, P.counts.p, s);
-    else if (affine_family(P.model)) a_generate_chunk(P, d_pts, N, cfg, 0, cnt, P.counts.p, s);
-    else f_generate_chunk(P, d_pts, N, cfg, 0, cnt, P.counts.p, s);
+    GenerateHook* generate = family_of(P.model).generate;
+    if (!generate) fail("LMedS: model %d has no rank kernel", P.model);
+    generate(P, d_pts, N, cfg, 0, cnt, P.counts.p, s);
     P.med.ensure((size_t)nSlots);
     P.h_med.ensure((size_t)nSlots);
     {
@@ -444,16 +445,56 @@ void require_device() {
              hipGetErrorString(e), n);
 }
 
-RansacConfig config_or_default(const RansacConfig* cfg) {
+RansacConfig config_or_default(int model, const RansacConfig* cfg) {
     if (cfg) return *cfg;
     RansacConfig c;
     std::memset(&c, 0, sizeof(c));
     c.threshold = 3.0;
-    c.confidence = 0.995;
+    c.confidence = family_of(model).defaultConfidence;
     c.maxIters = 2000;
     c.method = MCV_METHOD_RANSAC;
     c.flags = MCV_FLAG_CV_SAMPLER;   // no seed given: OpenCV's own sample stream
     return c;
+}
+
+int find_model_2d(int model, const char* who, const mcvV2d* a, const mcvV2d* b, int N, const RansacConfig* cfgp,
+                  double* model9, uint8_t* mask) {
+    const RansacFamily& f = family_of(model);
+    if (!a || !b || !model9 || N < 0) fail("%s: null argument or negative N", who);
+    if (mask) std::memset(mask, 0, (size_t)N);
+    if (!f.entry_refuse && N < f.points) fail("%s: need at least %d correspondences (N=%d)", who, f.points, N);
+    const RansacConfig cfg = config_or_default(model, cfgp);
+    check_flags(cfg, who);
+    if (f.entry_refuse) f.entry_refuse(who, N, cfg);
+    if (cfg.method != MCV_METHOD_RANSAC && cfg.method != MCV_METHOD_LMEDS && !(f.lsq && cfg.method == MCV_METHOD_LSQ))
+        fail("%s: unsupported method %d", who, cfg.method);
+    if (cfg.method != MCV_METHOD_LSQ && !(cfg.confidence > 0 && cfg.confidence < 1))
+        fail("%s: confidence must be in (0,1)", who);
+    require_device();
+    Plan& P = thread_plan(model);
+    hipStream_t s = P.own_stream();
+    P.reserve(N, 1);
+    pack_points(P, a, b, N, P.pts.p, s);
+    double M[9];
+    int count = N;
+    if (f.entry_direct(P, who, N, cfg, s, M)) {
+        if (mask) std::memset(mask, 1, (size_t)N);
+    } else {
+        const int m = model_points_cfg(model, cfg);
+        RansacConfig fin = cfg;   // LMedS: the winner's mask comes from the finalize with LMedS' own threshold
+        int64_t best;
+        if (cfg.method == MCV_METHOD_LMEDS) {
+            best = lmeds_search(P, P.pts.p, N, cfg, s, P.h_pack.p, &fin.threshold);
+        } else {
+            best = ransac_search(P, P.pts.p, N, cfg, s, P.h_pack.p);
+            if (best < 0) fail("%s: RANSAC found no model with >= %d inliers", who, m);
+        }
+        count = f.finalize(P, P.pts.p, N, fin, best, M, P.mask.p, s);
+        if (cfg.method == MCV_METHOD_LMEDS && count < m) fail("%s: LMedS model has %d inliers (< %d)", who, count, m);
+        mask_to_host(P, mask, N, s);
+    }
+    for (int k = 0; k < 9; ++k) model9[k] = M[k];
+    return count;
 }
 
 }  // namespace mcv
@@ -553,10 +594,9 @@ extern "C" MCV_API int mcvHostHypothesis(int model, const float* pts4, int N, ui
         if (!pts4 || !model9 || !modelf9) fail("mcvHostHypothesis: null argument");
         const bool fast = (model & MCV_HOST_FAST_MINIMAL) != 0;
         model &= ~MCV_HOST_FAST_MINIMAL;
-        if (model == MCV_MODEL_HOMOGRAPHY)
-            return h_host_hypothesis(pts4, N, seed, hyp, model9, modelf9, sampleIdx, fast);
-        if (affine_family(model)) return a_host_hypothesis(model, pts4, N, seed, hyp, model9, modelf9, sampleIdx);
-        return f_host_hypothesis(pts4, N, seed, hyp, model9, modelf9, sampleIdx, fast);
+        HostHypothesisHook* twin = family_of(model).host_hypothesis;
+        if (!twin) fail("mcvHostHypothesis: the %s family has no host twin here", family_of(model).name);
+        return twin(model, pts4, N, seed, hyp, model9, modelf9, sampleIdx, fast);
     })
 }
 
