@@ -1,7 +1,7 @@
-// batch_host.h — the host runtime pieces the batched calls share (host only): the per-thread, per-device
-// workspace, the timer and the counted stream calls, the first-failure report, the device-free refusals, OpenCV's
-// sample tables keyed by N and the hypothesis round driver of the RANSAC batches. The index
-// arithmetic is ransac_batch_index.h's.
+// batch_host.h — what the RANSAC batches share on the host (host only): their statistics record's counted stream
+// calls, the first-failure report, the device-free refusals, OpenCV's sample tables keyed by N and the hypothesis
+// round driver. The per-thread, per-device workspace, the timer and the counted calls themselves
+// are mcv_runtime.h's, shared with every other host driver; the index arithmetic is ransac_batch_index.h's.
 #pragma once
 
 #include "minicv_native.h"
@@ -12,47 +12,16 @@
 #include <chrono>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
 
 namespace mcv {
 
-// A workspace owns one non-blocking stream on one device; a thread keeps one workspace of a kind per device.
-struct DeviceWs {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    ~DeviceWs() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-template <class Ws>
-Ws& thread_device_ws() {
-    int dev = 0;
-    MCV_HIP(hipGetDevice(&dev));
-    thread_local std::vector<std::unique_ptr<Ws>> all;
-    for (auto& w : all)
-        if (w->device == dev) return *w;
-    all.emplace_back(new Ws());
-    all.back()->device = dev;
-    MCV_HIP(hipStreamCreateWithFlags(&all.back()->stream, hipStreamNonBlocking));
-    return *all.back();
-}
-
-inline long long us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-}
-// A stream synchronisation / an asynchronous copy, counted in `n`; the RANSAC batches count in batch_stats().
-inline void counted_sync(hipStream_t s, long long& n) {
-    MCV_HIP(hipGetLastError());
-    MCV_HIP(hipStreamSynchronize(s));
-    ++n;
-}
-inline void batch_sync(hipStream_t s) { counted_sync(s, batch_stats().syncs); }
+// A stream synchronisation / an asynchronous copy of a RANSAC batch, counted in batch_stats().
+inline void batch_sync(hipStream_t s) { counted_sync(batch_stats(), s); }
 inline void batch_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-    ++batch_stats().copies;
+    counted_copy(batch_stats(), dst, src, bytes, kind, s);
 }
 
 // A call starts its statistics afresh.

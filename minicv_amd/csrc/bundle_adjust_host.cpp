@@ -16,32 +16,19 @@ static_assert(sizeof(mcvBaConfig) == sizeof(BaConfig) && sizeof(mcvBaSummary) ==
               "the public records are read as ba_ref.h's");
 static_assert(sizeof(mcvCamera) == 112 && sizeof(mcvV3d) == 24 && sizeof(mcvV2d) == 16, "read as plain doubles");
 
-struct BaStats {
-    long long launches = 0, syncs = 0, copies = 0, memsets = 0, linearizations = 0, trials = 0, cgChunks = 0,
-              segments = 0;
+struct BaStats : CallStats {
+    long long linearizations = 0, trials = 0, cgChunks = 0, segments = 0;
 };
+thread_local BaStats t_stats;   // the calling thread's last call (mcvTestBundleAdjustStats)
 
-struct BaWork {
+struct BaWork : DeviceWs {
     DevBuf<int> ints;          // offsets, cameraIdx, obsTrack, camObs, segCam, segStart, segEnd, camSegPtr, longList
     DevBuf<double> doubles;    // everything fp64
     DevBuf<uint8_t> bytes;     // fixed, used, trackUsed, active
     DevBuf<unsigned int> ctr;
     DevBuf<BaCgState> cg;
     DevBuf<BaCostRecord> rec;
-    BaStats st;
-    hipStream_t s = nullptr;
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
-    ~BaWork() {
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
-BaWork& work() {
-    thread_local BaWork w;
-    return w;
-}
 
 // The checks every form shares; everything here runs before the device is touched. Fills the CSR.
 void check_arguments(const char* name, const mcvCamera* cameras, int nCameras, const int* cameraIdx,
@@ -85,22 +72,17 @@ void write_summary(mcvBaSummary* out, const BaSummary& sm) {
 
 // The device backend of ba_run.
 struct BaGpu {
-    BaWork& w;
     BaDevice D;
     hipStream_t s;
 
     void launched(int k) {
         MCV_HIP(hipGetLastError());
-        w.st.launches += k;
+        t_stats.launches += k;
     }
     void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-        if (bytes) MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-        w.st.copies += 1;
+        counted_copy(t_stats, dst, src, bytes, kind, s);
     }
-    void sync() {
-        MCV_HIP(hipStreamSynchronize(s));
-        w.st.syncs += 1;
-    }
+    void sync() { counted_wait(t_stats, s); }
     void read_cost(double& cost, bool& zok) {
         BaCostRecord rec;
         copy(&rec, D.rec, sizeof(rec), hipMemcpyDeviceToHost);
@@ -126,12 +108,11 @@ struct BaGpu {
     void linearize() {
         launch_ba_linearize(D, s);
         launched(kBaLaunchesLinearize);
-        w.st.linearizations += 1;
+        t_stats.linearizations += 1;
     }
     bool solve(double lambda, int& cgIters) {
         D.lambda = lambda;
-        MCV_HIP(hipMemsetAsync(D.ctr + 3, 0, sizeof(unsigned int), s));
-        w.st.memsets += 1;
+        counted_zero(t_stats, D.ctr + 3, sizeof(unsigned int), s);
         launch_ba_system(D, s);
         launched(kBaLaunchesSystem);
         BaCgState st;
@@ -140,7 +121,7 @@ struct BaGpu {
             launched(kBaCgChunk * kBaLaunchesCgIter);
             copy(&st, D.cg, sizeof(st), hipMemcpyDeviceToHost);
             sync();
-            w.st.cgChunks += 1;
+            t_stats.cgChunks += 1;
         } while (!st.done);
         cgIters = st.iter;
         return !st.failed;
@@ -148,7 +129,7 @@ struct BaGpu {
     void trial(double& c, bool& zok) {
         launch_ba_trial(D, s);
         launched(kBaLaunchesTrial);
-        w.st.trials += 1;
+        t_stats.trials += 1;
         read_cost(c, zok);
     }
     void accept() {
@@ -168,11 +149,11 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
                const mcvV2d* observations, const int* offsets, int T, const mcvV3d* points, const BaConfig& cfg,
                const BaCsr& csr, mcvCamera* outCameras, mcvV3d* outPoints, BaSummary& sm) {
     require_device();
-    BaWork& w = work();
-    w.st = BaStats();
+    BaWork& w = thread_device_ws<BaWork>();
+    t_stats = BaStats();
     hipStream_t s = w.stream();
     const size_t n = (size_t)offsets[T], nC = (size_t)nCameras, nT = (size_t)T, nSeg = csr.segCam.size();
-    w.st.segments = (long long)nSeg;
+    t_stats.segments = (long long)nSeg;
     const size_t nCp = nC ? nC : 1;
 
     w.ints.ensure((nT + 1) + 3 * n + 3 * nSeg + (nC + 1) + nT);
@@ -244,7 +225,7 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
     D.tol2 = cfg.cgTolerance * cfg.cgTolerance;
     D.maxCg = cfg.maxCgIterations;
 
-    BaGpu be{w, D, s};
+    BaGpu be{D, s};
     const hipMemcpyKind up = hipMemcpyHostToDevice;
     {
         ProfScope ps("ba_upload", s);
@@ -260,13 +241,9 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
         be.copy(be.D.cams, cameras, nC * sizeof(mcvCamera), up);
         be.copy(be.D.pts, points, nT * sizeof(mcvV3d), up);
         if (fixedCameras) be.copy(d_fixed, fixedCameras, nC, up);
-        else {
-            if (nC) MCV_HIP(hipMemsetAsync(d_fixed, 0, nC, s));
-            w.st.memsets += 1;
-        }
-        MCV_HIP(hipMemsetAsync(D.ctr, 0, kBaCtrs * sizeof(unsigned int), s));
-        MCV_HIP(hipMemsetAsync(D.pq, 0, nCp * sizeof(double), s));   // the setup's per-camera marks
-        w.st.memsets += 2;
+        else counted_zero(t_stats, d_fixed, nC, s);
+        counted_zero(t_stats, D.ctr, kBaCtrs * sizeof(unsigned int), s);
+        counted_zero(t_stats, D.pq, nCp * sizeof(double), s);   // the setup's per-camera marks
     }
 
     const int it = ba_run(be, cfg, sm);
@@ -386,11 +363,8 @@ extern "C" MCV_API int mcvHostBaStep(const mcvCamera* cameras, int nCameras, con
 
 extern "C" MCV_API int mcvTestBundleAdjustStats(long long* stats8) {
     MCV_GUARD(-1, {
-        if (!stats8) fail("mcvTestBundleAdjustStats: null argument");
-        const BaStats& st = work().st;
-        const long long v[8] = {st.launches, st.syncs, st.copies, st.memsets, st.linearizations, st.trials,
-                                st.cgChunks, st.segments};
-        for (int i = 0; i < 8; ++i) stats8[i] = v[i];
-        return 0;
+        const BaStats& st = t_stats;
+        return stats8_out("mcvTestBundleAdjustStats", stats8, st,
+                          {st.linearizations, st.trials, st.cgChunks, st.segments});
     })
 }

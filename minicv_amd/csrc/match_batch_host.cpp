@@ -17,7 +17,6 @@
 #include "mcv_runtime.h"
 #include "kernels.h"
 #include "plan.h"
-#include "batch_host.h"
 
 #include <algorithm>
 #include <climits>
@@ -31,8 +30,8 @@ namespace {
 const int kElemU8 = 0, kElemF32 = 5;
 const int kHammingMaxRows = 1 << 22;   // the key's index field (match_hamming.hip)
 
-struct MbStats {
-    long long launches = 0, syncs = 0, problems = 0, workgroups = 0, copies = 0;
+struct MbStats : CallStats {   // no memset is issued
+    long long problems = 0, workgroups = 0;
 };
 thread_local MbStats t_mb_stats;
 
@@ -107,7 +106,7 @@ struct MbWs : DeviceWs {
     PinnedBuf<int> h_tables, h_offsets;
 };
 
-void mb_sync(hipStream_t s) { counted_sync(s, t_mb_stats.syncs); }
+void mb_sync(hipStream_t s) { counted_sync(t_mb_stats, s); }
 
 int padded_width(bool ham, int dim) {
     if (ham) return dim <= 32 ? 32 : 64;
@@ -131,8 +130,7 @@ MbTables upload_tables(MbWs& W, const MbLayout& L, hipStream_t s) {
     if (!L.prob.empty()) std::memcpy(W.h_tables.p, L.prob.data(), L.prob.size() * sizeof(MatchBatchProblem));
     if (!L.wg.empty()) std::memcpy(W.h_tables.p + nProb, L.wg.data(), L.wg.size() * sizeof(int));
     std::memcpy(W.h_tables.p + nProb + nWg, L.qStart.data(), L.qStart.size() * sizeof(int));
-    MCV_HIP(hipMemcpyAsync(W.tables.p, W.h_tables.p, n * sizeof(int), hipMemcpyHostToDevice, s));
-    ++t_mb_stats.copies;
+    counted_copy(t_mb_stats, W.tables.p, W.h_tables.p, n * sizeof(int), hipMemcpyHostToDevice, s);
     return MbTables{(const MatchBatchProblem*)W.tables.p, W.tables.p + nProb, W.tables.p + nProb + nWg};
 }
 
@@ -149,10 +147,7 @@ MbTables mb_knn(MbWs& W, const MbLayout& L, int nImages, const int* counts, Rows
     for (int i = 0; i < nImages; ++i)
         if (L.rowOff[(size_t)i + 1] > L.rowOff[(size_t)i])
             std::memcpy(W.h_raw.p + (size_t)L.rowOff[(size_t)i] * dim, rowsOf(i), (size_t)counts[i] * dim);
-    if (rawBytes) {
-        MCV_HIP(hipMemcpyAsync(W.raw.p, W.h_raw.p, rawBytes, hipMemcpyHostToDevice, s));
-        ++t_mb_stats.copies;
-    }
+    if (rawBytes) counted_copy(t_mb_stats, W.raw.p, W.h_raw.p, rawBytes, hipMemcpyHostToDevice, s);
     const uint8_t* d_rows = W.raw.p;
     if (!ham || dim != KP) {
         W.rows.ensure((size_t)R * KP);
@@ -251,7 +246,7 @@ int match_features_batch(const char* who, const DetectorResult* images, int nIma
     if (L.totalQ == 0) return 0;
     require_device();
     MbWs& W = thread_device_ws<MbWs>();
-    hipStream_t s = W.stream;
+    hipStream_t s = W.stream();
     const MbTables T = mb_knn(W, L, nImages, counts.data(), [&](int i) { return images[i].Descriptors; }, dim, ham, s);
     const int totalQ = L.totalQ, nb = (totalQ + 255) / 256;
     W.keep.ensure((size_t)totalQ);
@@ -265,19 +260,14 @@ int match_features_batch(const char* who, const DetectorResult* images, int nIma
                                ham ? nullptr : W.df2.p, T.prob, T.qStart, B, cfg.crossCheck != 0, totalQ, cfg.ratio,
                                cfg.maxDistance, W.keep.p, W.cnt.p, W.off.p, W.pairs.p, W.dist.p, W.offsets.p, s);
     t_mb_stats.launches += 4;
-    MCV_HIP(hipMemcpyAsync(W.h_offsets.p, W.offsets.p, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    ++t_mb_stats.copies;
+    counted_copy(t_mb_stats, W.h_offsets.p, W.offsets.p, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, s);
     mb_sync(s);
     const int total = W.h_offsets.p[B];
     if (total > maxPairs) fail("%s: %d matches exceed maxPairs %d", who, total, maxPairs);
     std::memcpy(offsets, W.h_offsets.p, ((size_t)B + 1) * sizeof(int));
     if (total > 0) {
-        MCV_HIP(hipMemcpyAsync(pairs, W.pairs.p, (size_t)2 * total * sizeof(int), hipMemcpyDeviceToHost, s));
-        ++t_mb_stats.copies;
-        if (dist) {
-            MCV_HIP(hipMemcpyAsync(dist, W.dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s));
-            ++t_mb_stats.copies;
-        }
+        counted_copy(t_mb_stats, pairs, W.pairs.p, (size_t)2 * total * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (dist) counted_copy(t_mb_stats, dist, W.dist.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s);
         mb_sync(s);
     }
     return total;
@@ -423,7 +413,7 @@ extern "C" MCV_API int mcvTestMatchBatchKnn(const uint8_t* rows, const int* feat
         if (L.totalOut == 0) return 0;
         require_device();
         MbWs& W = thread_device_ws<MbWs>();
-        hipStream_t s = W.stream;
+        hipStream_t s = W.stream();
         mb_knn(W, L, nImages, featureCounts, [&](int i) { return rows + first[(size_t)i] * dim; }, dim, ham, s);
         const size_t n = (size_t)L.totalOut;
         MCV_HIP(hipMemcpyAsync(idx, W.idx.p, n * 4, hipMemcpyDeviceToHost, s));

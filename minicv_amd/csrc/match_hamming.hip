@@ -545,14 +545,8 @@ struct HammingWork {
     StreamFence fence;   // calls on different streams take turns on these buffers
 };
 
-// Per host thread and device (DevBuf does not follow a device switch).
-static HammingWork& hamming_work() {
-    int dev = 0;
-    MCV_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) fail("cvMatchHamming: device %d outside the 16 per-thread workspaces", dev);
-    thread_local HammingWork works[16];
-    return works[dev];
-}
+// The calling thread's workspace on the current device; it runs on the caller's stream and owns none.
+static HammingWork& hamming_work() { return thread_device_ws<HammingWork>(); }
 
 // The GEMM form's launch: WPB waves per block, QT query tiles per wave; stream-K ranges over the resident
 // blocks (occupancy of this instantiation).
@@ -561,11 +555,7 @@ static void launch_ham_gemm(HammingWork& wk, int W, const uint32_t* q, int nq, c
                             int* d_dist, int* d_idx2, int* d_dist2, hipStream_t s) {
     const int qblocks = (nq + 32 * QT * WPB - 1) / (32 * QT * WPB);
     const int ntTiles = (nt + 31) / 32;
-    static const int cus = [] {
-        int d = 0, n = 0;
-        (void)hipGetDevice(&d);
-        return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0 ? n : 256;
-    }();
+    static const int cus = device_cus();
     auto kern = W == 8 ? mcv_hamming_mfma<8, QT, WPB> : mcv_hamming_mfma<16, QT, WPB>;
     int perCu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kern, 64 * WPB, 0) != hipSuccess || perCu <= 0) perCu = 1;

@@ -1386,14 +1386,8 @@ struct L2Work {
     StreamFence fence;          // calls on different streams take turns on these buffers
 };
 
-// Per host thread and device (DevBuf does not follow a device switch of the calling thread).
-static L2Work& l2_work() {
-    int d = 0;
-    MCV_HIP(hipGetDevice(&d));
-    if (d < 0 || d >= 16) fail("cvMatchL2: device %d outside the 16 per-thread workspaces", d);
-    thread_local L2Work wk[16];
-    return wk[d];
-}
+// The calling thread's workspace on the current device; it runs on the caller's stream and owns none.
+static L2Work& l2_work() { return thread_device_ws<L2Work>(); }
 
 // dim <= 128 (the f16-capable path) is five launches, with no host round trip and no empty launch:
 //   mcv_l2_prep16 (split copies, norms, per-block maxima) -> mcv_l2_gemm (f16 form or f32 form, decided
@@ -1469,11 +1463,7 @@ int launch_match_l2(const float* d_q, int nq, const float* d_t, int nt, int dim,
         // mcv_l2_gemm's partition: one train chunk per XCD, 3 resident blocks per CU (the f16 form's
         // register budget) split evenly over the chunks, each block an equal range of its chunk's
         // (query block, tile) steps (at least 16 tiles, so small calls keep few partials per query)
-        static const int cus = [] {
-            int d = 0, n = 0;
-            (void)hipGetDevice(&d);
-            return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0 ? n : 256;
-        }();
+        static const int cus = device_cus();
         // (round 5, the same box alternating at cfg5: 1.905-1.909 ms per step against 1.996 ms for the
         // (query block, chunk) grid of 11 chunks chosen by round 4's round-count model)
         int C = std::min(8, ntTiles);

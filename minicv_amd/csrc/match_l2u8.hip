@@ -262,14 +262,8 @@ struct L2U8Work {
     StreamFence fence;        // calls on different streams take turns on these buffers
 };
 
-// Per host thread and device (DevBuf does not follow a device switch of the calling thread).
-static L2U8Work& l2u8_work() {
-    int d = 0;
-    MCV_HIP(hipGetDevice(&d));
-    if (d < 0 || d >= 16) fail("cvMatchL2U8: device %d outside the 16 per-thread workspaces", d);
-    thread_local L2U8Work wk[16];
-    return wk[d];
-}
+// The calling thread's workspace on the current device; it runs on the caller's stream and owns none.
+static L2U8Work& l2u8_work() { return thread_device_ws<L2U8Work>(); }
 
 void check_match_l2u8(const char* who, int nq, int nt, int dim) {
     if (dim < 1 || dim > kL2U8MaxDim) fail("%s: dim %d outside [1, %d]", who, dim, kL2U8MaxDim);

@@ -24,42 +24,20 @@ using namespace mcv;
 namespace {
 constexpr int kMaxMatchShards = 16;
 
-struct MatchWork {
+// Shard k of a call on device dev is the calling thread's workspace of slot k on that device.
+struct MatchWork : DeviceWs {
     DevBuf<uint8_t> q, t;
     DevBuf<int> idx, idx2, di, di2;
     DevBuf<float> df, df2;
-    hipStream_t s = nullptr;
     hipEvent_t ev = nullptr;   // home shard: its train upload finished (the peer copies wait on it)
-    int dev = -1;
-    // buffers, stream and event belong to one device: a shard slot that moves to another device
-    // (the calling thread switched devices) starts over
-    void bind(int d) {
-        if (dev == d) return;
-        release();
-        dev = d;
-    }
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
     hipEvent_t event() {
         if (!ev) MCV_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         return ev;
     }
-    void release() {
-        q.reset(); t.reset();
-        idx.reset(); idx2.reset(); di.reset(); di2.reset(); df.reset(); df2.reset();
-        if (s) (void)hipStreamDestroy(s);
+    ~MatchWork() {
         if (ev) (void)hipEventDestroy(ev);
-        s = nullptr;
-        ev = nullptr;
     }
-    ~MatchWork() { release(); }
 };
-MatchWork& work(int k) {
-    thread_local MatchWork w[kMaxMatchShards];
-    return w[k];
-}
 
 // One matcher call over D query blocks. Elem: the descriptor element type; Dist: the distance type
 // (int for Hamming, float for L2); launch(shard work, d_q, nq, d_t, d_idx, d_dist, d_idx2, d_dist2, s).
@@ -80,8 +58,8 @@ int match_sharded(const char* name, const void* q, int nq, const void* t, int nt
     const int D = std::min(deviceCount, nq);
     const size_t tb = (size_t)nt * rowBytes;
     // home shard: the train set once from the host
-    MatchWork& w0 = work(0);
-    w0.bind(home);
+    MatchWork* used[kMaxMatchShards];   // shard k's workspace, on device (home + k) % ndev
+    MatchWork& w0 = thread_device_ws_on<MatchWork>(home, 0);
     hipStream_t s0 = w0.stream();
     w0.t.ensure(tb ? tb : 1);
     if (tb) MCV_HIP(hipMemcpyAsync(w0.t.p, t, tb, hipMemcpyHostToDevice, s0));
@@ -91,8 +69,8 @@ int match_sharded(const char* name, const void* q, int nq, const void* t, int nt
         const int b = k * base + std::min(k, rem), c = base + (k < rem ? 1 : 0);
         const int dev = (home + k) % ndev;
         MCV_HIP(hipSetDevice(dev));
-        MatchWork& w = work(k);
-        w.bind(dev);
+        MatchWork& w = thread_device_ws_on<MatchWork>(dev, k);
+        used[k] = &w;
         hipStream_t s = w.stream();
         const uint8_t* d_t = w0.t.p;
         if (k > 0) {
@@ -123,8 +101,8 @@ int match_sharded(const char* name, const void* q, int nq, const void* t, int nt
         if (dist2) MCV_HIP(hipMemcpyAsync(dist2 + b, dd2, c * sizeof(Dist), hipMemcpyDeviceToHost, s));
     }
     for (int k = 0; k < D; ++k) {
-        MCV_HIP(hipSetDevice(work(k).dev));
-        MCV_HIP(hipStreamSynchronize(work(k).s));
+        MCV_HIP(hipSetDevice((home + k) % ndev));
+        MCV_HIP(hipStreamSynchronize(used[k]->stream()));
     }
     return nq;
 }

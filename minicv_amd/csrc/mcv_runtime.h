@@ -1,11 +1,18 @@
 // mcv_runtime.h — host runtime helpers for the C-ABI shim: per-thread last error, HIP error
-// checking, device-buffer RAII. No exception crosses an extern "C" boundary: every export wraps
-// its body in MCV_GUARD, which records the message and returns the export's failure value.
+// checking, device-buffer RAII, the per-thread, per-device workspace every host driver keeps its
+// buffers in, and the counted stream calls behind the mcvTest*Stats exports. No exception crosses an
+// extern "C" boundary: every export wraps its body in MCV_GUARD, which records the message and
+// returns the export's failure value.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <initializer_list>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 #include <cstdio>
 #include <cstdarg>
 
@@ -92,7 +99,7 @@ struct PinnedBuf {
     }
 };
 
-// Orders the uses of one per-thread workspace across streams: the device-level matchers are
+// Orders the uses of one workspace (below: per thread and device) across streams: the device-level matchers are
 // asynchronous on the caller's stream, so a call on stream B right after one on stream A would race on
 // the shared buffers (and on their finish counters). enter(s) makes s wait for the previous use when
 // that ran on another stream; leave(s) records this use's completion.
@@ -130,13 +137,99 @@ struct StreamFence {
     }
 };
 
-// Waves of `kernel` (blocks of `threads`) the current device holds at once: its occupancy x the CUs.
-template <class K>
-inline int64_t resident_waves(K kernel, int threads) {
-    int dev = 0, cus = 0, per = 0;
+// ---- workspaces. Device buffers, streams and events belong to one device and do not follow a device
+// switch of the calling thread, so a host driver keeps them in a workspace per (thread, device, slot):
+// thread_device_ws<Ws>(slot) is the calling thread's Ws for the current device, made on first use and kept
+// until the thread ends. The slot tells apart several workspaces of one kind on one device (the query
+// shards of cvMatch*Multi, as thread_plan(model, shard) does for plans). A caller that already knows the
+// current device passes it to thread_device_ws_on and spares the query.
+template <class Ws>
+Ws& thread_device_ws_on(int dev, int slot = 0) {
+    struct Entry {
+        int dev, slot;
+        Ws ws;
+    };
+    thread_local std::vector<std::unique_ptr<Entry>> all;
+    for (auto& e : all)
+        if (e->dev == dev && e->slot == slot) return e->ws;
+    all.emplace_back(new Entry{dev, slot, {}});
+    return all.back()->ws;
+}
+template <class Ws>
+Ws& thread_device_ws(int slot = 0) {
+    int dev = 0;
+    MCV_HIP(hipGetDevice(&dev));
+    return thread_device_ws_on<Ws>(dev, slot);
+}
+// Base of a workspace that runs on a stream of its own (non-blocking, made on first use). A workspace
+// that runs on its caller's stream (the matcher kernels', the pipeline's) does not derive from it.
+struct DeviceWs {
+    hipStream_t stream() {
+        if (!s_) MCV_HIP(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+        return s_;
+    }
+    DeviceWs() = default;
+    DeviceWs(const DeviceWs&) = delete;
+    DeviceWs& operator=(const DeviceWs&) = delete;
+    ~DeviceWs() {
+        if (s_) (void)hipStreamDestroy(s_);
+    }
+
+private:
+    hipStream_t s_ = nullptr;
+};
+
+// ---- what a call enqueued, for the mcvTest*Stats exports. A driver keeps the record of its last call
+// in a plain thread_local of its own (never in the workspace: reading it must not touch HIP) and
+// derives from CallStats to add its own fields.
+struct CallStats {
+    long long launches = 0, syncs = 0, copies = 0, memsets = 0;
+};
+// Copies and memsets are counted by the call's form: one of zero bytes issues no HIP call and counts.
+inline void counted_copy(CallStats& st, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (bytes) MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
+    ++st.copies;
+}
+inline void counted_zero(CallStats& st, void* p, size_t bytes, hipStream_t s) {
+    if (bytes) MCV_HIP(hipMemsetAsync(p, 0, bytes, s));
+    ++st.memsets;
+}
+// The bare synchronisation of the geometry drivers (they check their launches as they enqueue them), and
+// the batches' form, which asks for the launches' last error first.
+inline void counted_wait(CallStats& st, hipStream_t s) {
+    MCV_HIP(hipStreamSynchronize(s));
+    ++st.syncs;
+}
+inline void counted_sync(CallStats& st, hipStream_t s) {
+    MCV_HIP(hipGetLastError());
+    counted_wait(st, s);
+}
+// The body of a mcvTest*Stats export: launches, syncs, copies, memsets, then up to four of the driver's own.
+inline int stats8_out(const char* who, long long* stats8, const CallStats& st, std::initializer_list<long long> own) {
+    if (!stats8) fail("%s: null argument", who);
+    const long long v[8] = {st.launches, st.syncs, st.copies, st.memsets};
+    std::copy(v, v + 8, stats8);
+    std::copy(own.begin(), own.end(), stats8 + 4);
+    return 0;
+}
+inline long long us_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// CUs of the current device (256 when they cannot be read).
+inline int device_cus() {
+    int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         cus = 256;
+    return cus;
+}
+
+// Waves of `kernel` (blocks of `threads`) the current device holds at once: its occupancy x the CUs.
+template <class K>
+inline int64_t resident_waves(K kernel, int threads) {
+    const int cus = device_cus();
+    int per = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0) per = 1;
     return (int64_t)per * cus * (threads / 64);
 }

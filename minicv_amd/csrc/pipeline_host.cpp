@@ -14,16 +14,12 @@
 namespace mcv {
 
 namespace {
-struct PipeWork {
+struct PipeWork {   // runs on the plan's stream and owns none; looked up on the plan's device
     DevBuf<uint8_t> da, db, kpa, kpb, keep;
     DevBuf<int> idx, di1, di2, idxBack, diBack, cnt, off, pairs;
     DevBuf<float> df1, df2, dfBack, dist;
     PinnedBuf<int> h_total;
 };
-PipeWork& pipe_work() {
-    thread_local PipeWork w;
-    return w;
-}
 
 const int kElemU8 = 0, kElemF32 = 5;
 
@@ -143,7 +139,7 @@ extern "C" MCV_API int cvMatchFeaturesNorm(const DetectorResult* a, const Detect
         require_device();
         Plan& P = thread_plan(MCV_MODEL_HOMOGRAPHY);
         hipStream_t s = P.own_stream();
-        PipeWork& w = pipe_work();
+        PipeWork& w = thread_device_ws_on<PipeWork>(P.device);
         const int n = match_compact(a, b, cfg, norm, w, nullptr, &P, s, "cvMatchFeatures");
         if (n > maxPairs) fail("cvMatchFeatures: %d matches exceed maxPairs %d", n, maxPairs);
         if (n > 0) {
@@ -178,7 +174,7 @@ extern "C" MCV_API int cvMatchAndFindModelNorm(const DetectorResult* a, const De
         require_device();
         Plan& P = thread_plan(mcfg.model);
         hipStream_t s = P.own_stream();
-        PipeWork& w = pipe_work();
+        PipeWork& w = thread_device_ws_on<PipeWork>(P.device);
         const int n = match_compact(a, b, mcfg, norm, w, nullptr, &P, s, "cvMatchAndFindModel");
         if (n > maxPairs) fail("cvMatchAndFindModel: %d matches exceed maxPairs %d", n, maxPairs);
         if (matchCount) *matchCount = n;

@@ -384,11 +384,10 @@ extern const double kCheiralityDist;   // recoverPose's distanceThresh for the f
 // ---- the RANSAC batch calls (ransac_batch_host.cpp: cvFindModelBatch; ransac_batch_e_host.cpp: the essential
 // batches; ransac_batch_pnp_host.cpp: the PnP batches). Their layout and round plan: ransac_batch_index.h; the
 // round driver and the host helpers they share: batch_host.h.
-struct BatchStats {
-    long long launches = 0, syncs = 0, rounds = 0, lmRounds = 0, single = 0, problems = 0;
+struct BatchStats : CallStats {          // copies: host <-> device, every family; memsets are not counted
+    long long rounds = 0, lmRounds = 0, single = 0, problems = 0;
     long long packUs = 0, tableUs = 0;   // host time: point conversion, OpenCV sample tables
     long long problemRounds = 0;         // problems summed over the hypothesis rounds they ran in
-    long long copies = 0;                // host <-> device copies enqueued (every family; memsets are not counted)
 };
 BatchStats& batch_stats();   // the calling thread's last batch call (mcvTestBatchStats)
 // Throws what cvFindModelBatch refuses a (model, cfg) for, with its message; no device needed.

@@ -167,7 +167,7 @@ int e_batch(const char* who, bool pose, const mcvV2d* a, const mcvV2d* b, const 
     const size_t D = dev.size();
     if (D) {
         BatchEWs& W = thread_device_ws<BatchEWs>();
-        hipStream_t s = W.stream;
+        hipStream_t s = W.stream();
         // ---- points: the raw pixel pairs (a then b) in one copy, normalised by one launch
         auto t0 = std::chrono::steady_clock::now();
         W.h_raw.ensure((size_t)total * 4);

@@ -243,7 +243,7 @@ static int find_model_batch(int model, const mcvV2d* a, const mcvV2d* b, const i
     const size_t D = L.dev.size();
     if (D) {
         BatchWs& W = thread_device_ws<BatchWs>();
-        hipStream_t s = W.stream;
+        hipStream_t s = W.stream();
         // ---- points: one conversion pass (OpenCV's convertTo(CV_32F)), one copy
         W.h_pts.ensure((size_t)total * 4);
         W.pts.ensure((size_t)total * 4);

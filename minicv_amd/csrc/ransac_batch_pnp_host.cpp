@@ -494,7 +494,7 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
     const size_t D = dev.size();
     if (D) {
         BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
-        hipStream_t s = W.stream;
+        hipStream_t s = W.stream();
         // ---- points: refine_pack; the table of cameras in one more copy
         refine_pack(W, img, world, total, s);
         const auto t0 = std::chrono::steady_clock::now();
@@ -589,7 +589,7 @@ int pnp_batch(const char* who, const mcvV2d* img, const mcvV3d* world, const int
         // when no problem ran on the device, the mask when a direct solve or a failed inlier solve made the
         // returned one differ from the device's.
         BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
-        hipStream_t s = W.stream;
+        hipStream_t s = W.stream();
         if (!D) refine_pack(W, img, world, total, s);
         if (!maskOnDevice || directPoses > 0) mask_upload(W, mask, total, s);
         std::vector<uint8_t> run((size_t)B);
@@ -678,7 +678,7 @@ extern "C" MCV_API int cvRefinePnPBatch(const mcvV2d* imgPoints, const mcvV3d* w
         int ok = 0;
         if (!R.jobs.empty()) {
             BatchPnpWs& W = thread_device_ws<BatchPnpWs>();
-            hipStream_t s = W.stream;
+            hipStream_t s = W.stream();
             const int total = offsets[B];
             refine_pack(W, imgPoints, worldPoints, total, s);
             if (mask) mask_upload(W, mask, total, s);

@@ -18,33 +18,20 @@ namespace {
 static_assert(sizeof(ScaledSetup) == 59 * sizeof(double) && sizeof(ScaledBatchProb) == 16,
               "the setups, the problem table and the work list go up as one array of doubles");
 
-struct SbStats {
-    long long launches = 0, syncs = 0, copies = 0, memsets = 0, problems = 0, tiles = 0;
+struct SbStats : CallStats {
+    long long problems = 0, tiles = 0;
 };
+thread_local SbStats t_stats;   // the calling thread's last call (mcvTestScaledBatchStats)
 
-struct SbWork {
+struct SbWork : DeviceWs {
     DevBuf<double> w, o, soa, scales, costs, res, meta;
     DevBuf<uint8_t> used;
     std::vector<double> hmeta, hres;
     std::vector<int> hlist;
-    SbStats st;
-    hipStream_t s = nullptr;
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
-    ~SbWork() {
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
-SbWork& work() {
-    thread_local SbWork w;
-    return w;
-}
 
-void copy(SbWork& w, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-    w.st.copies += 1;
+void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    counted_copy(t_stats, dst, src, bytes, kind, s);
 }
 
 struct SbLayout {
@@ -87,7 +74,7 @@ bool check_batch(const char* name, const mcvCamera* srcCams, const mcvM33d* rota
 void run_device(SbWork& w, const SbLayout& L, const mcvCamera* srcCams, const mcvM33d* rotations,
                 const mcvV3d* translations, int P, const mcvV3d* worldPoints, const mcvV2d* observations, bool best,
                 double* h_scales, double* h_costs) {
-    w.st = SbStats();
+    t_stats = SbStats();
     hipStream_t s = w.stream();
     const size_t R = (size_t)L.rows, nb = (size_t)L.blocks, nc = (size_t)L.cands;
     // one array: setups[P], problem table[P], work list[blocks]
@@ -109,30 +96,29 @@ void run_device(SbWork& w, const SbLayout& L, const mcvCamera* srcCams, const mc
     w.scales.ensure(nc);
     w.costs.ensure(nc);
     w.used.ensure(nc / 2);
-    copy(w, w.meta.p, w.hmeta.data(), w.hmeta.size() * sizeof(double), hipMemcpyHostToDevice, s);
-    copy(w, w.w.p, worldPoints, R * sizeof(mcvV3d), hipMemcpyHostToDevice, s);
-    copy(w, w.o.p, observations, R * sizeof(mcvV2d), hipMemcpyHostToDevice, s);
+    copy(w.meta.p, w.hmeta.data(), w.hmeta.size() * sizeof(double), hipMemcpyHostToDevice, s);
+    copy(w.w.p, worldPoints, R * sizeof(mcvV3d), hipMemcpyHostToDevice, s);
+    copy(w.o.p, observations, R * sizeof(mcvV2d), hipMemcpyHostToDevice, s);
     const ScaledSetup* d_setups = reinterpret_cast<const ScaledSetup*>(w.meta.p);
     const ScaledBatchProb* d_probs = reinterpret_cast<const ScaledBatchProb*>(w.meta.p + setupDoubles);
     const int* d_list = reinterpret_cast<const int*>(w.meta.p + setupDoubles + probDoubles);
     launch_scaled_batch_pack(w.w.p, w.o.p, L.rows, w.soa.p, s);
     launch_scaled_batch_candidates(d_setups, d_probs, d_list, (int)nb, w.soa.p, L.rows, w.scales.p, w.used.p, s);
     launch_scaled_batch_costs(d_setups, d_probs, d_list, (int)nb, w.soa.p, L.rows, w.scales.p, w.used.p, w.costs.p, s);
-    w.st.launches += 3;
+    t_stats.launches += 3;
     if (best) {
         w.res.ensure(3 * (size_t)P);
         w.hres.resize(3 * (size_t)P);
         launch_scaled_batch_best(d_probs, P, w.costs.p, w.scales.p, w.used.p, w.res.p, s);
-        w.st.launches += 1;
+        t_stats.launches += 1;
     }
     MCV_HIP(hipGetLastError());
-    if (best) copy(w, w.hres.data(), w.res.p, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (h_scales) copy(w, h_scales, w.scales.p, nc * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (h_costs) copy(w, h_costs, w.costs.p, nc * sizeof(double), hipMemcpyDeviceToHost, s);
-    MCV_HIP(hipStreamSynchronize(s));
-    w.st.syncs += 1;
-    w.st.problems = L.live;
-    w.st.tiles = L.blocks;
+    if (best) copy(w.hres.data(), w.res.p, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (h_scales) copy(h_scales, w.scales.p, nc * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (h_costs) copy(h_costs, w.costs.p, nc * sizeof(double), hipMemcpyDeviceToHost, s);
+    counted_wait(t_stats, s);
+    t_stats.problems = L.live;
+    t_stats.tiles = L.blocks;
 }
 
 }  // namespace
@@ -156,7 +142,7 @@ extern "C" MCV_API int cvFindScaledPoseBatch(const mcvCamera* srcCams, const mcv
             return 0;
         }
         require_device();
-        SbWork& w = work();
+        SbWork& w = thread_device_ws<SbWork>();
         run_device(w, L, srcCams, rotations, translations, P, worldPoints, observations, true, nullptr, nullptr);
         int finite = 0;
         for (int p = 0; p < P; ++p) {
@@ -182,7 +168,7 @@ extern "C" MCV_API int cvFindScaledPoseBatchCosts(const mcvCamera* srcCams, cons
             return 0;
         if (L.cands == 0) return 0;
         require_device();
-        run_device(work(), L, srcCams, rotations, translations, P, worldPoints, observations, false, scales, costs);
+        run_device(thread_device_ws<SbWork>(), L, srcCams, rotations, translations, P, worldPoints, observations, false, scales, costs);
         return (int)(L.cands / 2);
     })
 }
@@ -233,10 +219,6 @@ extern "C" MCV_API int mcvHostFindScaledPoseBatch(const mcvCamera* srcCams, cons
 
 extern "C" MCV_API int mcvTestScaledBatchStats(long long* stats8) {
     MCV_GUARD(-1, {
-        if (!stats8) fail("mcvTestScaledBatchStats: null argument");
-        const SbStats& st = work().st;
-        const long long v[8] = {st.launches, st.syncs, st.copies, st.memsets, st.problems, st.tiles, 0, 0};
-        for (int i = 0; i < 8; ++i) stats8[i] = v[i];
-        return 0;
+        return stats8_out("mcvTestScaledBatchStats", stats8, t_stats, {t_stats.problems, t_stats.tiles});
     })
 }

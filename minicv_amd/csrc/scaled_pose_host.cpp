@@ -10,28 +10,16 @@ using namespace mcv;
 
 namespace {
 
-struct ScaledWork {
+struct ScaledWork : DeviceWs {
     DevBuf<double> w, o, soa, scales, costs;
     DevBuf<uint8_t> used;
     DevBuf<long long> out;
-    hipStream_t s = nullptr;
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
-    ~ScaledWork() {
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
-ScaledWork& work() {
-    thread_local ScaledWork w;
-    return w;
-}
 
 // Device part shared by the host-pointer and device-pointer exports. Synchronises s.
-int scaled_device(const ScaledSetup& S, const double* d_w3, const double* d_o2, int N, double* outCost,
-                  double* outScale, hipStream_t s, double* h_scales = nullptr, double* h_costs = nullptr) {
-    ScaledWork& w = work();
+int scaled_device(ScaledWork& w, const ScaledSetup& S, const double* d_w3, const double* d_o2, int N,
+                  double* outCost, double* outScale, hipStream_t s, double* h_scales = nullptr,
+                  double* h_costs = nullptr) {
     w.soa.ensure((size_t)N * 5);
     w.scales.ensure((size_t)N * 2);
     w.costs.ensure((size_t)N * 2);
@@ -75,13 +63,13 @@ extern "C" MCV_API int cvFindScaledPose(double inlierThreshold, const mcvCamera*
         }
         require_device();
         const ScaledSetup S = make_setup(*srcCam, *rotation, *translation);
-        ScaledWork& w = work();
+        ScaledWork& w = thread_device_ws<ScaledWork>();
         hipStream_t s = w.stream();
         w.w.ensure((size_t)N * 3);
         w.o.ensure((size_t)N * 2);
         MCV_HIP(hipMemcpyAsync(w.w.p, worldPoints, (size_t)N * 24, hipMemcpyHostToDevice, s));
         MCV_HIP(hipMemcpyAsync(w.o.p, observations, (size_t)N * 16, hipMemcpyHostToDevice, s));
-        return scaled_device(S, w.w.p, w.o.p, N, outCost, outScale, s);
+        return scaled_device(w, S, w.w.p, w.o.p, N, outCost, outScale, s);
     })
 }
 
@@ -94,13 +82,13 @@ extern "C" MCV_API int cvFindScaledPoseCosts(const mcvCamera* srcCam, const mcvV
         if (!scales || !costs) fail("cvFindScaledPoseCosts: bad argument");
         require_device();
         const ScaledSetup S = make_setup(*srcCam, *rotation, *translation);
-        ScaledWork& w = work();
+        ScaledWork& w = thread_device_ws<ScaledWork>();
         hipStream_t s = w.stream();
         w.w.ensure((size_t)N * 3);
         w.o.ensure((size_t)N * 2);
         MCV_HIP(hipMemcpyAsync(w.w.p, worldPoints, (size_t)N * 24, hipMemcpyHostToDevice, s));
         MCV_HIP(hipMemcpyAsync(w.o.p, observations, (size_t)N * 16, hipMemcpyHostToDevice, s));
-        scaled_device(S, w.w.p, w.o.p, N, nullptr, nullptr, s, scales, costs);
+        scaled_device(w, S, w.w.p, w.o.p, N, nullptr, nullptr, s, scales, costs);
         return N;
     })
 }
@@ -117,8 +105,8 @@ extern "C" MCV_API int mcvFindScaledPoseDevice(const mcvCamera* srcCam, const mc
         }
         require_device();
         const ScaledSetup S = make_setup(*srcCam, *rotation, *translation);
-        return scaled_device(S, (const double*)d_world, (const double*)d_obs, N, outCost, outScale,
-                             (hipStream_t)stream);
+        return scaled_device(thread_device_ws<ScaledWork>(), S, (const double*)d_world, (const double*)d_obs, N,
+                             outCost, outScale, (hipStream_t)stream);
     })
 }
 

@@ -14,38 +14,26 @@ using namespace mcv;
 
 namespace {
 
-struct TrkStats {
-    long long launches = 0, syncs = 0, copies = 0, memsets = 0, candidates = 0, longCandidates = 0, keptEdges = 0;
+struct TrkStats : CallStats {
+    long long candidates = 0, longCandidates = 0, keptEdges = 0;
 };
+// The host side of the calling thread's last call: its statistics (mcvTestTracksStats) and the staging
+// trk_prepare fills before the device is touched. No device resource, so not part of the workspace.
+struct TrkHost {
+    TrkStats st;
+    std::vector<int> base, edges;
+};
+thread_local TrkHost t_host;
 
-struct TrkWork {
+struct TrkWork : DeviceWs {
     DevBuf<int> edges, base, parent, size, cursor, trk, slots, candList, longList, trackOffsets, cameraIdx,
         featureIdx, trackOfFeature;
     DevBuf<uint8_t> touched;
     DevBuf<unsigned long long> blockSums, ctr;
-    std::vector<int> hBase, hEdges;
-    TrkStats st;
-    hipStream_t s = nullptr;
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
-    ~TrkWork() {
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
-TrkWork& work() {
-    thread_local TrkWork w;
-    return w;
-}
 
-void copy(TrkWork& w, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    if (bytes) MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-    w.st.copies += 1;   // counted by the call's form: an empty array changes no count
-}
-void sync(TrkWork& w, hipStream_t s) {
-    MCV_HIP(hipStreamSynchronize(s));
-    w.st.syncs += 1;
+void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    counted_copy(t_host.st, dst, src, bytes, kind, s);   // by the call's form: an empty array changes no count
 }
 
 void check_fit(const char* name, long long T, long long nObs, int maxTracks, int maxObs) {
@@ -61,16 +49,16 @@ extern "C" MCV_API int cvBuildTracks(const int* featureCounts, int nImages, cons
                                      int* trackOfFeature, long long* dropped) {
     MCV_GUARD(-1, {
         const char* name = "cvBuildTracks";
-        TrkWork& w = work();
+        TrkHost& h = t_host;
         std::string err;
         long long nEdges = 0;
         if (!trk_prepare(name, featureCounts, nImages, imagePairs, B, pairs, offsets, mask, minLength, trackOffsets,
-                         maxTracks, cameraIdx, featureIdx, maxObs, w.hBase, &w.hEdges, &nEdges, err))
+                         maxTracks, cameraIdx, featureIdx, maxObs, h.base, &h.edges, &nEdges, err))
             fail("%s", err.c_str());
         require_device();
-        w.st = TrkStats();
-        w.st.keptEdges = nEdges;
-        const int N = w.hBase[(size_t)nImages];
+        h.st = TrkStats();
+        h.st.keptEdges = nEdges;
+        const int N = h.base[(size_t)nImages];
         if (nEdges == 0) {   // nothing is touched: no component, no track
             trackOffsets[0] = 0;
             if (trackOfFeature)
@@ -78,6 +66,7 @@ extern "C" MCV_API int cvBuildTracks(const int* featureCounts, int nImages, cons
             if (dropped) dropped[0] = dropped[1] = dropped[2] = 0;
             return 0;
         }
+        TrkWork& w = thread_device_ws<TrkWork>();
         hipStream_t s = w.stream();
         const size_t n = (size_t)N;
         const size_t slotCap = (size_t)(2 * nEdges < (long long)N ? 2 * nEdges : (long long)N);
@@ -100,11 +89,10 @@ extern "C" MCV_API int cvBuildTracks(const int* featureCounts, int nImages, cons
         w.ctr.ensure(kTrkCtrs);
         {
             ProfScope ps("trk_upload", s);
-            copy(w, w.base.p, w.hBase.data(), ((size_t)nImages + 1) * sizeof(int), hipMemcpyHostToDevice, s);
-            copy(w, w.edges.p, w.hEdges.data(), 2 * (size_t)nEdges * sizeof(int), hipMemcpyHostToDevice, s);
+            copy(w.base.p, h.base.data(), ((size_t)nImages + 1) * sizeof(int), hipMemcpyHostToDevice, s);
+            copy(w.edges.p, h.edges.data(), 2 * (size_t)nEdges * sizeof(int), hipMemcpyHostToDevice, s);
         }
-        MCV_HIP(hipMemsetAsync(w.ctr.p, 0, kTrkCtrs * sizeof(unsigned long long), s));
-        w.st.memsets += 1;
+        counted_zero(h.st, w.ctr.p, kTrkCtrs * sizeof(unsigned long long), s);
         TrkDevice D;
         D.edges = w.edges.p;
         D.nEdges = nEdges;
@@ -128,26 +116,26 @@ extern "C" MCV_API int cvBuildTracks(const int* featureCounts, int nImages, cons
         D.trackOfFeature = trackOfFeature ? w.trackOfFeature.p : nullptr;
         D.ctr = w.ctr.p;
         launch_build_tracks(D, s);
-        w.st.launches += kTrkLaunches;
+        h.st.launches += kTrkLaunches;
         MCV_HIP(hipGetLastError());
         // the one read-back: T, nObs, the drop counters and the fail word; the outputs follow it
         unsigned long long ctr[kTrkCtrs];
-        copy(w, ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
-        sync(w, s);
+        copy(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
+        counted_wait(h.st, s);
         if (ctr[3]) fail("%s: a bounded loop of the union gave up (fail word %llu)", name, ctr[3]);
         const long long T = (long long)(ctr[5] >> 32), nObs = (long long)(ctr[5] & 0xffffffffull);
-        w.st.candidates = (long long)(ctr[4] >> 32);
-        w.st.longCandidates = (long long)ctr[6];
+        h.st.candidates = (long long)(ctr[4] >> 32);
+        h.st.longCandidates = (long long)ctr[6];
         check_fit(name, T, nObs, maxTracks, maxObs);
         {
             ProfScope ps("trk_download", s);
-            copy(w, trackOffsets, w.trackOffsets.p, ((size_t)T + 1) * sizeof(int), hipMemcpyDeviceToHost, s);
-            copy(w, cameraIdx, w.cameraIdx.p, (size_t)nObs * sizeof(int), hipMemcpyDeviceToHost, s);
-            copy(w, featureIdx, w.featureIdx.p, (size_t)nObs * sizeof(int), hipMemcpyDeviceToHost, s);
+            copy(trackOffsets, w.trackOffsets.p, ((size_t)T + 1) * sizeof(int), hipMemcpyDeviceToHost, s);
+            copy(cameraIdx, w.cameraIdx.p, (size_t)nObs * sizeof(int), hipMemcpyDeviceToHost, s);
+            copy(featureIdx, w.featureIdx.p, (size_t)nObs * sizeof(int), hipMemcpyDeviceToHost, s);
             if (trackOfFeature)
-                copy(w, trackOfFeature, w.trackOfFeature.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
+                copy(trackOfFeature, w.trackOfFeature.p, n * sizeof(int), hipMemcpyDeviceToHost, s);
         }
-        sync(w, s);
+        counted_wait(h.st, s);
         if (dropped)
             for (int k = 0; k < 3; ++k) dropped[k] = (long long)ctr[k];
         return (int)T;
@@ -185,11 +173,7 @@ extern "C" MCV_API int mcvHostBuildTracks(const int* featureCounts, int nImages,
 
 extern "C" MCV_API int mcvTestTracksStats(long long* stats8) {
     MCV_GUARD(-1, {
-        if (!stats8) fail("mcvTestTracksStats: null argument");
-        const TrkStats& st = work().st;
-        const long long v[8] = {st.launches, st.syncs,          st.copies,    st.memsets,
-                                st.candidates, st.longCandidates, st.keptEdges, 0};
-        for (int i = 0; i < 8; ++i) stats8[i] = v[i];
-        return 0;
+        const TrkStats& st = t_host.st;
+        return stats8_out("mcvTestTracksStats", stats8, st, {st.candidates, st.longCandidates, st.keptEdges});
     })
 }

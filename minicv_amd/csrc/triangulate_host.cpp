@@ -13,36 +13,19 @@ namespace {
 
 static_assert(sizeof(mcvRay3d) == 48 && sizeof(mcvCamera) == 112, "rays and cameras are read as plain doubles");
 
-struct TriStats {
-    long long launches = 0, syncs = 0, copies = 0, memsets = 0, shortTracks = 0, longTracks = 0;
+struct TriStats : CallStats {
+    long long shortTracks = 0, longTracks = 0;
 };
+thread_local TriStats t_stats;   // the calling thread's last call (mcvTestTriangulateStats)
 
-struct TriWork {
+struct TriWork : DeviceWs {
     DevBuf<double> rays, obs, cameras, points, cost;
     DevBuf<int> offsets, camIdx, counts, visible, longList;
     DevBuf<unsigned int> ctr;
-    TriStats st;
-    hipStream_t s = nullptr;
-    hipStream_t stream() {
-        if (!s) MCV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return s;
-    }
-    ~TriWork() {
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
-TriWork& work() {
-    thread_local TriWork w;
-    return w;
-}
 
-void copy(TriWork& w, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    if (bytes) MCV_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
-    w.st.copies += 1;   // counted by the call's form: an empty array changes no count
-}
-void sync(TriWork& w, hipStream_t s) {
-    MCV_HIP(hipStreamSynchronize(s));
-    w.st.syncs += 1;
+void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    counted_copy(t_stats, dst, src, bytes, kind, s);   // by the call's form: an empty array changes no count
 }
 
 void check_host_offsets(const char* name, const int* offsets, int T) {
@@ -71,23 +54,22 @@ void run_device(TriWork& w, const double* d_rays, const double* d_cameras, const
     if (d_cameras) {
         w.rays.ensure(6 * (size_t)nObs);
         launch_tri_unproject(d_cameras, d_camIdx, d_obs, d_offsets, T, w.rays.p, s);
-        w.st.launches += 1;
+        t_stats.launches += 1;
         d_rays = w.rays.p;
     }
     w.longList.ensure((size_t)T);
     launch_tri_intersect(d_rays, d_offsets, T, d_points, d_counts, w.longList.p, w.ctr.p, s);
-    w.st.launches += 2;
+    t_stats.launches += 2;
     if (d_cameras && (d_cost || d_visible)) {
         launch_tri_stats(d_cameras, d_camIdx, d_obs, d_offsets, T, d_points, d_cost, d_visible, s);
-        w.st.launches += 1;
+        t_stats.launches += 1;
     }
     MCV_HIP(hipGetLastError());
 }
 
 void zero_counters(TriWork& w, hipStream_t s) {
     w.ctr.ensure(kTriCtrs);
-    MCV_HIP(hipMemsetAsync(w.ctr.p, 0, kTriCtrs * sizeof(unsigned int), s));
-    w.st.memsets += 1;
+    counted_zero(t_stats, w.ctr.p, kTriCtrs * sizeof(unsigned int), s);
 }
 
 // Host-pointer calls: rays != nullptr (cvIntersectRays) or the camera form (cvTriangulateTracks).
@@ -103,39 +85,39 @@ int run_host_pointers(const char* name, const mcvRay3d* rays, const mcvCamera* c
     const long long n = offsets[T];
     if (cameras) check_host_cameras(name, cameraIdx, n, nCameras);
     require_device();
-    TriWork& w = work();
-    w.st = TriStats();
+    TriWork& w = thread_device_ws<TriWork>();
+    t_stats = TriStats();
     hipStream_t s = w.stream();
     w.offsets.ensure((size_t)T + 1);
     w.points.ensure(3 * (size_t)T);
     w.counts.ensure((size_t)T);
-    copy(w, w.offsets.p, offsets, ((size_t)T + 1) * sizeof(int), hipMemcpyHostToDevice, s);
+    copy(w.offsets.p, offsets, ((size_t)T + 1) * sizeof(int), hipMemcpyHostToDevice, s);
     if (cameras) {
         w.cameras.ensure(14 * (size_t)(nCameras ? nCameras : 1));
         w.camIdx.ensure((size_t)n);
         w.obs.ensure(2 * (size_t)n);
-        copy(w, w.cameras.p, cameras, (size_t)nCameras * sizeof(mcvCamera), hipMemcpyHostToDevice, s);
-        copy(w, w.camIdx.p, cameraIdx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s);
-        copy(w, w.obs.p, observations, (size_t)n * sizeof(mcvV2d), hipMemcpyHostToDevice, s);
+        copy(w.cameras.p, cameras, (size_t)nCameras * sizeof(mcvCamera), hipMemcpyHostToDevice, s);
+        copy(w.camIdx.p, cameraIdx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s);
+        copy(w.obs.p, observations, (size_t)n * sizeof(mcvV2d), hipMemcpyHostToDevice, s);
         if (cost) w.cost.ensure((size_t)T);
         if (visible) w.visible.ensure((size_t)T);
     } else {
         w.rays.ensure(6 * (size_t)n);
-        copy(w, w.rays.p, rays, (size_t)n * sizeof(mcvRay3d), hipMemcpyHostToDevice, s);
+        copy(w.rays.p, rays, (size_t)n * sizeof(mcvRay3d), hipMemcpyHostToDevice, s);
     }
     zero_counters(w, s);
     run_device(w, cameras ? nullptr : w.rays.p, cameras ? w.cameras.p : nullptr, w.camIdx.p, w.obs.p, w.offsets.p, T,
                n, w.points.p, w.counts.p, cameras && cost ? w.cost.p : nullptr,
                cameras && visible ? w.visible.p : nullptr, s);
     unsigned int ctr[kTriCtrs];
-    copy(w, points, w.points.p, (size_t)T * sizeof(mcvV3d), hipMemcpyDeviceToHost, s);
-    copy(w, pairCounts, w.counts.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s);
-    if (cameras && cost) copy(w, cost, w.cost.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (cameras && visible) copy(w, visible, w.visible.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s);
-    copy(w, ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
-    sync(w, s);
-    w.st.longTracks = ctr[0];
-    w.st.shortTracks = (long long)T - ctr[0];
+    copy(points, w.points.p, (size_t)T * sizeof(mcvV3d), hipMemcpyDeviceToHost, s);
+    copy(pairCounts, w.counts.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (cameras && cost) copy(cost, w.cost.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (cameras && visible) copy(visible, w.visible.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, s);
+    copy(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    counted_wait(t_stats, s);
+    t_stats.longTracks = ctr[0];
+    t_stats.shortTracks = (long long)T - ctr[0];
     return (int)ctr[1];
 }
 
@@ -171,18 +153,18 @@ extern "C" MCV_API int mcvTriangulateTracksDevice(const mcvCamera* d_cameras, in
             fail("%s: null argument", name);
         if (nCameras < 0) fail("%s: negative nCameras", name);
         require_device();
-        TriWork& w = work();
-        w.st = TriStats();
+        TriWork& w = thread_device_ws<TriWork>();
+        t_stats = TriStats();
         hipStream_t s = nullptr;
         zero_counters(w, s);
         launch_tri_validate(d_offsets, T, d_cameraIdx, nCameras, w.ctr.p, s);
-        w.st.launches += 2;
+        t_stats.launches += 2;
         MCV_HIP(hipGetLastError());
         unsigned int ctr[kTriCtrs];
         int nObs = 0;
-        copy(w, ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
-        copy(w, &nObs, d_offsets + T, sizeof(int), hipMemcpyDeviceToHost, s);
-        sync(w, s);
+        copy(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
+        copy(&nObs, d_offsets + T, sizeof(int), hipMemcpyDeviceToHost, s);
+        counted_wait(t_stats, s);
         if (ctr[2]) {   // the first bad track: read its offsets back for the message
             const int t = T - (int)ctr[2];
             int off[3];
@@ -196,21 +178,17 @@ extern "C" MCV_API int mcvTriangulateTracksDevice(const mcvCamera* d_cameras, in
         if (ctr[4]) fail("%s: cameraIdx[%d] outside [0, %d)", name, nObs - (int)ctr[4], nCameras);
         run_device(w, nullptr, (const double*)d_cameras, d_cameraIdx, (const double*)d_observations, d_offsets, T,
                    nObs, (double*)d_points, d_pairCounts, d_cost, d_visible, s);
-        copy(w, ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
-        sync(w, s);
-        w.st.longTracks = ctr[0];
-        w.st.shortTracks = (long long)T - ctr[0];
+        copy(ctr, w.ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, s);
+        counted_wait(t_stats, s);
+        t_stats.longTracks = ctr[0];
+        t_stats.shortTracks = (long long)T - ctr[0];
         return (int)ctr[1];
     })
 }
 
 extern "C" MCV_API int mcvTestTriangulateStats(long long* stats8) {
     MCV_GUARD(-1, {
-        if (!stats8) fail("mcvTestTriangulateStats: null argument");
-        const TriStats& st = work().st;
-        const long long v[8] = {st.launches, st.syncs, st.copies, st.memsets, st.shortTracks, st.longTracks, 0, 0};
-        for (int i = 0; i < 8; ++i) stats8[i] = v[i];
-        return 0;
+        return stats8_out("mcvTestTriangulateStats", stats8, t_stats, {t_stats.shortTracks, t_stats.longTracks});
     })
 }
 
