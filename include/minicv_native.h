@@ -90,7 +90,29 @@ MCV_API int  cvRecoverPose(const RecoverPoseConfig* config, const int N, const m
  * false if N < 5 or no model (ms untouched then). */
 MCV_API mcvBool cvRecoverPoses(const RecoverPoseConfig* config, const int N, const mcvV2d* pa, const mcvV2d* pb,
                             mcvM33d* rMat1, mcvM33d* rMat2, mcvV3d* tVec, uint8_t* ms);
-/* Feature detection — MiniCVNative.cpp:221-365 (out of scope: returns NULL). */
+/* Feature detection — MiniCVNative.cpp:221-365. mode is the reference's DetectorMode; only SIFT
+ * (mode 4) runs here, on the GPU: AKAZE, ORB and BRISK return NULL with an error, as does
+ * any other mode. config: NULL (the defaults {0, 3, 0.04, 10.0, 1.6, 0}) or a SiftConfig.
+ *   data: height x width x channels bytes, row-major. channels 1: grey; 3 or 4: RGB(A), grey =
+ *   (4899 R + 9617 G + 1868 B + 8192) >> 14; anything else: NULL. width and height: 1 .. 8192.
+ *   OctaveLayers 1 .. 6, 0 < Sigma <= 4, ContrastThreshold >= 0, EdgeThreshold > 0, DescriptorType 0
+ *   (uint8, the reference's default: rows for cvMatchFeaturesNorm(MCV_NORM_L2)) or 5 (float32).
+ * Keypoints come out ascending by (octave, layer, row, column, orientation bin); FeatureCount > 0 keeps
+ * that many of the largest response. The result (PointCount may be 0) is freed with cvFreeFeatures.
+ * The keypoints and descriptors are SIFT as cv::SIFT arranges it, defined bit for bit by DESIGN §7n;
+ * bit parity with cv::SIFT is not claimed. NULL on failure (mcvGetLastError). */
+#define MCV_FEATURE_MODE_AKAZE 1
+#define MCV_FEATURE_MODE_ORB   2
+#define MCV_FEATURE_MODE_BRISK 3
+#define MCV_FEATURE_MODE_SIFT  4
+typedef struct {   /* MiniCVNative.h:79-86 (40 bytes) */
+    int FeatureCount;
+    int OctaveLayers;
+    double ContrastThreshold;
+    double EdgeThreshold;
+    double Sigma;
+    int DescriptorType;
+} SiftConfig;
 MCV_API DetectorResult* cvDetectFeatures(char* data, int width, int height, int channels, int mode, void* config);
 MCV_API void cvFreeFeatures(DetectorResult* res);
 /* Debug export — MiniCVNative.cpp:504 (no-op). */
@@ -1116,6 +1138,15 @@ MCV_API int mcvHostBuildTracks(const int* featureCounts, int nImages, const int*
  * were sorted), of them the long ones (more than 32 nodes: one workgroup each), kept matches, 0}; all
  * are 0 for a call without a kept match, which launches nothing. Returns 0. */
 MCV_API int mcvTestTracksStats(long long* stats8);
+/* Host twin of cvDetectFeatures: the same arguments, checks and result (freed with cvFreeFeatures),
+ * computed sequentially by the host-compiled sample arithmetic (sift_math.h). No GPU. */
+MCV_API DetectorResult* mcvHostDetectFeatures(char* data, int width, int height, int channels, int mode,
+                                              void* config);
+/* What the calling thread's last cvDetectFeatures call enqueued and found: stats8 = {kernel launches,
+ * stream synchronisations, host<->device copies, memsets, extremum candidates, refined keypoints,
+ * keypoints with orientations (before duplicates and FeatureCount), keypoints returned}. The
+ * descriptor kernel has one path for every radius, so there is no short / long count. Returns 0. */
+MCV_API int mcvTestSiftStats(long long* stats8);
 /* Host twin of cvBundleAdjust: the same arguments, checks, outputs, summary and return value, computed
  * sequentially by the host-compiled kernel arithmetic (ba_terms.h) in the kernels' summation orders. No GPU. */
 MCV_API int mcvHostBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,

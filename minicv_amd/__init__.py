@@ -9,7 +9,8 @@ from . import native
 from .native import RansacConfig, NativeError
 from .opencv import RansacParams, findHomography, findFundamentalMat, matchHamming, matchL2, matchL2U8, \
     recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch, \
-    refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch
+    refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch, detectFeatures, DetectedFeatures
+from .native import SiftConfig
 from . import camera
 from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks, \
     buildTracks, trackObservations
@@ -18,4 +19,4 @@ __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomogra
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
            "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch",
            "refinePnPBatch", "solvePnPRansacWithRefine", "solvePnPRansacWithRefineBatch", "camera", "Camera", "CameraPose", "findScaled",
-           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts", "buildTracks", "trackObservations"]
+           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts", "buildTracks", "trackObservations", "detectFeatures", "DetectedFeatures", "SiftConfig"]

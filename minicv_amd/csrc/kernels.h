@@ -682,4 +682,69 @@ void launch_ba_system(const BaDevice& D, hipStream_t s);      // Vinv, t, L, b a
 void launch_ba_cg_iteration(const BaDevice& D, hipStream_t s);
 void launch_ba_trial(const BaDevice& D, hipStream_t s);       // cams2 / pts2 from x, and their cost -> D.rec
 
+// ---- SIFT detection (sift.hip; the records are sift_math.h's)
+struct SiftParams;
+struct SiftKp;
+struct SiftRec;
+static const int kSiftMaxOctaves = 16;   // round(log2(2 x 8192) - 2) = 12 at the size cap
+struct SiftPyramid {
+    const float* base;                    // every octave's nl + 3 Gaussian images
+    size_t obase[kSiftMaxOctaves];        // float offset of an octave's first image
+    int ow[kSiftMaxOctaves], oh[kSiftMaxOctaves];
+    int rowBase[kSiftMaxOctaves];         // first bucket of an octave: a bucket is one (octave, layer, row)
+};
+// bucket of the order stage: rowBase[o] + (layer - 1) oh[o] + r, layer in 1 .. OctaveLayers
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int sift_bucket(const SiftPyramid& Y, int o, int layer, int r) {
+    return Y.rowBase[o] + (layer - 1) * Y.oh[o] + r;
+}
+struct SiftKeyPointOut {   // KeyPoint2d's 28 bytes
+    float x, y, size, angle, response;
+    int octave, class_id;
+};
+static const int kSiftRowTile = 256;                        // outputs per block of the row blur
+static const int kSiftColTileW = 64, kSiftColTileH = 32;    // outputs per block of the column blur
+// d_ctr: [0] candidates, [1] refined, [2] keypoints with orientations, [3] keypoints kept
+static const int kSiftCtrs = 4;
+// Kernel launches of a cvDetectFeatures call: kSiftLaunchesFixed (grey + doubling, the base blur's two,
+// refine, orientation, the order's scan, scatter, rank and compaction, descriptors) + nOctaves x
+// (kSiftLaunchesPerBlur x (OctaveLayers + 2) + kSiftLaunchesExtrema) + (nOctaves - 1) x
+// kSiftLaunchesDownsample + kSiftLaunchesSelect if FeatureCount > 0. Stream synchronisations, copies and
+// memsets are the same for every call that reaches the device with nOctaves > 0.
+static const int kSiftLaunchesFixed = 10, kSiftLaunchesPerBlur = 2, kSiftLaunchesExtrema = 1,
+                 kSiftLaunchesDownsample = 1, kSiftLaunchesSelect = 1;
+static const int kSiftSyncs = 4, kSiftCopies = 7, kSiftMemsets = 1;
+void launch_sift_grey_double(const uint8_t* d_img, int w, int h, int ch, float* d_up, hipStream_t s);
+// d_out = blur of d_in (rows into d_tmp, then columns); taps[2 R + 1] on the device. Two launches.
+void launch_sift_blur(const float* d_in, float* d_out, float* d_tmp, int w, int h, const float* d_taps, int R,
+                      hipStream_t s);
+void launch_sift_downsample(const float* d_src, int pw, float* d_dst, int w, int h, hipStream_t s);
+// Appends (o, layer, r, c) int4 records to d_cand (places >= cap are counted, not written).
+void launch_sift_extrema(const float* d_g, int w, int h, int o, int nl, float thr, void* d_cand, unsigned cap,
+                         unsigned* d_ctr, hipStream_t s);
+void launch_sift_refine(const SiftPyramid& Y, const SiftParams& P, const void* d_cand, int nC, SiftKp* d_kps,
+                        unsigned* d_ctr, hipStream_t s);
+// d_recs, d_keys, d_starts, d_rkeys: 18 nC each (a candidate has at most 18 orientation peaks); d_bcnt: a
+// counter per bucket, zeroed by the caller.
+void launch_sift_orient(const SiftPyramid& Y, const void* d_cand, const SiftKp* d_kps, int nC, SiftRec* d_recs,
+                        unsigned long long* d_keys, unsigned long long* d_starts, unsigned long long* d_rkeys,
+                        unsigned* d_ctr, unsigned* d_bcnt, hipStream_t s);
+// The order stage over the n appended records: 4 launches, 5 with featureCount > 0 (sift.hip).
+struct SiftOrder {
+    int nBuckets;
+    unsigned *bcnt, *boff;                                   // nBuckets, nBuckets + 1
+    const unsigned long long *keys, *starts, *rkeys;         // as appended
+    const SiftRec* recs;
+    int *perm, *sortedIdx;                                   // n each
+    unsigned long long *skeys, *srkeys;                      // n each: the keys in order
+    uint8_t *keepA, *keepB;                                  // n each
+    SiftRec* out;                                            // n
+    unsigned* count;
+};
+void launch_sift_order(const SiftPyramid& Y, const SiftOrder& O, int n, int featureCount, hipStream_t s);
+void launch_sift_describe(const SiftPyramid& Y, const SiftRec* d_recs, int n, int descType, SiftKeyPointOut* d_kp,
+                          uint8_t* d_u8, float* d_f32, hipStream_t s);
+
 }  // namespace mcv

@@ -1,6 +1,7 @@
 // shim.cpp — the rest of the MiniCVNative C-ABI surface: error reporting, device query, and the
 // reference exports that are outside the hot path (they bind, and fail loudly with a message).
-//   cvDetectFeatures / cvFreeFeatures   MiniCVNative.cpp:221-365  (feature detection: out of scope)
+//   cvFreeFeatures                       MiniCVNative.cpp:347-365  (frees what cvDetectFeatures returns;
+//                                        detection itself is sift_host.cpp: SIFT on the GPU, the other modes refused)
 //   cvDetectQRCode / cvDetectArucoMarkers MiniCVNative.cpp:384-502 (fiducials: out of scope)
 //   cvTest                               MiniCVNative.cpp:504      (debug print: no-op)
 #include "minicv_native.h"
@@ -103,11 +104,6 @@ extern "C" MCV_API int mcvDeviceCount(void) {
 }
 
 #define MCV_NOT_IN_SCOPE(name, why) set_last_error(name ": " why)
-
-extern "C" MCV_API DetectorResult* cvDetectFeatures(char*, int, int, int, int, void*) {
-    MCV_NOT_IN_SCOPE("cvDetectFeatures", "feature detection is outside the MI355X hot path (SURVEY 2 row 4)");
-    return nullptr;
-}
 
 extern "C" MCV_API void cvFreeFeatures(DetectorResult* res) {
     // Frees a DetectorResult allocated with new[] members (fixes the reference's delete/new[]

@@ -87,6 +87,22 @@ class DetectorResult(C.Structure):
                 ("Points", C.c_void_p), ("Descriptors", C.c_void_p)]
 
 
+class SiftConfig(C.Structure):
+    """SiftConfig (MiniCVNative.h:79-86, 40 bytes); SiftConfig.default() holds cv::SIFT's defaults with byte
+    descriptors, which cvDetectFeatures also takes for a NULL config."""
+    _fields_ = [("FeatureCount", C.c_int), ("OctaveLayers", C.c_int), ("ContrastThreshold", C.c_double),
+                ("EdgeThreshold", C.c_double), ("Sigma", C.c_double), ("DescriptorType", C.c_int)]
+
+    @classmethod
+    def default(cls, **kw) -> "SiftConfig":
+        c = cls(0, 3, 0.04, 10.0, 1.6, 0)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"SiftConfig has no field {k}")
+            setattr(c, k, v)
+        return c
+
+
 class MatchConfig(C.Structure):
     _fields_ = [("ratio", C.c_float), ("crossCheck", C.c_int), ("maxDistance", C.c_float), ("model", C.c_int)]
 
@@ -133,6 +149,31 @@ BA_CG_CHUNK = 8                 # PCG iterations between two reads of the solve'
 # kernel launches of cvBundleAdjust's stages (kernels.h kBaLaunches*): the call's total is
 # SETUP + COST + LINEARIZE x linearisations + (SYSTEM + TRIAL) x trials + CG_ITER x BA_CG_CHUNK x chunks
 BA_LAUNCHES = {"setup": 3, "cost": 2, "linearize": 4, "system": 4, "cg_iter": 5, "trial": 5}
+FEATURE_AKAZE, FEATURE_ORB, FEATURE_BRISK, FEATURE_SIFT = 1, 2, 3, 4   # the reference's DetectorMode
+SIFT_MAX_SIDE = 8192            # width and height cap of cvDetectFeatures (sift_math.h kSiftMaxSide)
+SIFT_MAX_LAYERS = 6             # OctaveLayers 1 .. 6 (sift_math.h kSiftMaxLayers)
+SIFT_MAX_SIGMA = 4.0            # sift_math.h kSiftMaxSigma
+# kernel launches of a cvDetectFeatures call (kernels.h kSiftLaunches*), and its synchronisations,
+# copies and memsets (kSiftSyncs, kSiftCopies, kSiftMemsets)
+SIFT_LAUNCHES = {"fixed": 10, "per_blur": 2, "extrema": 1, "downsample": 1, "select": 1}
+SIFT_SYNCS, SIFT_COPIES, SIFT_MEMSETS = 4, 7, 1
+
+
+def sift_octaves(width: int, height: int) -> int:
+    """nOctaves of a width x height image: round(log2(min(2 w, 2 h)) - 2), at least 0."""
+    import math
+    return max(int(round(math.log2(2 * min(width, height)) - 2.0)), 0)
+
+
+def sift_launches(width: int, height: int, octave_layers: int = 3, feature_count: int = 0) -> int:
+    """Kernel launches of one cvDetectFeatures call on a width x height image (0 without an octave)."""
+    n, L = sift_octaves(width, height), SIFT_LAUNCHES
+    if n == 0:
+        return 0
+    return (L["fixed"] + n * (L["per_blur"] * (octave_layers + 2) + L["extrema"]) + (n - 1) * L["downsample"]
+            + (L["select"] if feature_count > 0 else 0))
+
+
 SIN_MIN_ANGLE = float.fromhex("0x1.1de58c9f7dc27p-5")   # hyp_rays.h kSinMinAngle
 E_SLOTS = 10
 NORM_AUTO = 0       # by element type: uint8 -> Hamming, float32 -> L2 (cvMatchFeatures' rule)
@@ -278,6 +319,8 @@ SIGNATURES = {
     "mcvTestScaledBatchStats": (_I, [_P]),
     "mcvHostBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
     "mcvTestTracksStats": (_I, [_P]),
+    "mcvHostDetectFeatures": (_P, [_P, _I, _I, _I, _I, _P]),
+    "mcvTestSiftStats": (_I, [_P]),
     "mcvHostBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcvHostBaLinearize": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),

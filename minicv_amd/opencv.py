@@ -695,3 +695,66 @@ def matchAndFindModelBatch(images, pairs, model: int = N.MODEL_HOMOGRAPHY, ratio
     N.check(ret >= 0, "cvMatchAndFindModelBatch")
     return [(int(counts[p]), models[p].reshape(3, 3).copy(), out[offsets[p]:offsets[p + 1]].copy(),
              mask[offsets[p]:offsets[p + 1]] != 0) for p in range(B)]
+
+
+# ---- feature detection: SIFT on the GPU (cvDetectFeatures mode 4) ---------------------
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
+                           ("octave", "<i4"), ("class_id", "<i4")])   # KeyPoint2d, 28 bytes
+
+
+class DetectedFeatures(Features):
+    """What cvDetectFeatures returned, copied out of the native result: a Features (so it goes straight
+    into matchFeatures(..., norm=N.NORM_L2), matchFeaturesBatch and matchAndFindModel) that also carries
+    keypoints (KEYPOINT_DTYPE [n]), points float32 [n][2], size, angle, response, octave and descriptors
+    (uint8 or float32 [n][128])."""
+
+    def __init__(self, keypoints, descriptors):
+        kp = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE).reshape(-1)
+        n = len(kp)
+        d = np.ascontiguousarray(descriptors)
+        if d.dtype not in (np.uint8, np.float32):
+            raise ValueError("descriptors must be uint8 or float32")
+        d = d.reshape(n, -1) if n else d.reshape(0, 128)
+        self._kp = (N.KeyPoint2d * max(n, 1))()
+        if n:
+            N.C.memmove(self._kp, kp.ctypes.data, n * KEYPOINT_DTYPE.itemsize)
+        self._d = d
+        self.struct = N.DetectorResult(n, int(d.size), 0 if d.dtype == np.uint8 else 5,
+                                       N.C.cast(self._kp, N.C.c_void_p), d.ctypes.data)
+        self.keypoints = kp
+        self.points = np.stack([kp["x"], kp["y"]], axis=1)
+        self.size, self.angle, self.response, self.octave = kp["size"], kp["angle"], kp["response"], kp["octave"]
+        self.descriptors = d
+
+    def __len__(self):
+        return len(self.keypoints)
+
+
+def _detect_features(export: str, img, mode: int, config) -> DetectedFeatures:
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError("img must be a uint8 array [h][w] or [h][w][c]")
+    h, w = a.shape[:2]
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    L = N.lib()
+    p = getattr(L, export)(a.ctypes.data, w, h, ch, int(mode), N.C.addressof(config) if config is not None else None)
+    N.check(bool(p), export)
+    try:
+        r = N.C.cast(p, N.C.POINTER(N.DetectorResult)).contents
+        n, f32 = r.PointCount, r.DescriptorElementType == 5
+        kp = np.zeros(n, dtype=KEYPOINT_DTYPE)
+        d = np.zeros((n, 128), dtype=np.float32 if f32 else np.uint8)
+        if n:
+            N.C.memmove(kp.ctypes.data, r.Points, kp.nbytes)
+            N.C.memmove(d.ctypes.data, r.Descriptors, d.nbytes)
+        assert r.DescriptorEntries == 128 * n
+    finally:
+        L.cvFreeFeatures(p)
+    return DetectedFeatures(kp, d)
+
+
+def detectFeatures(img, mode: int = N.FEATURE_SIFT, config: "N.SiftConfig | None" = None) -> DetectedFeatures:
+    """cvDetectFeatures on a uint8 image [h][w] (grey) or [h][w][c] (c = 3, 4: RGB(A)). Only
+    mode=N.FEATURE_SIFT is built; config: a N.SiftConfig, or None for cv::SIFT's defaults with byte
+    descriptors. Raises N.NativeError where the library returns NULL."""
+    return _detect_features("cvDetectFeatures", img, mode, config)
