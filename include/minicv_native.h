@@ -1147,6 +1147,14 @@ MCV_API DetectorResult* mcvHostDetectFeatures(char* data, int width, int height,
  * keypoints with orientations (before duplicates and FeatureCount), keypoints returned}. The
  * descriptor kernel has one path for every radius, so there is no short / long count. Returns 0. */
 MCV_API int mcvTestSiftStats(long long* stats8);
+/* A stage of the calling thread's last finished cvDetectFeatures call, read from that thread's
+ * workspace on the current device. what 0: the Gaussian pyramid, floats, octave by octave, image by
+ * image (OctaveLayers + 3 per octave), row-major; *count = the floats. what 1: the extremum
+ * candidates, int[4] records (octave, layer, row, column) in arrival order, which differs from run to
+ * run; *count = the records. One device-to-host copy, no launch; mcvTestSiftStats reads the same after
+ * it. Returns 0, or -1 with an error for an unknown `what`, a null argument, a capBytes below the
+ * stage's size, or a thread without a finished call on the current device. */
+MCV_API int mcvTestSiftStage(int what, void* out, long long capBytes, long long* count);
 /* Host twin of cvBundleAdjust: the same arguments, checks, outputs, summary and return value, computed
  * sequentially by the host-compiled kernel arithmetic (ba_terms.h) in the kernels' summation orders. No GPU. */
 MCV_API int mcvHostBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,

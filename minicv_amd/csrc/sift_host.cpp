@@ -23,6 +23,17 @@ struct SiftStats : CallStats {
 };
 thread_local SiftStats t_st;
 
+// What mcvTestSiftStage reads of the calling thread's last finished call: the device whose workspace
+// holds the stages, and their sizes. Like the statistics it is reset once the arguments have passed
+// their checks, so a call that fails on the device leaves none.
+struct SiftStage {
+    bool done = false;
+    int dev = -1;
+    size_t pyramidFloats = 0;
+    long long candidates = 0;
+};
+thread_local SiftStage t_stage;
+
 struct SiftWork : DeviceWs {
     DevBuf<uint8_t> img, flagA, flagB, descU8;
     DevBuf<float> up, tmp, pyr, taps, descF32;
@@ -62,8 +73,14 @@ extern "C" MCV_API DetectorResult* cvDetectFeatures(char* data, int width, int h
         require_device();
         SiftStats& st = t_st;
         st = SiftStats();
-        if (S.nOctaves == 0) return make_result(0, S.descType);
-        SiftWork& w = thread_device_ws<SiftWork>();
+        SiftStage& stage = t_stage;
+        stage = SiftStage();
+        MCV_HIP(hipGetDevice(&stage.dev));
+        if (S.nOctaves == 0) {
+            stage.done = true;
+            return make_result(0, S.descType);
+        }
+        SiftWork& w = thread_device_ws_on<SiftWork>(stage.dev);
         hipStream_t s = w.stream();
         const int nl = S.P.nl, W0 = S.ow[0], H0 = S.oh[0];
         const size_t imgBytes = (size_t)width * (size_t)height * (size_t)channels;
@@ -209,6 +226,9 @@ extern "C" MCV_API DetectorResult* cvDetectFeatures(char* data, int width, int h
             cvFreeFeatures(res);
             throw;
         }
+        stage.pyramidFloats = S.pyramidFloats;
+        stage.candidates = st.candidates;
+        stage.done = true;
         return res;
     })
 }
@@ -244,6 +264,35 @@ extern "C" MCV_API DetectorResult* mcvHostDetectFeatures(char* data, int width, 
             }
         }
         return res;
+    })
+}
+
+// A stage of the calling thread's last finished cvDetectFeatures call on the current device, read from
+// the workspace: one copy, no launch, and the call's statistics stay as they are.
+extern "C" MCV_API int mcvTestSiftStage(int what, void* out, long long capBytes, long long* count) {
+    MCV_GUARD(-1, {
+        const char* name = "mcvTestSiftStage";
+        if (what != 0 && what != 1) fail("%s: unknown stage %d (0: Gaussian pyramid, 1: candidates)", name, what);
+        if (!out || !count) fail("%s: null argument", name);
+        if (capBytes < 0) fail("%s: capBytes %lld is too small", name, capBytes);
+        const SiftStage& stage = t_stage;
+        if (!stage.done) fail("%s: the calling thread has no finished cvDetectFeatures call", name);
+        int dev = -1;
+        MCV_HIP(hipGetDevice(&dev));
+        if (dev != stage.dev)
+            fail("%s: the calling thread's last cvDetectFeatures call ran on device %d, not on the current device %d",
+                 name, stage.dev, dev);
+        const long long n = what == 0 ? (long long)stage.pyramidFloats : stage.candidates;
+        const long long bytes = n * (what == 0 ? (long long)sizeof(float) : (long long)(4 * sizeof(int)));
+        if (capBytes < bytes) fail("%s: capBytes %lld is too small: stage %d holds %lld bytes", name, capBytes, what, bytes);
+        if (bytes) {
+            SiftWork& w = thread_device_ws_on<SiftWork>(dev);
+            const void* src = what == 0 ? (const void*)w.pyr.p : (const void*)w.cand.p;
+            MCV_HIP(hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, w.stream()));
+            MCV_HIP(hipStreamSynchronize(w.stream()));
+        }
+        *count = n;
+        return 0;
     })
 }
 

@@ -321,6 +321,7 @@ SIGNATURES = {
     "mcvTestTracksStats": (_I, [_P]),
     "mcvHostDetectFeatures": (_P, [_P, _I, _I, _I, _I, _P]),
     "mcvTestSiftStats": (_I, [_P]),
+    "mcvTestSiftStage": (_I, [_I, _P, C.c_longlong, _P]),
     "mcvHostBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcvHostBaLinearize": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),

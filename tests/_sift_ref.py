@@ -4,7 +4,8 @@ tests/test_gpu_sift.py.
 Written from the specification, not from the host twin: numpy float32 array and scalar operations are
 single IEEE operations, in the order §7n fixes; exp and atan2 are Python's math.exp / math.atan2 (glibc),
 evaluated in double and rounded once; both histograms are sums of integers, so their order is free.
-detect() returns (keypoints KEYPOINT_DTYPE [n], descriptors [n][128], counts) and is cached per case.
+detect() returns (keypoints KEYPOINT_DTYPE [n], descriptors [n][128], counts); expected(name) is that and
+stages(name) the Gaussian pyramid and the candidates of a case, computed once per case.
 """
 from __future__ import annotations
 
@@ -57,6 +58,12 @@ def noise(w, h, seed):
     return np.ascontiguousarray(np.kron(b, np.ones((2, 2), np.uint8))[:h, :w])
 
 
+def tiled_image():
+    """A 16 x 16 pattern of 0 / 255 in 2 x 2 blocks, repeated 4 x 5 times: 128 x 160."""
+    z = ((np.random.default_rng(3).random((16, 16)) < 0.5) * 255).astype(np.uint8)
+    return np.ascontiguousarray(np.tile(np.kron(z, np.ones((2, 2), np.uint8)), (4, 5)))
+
+
 def grey(img):
     """The specification's grey conversion of an [h][w][3 or 4] image."""
     a = img.astype(np.int64)
@@ -66,6 +73,9 @@ def grey(img):
 def _smooth_rgb(w, h, seed, ch):
     return np.stack([texture(w, h, seed + c) for c in range(ch)], axis=2)
 
+
+SEAM_CASES = ("seam_257x33", "seam_129x65", "seam_128x32", "tall_9x300")
+TILED_FC = (1, 256, 257, 513, 809)   # cuts inside the first select tile, at and past tile ends, one short of all
 
 # name -> (image factory, config overrides)
 CASES = {
@@ -82,6 +92,28 @@ CASES = {
     "feature_count_10": (lambda: texture(97, 61, 11), dict(FeatureCount=10)),
     "rgb": (lambda: _smooth_rgb(64, 48, 21, 3), {}),
     "rgba": (lambda: _smooth_rgb(64, 48, 21, 4), {}),
+    # configuration edges: the largest blur (radii 28, 56, 111), the s0 <= 0.01 base blur, every layer count,
+    # the thresholds
+    "sigma_max_layers_1": (lambda: blob_image(200, 160, [(100.3, 80.6, 20.0, 150), (40, 40, 9.0, 120),
+                                                         (150, 40, 12.0, 150)]), dict(Sigma=4.0, OctaveLayers=1)),
+    "sigma_1_0": (lambda: texture(72, 40, 7), dict(Sigma=1.0)),
+    "sigma_0_8": (lambda: texture(72, 40, 7), dict(Sigma=0.8)),
+    "layers_1": (lambda: texture(97, 61, 11), dict(OctaveLayers=1)),
+    "layers_6": (lambda: texture(97, 61, 11), dict(OctaveLayers=6)),
+    "contrast_0": (lambda: texture(97, 61, 11), dict(ContrastThreshold=0.0)),
+    "edge_2": (lambda: texture(97, 61, 11), dict(EdgeThreshold=2.0)),
+    "edge_1e6": (lambda: texture(97, 61, 11), dict(EdgeThreshold=1e6)),
+    # tile seams: octaves one tile wide or high, and one tile plus one (row tile 256, column tile 64 x 32,
+    # extrema tile 64 x 4)
+    "seam_257x33": (lambda: texture(257, 33, 4, k=3), {}),
+    "seam_129x65": (lambda: texture(129, 65, 4, k=3), {}),
+    "seam_128x32": (lambda: texture(128, 32, 4, k=3), {}),
+    "tall_9x300": (lambda: texture(9, 300, 4, k=3), {}),
+    # a blob whose descriptor radius reaches the octave's diagonal
+    "clamped_radius": (lambda: blob_image(48, 48, [(24.2, 23.7, 7.0, 150)]), {}),
+    # one 32 x 32 pattern 4 x 5 times: equal responses at different positions, more than three select tiles
+    "tiled": (lambda: tiled_image(), {}),
+    **{f"tiled_fc_{n}": (lambda: tiled_image(), dict(FeatureCount=n)) for n in TILED_FC},
 }
 
 
@@ -97,8 +129,24 @@ def config(name):
 
 
 @functools.lru_cache(maxsize=None)
+def _full(name):
+    return detect_full(image(name), **config(name))
+
+
 def expected(name):
-    return detect(image(name), **config(name))
+    """-> (keypoints, descriptors, counts) of the case."""
+    return _full(name)[:3]
+
+
+def stages(name):
+    """-> (Gaussian pyramid: [octave] of [nl + 3][h][w], candidates: [(o, layer, r, c)] in scan order)."""
+    return _full(name)[3:]
+
+
+def octave_sizes(name):
+    """-> [(w, h)] of the case's octaves."""
+    h, w = image(name).shape[:2]
+    return [((2 * w) >> o, (2 * h) >> o) for o in range(n_octaves(w, h))]
 
 
 # ---- the specification ----------------------------------------------------------------------------
@@ -146,11 +194,12 @@ def doubled(g):
     return up
 
 
-def pyramid(g, nl, sigma):
-    h, w = g.shape
-    n_oct = max(int(round(math.log2(2 * min(w, h)) - 2.0)), 0)
-    if n_oct == 0:
-        return []
+def n_octaves(w, h):
+    return max(int(round(math.log2(2 * min(w, h)) - 2.0)), 0)
+
+
+def sigmas(nl, sigma):
+    """-> the nl + 3 blur sigmas: the base blur, then the increment of Gaussian image i from i - 1."""
     s0 = sigma * sigma - 1.0
     sig = [math.sqrt(s0 if s0 > 0.01 else 0.01)]
     k = math.pow(2.0, 1.0 / nl)
@@ -158,6 +207,15 @@ def pyramid(g, nl, sigma):
         prev = math.pow(k, float(i - 1)) * sigma
         total = prev * k
         sig.append(math.sqrt(total * total - prev * prev))
+    return sig
+
+
+def pyramid(g, nl, sigma):
+    h, w = g.shape
+    n_oct = n_octaves(w, h)
+    if n_oct == 0:
+        return []
+    sig = sigmas(nl, sigma)
     octaves = []
     base = blur(doubled(g), sig[0])
     for o in range(n_oct):
@@ -330,6 +388,25 @@ def sincos_deg(deg):
     return F(cd), F(sd)
 
 
+def descriptor_radius(scl):
+    """The descriptor window's radius before the clamp to the octave's diagonal."""
+    return rint32((((F(3.0) * F(scl)) * F(1.4142135623730951)) * F(5.0)) * F(0.5))
+
+
+def diagonal(w, h):
+    return int(math.sqrt(float(w) * w + float(h) * h))
+
+
+def keypoint_octave(k):
+    """The octave index (0 = the doubled image) of a returned keypoint."""
+    return ((int(k["octave"]) & 255) + 1) & 255
+
+
+def keypoint_scale(k):
+    """scl of a returned keypoint: size is scl x 2^octave, a power of two, so the quotient is exact."""
+    return F(k["size"]) / F(1 << keypoint_octave(k))
+
+
 def descriptor(img, r, c, angle, scl):
     """-> float32 [128], scaled to 512, unrounded."""
     h, w = img.shape
@@ -338,8 +415,7 @@ def descriptor(img, r, c, angle, scl):
         ori = F(0.0)
     ct, st = sincos_deg(ori)
     hw = F(3.0) * scl
-    radius = rint32(((hw * F(1.4142135623730951)) * F(5.0)) * F(0.5))
-    radius = min(radius, int(math.sqrt(float(w) * w + float(h) * h)))
+    radius = min(descriptor_radius(scl), diagonal(w, h))
     ct, st = ct / hw, st / hw
     ori_rad = float(ori) * 0.017453292519943295
     i, j = np.mgrid[-radius:radius + 1, -radius:radius + 1]
@@ -389,8 +465,32 @@ def to_bytes(d):
     return np.clip(np.rint(d), 0, 255).astype(np.uint8)
 
 
-def detect(img, FeatureCount=0, OctaveLayers=3, ContrastThreshold=0.04, EdgeThreshold=10.0, Sigma=1.6,
-           DescriptorType=0):
+def candidates(octaves, nl, thr):
+    """The extremum candidates of a Gaussian pyramid -> [(o, layer, r, c)], octave by octave, layer by
+    layer, in raster order."""
+    out = []
+    for o, G in enumerate(octaves):
+        D = G[1:] - G[:-1]
+        h, w = D.shape[1:]
+        if h <= 2 * BORDER or w <= 2 * BORDER:
+            continue
+        for layer in range(1, nl + 1):
+            v = D[layer, BORDER:h - BORDER, BORDER:w - BORDER]
+            nb = np.stack([D[layer + dl, BORDER + dr:h - BORDER + dr, BORDER + dc:w - BORDER + dc]
+                           for dl in (-1, 0, 1) for dr in (-1, 0, 1) for dc in (-1, 0, 1)])
+            is_c = (np.abs(v) > thr) & (((v > 0) & (v >= nb.max(axis=0))) | ((v < 0) & (v <= nb.min(axis=0))))
+            out.extend((o, layer, int(r0), int(c0)) for r0, c0 in np.argwhere(is_c) + BORDER)
+    return out
+
+
+def detect(img, **cfg):
+    """-> (keypoints, descriptors, counts)."""
+    return detect_full(img, **cfg)[:3]
+
+
+def detect_full(img, FeatureCount=0, OctaveLayers=3, ContrastThreshold=0.04, EdgeThreshold=10.0, Sigma=1.6,
+                DescriptorType=0):
+    """detect() and its stages -> (keypoints, descriptors, counts, Gaussian pyramid, candidates)."""
     g = grey(img) if img.ndim == 3 else img
     nl = OctaveLayers
     thr = F(int(math.floor(0.5 * ContrastThreshold / nl * 255.0)))
@@ -398,29 +498,21 @@ def detect(img, FeatureCount=0, OctaveLayers=3, ContrastThreshold=0.04, EdgeThre
     items = {}   # (o, layer, r, c, bin) -> (start key, fields)
     with np.errstate(all="ignore"):
         octaves = pyramid(g, nl, Sigma)
-        for o, G in enumerate(octaves):
-            D = G[1:] - G[:-1]
-            h, w = D.shape[1:]
-            if h <= 2 * BORDER or w <= 2 * BORDER:
+        cands = candidates(octaves, nl, thr)
+        dogs = [G[1:] - G[:-1] for G in octaves]
+        for o, layer, r0, c0 in cands:
+            counts["candidates"] += 1
+            k = refine(dogs[o], nl, layer, r0, c0, Sigma, ContrastThreshold, EdgeThreshold, o)
+            if k is None:
                 continue
-            for layer in range(1, nl + 1):
-                v = D[layer, BORDER:h - BORDER, BORDER:w - BORDER]
-                nb = np.stack([D[layer + dl, BORDER + dr:h - BORDER + dr, BORDER + dc:w - BORDER + dc]
-                               for dl in (-1, 0, 1) for dr in (-1, 0, 1) for dc in (-1, 0, 1)])
-                is_c = (np.abs(v) > thr) & (((v > 0) & (v >= nb.max(axis=0))) | ((v < 0) & (v <= nb.min(axis=0))))
-                for r0, c0 in np.argwhere(is_c) + BORDER:
-                    counts["candidates"] += 1
-                    k = refine(D, nl, layer, int(r0), int(c0), Sigma, ContrastThreshold, EdgeThreshold, o)
-                    if k is None:
-                        continue
-                    counts["refined"] += 1
-                    ly, r, c, xc, xr, xi, resp, scl, size, code = k
-                    sc = F(1 << o) * F(0.5)
-                    for b, ang in orientations(G[ly], r, c, scl):
-                        counts["oriented"] += 1
-                        key, start = (o, ly, r, c, b), (o, layer, int(r0), int(c0), b)
-                        if key not in items or start < items[key][0]:
-                            items[key] = (start, ((F(c) + xc) * sc, (F(r) + xr) * sc, size, ang, resp, code, scl))
+            counts["refined"] += 1
+            ly, r, c, xc, xr, xi, resp, scl, size, code = k
+            sc = F(1 << o) * F(0.5)
+            for b, ang in orientations(octaves[o][ly], r, c, scl):
+                counts["oriented"] += 1
+                key, start = (o, ly, r, c, b), (o, layer, r0, c0, b)
+                if key not in items or start < items[key][0]:
+                    items[key] = (start, ((F(c) + xc) * sc, (F(r) + xr) * sc, size, ang, resp, code, scl))
         keys = sorted(items)
         if FeatureCount > 0 and len(keys) > FeatureCount:
             by_resp = sorted(range(len(keys)), key=lambda n: (-float(items[keys[n]][1][4]), n))
@@ -431,7 +523,7 @@ def detect(img, FeatureCount=0, OctaveLayers=3, ContrastThreshold=0.04, EdgeThre
             x, y, size, ang, resp, code, scl = items[key][1]
             kp[n] = (x, y, size, ang, resp, code, -1)
             desc[n] = descriptor(octaves[key[0]][key[1]], key[2], key[3], ang, scl)
-    return kp, (desc if DescriptorType == 5 else to_bytes(desc)), counts
+    return kp, (desc if DescriptorType == 5 else to_bytes(desc)), counts, octaves, cands
 
 
 # ---- calling the library ----------------------------------------------------------------------------

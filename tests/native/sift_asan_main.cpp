@@ -1,8 +1,9 @@
 // sift_asan_main.cpp — sift_ref.h (the host twin of cvDetectFeatures) as a stand-alone program for
 // AddressSanitizer + UBSan (tests/test_sift.py builds and runs it; nothing is loaded into Python).
-// Input: one line per grey image, "w h" and the w h bytes; default configuration. Output per image:
-// the keypoint count, then per keypoint the 7 KeyPoint2d words (as unsigned integers) and the 128
-// descriptor bytes; a final "sift_asan ok" line.
+// Input: one line per grey image, "w h", the six SiftConfig fields in their order (FeatureCount,
+// OctaveLayers, ContrastThreshold, EdgeThreshold, Sigma, DescriptorType) and the w h bytes. Output per
+// image: the keypoint count, then per keypoint the 7 KeyPoint2d words (as unsigned integers) and the
+// 128 descriptor bytes; a final "sift_asan ok" line.
 #include "sift_ref.h"
 
 #include <cstring>
@@ -19,7 +20,10 @@ int main(int argc, char** argv) {
         if (line.empty()) continue;
         std::istringstream ls(line);
         int w = 0, h = 0;
-        ls >> w >> h;
+        mcv::SiftConfigIn cfg = {};
+        ls >> w >> h >> cfg.FeatureCount >> cfg.OctaveLayers >> cfg.ContrastThreshold >> cfg.EdgeThreshold >>
+            cfg.Sigma >> cfg.DescriptorType;
+        if (!ls || w <= 0 || h <= 0) return 3;
         std::vector<uint8_t> img((size_t)w * (size_t)h);
         for (auto& b : img) {
             int v = 0;
@@ -29,7 +33,7 @@ int main(int argc, char** argv) {
         if (!ls) return 3;
         mcv::SiftPlan S;
         std::string err;
-        if (!mcv::sift_plan("sift_asan", img.data(), w, h, 1, 4, nullptr, S, err)) {
+        if (!mcv::sift_plan("sift_asan", img.data(), w, h, 1, 4, &cfg, S, err)) {
             std::cerr << err << "\n";
             return 4;
         }

@@ -1,7 +1,9 @@
 """SIFT detection on the CPU: the host twin (mcvHostDetectFeatures, sift_ref.h) against the
-independent numpy reference on the shared case list, every output bit equal; the blob image's
-detections; every refusal of cvDetectFeatures and of the twin; the declarations; and sift_ref.h under
-AddressSanitizer + UBSan in a stand-alone program. No kernel is launched."""
+independent numpy reference on the shared case list, every output bit equal; that each case still reaches
+the branch it is there for; the blob image's detections; every refusal of cvDetectFeatures, of the twin
+and of mcvTestSiftStage; the declarations; and sift_ref.h under AddressSanitizer + UBSan in a stand-alone
+program. No kernel is launched."""
+import ctypes as C
 import shutil
 import subprocess
 
@@ -30,6 +32,75 @@ def test_cases_cover_what_they_are_for():
     # the s = 20 blob is found, with a descriptor radius far above the others'
     big = [d for d in R.detections(R.expected("big_blob")[0]) if abs(d[0] - 100.3) < 0.5 and abs(d[1] - 80.6) < 0.5]
     assert len(big) == 1 and big[0][2] > 30.0
+    # the largest blur: radii up to kSiftMaxRadius, and keypoints in more than one octave
+    cfg = R.config("sigma_max_layers_1")
+    assert R.blur_taps(R.sigmas(cfg["OctaveLayers"], cfg["Sigma"])[3])[1] == 111
+    assert len({R.keypoint_octave(k) for k in R.expected("sigma_max_layers_1")[0]}) >= 2
+    # Sigma^2 - 1 <= 0.01: the base blur has three taps
+    for name in ("sigma_1_0", "sigma_0_8"):
+        cfg = R.config(name)
+        assert R.blur_taps(R.sigmas(cfg["OctaveLayers"], cfg["Sigma"])[0])[1] == 1 and n[name] > 20, name
+    assert n["layers_1"] > 50 and n["layers_6"] > 50
+    assert n["edge_2"] < n["texture_97x61"] <= n["edge_1e6"]
+    assert R.expected("contrast_0")[2]["candidates"] >= R.expected("texture_97x61")[2]["candidates"]
+    # the seams of the row tile (256), the column tile (64 x 32) and the extrema tile (64 x 4): an octave
+    # of exactly one tile and one of a tile plus one, along each axis
+    sizes = [s for name in R.SEAM_CASES for s in R.octave_sizes(name)]
+    for what, hit in (("w % 256 == 1", [w % 256 == 1 for w, h in sizes]), ("w % 64 == 1", [w % 64 == 1 for w, h in sizes]),
+                      ("h % 32 == 1", [h % 32 == 1 for w, h in sizes]), ("h % 4 == 1", [h % 4 == 1 for w, h in sizes]),
+                      ("w == 256", [w == 256 for w, h in sizes]), ("w == 64", [w == 64 for w, h in sizes]),
+                      ("h == 32", [h == 32 for w, h in sizes])):
+        assert any(hit), (what, sizes)
+    assert all(n[name] > (30 if name == "tall_9x300" else 100) for name in R.SEAM_CASES), n
+    # every descriptor window of the small blob image is cut to its octave's diagonal
+    kp, sizes = R.expected("clamped_radius")[0], R.octave_sizes("clamped_radius")
+    assert len(kp) > 0
+    for k in kp:
+        assert R.descriptor_radius(R.keypoint_scale(k)) >= R.diagonal(*sizes[R.keypoint_octave(k)]), k
+    # FeatureCount on ties: four select tiles of 256 records, responses shared across positions, and every
+    # cut between two records of equal response
+    kp = R.expected("tiled")[0]
+    assert n["tiled"] > 768
+    where = {}
+    for k in kp:
+        where.setdefault(float(k["response"]), set()).add((float(k["x"]), float(k["y"])))
+    assert sum(len(p) > 1 for p in where.values()) >= 20
+    order = np.argsort(-kp["response"], kind="stable")
+    for fc in R.TILED_FC:
+        assert n[f"tiled_fc_{fc}"] == fc < n["tiled"]
+        assert kp["response"][order[fc - 1]] == kp["response"][order[fc]], fc
+
+
+def test_stage_export_refusals(native):
+    """mcvTestSiftStage refuses an unknown stage, a null argument, a capacity that cannot hold anything and a
+    thread that has made no call; no device is needed for any of them."""
+    import threading
+    L = native.lib()
+    txt = (N.ROOT / "include" / "minicv_native.h").read_text()
+    assert "MCV_API int mcvTestSiftStage(int what, void* out, long long capBytes, long long* count);" in txt
+    assert "mcvTestSiftStage" in N.SIGNATURES
+    buf, cnt = np.zeros(16, np.float32), C.c_longlong(-7)
+    for what in (-1, 2, 99):
+        assert L.mcvTestSiftStage(what, buf.ctypes.data, buf.nbytes, C.byref(cnt)) == -1
+        assert "unknown stage" in N.last_error()
+    for what in (0, 1):
+        assert L.mcvTestSiftStage(what, None, buf.nbytes, C.byref(cnt)) == -1 and "null argument" in N.last_error()
+        assert L.mcvTestSiftStage(what, buf.ctypes.data, buf.nbytes, None) == -1 and "null argument" in N.last_error()
+        assert L.mcvTestSiftStage(what, buf.ctypes.data, -1, C.byref(cnt)) == -1 and "too small" in N.last_error()
+    got = []
+
+    def fresh_thread():
+        b, c = np.zeros(16, np.float32), C.c_longlong(-7)
+        got.append([(L.mcvTestSiftStage(what, b.ctypes.data, b.nbytes, C.byref(c)), N.last_error(), c.value)
+                    for what in (0, 1)])
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join(60)
+    assert not t.is_alive() and len(got) == 1
+    for rc, err, c in got[0]:
+        assert rc == -1 and "no finished cvDetectFeatures call" in err and c == -7
+    assert cnt.value == -7 and not buf.any()
 
 
 def test_blobs(native):
@@ -148,7 +219,9 @@ def test_result_is_a_features(native):
 def test_host_twin_under_sanitizers(tmp_path):
     """tests/native/sift_asan_main.cpp: a stand-alone program (its own main, nothing preloaded, nothing
     loaded into Python) over sift_ref.h, built with -fsanitize=address,undefined and run on the 97 x 61
-    and 24 x 9 cases; its keypoints and descriptor bytes equal the reference's."""
+    and 24 x 9 cases, the radius-111 blurs, their reflections over the 18- and 9-wide octaves of the tall
+    image, the clamped descriptor window and six layers, each with its own configuration; its keypoints
+    and descriptor bytes equal the reference's."""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
     exe, inp = tmp_path / "sift_asan", tmp_path / "cases.txt"
@@ -156,11 +229,12 @@ def test_host_twin_under_sanitizers(tmp_path):
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", f"-I{N.ROOT / 'minicv_amd' / 'csrc'}", str(src), "-o", str(exe)],
                    check=True, capture_output=True, text=True)
-    names = ["texture_97x61", "narrow_24x9"]
+    names = ["texture_97x61", "narrow_24x9", "sigma_max_layers_1", "clamped_radius", "tall_9x300", "layers_6"]
     with open(inp, "w") as f:
         for name in names:
-            img = R.image(name)
-            f.write(" ".join(map(str, [img.shape[1], img.shape[0], *img.reshape(-1).tolist()])) + "\n")
+            img, cfg = R.image(name), R.config(name)
+            f.write(" ".join(map(repr, [img.shape[1], img.shape[0], *(cfg[k] for k, _ in N.SiftConfig._fields_),
+                                        *img.reshape(-1).tolist()])) + "\n")
     r = subprocess.run([str(exe), str(inp)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.strip().split("\n")
