@@ -20,9 +20,6 @@
 
 namespace mcv {
 
-static const int kBaGrid = 2048;       // blocks of the grid-stride kernels
-static const int kBaLongBlocks = 1024; // blocks (4 waves each) striding over the long-track queue
-
 // ---- the reductions ----
 
 // Wave per long track: lane's chain, then the fold. Every lane of the wave must call it; lane 0

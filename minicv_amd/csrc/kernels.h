@@ -589,6 +589,7 @@ void launch_scaled_batch_best(const ScaledBatchProb* d_probs, int P, const doubl
 
 // ---- Ray.intersection over many tracks (triangulate.hip)
 static const int kTriShortMax = 16;   // tracks of at most this many rays: one lane each; longer: one workgroup each
+static const int kTriGrid = 2048;     // blocks of the grid-stride kernels whose length lives on the device
 // d_ctr: kTriCtrs counters, zeroed by the caller before the launches below.
 //   [0] long tracks queued, [1] tracks with a point, [2] first bad track + 1 (validation), [3] its kind,
 //   [4] first bad observation + 1
@@ -608,11 +609,13 @@ void launch_tri_stats(const double* d_cameras, const int* d_cameraIdx, const dou
 
 // ---- track building: pairwise matches -> track CSR (tracks.hip)
 static const int kTrkShortMax = 32;   // components of at most this many nodes: one lane each; longer: one workgroup each
+static const int kTrkGrid = 2048;     // blocks of the grid-stride kernels
 // d_ctr: kTrkCtrs 64-bit words, zeroed by the caller before launch_build_tracks.
 //   [0] oversize, [1] conflicts, [2] short, [3] fail word (a bounded loop gave up),
 //   [4] candidates << 32 | their nodes, [5] tracks << 32 | observations, [6] long candidates queued
 static const int kTrkCtrs = 8;
 static const int kTrkScanItems = 2048;   // nodes per block of the two scans
+static const int kTrkScanChunk = 1024;   // block sums per trip (and threads) of the one-block scan over them: it carries between trips
 struct TrkDevice {
     const int* edges;        // 2 nEdges node ids
     long long nEdges;
@@ -639,6 +642,8 @@ static const int kTrkLaunches = 13;
 void launch_build_tracks(const TrkDevice& D, hipStream_t s);
 
 // ---- bundle adjustment (bundle_adjust.hip)
+static const int kBaGrid = 2048;         // blocks of the grid-stride kernels
+static const int kBaLongBlocks = 1024;   // blocks (4 waves each) striding over the long-track queue
 // The record of one PCG solve, on the device: read back once per chunk of kBaCgChunk iterations.
 struct BaCgState {
     double rz, rz0;

@@ -31,7 +31,6 @@ namespace mcv {
 
 typedef unsigned long long u64;
 
-static const int kTrkGrid = 2048;   // blocks of the grid-stride kernels
 static_assert(MCV_MAX_TRACK_LEN == 4096, "mcv_trk_long sorts one component in 16 KiB of LDS");
 static_assert(kTrkScanItems == 256 * 8, "eight nodes per thread of the scan blocks");
 
@@ -217,18 +216,19 @@ __global__ __launch_bounds__(256) void mcv_trk_sums(TrkScan a, u64* __restrict__
     if (threadIdx.x == 0) blockSums[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
 }
 
-// Exclusive scan of nb block sums in one block, in place (chunks of 1024, fixed order); *total = the sum.
-__global__ __launch_bounds__(1024) void mcv_trk_scan(u64* __restrict__ sums, int nb, u64* __restrict__ total) {
-    __shared__ u64 sh[1024];
+// Exclusive scan of nb block sums in one block, in place (chunks of kTrkScanChunk, fixed order); *total = the sum.
+__global__ __launch_bounds__(kTrkScanChunk) void mcv_trk_scan(u64* __restrict__ sums, int nb,
+                                                               u64* __restrict__ total) {
+    __shared__ u64 sh[kTrkScanChunk];
     __shared__ u64 carry;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
+    for (int b0 = 0; b0 < nb; b0 += kTrkScanChunk) {
         const int i = b0 + threadIdx.x;
         const u64 v = i < nb ? sums[i] : 0;
         sh[threadIdx.x] = v;
         __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
+        for (int o = 1; o < kTrkScanChunk; o <<= 1) {
             const u64 t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
             __syncthreads();
             sh[threadIdx.x] += t;
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(1024) void mcv_trk_scan(u64* __restrict__ sums, int
         }
         if (i < nb) sums[i] = carry + sh[threadIdx.x] - v;
         __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
+        if (threadIdx.x == kTrkScanChunk - 1) carry += sh[kTrkScanChunk - 1];
         __syncthreads();
     }
     if (threadIdx.x == 0) *total = carry;
@@ -429,7 +429,7 @@ void launch_build_tracks(const TrkDevice& D, hipStream_t s) {
     {
         ProfScope ps("trk_layout", s);
         hipLaunchKernelGGL(mcv_trk_sums<0>, dim3(nb), dim3(256), 0, s, a, D.blockSums, D.ctr);
-        hipLaunchKernelGGL(mcv_trk_scan, dim3(1), dim3(1024), 0, s, D.blockSums, nb, D.ctr + 4);
+        hipLaunchKernelGGL(mcv_trk_scan, dim3(1), dim3(kTrkScanChunk), 0, s, D.blockSums, nb, D.ctr + 4);
         hipLaunchKernelGGL(mcv_trk_place<0>, dim3(nb), dim3(256), 0, s, a, D.blockSums);
     }
     {
@@ -452,7 +452,7 @@ void launch_build_tracks(const TrkDevice& D, hipStream_t s) {
     {
         ProfScope ps("trk_compact", s);
         hipLaunchKernelGGL(mcv_trk_sums<1>, dim3(nb), dim3(256), 0, s, a, D.blockSums, D.ctr);
-        hipLaunchKernelGGL(mcv_trk_scan, dim3(1), dim3(1024), 0, s, D.blockSums, nb, D.ctr + 5);
+        hipLaunchKernelGGL(mcv_trk_scan, dim3(1), dim3(kTrkScanChunk), 0, s, D.blockSums, nb, D.ctr + 5);
         hipLaunchKernelGGL(mcv_trk_place<1>, dim3(nb), dim3(256), 0, s, a, D.blockSums);
     }
     {

@@ -22,7 +22,6 @@
 
 namespace mcv {
 
-static const int kTriGrid = 2048;       // blocks of the grid-stride kernels whose length lives on the device
 static const int kTriLdsRays = 256;     // kept rays of a long track held in LDS (12 KiB)
 static const int kTriTile = 128;        // pairs per tile: one per thread of the two compute waves
 static const int kTriLongThreads = 192; // two compute waves + the adding wave

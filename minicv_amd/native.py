@@ -143,6 +143,14 @@ MAX_TRACK_LEN = 4096            # rays per track of the triangulation exports (M
 TRI_SHORT_MAX = 16              # longer tracks take the workgroup-per-track kernel (kernels.h kTriShortMax)
 TRK_SHORT_MAX = 32              # larger components are sorted by a workgroup each (kernels.h kTrkShortMax)
 TRK_LAUNCHES = 13               # kernel launches of a cvBuildTracks call (kernels.h kTrkLaunches)
+TRK_SCAN_ITEMS = 2048           # nodes per block of the two scans of cvBuildTracks (kernels.h kTrkScanItems)
+TRK_SCAN_CHUNK = 1024           # block sums per trip of mcv_trk_scan, which carries between trips (kernels.h kTrkScanChunk)
+# blocks of the fixed grids that stride over a length (kernels.h kTrkGrid, kTriGrid, kBaGrid, kBaLongBlocks):
+# the sizes past which a kernel takes a second trip, for the scale cases of the test suite
+TRK_GRID = 2048                 # of 256 threads: nodes, edges, slots, candidates; blocks over the long queue
+TRI_GRID = 2048                 # of 256 threads over the observations; 8 x as many blocks over the long queue
+BA_GRID = 2048                  # of 256 threads over the observations
+BA_LONG_BLOCKS = 1024           # of 4 waves, one long track per wave and trip
 BA_SEG = 1024                   # entries per segment of a camera's list in cvBundleAdjust (ba_terms.h kBaSeg)
 BA_SHORT_MAX = 64               # longer tracks take the wave-per-track kernels (ba_terms.h kBaShortMax)
 BA_CG_CHUNK = 8                 # PCG iterations between two reads of the solve's record (ba_terms.h kBaCgChunk)

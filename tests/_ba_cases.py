@@ -58,6 +58,43 @@ def cost(cams, pts, idx, obs, off, used, delta=0.0):
     return float(rho(r[used], delta).sum())
 
 
+def residuals_v(cams, pts, idx, obs, off):
+    """residuals() without the loop over the observations. The three products of a row of R with
+    (X - c) are summed left to right here and by numpy's matrix product there, so pc may differ from the
+    loop form's in the last place (a product may be fused into the sum there): test_bundle_adjust.py
+    bounds the difference on a small case."""
+    cams, pts, obs = np.asarray(cams, float).reshape(-1, 14), np.asarray(pts, float).reshape(-1, 3), np.asarray(obs, float).reshape(-1, 2)
+    idx, off = np.asarray(idx), np.asarray(off)
+    trk = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    c = cams[idx]
+    d = pts[trk] - c[:, 0:3]
+    pc = np.stack([c[:, 9] * d[:, 0] + c[:, 10] * d[:, 1] + c[:, 11] * d[:, 2],
+                   c[:, 6] * d[:, 0] + c[:, 7] * d[:, 1] + c[:, 8] * d[:, 2],
+                   c[:, 3] * d[:, 0] + c[:, 4] * d[:, 1] + c[:, 5] * d[:, 2]], axis=1)
+    with np.errstate(all="ignore"):
+        r = c[:, 12:14] * pc[:, :2] / pc[:, 2:3] - obs
+    return r, pc
+
+
+def used_set_v(cams, pts, idx, obs, off):
+    r, pc = residuals_v(cams, pts, idx, obs, off)
+    off = np.asarray(off)
+    trk = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    pts = np.asarray(pts, float).reshape(-1, 3)
+    u = np.isfinite(pts[trk]).all(axis=1) & (pc[:, 2] > 0) & np.isfinite(r).all(axis=1)
+    return u & (np.bincount(trk, u, len(off) - 1) >= 2)[trk]
+
+
+def cost_terms_v(cams, pts, idx, obs, off, used, delta=0.0):
+    """rho of every used observation: cost_v is their numpy (pairwise) sum."""
+    r, _ = residuals_v(cams, pts, idx, obs, off)
+    return rho(r[used], delta)
+
+
+def cost_v(cams, pts, idx, obs, off, used, delta=0.0):
+    return float(cost_terms_v(cams, pts, idx, obs, off, used, delta).sum())
+
+
 def cayley(w):
     a = np.asarray(w, float) / 2
     K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
@@ -90,8 +127,8 @@ class Case:
         return N.BaConfig.default(**self.cfg)
 
 
-def ring(nCam, focal=1.5, radius=6.0):
-    return CM.cameras_array([CM.lookAt((radius * np.cos(a), radius * np.sin(a), 1.0 + 0.1 * i), (0, 0, 0), (0, 0, 1),
+def ring(nCam, focal=1.5, radius=6.0, rise=0.1):
+    return CM.cameras_array([CM.lookAt((radius * np.cos(a), radius * np.sin(a), 1.0 + rise * i), (0, 0, 0), (0, 0, 1),
                                        (focal, focal)) for i, a in enumerate(2 * np.pi * np.arange(nCam) / nCam)])
 
 
@@ -103,6 +140,22 @@ def observe(cams, world, camLists, noise=0.0, rng=None):
     assert (pc[:, 2] > 0).all()
     obs = r + (rng.normal(0, noise, r.shape) if noise else 0.0)
     return idx, obs, off
+
+
+def observe_v(cams, world, idx, off, noise=0.0, rng=None):
+    """observe() for a CSR that is already laid out, through residuals_v."""
+    r, pc = residuals_v(cams, world, idx, np.zeros((len(idx), 2)), off)
+    assert (pc[:, 2] > 0).all()
+    return r + (rng.normal(0, noise, r.shape) if noise else 0.0)
+
+
+def perturbed(rng, cams, fixed, dCam):
+    """scene()'s start: every camera that is not fixed moved by dCam = (rad, units)."""
+    start = cams.copy()
+    for j in np.nonzero(~np.asarray(fixed, bool))[0]:
+        w = rng.normal(size=3)
+        start[j] = retract(cams[j], np.concatenate([dCam[0] * w / np.linalg.norm(w), rng.uniform(-1, 1, 3) * dCam[1]]))
+    return start
 
 
 def scene(seed, nCam, T, lengths=None, noise=0.0, dCam=(0.02, 0.05), dPts=0.05, nFixed=2, **cfg):
@@ -169,6 +222,70 @@ def _seg_edges():
                 dict(maxIterations=3), (cams, world))
 
 
+def camera_ring_special(nCam):
+    """(the camera without an observation, the fixed camera beyond the two at the front) of camera_ring:
+    the last two cameras, but the two before the last where the last camera is alone in its trip of the
+    chains over j, j + 256, ... (nCam = 257, 513): that camera stays free and observed, so the trip adds
+    a non-zero term to r.z, p.q and the cost. With 513 cameras both are beyond the first 256."""
+    return (nCam - 3, nCam - 2) if nCam % 256 == 1 else (nCam - 2, nCam - 1)
+
+
+def camera_ring(nCam, seed=None, perCam=None, **cfg):
+    """A ring of nCam cameras (risen by 5 units over the whole ring) and tracks of 4 to 6 observations
+    dealt from perCam shuffles of the cameras (about 2000 observations by default, at least 3 per
+    camera), so every camera has at least perCam observations but one with none; cameras 0, 1 and one
+    more are fixed (camera_ring_special); noise 1e-3, scene()'s perturbation."""
+    rng = np.random.default_rng(1000 + nCam if seed is None else seed)
+    cams = ring(nCam, rise=5.0 / nCam)
+    empty, alsoFixed = camera_ring_special(nCam)
+    seen = np.setdiff1d(np.arange(nCam), [empty])
+    perCam = max(3, -(-2000 // nCam)) if perCam is None else perCam
+    pool = np.concatenate([rng.permutation(seen) for _ in range(perCam)])
+    lens, k = [], 0
+    while k < len(pool):
+        L = int(rng.integers(4, 7))
+        if len(pool) - k - L < 4:
+            L = len(pool) - k
+        lens.append(L)
+        k += L
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    idx = pool.astype(np.int32)
+    world = rng.uniform(-1, 1, (len(lens), 3))
+    obs = observe_v(cams, world, idx, off, 1e-3, rng)
+    fixed = np.zeros(nCam, np.uint8)
+    fixed[[0, 1, alsoFixed]] = 1
+    start = perturbed(rng, cams, fixed, (0.02, 0.05))
+    pts = world + rng.uniform(-1, 1, world.shape) * 0.05
+    return Case(start, idx, obs, off, pts, fixed, dict(dict(maxIterations=3), **cfg), (cams, world))
+
+
+SCALE_LONG, SCALE_SHORT, SCALE_CAMERAS = 4200, 84000, 70
+
+
+def scale_scene(seed=77):
+    """70 cameras, SCALE_LONG tracks of kBaShortMax + 1 observations among SCALE_SHORT tracks of 3 in a
+    seeded shuffle, every track from distinct cameras: more observations than a grid of threads, more
+    long tracks than the waves of the long-track kernels, several segments per camera. Noise 1e-3,
+    scene()'s perturbation, Huber on, two iterations of one PCG chunk."""
+    rng = np.random.default_rng(seed)
+    nCam = SCALE_CAMERAS
+    cams = ring(nCam)
+    lens = np.concatenate([np.full(SCALE_LONG, N.BA_SHORT_MAX + 1), np.full(SCALE_SHORT, 3)])
+    lens = lens[rng.permutation(len(lens))]
+    T = len(lens)
+    first = np.argsort(rng.random((T, nCam)), axis=1)             # a shuffle of the cameras per track
+    idx = first[np.arange(nCam)[None, :] < lens[:, None]].astype(np.int32)   # row-major: track by track
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    world = rng.uniform(-1, 1, (T, 3))
+    obs = observe_v(cams, world, idx, off, 1e-3, rng)
+    fixed = np.zeros(nCam, np.uint8)
+    fixed[:2] = 1
+    start = perturbed(rng, cams, fixed, (0.02, 0.05))
+    pts = world + rng.uniform(-1, 1, world.shape) * 0.05
+    return Case(start, idx, obs, off, pts, fixed,
+                dict(maxIterations=2, maxCgIterations=N.BA_CG_CHUNK, huberDelta=0.01), (cams, world))
+
+
 def _zero_cost():
     """Axis-aligned cameras and dyadic coordinates: every residual is exactly zero."""
     cams = np.array([[0, 0, 0, 0, 0, 1, 0, 1, 0, 1, 0, 0, 1, 1], [1, 0, 0, 0, 0, 1, 0, 1, 0, 1, 0, 0, 1, 1]], float)
@@ -207,6 +324,8 @@ CASES = {
     "segment_edges": _seg_edges,
     "all_fixed": lambda: scene(9, 4, 30, noise=1e-3, nFixed=4, maxIterations=5),
     "none_fixed": lambda: scene(10, 4, 30, noise=1e-3, nFixed=0, maxIterations=5),
+    # more cameras than one workgroup chains in one trip, and than one block of the per-camera kernels
+    **{f"cameras_{n}": (lambda n=n: camera_ring(n)) for n in (255, 256, 257, 513)},
     # the termination codes reachable from valid input
     "term_function": lambda: scene(12, 5, 40, noise=1e-3),
     "term_iterations": lambda: scene(13, 5, 40, noise=1e-3, maxIterations=2),
@@ -220,8 +339,9 @@ _cache = {}
 
 
 def case(name) -> Case:
+    """A named case, or "scale" (not in CASES: its tests ask more of it than the list's do)."""
     if name not in _cache:
-        _cache[name] = CASES[name]()
+        _cache[name] = scale_scene() if name == "scale" else CASES[name]()
     return _cache[name]
 
 

@@ -15,24 +15,60 @@ RANDOM_SEED = 11   # the random scene: see random_scene()
 
 
 class Case:
-    """One call's inputs, from a list of problems (i, j, [(a, b), ...], mask bytes or None)."""
+    """One call's inputs, from a list of problems (i, j, [(a, b), ...], mask bytes or None), or from the
+    call's own arrays (from_arrays: the large scenes, which never exist as Python tuples)."""
 
     def __init__(self, counts, problems, minLength=2, use_mask=None):
         self.counts = np.ascontiguousarray(counts, np.int32)
-        self.problems = [(int(i), int(j), [tuple(map(int, m)) for m in ms],
-                          None if mk is None else [int(b) for b in mk]) for i, j, ms, mk in problems]
+        self._problems = [(int(i), int(j), [tuple(map(int, m)) for m in ms],
+                           None if mk is None else [int(b) for b in mk]) for i, j, ms, mk in problems]
         self.minLength = minLength
-        self.use_mask = any(p[3] is not None for p in self.problems) if use_mask is None else use_mask
-        self.imagePairs = np.array([[p[0], p[1]] for p in self.problems], np.int32).reshape(-1, 2)
-        self.pairs = np.array([m for p in self.problems for m in p[2]], np.int32).reshape(-1, 2)
-        self.offsets = np.concatenate([[0], np.cumsum([len(p[2]) for p in self.problems])]).astype(np.int32)
-        self.mask = (np.array([b for p in self.problems for b in (p[3] if p[3] is not None else [1] * len(p[2]))],
+        self.use_mask = any(p[3] is not None for p in self._problems) if use_mask is None else use_mask
+        self.imagePairs = np.array([[p[0], p[1]] for p in self._problems], np.int32).reshape(-1, 2)
+        self.pairs = np.array([m for p in self._problems for m in p[2]], np.int32).reshape(-1, 2)
+        self.offsets = np.concatenate([[0], np.cumsum([len(p[2]) for p in self._problems])]).astype(np.int32)
+        self.mask = (np.array([b for p in self._problems for b in (p[3] if p[3] is not None else [1] * len(p[2]))],
                               np.uint8) if self.use_mask else None)
         self.nodes = int(self.counts.sum())
+
+    @classmethod
+    def from_arrays(cls, counts, imagePairs, pairs, offsets, mask=None, minLength=2):
+        c = cls.__new__(cls)
+        c.counts = np.ascontiguousarray(counts, np.int32)
+        c._problems = None
+        c.minLength, c.use_mask = minLength, mask is not None
+        c.imagePairs = np.ascontiguousarray(imagePairs, np.int32).reshape(-1, 2)
+        c.pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        c.offsets = np.ascontiguousarray(offsets, np.int32)
+        c.mask = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        c.nodes = int(c.counts.sum())
+        assert len(c.offsets) == len(c.imagePairs) + 1 and c.offsets[0] == 0 and c.offsets[-1] == len(c.pairs)
+        assert c.mask is None or len(c.mask) == len(c.pairs)
+        return c
+
+    @property
+    def problems(self):
+        if self._problems is None:
+            o, pr = self.offsets.tolist(), self.pairs.tolist()
+            mk = None if self.mask is None else self.mask.tolist()
+            self._problems = [(i, j, [tuple(m) for m in pr[o[q]:o[q + 1]]], None if mk is None else mk[o[q]:o[q + 1]])
+                              for q, (i, j) in enumerate(self.imagePairs.tolist())]
+        return self._problems
 
     def permuted(self, seed):
         """The same graph with the problems, and the matches of each problem with their mask bytes, reordered."""
         rng = np.random.default_rng(seed)
+        if self._problems is None:   # the same reordering on the arrays
+            B, n = len(self.imagePairs), len(self.pairs)
+            q = rng.permutation(B)
+            rank = np.empty(B, np.int64)
+            rank[q] = np.arange(B)
+            prob = np.repeat(np.arange(B), np.diff(self.offsets))
+            order = np.lexsort((rng.random(n), rank[prob]))
+            lens = np.diff(self.offsets)[q]
+            return Case.from_arrays(self.counts, self.imagePairs[q], self.pairs[order],
+                                    np.concatenate([[0], np.cumsum(lens)]),
+                                    None if self.mask is None else self.mask[order], self.minLength)
         probs = []
         for q in rng.permutation(len(self.problems)):
             i, j, ms, mk = self.problems[q]
@@ -189,14 +225,198 @@ CASES = {
 }
 
 
+# ---- the edges of the scan blocks (kTrkScanItems nodes each, eight nodes per thread of mcv_trk_place)
+
+SCAN = N.TRK_SCAN_ITEMS
+SCAN_NODES = (SCAN - 1, SCAN, SCAN + 1, 2 * SCAN, 2 * SCAN + 1)
+
+
+def _cut_case(nNodes, tracks):
+    """nNodes nodes and the given tracks (tuples of ascending node ids, disjoint), every other node
+    untouched: a new image begins at every node of a track but its first, so a track has one node per image."""
+    cuts = sorted({0} | {v for t in tracks for v in t[1:]})
+    counts = np.diff(cuts + [nNodes])
+    where = lambda g: (int(np.searchsorted(cuts, g, side="right")) - 1, g - cuts[int(np.searchsorted(cuts, g, side="right")) - 1])
+    probs = []
+    for t in tracks:
+        assert all(0 <= u < v < nNodes for u, v in zip(t, t[1:]))
+        for u, v in zip(t, t[1:]):
+            (i, a), (j, b) = where(u), where(v)
+            probs.append((i, j, [(a, b)], None))
+    return Case(counts, probs)
+
+
+def _scan_tracks(n, kind):
+    S = SCAN
+    if kind == "ends":      # nodes 0 and n - 1 in one track; the root S - 1 with its partner S
+        return [(0, n - 1)] + ([(S - 1, S)] if S < n - 1 else [])
+    if kind == "root_S":    # the root S; a track whose last member is n - 1
+        return [(S, S + 1), (5, n - 1)]
+    return [(n - 2, n - 1)]  # "tail": the only root is the partner of n - 1, every earlier node untouched
+
+
+SCAN_CASES = {f"scan_{n}_{kind}": (lambda n=n, kind=kind: _cut_case(n, _scan_tracks(n, kind)))
+              for n in SCAN_NODES for kind in ("ends", "root_S", "tail") if kind != "root_S" or n > SCAN + 2}
+CASES.update(SCAN_CASES)
+
+
+# ---- the large scenes: built with numpy from components of known membership, answered by construction
+
+def expected_by_construction(c, node, label) -> Result:
+    """The answer from the membership the generator laid down: node[k] belongs to component label[k]
+    (every touched node once). The three drop rules and the ordering with numpy sorts; no union-find."""
+    F = c.counts.astype(np.int64)
+    base = np.concatenate([[0], np.cumsum(F)])
+    node, label = np.asarray(node, np.int64), np.asarray(label, np.int64)
+    assert len(np.unique(node)) == len(node)
+    o = np.lexsort((node, label))
+    node, label = node[o], label[o]
+    first = np.concatenate([[True], label[1:] != label[:-1]])
+    start = np.nonzero(first)[0]
+    size = np.diff(np.concatenate([start, [len(node)]]))
+    comp = np.cumsum(first) - 1                                   # 0 .. C - 1 in label order
+    img = np.searchsorted(base, node, side="right") - 1
+    same_img = np.concatenate([[False], (img[1:] == img[:-1]) & ~first[1:]])   # nodes ascending within a component
+    conflict = np.bincount(comp, same_img, len(size)) > 0
+    over = size > MAX_LEN
+    conf = ~over & conflict
+    short = ~over & ~conf & (size < c.minLength)
+    keep = ~(over | conf | short)
+    root = node[start]
+    order = np.argsort(root[keep], kind="stable")                 # tracks by their smallest node
+    track_of_comp = np.full(len(size), -1, np.int64)
+    track_of_comp[np.nonzero(keep)[0][order]] = np.arange(int(keep.sum()))
+    t = track_of_comp[comp]
+    sel = t >= 0
+    o2 = np.lexsort((node[sel], t[sel]))
+    tn, ti = node[sel][o2], img[sel][o2]
+    tof = np.full(c.nodes, -1, np.int32)
+    tof[node[sel]] = t[sel]
+    toff = np.concatenate([[0], np.cumsum(size[keep][order])])
+    return Result(int(keep.sum()), toff.astype(np.int32), ti.astype(np.int32), (tn - base[ti]).astype(np.int32), tof,
+                  np.array([over.sum(), conf.sum(), short.sum()], np.int64))
+
+
+def _assemble(rng, counts, ia, fa, ib, fb, mask, minLength):
+    """Edges (image, feature) - (image, feature) in a seeded random order, grouped into one problem per
+    ordered image pair, the problems in a seeded random order too."""
+    nImg = len(counts)
+    key = ia.astype(np.int64) * nImg + ib
+    keys, inv = np.unique(key, return_inverse=True)
+    rank = rng.permutation(len(keys))
+    order = np.lexsort((rng.random(len(key)), rank[inv]))
+    lens = np.bincount(rank[inv], minlength=len(keys))
+    kk = np.empty(len(keys), np.int64)
+    kk[rank] = keys
+    return Case.from_arrays(counts, np.stack([kk // nImg, kk % nImg], axis=1),
+                            np.stack([fa, fb], axis=1)[order], np.concatenate([[0], np.cumsum(lens)]),
+                            mask[order], minLength)
+
+
+def _random_tree(rng, nodes):
+    """A random spanning tree over the given nodes (shuffled; each hangs on a random earlier one)."""
+    v = rng.permutation(nodes)
+    up = (rng.random(len(v) - 1) * np.arange(1, len(v))).astype(np.int64)
+    return v[1:], v[up]
+
+
+OVERSIZE = MAX_LEN + 904
+SCALE_CONFLICTS = 300 + 32   # of scale_scene(): the zigzags and the same-image pairs
+
+
+def scale_scene(div=1, seed=21):
+    """40 images of 52,500 / div features, minLength 2 (-> the case, the nodes, their components):
+    features [0, 2100 / div) are full 40-image paths (long candidates), the next 30,000 / div are matched
+    inside the 20 disjoint image pairs (0, 1), (2, 3), ..., then 300 / div four-node zigzags over images
+    0 and 1 and 32 / div same-image pairs at the end of the last image (conflicts), one oversize component (a random spanning tree over OVERSIZE nodes spread over
+    all images), the rest untouched. 10 % of the matches are masked-out decoys between random features,
+    which would join components if kept. div = 40 is the sub-scene the pure-Python reference judges."""
+    rng = np.random.default_rng(seed)
+    nImg, F = 40, 52500 // div
+    nLong, nPair, nZig, nTail = 2100 // div, 30000 // div, max(300 // div, 3), max(32 // div, 2)
+    perImg = -(-OVERSIZE // nImg)
+    z0 = nLong + nPair
+    o0 = z0 + 2 * nZig
+    assert o0 + perImg < F - 2 * nTail
+    gid = lambda i, f: np.asarray(i, np.int64) * F + f
+    E, node, label = [], [], []            # edges as (global node, global node); membership
+    f = np.arange(nLong)
+    for i in range(nImg - 1):
+        E.append((gid(i, f), gid(i + 1, f)))
+    node.append(gid(np.repeat(np.arange(nImg), nLong), np.tile(f, nImg)))
+    label.append(np.tile(f, nImg))
+    f = nLong + np.arange(nPair)
+    for p in range(nImg // 2):
+        E.append((gid(2 * p, f), gid(2 * p + 1, f)))
+        node += [gid(2 * p, f), gid(2 * p + 1, f)]
+        label += [nLong + p * nPair + np.arange(nPair)] * 2
+    nl = nLong + (nImg // 2) * nPair
+    k = np.arange(nZig)
+    a0, a1, b0, b1 = gid(0, z0 + 2 * k), gid(0, z0 + 2 * k + 1), gid(1, z0 + 2 * k), gid(1, z0 + 2 * k + 1)
+    E += [(a0, b0), (a1, b0), (a1, b1)]    # A.f0 - B.f0 - A.f1 - B.f1
+    node += [a0, a1, b0, b1]
+    label += [nl + k] * 4
+    # two-node components inside the last image, at its end (conflicts): the only candidates whose roots
+    # lie in the last scan blocks, beyond the first chunk of mcv_trk_scan (every other root has a partner
+    # in a later image, so it lies in an earlier one: no kept track is rooted there, and the second scan's
+    # carry shows only in offsets[T] and T, written at the last node)
+    k = np.arange(nTail)
+    t0, t1 = gid(nImg - 1, F - 2 * nTail + 2 * k), gid(nImg - 1, F - 2 * nTail + 2 * k + 1)
+    E.append((t0, t1))
+    node += [t0, t1]
+    label += [nl + nZig + 1 + k] * 2
+    big = gid(np.repeat(np.arange(nImg), perImg), np.tile(o0 + np.arange(perImg), nImg))[:OVERSIZE]
+    E.append(_random_tree(rng, big))
+    node.append(big)
+    label.append(np.full(OVERSIZE, nl + nZig))
+    u, v = np.concatenate([e[0] for e in E]), np.concatenate([e[1] for e in E])
+    flip = rng.random(len(u)) < 0.5         # the order of an edge's two ends plays no part either
+    u, v = np.where(flip, v, u), np.where(flip, u, v)
+    nDecoy = len(u) // 9
+    du, dv = rng.integers(0, nImg * F, nDecoy), rng.integers(0, nImg * F, nDecoy)
+    mask = np.concatenate([rng.choice(np.array([1, 1, 1, 2, 255], np.uint8), len(u)), np.zeros(nDecoy, np.uint8)])
+    u, v = np.concatenate([u, du]), np.concatenate([v, dv])
+    c = _assemble(rng, [F] * nImg, u // F, u % F, v // F, v % F, mask, 2)
+    return c, np.concatenate(node), np.concatenate(label)
+
+
+def contended_scene(seed=22):
+    """50 images of 2,100 features, minLength 2: one component of 100,000 nodes (2,000 seeded features of
+    every image; a random spanning tree plus two extra random edges per node, about 300k edges in random
+    order), dropped as oversize, beside 1,000 three-image bystander tracks on features between its own."""
+    rng = np.random.default_rng(seed)
+    nImg, F, nBig, nBy = 50, 2100, 2000, 1000
+    pick = np.stack([rng.permutation(F) for _ in range(nImg)])           # [:, :nBig] the big component's
+    big = (np.arange(nImg)[:, None] * F + pick[:, :nBig]).reshape(-1)
+    free = np.sort(pick[:, nBig:], axis=1)
+    tu, tv = _random_tree(rng, big)
+    xu, xv = np.repeat(big, 2), big[rng.integers(0, len(big), 2 * len(big))]
+    b = np.arange(nBy)
+    g, k = b % 16, b // 16
+    by = [(3 * g + d) * F + free[3 * g + d, k] for d in range(3)]
+    u = np.concatenate([tu, xu, by[0], by[1]])
+    v = np.concatenate([tv, xv, by[1], by[2]])
+    c = _assemble(rng, [F] * nImg, u // F, u % F, v // F, v % F, np.ones(len(u), np.uint8), 2)
+    return c, np.concatenate([big] + by), np.concatenate([np.full(len(big), nBy), b, b, b])
+
+
+LARGE = {"scale": scale_scene, "contended": contended_scene, "scale_sub40": lambda: scale_scene(div=40)}
+
+
+@functools.lru_cache(maxsize=None)
+def _large(name):
+    c, node, label = LARGE[name]()
+    return c, expected_by_construction(c, node, label)
+
+
 @functools.lru_cache(maxsize=None)
 def case(name) -> Case:
-    return CASES[name]()
+    return _large(name)[0] if name in LARGE else CASES[name]()
 
 
 @functools.lru_cache(maxsize=None)
 def expected(name) -> Result:
-    return reference(case(name))
+    return _large(name)[1] if name in LARGE else reference(case(name))
 
 
 # ---- the native call

@@ -268,6 +268,65 @@ def bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
+# ---- the scale case: more observations than a grid of threads, more long tracks than blocks of the queue
+
+SCALE_LONG, SCALE_SHORT, SCALE_SAMPLE = 16500, 82000, 256
+
+
+def unproject_all(cams, idx, obs):
+    """ref_unproject over arrays: the same operations in the same order, one IEEE operation per numpy
+    call (no fused multiply-add, no reordered sum), so the rays are the reference's to the bit."""
+    c = cams[idx]
+    loc, fw, up, rt = c[:, 0:3], c[:, 3:6], c[:, 6:9], c[:, 9:12]
+    a, b = (obs[:, 0] / c[:, 12])[:, None], (obs[:, 1] / c[:, 13])[:, None]
+    d = a * rt + b * up + fw
+    l = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+    assert np.all(l > 0.0)
+    return np.ascontiguousarray(np.concatenate([loc, d * (1.0 / l)[:, None]], axis=1))
+
+
+class ScaleProblem:
+    """SCALE_LONG tracks of TRI_SHORT_MAX + 1 rays among SCALE_SHORT tracks of 3 in a seeded shuffle (no
+    period in 256), 64 cameras, noise, wrong and repeated observations. The pure-Python reference judges
+    a seeded sample of SCALE_SAMPLE tracks, half of them long: .sample the tracks, .ref their Problem."""
+
+    def __init__(self, seed=97):
+        rng = np.random.default_rng(seed)
+        lens = np.concatenate([np.full(SCALE_LONG, N.TRI_SHORT_MAX + 1), np.full(SCALE_SHORT, 3)])
+        lens = lens[rng.permutation(lens.size)]
+        self.T = int(lens.size)
+        self.cams, self.idx, self.obs, self.offsets, _ = S.track_problem(
+            self.T, seed, lengths=lens, n_cameras=64, sigma=1e-3, wrong_frac=0.05, dup_frac=0.02)
+        self.n, self.nLong = int(self.offsets[-1]), SCALE_LONG
+        self.rays = unproject_all(self.cams, self.idx, self.obs)
+        longs, shorts = np.nonzero(lens > N.TRI_SHORT_MAX)[0], np.nonzero(lens <= N.TRI_SHORT_MAX)[0]
+        self.sample = np.sort(np.concatenate([rng.choice(longs, SCALE_SAMPLE // 2, replace=False),
+                                              rng.choice(shorts, SCALE_SAMPLE // 2, replace=False)]))
+        sel = np.concatenate([np.arange(self.offsets[t], self.offsets[t + 1]) for t in self.sample])
+        self.sample_obs = sel
+        self.ref = Problem(self.cams, self.idx[sel], self.obs[sel],
+                           np.concatenate([[0], np.cumsum(lens[self.sample])]))
+
+    def lengths(self):
+        return np.diff(self.offsets)
+
+    def assert_sample(self, got, what):
+        """The sampled tracks of a full result against the pure-Python reference, bit for bit."""
+        assert_same(tuple(None if a is None else a[self.sample] for a in got), self.ref, what)
+
+
+@functools.lru_cache(maxsize=None)
+def scale() -> ScaleProblem:
+    return ScaleProblem()
+
+
+def assert_bits(got, want, what):
+    """Two results of the exports (points, pair counts[, cost, visible]) against each other, bit for bit."""
+    for a, b, f in zip(got, want, ("points", "pair counts", "cost", "visible")):
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)), \
+            f"{what}: {f} differ"
+
+
 def assert_same(got, ref, what):
     """Bit for bit, NaN payloads and zero signs included."""
     gp, gc = got[0], got[1]

@@ -165,17 +165,37 @@ def test_jacobians_against_central_differences(native):
         assert np.abs(Bm[k] - numB).max() <= 1e-7 * np.abs(numB).max(), k
 
 
+def _one_step_scenes():
+    return {"4_cameras": (lambda: B.scene(51, 4, 40, nFixed=1, noise=1e-3, cgTolerance=1e-14, maxCgIterations=60), 60),
+            "257_cameras": (lambda: B.camera_ring(257, seed=52, perCam=6, cgTolerance=1e-14, maxCgIterations=400), 400)}
+
+
 def test_one_step_against_numpy(native):
-    """4 cameras (1 fixed), 40 points: the dense J from the hook's blocks, numpy's solve of the damped
-    normal equations at lambda = 1e-3 (condition number asserted <= 1e8), and the twin's step with
-    cgTolerance 1e-14 and 60 CG iterations: 1e-6 relative in the 2-norm (cond x eps with a hundredfold
-    margin)."""
-    c = contiguous(B.scene(51, 4, 40, nFixed=1, noise=1e-3, cgTolerance=1e-14, maxCgIterations=60))
+    _one_step("4_cameras")
+
+
+def test_one_step_against_numpy_257_cameras(native):
+    _one_step("257_cameras")
+
+
+def _one_step(which):
+    """4 cameras (1 fixed), 40 points, and 257 cameras (3 fixed, one without an observation: not a
+    column of J; camera 256 free and observed), about 300 points, where the twin's chains over the cameras (r.z, p.q, the cost) take a
+    second trip of 256: the dense J from the hook's blocks, numpy's solve of the damped normal equations
+    at lambda = 1e-3 (condition number asserted <= 1e8), and the twin's step with cgTolerance 1e-14 and
+    60 (400) CG iterations: 1e-6 relative in the 2-norm (cond x eps with a hundredfold margin)."""
+    make, maxCg = _one_step_scenes()[which]
+    c = contiguous(make())
     lam = 1e-3
     used, A, Bm, r, _ = linearize(c)
     assert used.all()
-    nC, T, n = 4, 40, len(c.idx)
-    free = [j for j in range(nC) if not c.fixed[j]]
+    nC, T, n = len(c.cams), len(c.off) - 1, len(c.idx)
+    seen = np.bincount(c.idx, minlength=nC) > 0
+    free = [j for j in range(nC) if not c.fixed[j] and seen[j]]
+    if which == "257_cameras":
+        assert nC == 257 > 256 and 250 <= T <= 350 and len(free) == nC - 4 and not seen[254] and c.fixed[255]
+        assert 256 in free   # the second trip of the chains holds a free, observed camera: its terms are not zero
+        assert np.bincount(c.idx, minlength=nC)[seen].min() >= 6
     col = {j: 6 * m for m, j in enumerate(free)}
     trk = np.repeat(np.arange(T), np.diff(c.off))
     J = np.zeros((2 * n, 6 * len(free) + 3 * T))
@@ -194,12 +214,93 @@ def test_one_step_against_numpy(native):
     it = N.lib().mcvHostBaStep(c.cams.ctypes.data, nC, c.fixed.ctypes.data, c.idx.ctypes.data, c.obs.ctypes.data,
                                c.off.ctypes.data, T, c.pts.ctypes.data, C.addressof(cfg), lam, dC.ctypes.data,
                                dP.ctypes.data)
-    assert 0 < it <= 60, N.last_error()
-    assert (dC[0] == 0).all()
+    assert 0 < it <= maxCg, N.last_error()
+    rest = np.setdiff1d(np.arange(nC), free)
+    assert (dC[rest] == 0).all()          # fixed cameras and the one nothing sees
     got = np.concatenate([dC[free].reshape(-1), dP.reshape(-1)])
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
     print("relative difference of the step", rel, "after", it, "CG iterations")
     assert rel <= 1e-6
+
+
+def test_constants_pinned():
+    """The mirrors of the sizes the scale cases are derived from, read from the headers' text."""
+    ktxt = (N.ROOT / "minicv_amd" / "csrc" / "kernels.h").read_text()
+    ttxt = (N.ROOT / "minicv_amd" / "csrc" / "ba_terms.h").read_text()
+    assert f"kBaGrid = {N.BA_GRID};" in ktxt and f"kBaLongBlocks = {N.BA_LONG_BLOCKS};" in ktxt
+    assert f"kBaSeg = {N.BA_SEG};" in ttxt and f"kBaShortMax = {N.BA_SHORT_MAX};" in ttxt
+    assert f"kBaCgChunk = {N.BA_CG_CHUNK};" in ttxt
+
+
+def test_vectorised_model_equals_loop_model():
+    """residuals_v against residuals on existing cases: not 0 ulp. pc's three products are summed left
+    to right there and by numpy's matrix product in the loop form, so pc differs by at most 2 ulp of its
+    largest entry and a residual of a used observation (below 1) by at most 2^-52; the used sets are equal."""
+    for name in ("track_lengths", "segment_edges", "huber_on", "exclusions"):
+        c = B.case(name)
+        r, pc = B.residuals(c.cams, c.pts, c.idx, c.obs, c.off)
+        rv, pcv = B.residuals_v(c.cams, c.pts, c.idx, c.obs, c.off)
+        used = ok = B.used_set(c.cams, c.pts, c.idx, c.obs, c.off)
+        assert np.array_equal(used, B.used_set_v(c.cams, c.pts, c.idx, c.obs, c.off)) and ok.sum() >= len(ok) - 8
+        assert np.abs(pc[ok] - pcv[ok]).max() <= 2 * np.spacing(np.abs(pc[ok]).max())
+        assert np.abs(r[ok]).max() < 1 and np.abs(r[ok] - rv[ok]).max() <= 2.0 ** -52
+        a, b = B.cost(c.cams, c.pts, c.idx, c.obs, c.off, used, 0.01), B.cost_v(c.cams, c.pts, c.idx, c.obs, c.off, used, 0.01)
+        assert abs(a - b) <= 1e-13 * a
+
+
+@pytest.mark.parametrize("nCam", [255, 256, 257, 513])
+def test_camera_rings(native, nCam):
+    """The cases with more cameras than one trip of 256: every camera has at least 3 observations but
+    the one with none; the twin's costs against numpy's own evaluation (test_end_to_end's 1e-12)."""
+    c = B.case(f"cameras_{nCam}")
+    empty, alsoFixed = B.camera_ring_special(nCam)
+    per = np.bincount(c.idx, minlength=nCam)
+    assert len(c.cams) == nCam and per[empty] == 0 and per[np.arange(nCam) != empty].min() >= 3
+    assert np.nonzero(c.fixed)[0].tolist() == [0, 1, alsoFixed] and per[alsoFixed] >= 3
+    if nCam > 257:
+        assert empty >= 256 and alsoFixed >= 256
+    if nCam > 256:   # the last camera, alone in its trip of the chains over the cameras, is free and observed
+        assert nCam % 256 == 1 and not c.fixed[nCam - 1] and per[nCam - 1] >= 3
+    L = np.diff(c.off)
+    assert 350 <= len(L) <= 450 and L.min() >= 4 and L.max() <= 9 and c.cfg["maxIterations"] == 3
+    cams, pts, sm = twin(c)
+    used = B.used_set_v(c.cams, c.pts, c.idx, c.obs, c.off)
+    assert used.all() and sm["usedObservations"] == len(c.idx) and sm["usedTracks"] == len(L)
+    c0, c1 = B.cost_v(c.cams, c.pts, c.idx, c.obs, c.off, used), B.cost_v(cams, pts, c.idx, c.obs, c.off, used)
+    assert abs(sm["initialCost"] - c0) <= 1e-12 * c0 and abs(sm["finalCost"] - c1) <= 1e-12 * c1
+    assert sm["accepted"] > 0 and sm["finalCost"] < 0.1 * sm["initialCost"] and sm["cgIterations"] > 0
+    keep = [0, 1, alsoFixed, empty]
+    assert B.same_bits(cams[keep], c.cams[keep])
+    moved = np.setdiff1d(np.arange(nCam), keep)
+    assert (B.bits(cams[moved]) != B.bits(c.cams[moved])).any(axis=1).all()
+
+
+def scale_segments(c):
+    return int(np.sum(-(-np.bincount(c.idx, minlength=len(c.cams)) // N.BA_SEG)))
+
+
+def test_scale_case(native):
+    """What makes `scale` a second-trip case, from the mirrored constants, and the twin on it against
+    the vectorised numpy model."""
+    c = B.case("scale")
+    n, T, L = len(c.idx), len(c.off) - 1, np.diff(c.off)
+    nLong = int((L > N.BA_SHORT_MAX).sum())
+    assert n > N.BA_GRID * 256 and nLong > 4 * N.BA_LONG_BLOCKS and T >= 1024
+    assert set(L.tolist()) == {3, N.BA_SHORT_MAX + 1} and len(c.cams) == 70
+    per = np.bincount(c.idx, minlength=70)
+    assert per.min() > 3 * N.BA_SEG and scale_segments(c) > 3 * 70
+    trk = np.repeat(np.arange(T), L)
+    assert len(np.unique(trk.astype(np.int64) * 70 + c.idx)) == n      # distinct cameras within a track
+    cams, pts, sm = twin(c)
+    used = B.used_set_v(c.cams, c.pts, c.idx, c.obs, c.off)
+    assert used.all() and sm["usedTracks"] == T and sm["usedObservations"] == n
+    delta = c.cfg["huberDelta"]
+    r, _ = B.residuals_v(c.cams, c.pts, c.idx, c.obs, c.off)
+    assert 0.2 < (np.sqrt((r * r).sum(axis=1)) > delta).mean() < 1.0   # both branches of the loss are taken
+    c0, c1 = B.cost_v(c.cams, c.pts, c.idx, c.obs, c.off, used, delta), B.cost_v(cams, pts, c.idx, c.obs, c.off, used, delta)
+    print("scale: twin against numpy, relative", abs(sm["initialCost"] - c0) / c0, abs(sm["finalCost"] - c1) / c1)
+    assert abs(sm["initialCost"] - c0) <= 1e-12 * c0 and abs(sm["finalCost"] - c1) <= 1e-12 * c1
+    assert sm["finalCost"] < sm["initialCost"] and sm["iterations"] == 2
 
 
 def test_convergence_noise_free(native):

@@ -3,6 +3,8 @@ points, every summary field) on the named cases of tests/_ba_cases.py, which cov
 kernels' shapes; what a permutation of the tracks may and may not change; the launch, synchronisation
 and copy counts; and the chain buildTracks -> trackObservations -> triangulateTracks -> bundleAdjust."""
 import ctypes as C
+import math
+import time
 
 import numpy as np
 import pytest
@@ -43,11 +45,22 @@ def assert_equal(twin, got, what):
 def test_export_equals_twin(native, gpu, name):
     """T = 63 / 64 / 65; tracks of 2, 63, 64, 65, 130 and 600 observations (the lane and the wave
     form); cameras with kBaSeg - 1, kBaSeg, kBaSeg + 1, 2 kBaSeg + 3 observations and with none; all and
-    no cameras fixed; Huber on and off; rejected steps; every termination code."""
+    no cameras fixed; Huber on and off; rejected steps; every termination code; 255, 256, 257 and 513
+    cameras (the second and third trip of the one-workgroup chains over the cameras, the second and third
+    block of the per-camera kernels), one of them without an observation, one more fixed,
+    the last camera of 257 and of 513 (alone in its trip) free and observed."""
     c = B.case(name)
     twin, got = both(c)
     assert_equal(twin, got, name)
     sm = got[3]
+    if name.startswith("cameras_"):
+        nCam = int(name.split("_")[1])
+        empty, alsoFixed = B.camera_ring_special(nCam)
+        assert len(c.cams) == nCam and (nCam <= 257 or min(empty, alsoFixed) >= 256)
+        if nCam > 256:   # the last trip of the chains over the cameras holds one camera, and it moves
+            assert nCam % 256 == 1 and not B.same_bits(got[1][nCam - 1], c.cams[nCam - 1])
+        assert B.same_bits(got[1][[0, 1, alsoFixed, empty]], c.cams[[0, 1, alsoFixed, empty]])
+        assert sm["accepted"] > 0 and sm["cgIterations"] > 0 and sm["usedObservations"] == len(c.idx)
     if name in B.TERMINATION:
         assert sm["termination"] == B.TERMINATION[name]
     if name == "rejected":
@@ -68,7 +81,7 @@ def test_export_equals_twin(native, gpu, name):
         assert sm["finalCost"] < sm["initialCost"]
 
 
-@pytest.mark.parametrize("name", ["exclusions", "track_lengths", "all_fixed"])
+@pytest.mark.parametrize("name", ["exclusions", "track_lengths", "all_fixed", "cameras_257"])
 def test_track_permutation(native, gpu, name):
     """The per-point sums follow the track's own order and the per-camera sums the ascending observation
     index, so permuting the tracks regroups only the camera-side sums and the total cost. What must
@@ -96,6 +109,36 @@ def test_track_permutation(native, gpu, name):
         else:
             ok = np.isfinite(want).all(axis=1)
             assert np.abs(pg[ok] - want[ok]).max() < 1e-9 and np.abs(cg - base[1]).max() < 1e-9
+
+
+def test_scale(native, gpu):
+    """More observations than kBaGrid x 256 threads (mcv_ba_used_obs strides), more long tracks than the
+    4 kBaLongBlocks waves of the long-track kernels, T >= 1024, several segments per camera: cameras,
+    points and every summary field equal the twin's bit for bit, and both costs are numpy's own
+    evaluation of the model within 1e-12 (against its pairwise sum and against math.fsum of its terms)."""
+    c = B.case("scale")
+    n, T, L = len(c.idx), len(c.off) - 1, np.diff(c.off)
+    assert n > N.BA_GRID * 256 and int((L > N.BA_SHORT_MAX).sum()) > 4 * N.BA_LONG_BLOCKS and T >= 1024
+    assert c.cfg["maxCgIterations"] == N.BA_CG_CHUNK and c.cfg["maxIterations"] == 2 and c.cfg["huberDelta"] > 0
+    t0 = time.perf_counter()
+    got = B.run("cvBundleAdjust", c)
+    t1 = time.perf_counter()
+    twin = B.run("mcvHostBundleAdjust", c)
+    print(f"scale: cvBundleAdjust {t1 - t0:.3f} s, the twin {time.perf_counter() - t1:.3f} s")
+    assert got[0] >= 0 and twin[0] >= 0, N.last_error()
+    st = stats()
+    assert_equal(twin, got, "scale")
+    sm = got[3]
+    assert sm["usedTracks"] == T and sm["usedObservations"] == n and sm["iterations"] == 2
+    assert st["segments"] == int(np.sum(-(-np.bincount(c.idx, minlength=len(c.cams)) // N.BA_SEG))) > 3 * len(c.cams)
+    used = np.ones(n, bool)
+    for what, cams, pts in (("initialCost", c.cams, c.pts), ("finalCost", got[1], got[2])):
+        terms = B.cost_terms_v(cams, pts, c.idx, c.obs, c.off, used, c.cfg["huberDelta"])
+        pairwise, exact = float(terms.sum()), math.fsum(terms)
+        print(f"scale: {what} {sm[what]!r}, relative to numpy's sum {abs(sm[what] - pairwise) / pairwise:.3e}, "
+              f"to fsum {abs(sm[what] - exact) / exact:.3e}")
+        assert abs(sm[what] - pairwise) <= 1e-12 * pairwise and abs(sm[what] - exact) <= 1e-12 * exact
+    assert sm["finalCost"] < sm["initialCost"] and sm["accepted"] > 0
 
 
 def test_fixed_costs(native, gpu):

@@ -3,6 +3,7 @@ shared case list (tests/_tracks_ref.py), the order independence of the device un
 counts of DESIGN §7l, and the chain buildTracks -> trackObservations -> triangulateTracks end to end.
 Every comparison of tracks is an equality."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -63,6 +64,49 @@ def test_order_independence(native, gpu, name):
         T, got, _ = R.run("cvBuildTracks", R.case(name).permuted(seed))
         assert T == want.T, native.last_error()
         R.assert_same(got, want, f"{name} permuted {seed}")
+
+
+def test_scale(native, gpu):
+    """The second trips (tests/_tracks_ref.py scale_scene): 2.1 M nodes are more than kTrkScanChunk scan
+    blocks, so mcv_trk_scan carries from chunk to chunk (32 candidates, all dropped as conflicts, have their
+    roots past the first chunk; no kept track can: the carry of the second scan shows in offsets[T] and T);
+    candidates, kept edges, slots and nodes are each more than kTrkGrid x 256, so every grid-stride kernel
+    strides; more long candidates than kTrkGrid blocks of mcv_trk_long. Against the by-construction answer
+    and the twin; one permuted re-run, the same bits."""
+    c, want = R.case("scale"), R.expected("scale")
+    assert -(-c.nodes // N.TRK_SCAN_ITEMS) > N.TRK_SCAN_CHUNK and c.nodes > N.TRK_GRID * 256
+    T, twin, _ = R.run("mcvHostBuildTracks", c)
+    assert T == want.T
+    R.assert_same(twin, want, "host twin")
+    t0 = time.perf_counter()
+    T, got, _ = R.run("cvBuildTracks", c)
+    print(f"scale: cvBuildTracks {time.perf_counter() - t0:.3f} s with the buffers of run(), T = {T}")
+    assert T == want.T, native.last_error()
+    st = stats()
+    R.assert_same(got, want, "cvBuildTracks")
+    R.assert_same(got, twin, "cvBuildTracks against the twin")
+    assert got.dropped.tolist() == [1, R.SCALE_CONFLICTS, 0]
+    assert st[:4] == COUNTS_FULL, st
+    assert st[4] == want.T + R.SCALE_CONFLICTS and st[4] > N.TRK_GRID * 256 and st[5] > N.TRK_GRID, st
+    assert st[6] == int(c.mask.astype(bool).sum()) > N.TRK_GRID * 256 and len(want.cameraIdx) > N.TRK_GRID * 256
+    T, got, _ = R.run("cvBuildTracks", c.permuted(1))
+    assert T == want.T, native.last_error()
+    R.assert_same(got, want, "scale permuted")
+
+
+def test_contended(native, gpu):
+    """One 100,000-node component with 300k edges in random order (dropped as oversize) beside 1,000
+    bystanders: the bounded loops of the hook end without the fail word under contended CAS, and the
+    outputs are the by-construction ones whatever the edge order. One call per permutation."""
+    c, want = R.case("contended"), R.expected("contended")
+    assert want.T == 1000 and want.dropped.tolist() == [1, 0, 0]
+    for k, p in enumerate((c, c.permuted(1), c.permuted(2))):
+        t0 = time.perf_counter()
+        T, got, _ = R.run("cvBuildTracks", p)
+        print(f"contended: cvBuildTracks {time.perf_counter() - t0:.3f} s, order {k}")
+        assert T == want.T, native.last_error()   # a fail word is a refusal: T = -1 with its message
+        R.assert_same(got, want, f"contended, order {k}")
+        assert stats()[4:6] == [1000, 0]
 
 
 def test_launch_counts(native, gpu):

@@ -3,6 +3,7 @@ against the host twin and the pure-Python reference (_triangulate_ref.ref_inters
 points, pair counts, cost and visible. The cases and their reference answers are shared with
 tests/test_triangulate.py and computed once."""
 import ctypes as C
+import time
 from collections import Counter
 
 import numpy as np
@@ -280,13 +281,59 @@ def test_device_export(native, gpu):
         assert np.array_equal(x.view(np.uint8), y.view(np.uint8)) and np.array_equal(x.view(np.uint8), z.view(np.uint8))
 
 
+# ---- scale: the second trips of the grid-stride kernels and of the long-track queue
+
+def test_scale(native, gpu):
+    """n > kTriGrid x 256 observations (mcv_tri_unproject and mcv_tri_check_cameras stride) and more
+    long tracks than the 8 kTriGrid blocks of mcv_tri_long: all three exports and the device export
+    equal the host twin bit for bit, and the pure-Python reference on a seeded sample of 256 tracks."""
+    p = R.scale()
+    assert p.n > N.TRI_GRID * 256 and p.nLong > 8 * N.TRI_GRID and p.T > 8 * N.TRI_GRID
+    assert p.ref.enough_points(), "the sample hides failures: fewer than half of its tracks have a point"
+    k, hp, hc, hcost, hvis = R.host_tracks(p)
+    twin = (hp, hc, hcost, hvis)
+    assert k == int((hc > 0).sum()) > p.T // 2
+    p.assert_sample(twin, "host twin")
+    st = (C.c_longlong * 8)()
+    for name, call in (("cvIntersectRays", lambda: R.call_export("cvIntersectRays", p)),
+                       ("cvTriangulateTracks", lambda: R.call_export("cvTriangulateTracks", p)),
+                       ("mcvTriangulateTracksDevice", lambda: device_call(p))):
+        t0 = time.perf_counter()
+        kk, _, out = call()
+        print(f"scale: {name} {time.perf_counter() - t0:.3f} s")
+        assert kk == k, (name, kk, k, native.last_error())
+        assert N.lib().mcvTestTriangulateStats(st) == 0 and list(st)[4:6] == [p.T - p.nLong, p.nLong]
+        got = out[:2] if name == "cvIntersectRays" else out
+        R.assert_bits(got, twin, name)
+        p.assert_sample(got, name)
+
+
+def test_validation_at_scale(native, gpu):
+    """A bad cameraIdx beyond the first trip of mcv_tri_check_cameras, and at the last observation:
+    the exports refuse, name the first bad index, write nothing, and the next good call is unaffected."""
+    p = R.scale()
+    first, last = N.TRI_GRID * 256 + 3, p.n - 1
+    assert first < last
+    for bad, named in (((first, last), first), ((last,), last)):
+        idx = p.idx.copy()
+        idx[list(bad)] = p.cams.shape[0]
+        k, untouched, _ = R.call_export("cvTriangulateTracks", p, idx=idx)
+        assert k == -1 and untouched and f"cameraIdx[{named}]" in native.last_error(), native.last_error()
+        k, untouched, _ = device_call(p, idx=idx)
+        assert k == -1 and untouched and f"cameraIdx[{named}]" in native.last_error(), native.last_error()
+    k, hp, hc, hcost, hvis = R.host_tracks(p)
+    kk, _, out = device_call(p)
+    assert kk == k, native.last_error()
+    R.assert_bits(out, (hp, hc, hcost, hvis), "after a refused call")
+
+
 # ---- every subject above has its test, and none of them is switched off
 
 def test_every_subject_has_its_test():
     subjects = ("test_empty_and_minimal_tracks", "test_empty_and_minimal_tracks_T0", "test_wave_edges",
                 "test_track_length_edges", "test_duplicates", "test_angle_threshold", "test_rays_behind_the_origin",
                 "test_non_finite_midpoints", "test_statistics", "test_validation", "test_launch_counts",
-                "test_device_export", "test_reference_conditions")
+                "test_device_export", "test_reference_conditions", "test_scale", "test_validation_at_scale")
     for name in subjects:
         f = globals().get(name)
         assert callable(f), f"{name} is missing"

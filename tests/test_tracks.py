@@ -51,6 +51,74 @@ def test_case_list_covers_the_cuts():
         R.assert_same(R.expected(f"path_L600_{o}"), R.expected("path_L600"), o)
 
 
+def test_scan_block_edges():
+    """The scan cases put roots and last members on the edges of the kTrkScanItems-node scan blocks and
+    of the eight-node runs of a thread, for every nNodes around one and two blocks."""
+    S = N.TRK_SCAN_ITEMS
+    assert R.SCAN_NODES == (S - 1, S, S + 1, 2 * S, 2 * S + 1) and {n % 8 for n in R.SCAN_NODES} == {0, 1, 7}
+    base = lambda c: np.concatenate([[0], np.cumsum(c.counts)])
+    roots = {name: (base(R.case(name))[R.expected(name).cameraIdx] + R.expected(name).featureIdx)
+             [R.expected(name).trackOffsets[:-1]].tolist() for name in R.SCAN_CASES}
+    for n in R.SCAN_NODES:
+        assert R.case(f"scan_{n}_tail").nodes == n and roots[f"scan_{n}_tail"] == [n - 2]
+        assert R.expected(f"scan_{n}_tail").trackOfFeature.tolist() == [-1] * (n - 2) + [0, 0]
+        assert roots[f"scan_{n}_ends"][0] == 0 and R.expected(f"scan_{n}_ends").trackOfFeature[n - 1] == 0
+    assert roots[f"scan_{2 * S}_ends"] == [0, S - 1] and roots[f"scan_{2 * S + 1}_root_S"] == [5, S]
+    assert roots[f"scan_{S + 1}_tail"] == [S - 1]       # the root S - 1 with its partner S, nothing else
+    assert all(R.expected(name).dropped.tolist() == [0, 0, 0] for name in R.SCAN_CASES)
+
+
+def scale_sizes(c):
+    """Of a scene: nodes, scan blocks, kept edges, matches."""
+    kept = len(c.pairs) if c.mask is None else int(c.mask.astype(bool).sum())
+    return c.nodes, -(-c.nodes // N.TRK_SCAN_ITEMS), kept, len(c.pairs)
+
+
+def test_scale_scene_is_a_second_trip_case():
+    """What makes `scale` a second-trip case, from the mirrored constants: more scan blocks than one
+    chunk of mcv_trk_scan (the carry), more candidates, kept edges and slots than a grid of threads,
+    more long candidates than blocks of mcv_trk_long; all three drop counters by construction."""
+    c, want = R.case("scale"), R.expected("scale")
+    nodes, nb, kept, matches = scale_sizes(c)
+    sizes = np.diff(want.trackOffsets)
+    assert nb > N.TRK_SCAN_CHUNK and kept > N.TRK_GRID * 256 and nodes > N.TRK_GRID * 256
+    assert want.T + int(want.dropped[1]) > N.TRK_GRID * 256            # candidates: the tracks and the conflicts
+    assert len(want.cameraIdx) > N.TRK_GRID * 256                      # slots
+    assert int((sizes > N.TRK_SHORT_MAX).sum()) > N.TRK_GRID           # long candidates
+    assert 0.09 < 1.0 - kept / matches < 0.11 and want.dropped.tolist() == [1, R.SCALE_CONFLICTS, 0]
+    # candidates with their root in the scan blocks past the first chunk of kTrkScanChunk: the same-image pairs
+    prob = np.repeat(np.arange(len(c.imagePairs)), np.diff(c.offsets))
+    last = np.all(c.imagePairs[prob] == len(c.counts) - 1, axis=1) & c.mask.astype(bool)
+    lo = (len(c.counts) - 1) * int(c.counts[0]) + c.pairs[last].min(axis=1)
+    assert int((lo >= N.TRK_SCAN_CHUNK * N.TRK_SCAN_ITEMS).sum()) == 32           # (the oversize tree has same-image edges too)
+    assert R.OVERSIZE == R.MAX_LEN + 904
+    c, want = R.case("contended"), R.expected("contended")
+    assert want.T == 1000 and want.dropped.tolist() == [1, 0, 0] and len(c.pairs) > 300000
+    assert np.all(np.diff(want.trackOffsets) == 3)
+
+
+def test_by_construction_equals_reference():
+    """The by-construction answer of the large generator is the pure-Python reference's on its 1 / 40
+    sub-scene (every class of component of the full scene, the oversize one at full size)."""
+    c, want = R.case("scale_sub40"), R.expected("scale_sub40")
+    assert c.nodes == 40 * (52500 // 40) and want.dropped[0] == 1 and want.dropped[1] > 0
+    assert int((np.diff(want.trackOffsets) > N.TRK_SHORT_MAX).sum()) == 2100 // 40
+    R.assert_same(want, R.reference(c), "by construction against reference()")
+
+
+@pytest.mark.parametrize("name", list(R.LARGE))
+def test_twin_on_the_large_scenes(native, name):
+    c, want = R.case(name), R.expected(name)
+    T, got, _ = R.run("mcvHostBuildTracks", c)
+    assert T == want.T, native.last_error()
+    R.assert_same(got, want, name)
+    p = c.permuted(1)
+    assert not np.array_equal(p.pairs, c.pairs) and len(p.pairs) == len(c.pairs)
+    T, got, _ = R.run("mcvHostBuildTracks", p)
+    assert T == want.T, native.last_error()
+    R.assert_same(got, want, f"{name} permuted")
+
+
 @pytest.mark.parametrize("name", ["random_scene", "path_L600", "duplicate_edges", "joined_by_the_last_edge",
                                   "same_image_and_self_loop", "masked_half", "min_length_3"])
 def test_order_independence(native, name):
@@ -164,6 +232,8 @@ def test_declarations(native):
     assert "maxObs >= min(2 offsets[B], base[nImages])" in txt and "maxTracks >= maxObs / 2" in txt
     ktxt = (N.ROOT / "minicv_amd" / "csrc" / "kernels.h").read_text()
     assert f"kTrkShortMax = {N.TRK_SHORT_MAX};" in ktxt and f"kTrkLaunches = {N.TRK_LAUNCHES};" in ktxt
+    assert f"kTrkGrid = {N.TRK_GRID};" in ktxt and f"kTrkScanItems = {N.TRK_SCAN_ITEMS};" in ktxt
+    assert f"kTrkScanChunk = {N.TRK_SCAN_CHUNK};" in ktxt
     import minicv_amd
     assert minicv_amd.buildTracks is CM.buildTracks and minicv_amd.trackObservations is CM.trackObservations
     assert native.lib().mcvTestTracksStats(None) == -1

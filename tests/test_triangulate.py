@@ -71,6 +71,33 @@ def test_host_twins_equal_reference(native, name):
     assert p.enough_points()
 
 
+def test_scale_case_is_a_second_trip_case():
+    """What makes `scale` a second-trip case, from the mirrored constants, and what keeps it honest."""
+    ktxt = (N.ROOT / "minicv_amd" / "csrc" / "kernels.h").read_text()
+    assert f"kTriGrid = {N.TRI_GRID};" in ktxt and f"kTriShortMax = {N.TRI_SHORT_MAX};" in ktxt
+    p = R.scale()
+    assert p.n > N.TRI_GRID * 256 and p.nLong > 8 * N.TRI_GRID and p.T > 8 * N.TRI_GRID
+    L = p.lengths()
+    assert set(L.tolist()) == {3, N.TRI_SHORT_MAX + 1} and int((L > N.TRI_SHORT_MAX).sum()) == p.nLong
+    is_long = L > N.TRI_SHORT_MAX
+    assert not any(np.array_equal(is_long[:-k], is_long[k:]) for k in (64, 256, 1024))   # no period of the launch shape
+    s = p.lengths()[p.sample]
+    assert len(s) == R.SCALE_SAMPLE and int((s > N.TRI_SHORT_MAX).sum()) == R.SCALE_SAMPLE // 2
+    assert p.ref.enough_points() and p.ref.counters["duplicate"] >= 1 and p.ref.counters["angle"] >= 1
+    # the vectorised unproject is the reference's, to the bit
+    assert np.array_equal(R.bits(p.rays[p.sample_obs]), R.bits(p.ref.rays))
+
+
+def test_host_twins_on_the_scale_case(native):
+    p = R.scale()
+    k, pts, cnt, cost, vis = R.host_tracks(p)
+    assert k == int((cnt > 0).sum()) > p.T // 2, native.last_error()
+    p.assert_sample((pts, cnt, cost, vis), "mcvHostTriangulateTracks")
+    k2, rpts, rcnt = R.host_rays(p)
+    assert k2 == k
+    R.assert_bits((rpts, rcnt), (pts, cnt), "mcvHostIntersectRays against mcvHostTriangulateTracks")
+
+
 def test_host_twin_optional_statistics(native):
     p = R.problem("statistics")
     k, pts, cnt, cost, vis = R.host_tracks(p, stats=False)
