@@ -115,6 +115,30 @@ typedef struct {   /* MiniCVNative.h:79-86 (40 bytes) */
 } SiftConfig;
 MCV_API DetectorResult* cvDetectFeatures(char* data, int width, int height, int channels, int mode, void* config);
 MCV_API void cvFreeFeatures(DetectorResult* res);
+/* Batched detection: nImages independent cvDetectFeatures(mode 4) calls under one
+ * SiftConfig (NULL: the defaults), in one call whose kernel launches, stream synchronisations, copies
+ * and memsets do not grow with nImages. The images may differ in width, height and channels.
+ * results: the caller's array of nImages DetectorResult, filled by the call: results[i] holds exactly
+ * what cvDetectFeatures(images[i].data, width, height, channels, 4, config) returns (FeatureCount
+ * applies per image; an image without an octave or a keypoint gives PointCount 0 with non-NULL
+ * members), so the array goes straight into cvMatchFeaturesBatch / cvMatchAndFindModelBatch. Free it
+ * with cvFreeFeaturesBatch. Returns the total keypoint count (0 for nImages == 0), -1 on failure
+ * (mcvGetLastError; every results[i] is then all zero). Every argument is checked on the host before
+ * the device is touched, an image's checks are cvDetectFeatures' with the image index in the message,
+ * and one bad image fails the whole call. Design constants, not measurements: at most 4096 images
+ * (kSiftBatchMaxImages), at most 1 << 24 extremum candidates of all images together
+ * (kSiftBatchMaxCandidates; an image alone is held to cvDetectFeatures' 1 << 22), and at most 1 << 35
+ * bytes (kSiftBatchMaxWorkspaceBytes) of the buffers whose size the arguments fix (images, pyramids,
+ * blur scratch, buckets, candidate list); past any of them the error says to split the batch. */
+typedef struct {            /* 24 bytes */
+    const uint8_t* data;    /* height x width x channels bytes, row-major */
+    int width, height, channels;
+    int reserved;           /* must be 0 */
+} mcvImage;
+MCV_API long long cvDetectFeaturesBatch(const mcvImage* images, int nImages, int mode, void* config,
+                                        DetectorResult* results);
+/* Frees the members of results[0 .. nImages) and zeroes the structs. NULL and all-zero entries are fine. */
+MCV_API void cvFreeFeaturesBatch(DetectorResult* results, int nImages);
 /* Debug export — MiniCVNative.cpp:504 (no-op). */
 MCV_API void cvTest(void);
 /* Five-point minimal solver — MiniCVNative.cpp:368-382 / fivepoint.cpp:233-339 (one GPU solve of
@@ -1155,6 +1179,12 @@ MCV_API int mcvTestSiftStats(long long* stats8);
  * it. Returns 0, or -1 with an error for an unknown `what`, a null argument, a capBytes below the
  * stage's size, or a thread without a finished call on the current device. */
 MCV_API int mcvTestSiftStage(int what, void* out, long long capBytes, long long* count);
+/* stats8 of the calling thread's last cvDetectFeaturesBatch: {launches, synchronisations, copies, memsets,
+ * candidates, refined, oriented, returned}, the last four summed over the images. */
+MCV_API int mcvTestSiftBatchStats(long long* stats8);
+/* The plan of a batch, on the host alone (no device): out8 = {maxOctaves, launches, synchronisations,
+ * copies, memsets, buckets, workspace bytes, nImages with no octave}. Same argument checks as the call. */
+MCV_API int mcvTestSiftBatchPlan(const mcvImage* images, int nImages, int mode, const void* config, long long* out8);
 /* Host twin of cvBundleAdjust: the same arguments, checks, outputs, summary and return value, computed
  * sequentially by the host-compiled kernel arithmetic (ba_terms.h) in the kernels' summation orders. No GPU. */
 MCV_API int mcvHostBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,

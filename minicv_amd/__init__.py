@@ -9,7 +9,8 @@ from . import native
 from .native import RansacConfig, NativeError
 from .opencv import RansacParams, findHomography, findFundamentalMat, matchHamming, matchL2, matchL2U8, \
     recoverPose, findEssentialMatBatch, recoverPoseBatch, matchFeaturesBatch, matchAndFindModelBatch, solvePnPRansacBatch, \
-    refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch, detectFeatures, DetectedFeatures
+    refinePnPBatch, solvePnPRansacWithRefine, solvePnPRansacWithRefineBatch, detectFeatures, DetectedFeatures, \
+    detectFeaturesBatch
 from .native import SiftConfig
 from . import camera
 from .camera import Camera, CameraPose, findScaled, findScaledBatch, findScaledBatchCosts, triangulateTracks, \
@@ -19,4 +20,5 @@ __all__ = ["native", "RansacConfig", "NativeError", "RansacParams", "findHomogra
            "matchHamming", "matchL2", "matchL2U8", "recoverPose", "findEssentialMatBatch",
            "recoverPoseBatch", "matchFeaturesBatch", "matchAndFindModelBatch", "solvePnPRansacBatch",
            "refinePnPBatch", "solvePnPRansacWithRefine", "solvePnPRansacWithRefineBatch", "camera", "Camera", "CameraPose", "findScaled",
-           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts", "buildTracks", "trackObservations", "detectFeatures", "DetectedFeatures", "SiftConfig"]
+           "triangulateTracks", "findScaledBatch", "findScaledBatchCosts", "buildTracks", "trackObservations", "detectFeatures", "DetectedFeatures", "SiftConfig",
+           "detectFeaturesBatch"]

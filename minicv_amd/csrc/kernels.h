@@ -752,4 +752,40 @@ void launch_sift_order(const SiftPyramid& Y, const SiftOrder& O, int n, int feat
 void launch_sift_describe(const SiftPyramid& Y, const SiftRec* d_recs, int n, int descType, SiftKeyPointOut* d_kp,
                           uint8_t* d_u8, float* d_f32, hipStream_t s);
 
+// ---- batched SIFT detection (sift_batch.hip): the stages above over (image, tile),
+// (image, candidate) and (image, keypoint) grids. The kernels find an image's sizes and offsets in the
+// table of SiftBatchImage (sift_batch_plan.h), uploaded once; a block outside its image's extent or
+// past its last octave leaves before it touches memory or a barrier.
+struct SiftBatchImage;
+struct SiftBatchDevice {
+    const SiftBatchImage* table;
+    int nImages;
+    const uint8_t* img;                                      // the staged images
+    float *up, *tmp, *pyr;                                   // doubled bases, row-blur scratch, pyramids
+    const float* taps;
+    // d_ctr as above; icnt: candidates per image; koff: nImages + 1 offsets of the images' kept keypoints;
+    // part: kSiftBatchScanBlocks + 1 words of the grid-wide scans
+    unsigned *ctr, *icnt, *bcnt, *boff, *koff, *part;
+    int nBuckets;
+    int4* cand;                                              // (image << 4 | octave, layer, r, c)
+    unsigned capC;
+};
+void launch_sift_batch_grey_double(const SiftBatchDevice& D, int maxW, int maxH, hipStream_t s);
+// Blur `blur` (0: the doubled base into image 0 of octave 0; i: image i - 1 into image i) of octave o
+// of every image that has it. Two launches, sized by the largest image of that octave.
+void launch_sift_batch_blur(const SiftBatchDevice& D, int o, int blur, int tapOff, int R, int maxW, int maxH,
+                            hipStream_t s);
+void launch_sift_batch_downsample(const SiftBatchDevice& D, int o, int nl, int maxW, int maxH, hipStream_t s);
+void launch_sift_batch_extrema(const SiftBatchDevice& D, int o, int nl, float thr, int maxW, int maxH, hipStream_t s);
+void launch_sift_batch_refine(const SiftBatchDevice& D, const SiftParams& P, int nC, SiftKp* d_kps, hipStream_t s);
+void launch_sift_batch_orient(const SiftBatchDevice& D, const SiftKp* d_kps, int nC, SiftRec* d_recs,
+                              unsigned long long* d_keys, unsigned long long* d_starts, unsigned long long* d_rkeys,
+                              hipStream_t s);
+// The order stage over the n appended records of all images: 10 launches, 11 with featureCount > 0. O as
+// for the single call (its nBuckets, bcnt, boff and count are D's); d_pos: n + 1 words.
+void launch_sift_batch_order(const SiftBatchDevice& D, const SiftOrder& O, unsigned* d_pos, int n, int featureCount,
+                             hipStream_t s);
+void launch_sift_batch_describe(const SiftBatchDevice& D, const SiftRec* d_recs, int n, int descType,
+                                SiftKeyPointOut* d_kp, uint8_t* d_u8, float* d_f32, hipStream_t s);
+
 }  // namespace mcv

@@ -2,10 +2,12 @@
 // the separable blur on LDS tiles, the fused DoG / 26-neighbour pass, refinement (one lane per
 // candidate), orientation and descriptor (one wave per keypoint, integer histograms in LDS), and the
 // bucket passes that order, de-duplicate and select the keypoints. The arithmetic of every sample is
-// sift_math.h's, which the host twin compiles too; no kernel adds floats in an order that depends on
-// the hardware's scheduling.
+// sift_math.h's, which the host twin compiles too; the loops over tiles, patches and windows are
+// sift_device.h's, which the batch's kernels (sift_batch.hip) call too; no kernel adds floats in an
+// order that depends on the hardware's scheduling.
 #include "kernels.h"
 #include "sift_math.h"
+#include "sift_device.h"
 
 namespace mcv {
 namespace {
@@ -14,56 +16,20 @@ typedef unsigned long long u64;
 
 __global__ __launch_bounds__(256) void sift_grey_double_kernel(const uint8_t* __restrict__ img, int w, int h, int ch,
                                                                float* __restrict__ up) {
-    const int C = blockIdx.x * 256 + threadIdx.x, R = blockIdx.y;
-    if (C >= 2 * w) return;
-    const int c0 = C >> 1, r0 = R >> 1;
-    const int c1 = (C & 1) ? (c0 + 1 < w ? c0 + 1 : w - 1) : c0;
-    const int r1 = (R & 1) ? (r0 + 1 < h ? r0 + 1 : h - 1) : r0;
-    // rows (along x) first, then columns; every value is exact in float
-    float a = sift_grey(img + ((size_t)r0 * w + c0) * ch, ch);
-    float b = sift_grey(img + ((size_t)r1 * w + c0) * ch, ch);
-    if (C & 1) {
-        a = 0.5f * a + 0.5f * sift_grey(img + ((size_t)r0 * w + c1) * ch, ch);
-        b = 0.5f * b + 0.5f * sift_grey(img + ((size_t)r1 * w + c1) * ch, ch);
-    }
-    up[(size_t)R * (size_t)(2 * w) + C] = (R & 1) ? 0.5f * a + 0.5f * b : a;
+    sift_dev_grey_double(img, w, h, ch, up, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
 }
 
-// One row segment of kSiftRowTile outputs per block, the segment and its halo in LDS.
 __global__ __launch_bounds__(kSiftRowTile) void sift_blur_rows_kernel(const float* __restrict__ in,
                                                                       float* __restrict__ out, int w, int h,
                                                                       const float* __restrict__ taps, int R) {
     extern __shared__ float tile[];
-    const int r = blockIdx.y, x0 = blockIdx.x * kSiftRowTile;
-    const float* row = in + (size_t)r * (size_t)w;
-    for (int k = threadIdx.x; k < kSiftRowTile + 2 * R; k += kSiftRowTile) tile[k] = row[sift_reflect(x0 + k - R, w)];
-    __syncthreads();
-    const int c = x0 + threadIdx.x;
-    if (c >= w) return;
-    float acc = 0.0f;
-    for (int t = 0; t <= 2 * R; ++t) acc = acc + taps[t] * tile[threadIdx.x + t];
-    out[(size_t)r * (size_t)w + c] = acc;
+    sift_dev_blur_rows(in, out, w, taps, R, blockIdx.y, blockIdx.x * kSiftRowTile, tile);
 }
 
-// A tile of kSiftColTileW columns x kSiftColTileH rows per block, with a halo of R rows above and below.
 __global__ __launch_bounds__(256) void sift_blur_cols_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                              int w, int h, const float* __restrict__ taps, int R) {
     extern __shared__ float tile[];
-    const int cx = threadIdx.x & (kSiftColTileW - 1), ty = threadIdx.x / kSiftColTileW;
-    const int c = blockIdx.x * kSiftColTileW + cx, y0 = blockIdx.y * kSiftColTileH;
-    const int cc = c < w ? c : w - 1;
-    for (int k = ty; k < kSiftColTileH + 2 * R; k += 256 / kSiftColTileW)
-        tile[k * kSiftColTileW + cx] = in[(size_t)sift_reflect(y0 + k - R, h) * (size_t)w + cc];
-    __syncthreads();
-    if (c >= w) return;
-    const int per = kSiftColTileH / (256 / kSiftColTileW);
-    for (int q = 0; q < per; ++q) {
-        const int rr = ty * per + q, r = y0 + rr;
-        if (r >= h) break;
-        float acc = 0.0f;
-        for (int t = 0; t <= 2 * R; ++t) acc = acc + taps[t] * tile[(rr + t) * kSiftColTileW + cx];
-        out[(size_t)r * (size_t)w + c] = acc;
-    }
+    sift_dev_blur_cols(in, out, w, h, taps, R, blockIdx.x, blockIdx.y, tile);
 }
 
 __global__ __launch_bounds__(256) void sift_downsample_kernel(const float* __restrict__ src, int pw, float* __restrict__ dst,
@@ -72,56 +38,15 @@ __global__ __launch_bounds__(256) void sift_downsample_kernel(const float* __res
     if (c < w) dst[(size_t)r * (size_t)w + c] = src[(size_t)(2 * r) * (size_t)pw + 2 * c];
 }
 
-// DoG and the 26-neighbour test of one octave in one pass: a lane walks its pixel's 3 x 3 patch up the
-// Gaussian stack, keeps three DoG patches in registers, and tests the middle one. Candidates are
-// appended wave by wave: one counter add per wave, the lanes' places by their rank in the ballot.
+// DoG and the 26-neighbour test of one octave in one pass (sift_device.h); a wave covers 64 columns of
+// one row. Candidates are appended wave by wave.
 __global__ __launch_bounds__(256) void sift_extrema_kernel(const float* __restrict__ g, int w, int h, int o, int nl,
                                                            float thr, int4* __restrict__ cand, unsigned cap,
                                                            unsigned* __restrict__ ctr) {
-    const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * 64 + lane, r = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const bool active = r >= kSiftBorder && r < h - kSiftBorder && c >= kSiftBorder && c < w - kSiftBorder;
-    const size_t plane = (size_t)w * (size_t)h;
-    float gp[9], d0[9], d1[9], d2[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        gp[k] = active ? g[(size_t)(r + k / 3 - 1) * (size_t)w + (size_t)(c + k % 3 - 1)] : 0.0f;
-        d0[k] = d1[k] = d2[k] = 0.0f;
-    }
-    for (int L = 0; L < nl + 2; ++L) {
-        const float* gn = g + (size_t)(L + 1) * plane;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const float v = active ? gn[(size_t)(r + k / 3 - 1) * (size_t)w + (size_t)(c + k % 3 - 1)] : 0.0f;
-            d0[k] = d1[k];
-            d1[k] = d2[k];
-            d2[k] = v - gp[k];
-            gp[k] = v;
-        }
-        if (L < 2) continue;
-        const float v = d1[4];
-        bool is = active && fabsf(v) > thr;
-        if (is) {
-            bool mx = true, mn = true;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                mx = mx && v >= d0[k] && v >= d1[k] && v >= d2[k];
-                mn = mn && v <= d0[k] && v <= d1[k] && v <= d2[k];
-            }
-            is = v > 0.0f ? mx : mn;
-        }
-        const u64 m = __ballot(is);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            unsigned base = 0;
-            if (lane == leader) base = atomicAdd(&ctr[0], (unsigned)__popcll(m));
-            base = __shfl(base, leader);
-            if (is) {
-                const unsigned at = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                if (at < cap) cand[at] = make_int4(o, L - 1, r, c);
-            }
-        }
-    }
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    sift_dev_extrema(g, w, h, nl, thr, r, c, [=](bool is, int layer) {
+        sift_dev_append(is, make_int4(o, layer, r, c), cand, cap, &ctr[0], nullptr);
+    });
 }
 
 __global__ __launch_bounds__(256) void sift_refine_kernel(SiftPyramid Y, SiftParams P, const int4* __restrict__ cand,
@@ -136,52 +61,30 @@ __global__ __launch_bounds__(256) void sift_refine_kernel(SiftPyramid Y, SiftPar
     if (ok) atomicAdd(&ctr[1], 1u);
 }
 
-// One wave per refined candidate: the 36-bin histogram as 64-bit integer LDS atomics (the sum does not
-// depend on the order), then lane 0 smooths it and appends one record per peak.
+// One wave per refined candidate: the histogram and its peaks (sift_device.h), then lane 0 appends one
+// record per peak.
 __global__ __launch_bounds__(256) void sift_orient_kernel(SiftPyramid Y, const int4* __restrict__ cand,
                                                           const SiftKp* __restrict__ kps, int nC,
                                                           SiftRec* __restrict__ recs, u64* __restrict__ keys,
                                                           u64* __restrict__ starts, u64* __restrict__ rkeys,
                                                           unsigned* __restrict__ ctr, unsigned* __restrict__ bcnt) {
     __shared__ u64 hist[4][kSiftOriBins];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wv;
     bool valid = i < nC;
     SiftKp kp;
     kp.o = -1;
     if (valid) kp = kps[i];
     valid = valid && kp.o >= 0;
-    if (lane < kSiftOriBins) hist[wv][lane] = 0;
-    __syncthreads();
-    if (valid) {
-        const int w = Y.ow[kp.o], h = Y.oh[kp.o];
-        const float* img = Y.base + Y.obase[kp.o] + (size_t)kp.layer * (size_t)w * (size_t)h;
-        const int rad = sift_ori_radius(kp.scl), side = 2 * rad + 1, n = side * side;
-        const float es = sift_ori_escale(kp.scl);
-        for (int s = lane; s < n; s += 64) {
-            int bin;
-            long long q;
-            if (sift_ori_sample(img, w, h, kp.r, kp.c, s / side - rad, s % side - rad, es, bin, q))
-                atomicAdd(&hist[wv][bin], (u64)q);
-        }
-    }
-    __syncthreads();
-    if (valid && lane == 0) {
-        int bins[kSiftMaxPeaks];
-        float angles[kSiftMaxPeaks];
-        const int np = sift_ori_peaks((const long long*)hist[wv], bins, angles);
-        const unsigned base = np ? atomicAdd(&ctr[2], (unsigned)np) : 0u;
-        if (np) atomicAdd(&bcnt[sift_bucket(Y, kp.o, kp.layer, kp.r)], (unsigned)np);   // the row's count, for the order
-        const int4 q = cand[i];
-        const float sc = (float)(1 << kp.o) * 0.5f;
-        for (int k = 0; k < np; ++k) {
-            const size_t at = (size_t)base + (size_t)k;   // at < 18 nC, the buffers' size
-            recs[at] = SiftRec{((float)kp.c + kp.xc) * sc, ((float)kp.r + kp.xr) * sc, kp.size, angles[k],
-                               kp.response, kp.octave, kp.o, kp.layer, kp.r, kp.c, kp.scl, 0};
-            keys[at] = sift_key(kp.o, kp.layer, kp.r, kp.c, bins[k]);
-            starts[at] = sift_key(q.x, q.y, q.z, q.w, bins[k]);
-            rkeys[at] = (u64)(0xffffffffu - __float_as_uint(kp.response));
-        }
+    const int o = valid ? kp.o : 0;
+    int bins[kSiftMaxPeaks];
+    float angles[kSiftMaxPeaks];
+    const int np = sift_dev_orient(Y.base + Y.obase[o], Y.ow[o], Y.oh[o], kp, valid, hist[wv], bins, angles);
+    if (np) {   // lane 0 of a valid wave
+        const unsigned base = atomicAdd(&ctr[2], (unsigned)np);
+        atomicAdd(&bcnt[sift_bucket(Y, kp.o, kp.layer, kp.r)], (unsigned)np);   // the row's count, for the order
+        // base + np <= 18 nC, the buffers' size
+        sift_dev_orient_records(kp, cand[i], np, bins, angles, (size_t)base, 0, recs, keys, starts, rkeys);
     }
 }
 
@@ -244,15 +147,8 @@ __global__ __launch_bounds__(256) void sift_bucket_rank_kernel(SiftPyramid Y, co
     const int i = perm[p];
     const u64 ki = keys[i], si = starts[i];
     const int b = sift_key_bucket(Y, ki);
-    const unsigned lo = boff[b], hi = boff[b + 1];
-    unsigned L = 0, E = 0;
-    for (unsigned m = lo; m < hi; ++m) {
-        const int j = perm[m];
-        const u64 kj = keys[j];
-        L += kj < ki ? 1u : 0u;
-        E += (kj == ki && starts[j] < si) ? 1u : 0u;
-    }
-    const unsigned q = lo + L + E;   // < hi <= n: the other records of the row are hi - lo - 1
+    unsigned E;
+    const unsigned q = sift_dev_rank(keys, starts, perm, boff[b], boff[b + 1], ki, si, E);   // < n
     sortedIdx[q] = i;
     skeys[q] = ki;
     srkeys[q] = rkeys[i];
@@ -312,42 +208,20 @@ __global__ __launch_bounds__(1024) void sift_compact_kernel(const uint8_t* __res
     if (threadIdx.x == 0) *count = base;
 }
 
-// One wave per output keypoint: the 4 x 4 x 8 histogram as 64-bit integer LDS atomics, lane 0
-// normalises, the wave writes the row and the KeyPoint2d.
+// One wave per output keypoint (sift_device.h).
 __global__ __launch_bounds__(256) void sift_describe_kernel(SiftPyramid Y, const SiftRec* __restrict__ recs, int n,
                                                             int descType, SiftKeyPointOut* __restrict__ kpOut,
                                                             uint8_t* __restrict__ descU8, float* __restrict__ descF32) {
     __shared__ u64 sum[4][kSiftDescLen];
     __shared__ float fo[4][kSiftDescLen];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wv;
     const bool valid = i < n;
-    for (int k = lane; k < kSiftDescLen; k += 64) sum[wv][k] = 0;
-    __syncthreads();
     SiftRec q;
-    if (valid) {
-        q = recs[i];
-        const int w = Y.ow[q.o], h = Y.oh[q.o];
-        const float* img = Y.base + Y.obase[q.o] + (size_t)q.layer * (size_t)w * (size_t)h;
-        const SiftDescFrame F = sift_desc_frame(q.angle, q.scl, w, h);
-        const int side = 2 * F.radius + 1;
-        const long long ns = (long long)side * side;
-        u64* mySum = sum[wv];
-        for (long long s = lane; s < ns; s += 64)
-            sift_desc_sample(img, w, h, q.r, q.c, (int)(s / side) - F.radius, (int)(s % side) - F.radius, F,
-                             [mySum](int k, long long v) { atomicAdd(&mySum[k], (u64)v); });
-    }
-    __syncthreads();
-    if (valid && lane == 0) sift_desc_finish((const long long*)sum[wv], fo[wv]);
-    __syncthreads();
-    if (!valid) return;
-    for (int k = lane; k < kSiftDescLen; k += 64) {
-        if (descType == 0)
-            descU8[(size_t)i * kSiftDescLen + k] = sift_desc_byte(fo[wv][k]);
-        else
-            descF32[(size_t)i * kSiftDescLen + k] = fo[wv][k];
-    }
-    if (lane == 0) kpOut[i] = SiftKeyPointOut{q.x, q.y, q.size, q.angle, q.response, q.octave, -1};
+    q.o = 0;
+    if (valid) q = recs[i];
+    sift_dev_describe(Y.base + Y.obase[q.o], Y.ow[q.o], Y.oh[q.o], q, valid, (size_t)(valid ? i : 0), descType, kpOut,
+                      descU8, descF32, sum[wv], fo[wv]);
 }
 
 inline unsigned blocks(long long n, int per) { return (unsigned)(n > 0 ? (n + per - 1) / per : 1); }

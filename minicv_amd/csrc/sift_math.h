@@ -23,6 +23,14 @@ static const double kSiftMaxSigma = 4.0;
 // (32 + 2 x 111 rows of 64 floats) is then 65 024 bytes, under the 64 KiB a launch gets without opting in
 static const int kSiftMaxRadius = 111;
 static const int kSiftMaxCandidates = 1 << 22;   // extremum candidates of one call
+// cvDetectFeaturesBatch. The three caps are design constants, not measurements: the image
+// count keeps the image index in a grid's z and in 27 bits of a candidate record, the candidate cap
+// keeps 18 records per candidate in 32-bit places, and the workspace cap (the buffers the plan sizes:
+// images, pyramids, scratch, buckets, candidates) refuses a batch that should be split.
+static const int kSiftBatchMaxImages = 4096;
+static const int kSiftBatchMaxCandidates = 1 << 24;              // of all images of one call together
+static const unsigned long long kSiftBatchMaxWorkspaceBytes = 1ull << 35;
+static const int kSiftKeyBits = 45;        // of sift_key; a batch puts the image index above them
 
 struct SiftParams {
     int nl;              // OctaveLayers

@@ -103,6 +103,12 @@ class SiftConfig(C.Structure):
         return c
 
 
+class mcvImage(C.Structure):
+    """One image of cvDetectFeaturesBatch (24 bytes): data is height x width x channels bytes, reserved 0."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int),
+                ("reserved", C.c_int)]
+
+
 class MatchConfig(C.Structure):
     _fields_ = [("ratio", C.c_float), ("crossCheck", C.c_int), ("maxDistance", C.c_float), ("model", C.c_int)]
 
@@ -180,6 +186,29 @@ def sift_launches(width: int, height: int, octave_layers: int = 3, feature_count
         return 0
     return (L["fixed"] + n * (L["per_blur"] * (octave_layers + 2) + L["extrema"]) + (n - 1) * L["downsample"]
             + (L["select"] if feature_count > 0 else 0))
+
+
+# cvDetectFeaturesBatch: the caps (sift_math.h kSiftBatchMax*), the bytes of one row of the
+# per-image table, the launches that do not depend on the octaves, the other three counts and the blocks
+# of the grid-wide scans (sift_batch_plan.h)
+SIFT_BATCH_MAX_IMAGES = 4096
+SIFT_BATCH_MAX_CANDIDATES = 1 << 24
+SIFT_BATCH_MAX_WORKSPACE_BYTES = 1 << 35
+SIFT_BATCH_IMAGE_BYTES = 360
+SIFT_BATCH_LAUNCHES_FIXED = 16
+SIFT_BATCH_SYNCS, SIFT_BATCH_COPIES, SIFT_BATCH_MEMSETS = 4, 8, 1
+SIFT_BATCH_SCAN_BLOCKS = 1024
+
+
+def sift_batch_launches(sizes, octave_layers: int = 3, feature_count: int = 0) -> int:
+    """Kernel launches of one cvDetectFeaturesBatch call on images of the (width, height) in `sizes`: the
+    single call's formula for the largest nOctaves among them, with SIFT_BATCH_LAUNCHES_FIXED (0 when no
+    image has an octave)."""
+    n, L = max([sift_octaves(w, h) for w, h in sizes], default=0), SIFT_LAUNCHES
+    if n == 0:
+        return 0
+    return (SIFT_BATCH_LAUNCHES_FIXED + n * (L["per_blur"] * (octave_layers + 2) + L["extrema"])
+            + (n - 1) * L["downsample"] + (L["select"] if feature_count > 0 else 0))
 
 
 SIN_MIN_ANGLE = float.fromhex("0x1.1de58c9f7dc27p-5")   # hyp_rays.h kSinMinAngle
@@ -330,6 +359,10 @@ SIGNATURES = {
     "mcvHostDetectFeatures": (_P, [_P, _I, _I, _I, _I, _P]),
     "mcvTestSiftStats": (_I, [_P]),
     "mcvTestSiftStage": (_I, [_I, _P, C.c_longlong, _P]),
+    "cvDetectFeaturesBatch": (C.c_longlong, [_P, _I, _I, _P, _P]),
+    "cvFreeFeaturesBatch": (None, [_P, _I]),
+    "mcvTestSiftBatchStats": (_I, [_P]),
+    "mcvTestSiftBatchPlan": (_I, [_P, _I, _I, _P, _P]),
     "mcvHostBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcvHostBaLinearize": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),

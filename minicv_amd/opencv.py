@@ -758,3 +758,45 @@ def detectFeatures(img, mode: int = N.FEATURE_SIFT, config: "N.SiftConfig | None
     mode=N.FEATURE_SIFT is built; config: a N.SiftConfig, or None for cv::SIFT's defaults with byte
     descriptors. Raises N.NativeError where the library returns NULL."""
     return _detect_features("cvDetectFeatures", img, mode, config)
+
+
+def _image_array(img, what: str):
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError(f"{what} must be a uint8 array [h][w] or [h][w][c]")
+    return a
+
+
+def _copy_out(r) -> DetectedFeatures:
+    """A filled native DetectorResult -> DetectedFeatures (the native arrays are copied, not kept)."""
+    n, f32 = r.PointCount, r.DescriptorElementType == 5
+    kp = np.zeros(n, dtype=KEYPOINT_DTYPE)
+    d = np.zeros((n, 128), dtype=np.float32 if f32 else np.uint8)
+    if n:
+        N.C.memmove(kp.ctypes.data, r.Points, kp.nbytes)
+        N.C.memmove(d.ctypes.data, r.Descriptors, d.nbytes)
+    assert r.DescriptorEntries == 128 * n
+    return DetectedFeatures(kp, d)
+
+
+def detectFeaturesBatch(images, mode: int = N.FEATURE_SIFT, config: "N.SiftConfig | None" = None) -> list:
+    """cvDetectFeaturesBatch: detectFeatures on every image of a list in one call, under one
+    config; the images may differ in size and channels. -> a list of DetectedFeatures, element i equal to
+    detectFeatures(images[i], mode, config) bit for bit, ready for matchFeaturesBatch and
+    matchAndFindModelBatch. Raises N.NativeError where the library fails (one bad image fails the call)."""
+    arrays = [_image_array(img, f"images[{i}]") for i, img in enumerate(images)]
+    n = len(arrays)
+    ims = (N.mcvImage * max(n, 1))()
+    for i, a in enumerate(arrays):
+        ims[i] = N.mcvImage(a.ctypes.data, a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2], 0)
+    res = (N.DetectorResult * max(n, 1))()
+    L = N.lib()
+    total = L.cvDetectFeaturesBatch(N.C.addressof(ims), n, int(mode), N.C.addressof(config) if config is not None else None,
+                                    N.C.addressof(res))
+    try:
+        N.check(total >= 0, "cvDetectFeaturesBatch")
+        out = [_copy_out(res[i]) for i in range(n)]
+        assert sum(len(f) for f in out) == total
+    finally:
+        L.cvFreeFeaturesBatch(N.C.addressof(res), n)
+    return out
