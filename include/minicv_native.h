@@ -945,7 +945,9 @@ MCV_API int mcvTestEigLogCap(int cap);
  * homography evaluate, read after its stream was synchronised: [0] 0 = the stages pruned, 1 = no
  * candidate, 2 = sampler failure in the chunk, 3 = first boundary too late, 4 = forced off (mode 2),
  * 5 = the call did not qualify, -1 = no evaluate yet; [1] B, the candidate's full count; [2] the
- * number of stages; [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
+ * number of stages (4, or 5 where the per-cell bound's second pass runs: the plan then has the half boundary,
+ * stage 1 in two launches);
+ * [3..9] the stage boundaries in points (stage s sweeps [3 + s], [4 + s]);
  * [10..15] the slots alive entering each stage ([10]: the slots stage 0 swept, fewer than the chunk's where
  * stage 0 ran on a leading subset, see mcvTestHStage0Slots; [4] then reads 0). Not thread-safe: tests only. */
 MCV_API int mcvTestHStaging(int mode, long long* stats);
@@ -957,6 +959,22 @@ MCV_API int mcvTestHStaging(int mode, long long* stats);
  * slots stage 0 swept, not the chunk's, and stats[4] (the boundary stage 1 starts at) reads 0. Not thread-safe:
  * tests only. */
 MCV_API int mcvTestHStage0Slots(int slots);
+/* The second pass of the per-cell bound (the candidate-relative test and the per-slot points-left). mode 0: where
+ * the rule or mcvTestHCellMode's mode 1 engages it, 2: never (the box pass alone; the stages' survivor tests then
+ * use the points not yet processed, and the plan has no half boundary); any other mode leaves the setting. Returns
+ * the previous mode, -1 on error. It exists because mcvTestHCellMode's mode 1 forces both passes: the box pass
+ * alone otherwise runs only under the automatic rule, from 2^31 (hypothesis, correspondence) evaluations, which no
+ * test can afford to check against the oracle. Not thread-safe: tests only. */
+MCV_API int mcvTestHCellSecondPass(int mode);
+/* The stage plan of the staged homography sweep for N correspondences, computed on the host by the function the
+ * planner kernel runs (no device is touched). candidate: stage 0 named one (its full count is B); failure: the
+ * chunk holds a sampler failure; cellBound 0: no per-cell bound, 1: its box pass alone (a shorter stage 0), 2: with
+ * its second pass, which puts the half boundary in the middle of stage 1's range; subset: stage 0 swept a leading
+ * subset (only with cellBound), so stage 1 starts at point 0. out (10 ints): [0] the reason as mcvTestHStaging's
+ * stats[0] (0 = the stages prune), [1] the number of stages, [2] stage 0's range in pairs of correspondences,
+ * [3..9] the stage boundaries in pairs (stage s sweeps the pairs [3 + s], [4 + s]; the last boundary is
+ * (N + 1) / 2). Returns the number of stages, -1 on error. */
+MCV_API int mcvHostHStagePlan(int N, int candidate, int failure, int B, int cellBound, int subset, int* out);
 /* The per-cell inlier upper bound that drops hypotheses before stage 1 of the staged homography sweep.
  * mode 0: automatic (where the staged sweep's own size rule holds, from 20000 correspondences; its second pass,
  * the candidate-relative test and the per-slot points-left of the later compactions, from 35000), 1: both

@@ -97,12 +97,68 @@ static const int kHStageMinN = 4096;
 // why a staged evaluation pruned nothing (control block / mcvTestHStaging stats[0]; 0 = it pruned)
 enum { kHStageNoCandidate = 1, kHStageSamplerFailure = 2, kHStageLate = 3, kHStageForcedOff = 4,
        kHStageNotApplicable = 5 };
-// the per-cell bound's other buffers (with d_cells): cell ids (N ints), prefix table (kHStageLater x cells ints),
-// per-slot points left in uncertified cells (kHStageLater x hypCount ints)
+// Where the per-cell bound's second pass runs, one more boundary halves stage 1's range (the half boundary,
+// DESIGN.md §7): stage 1 then runs its list in two launches, and the slots that cannot reach B any more at the
+// middle skip the second. Only there: without the per-slot `left` the test at a boundary before the first
+// pruning boundary can drop nothing (count + N - processed >= B by that boundary's construction).
+// kHStageCellLater: the boundaries behind a list stage there, each with a `left` row.
+static const int kHStageCellLater = kHStageLater + 1;
+// the per-cell bound's other buffers (with d_cells): cell ids (N ints), prefix table (kHStageCellLater x cells
+// ints), per-slot points left in uncertified cells (kHStageCellLater x hypCount ints)
 struct HCellBufs {
     int *id, *pref, *left;
 };
 static const int kHCellLater = kHStageMax - 2;   // the most later boundaries a slot keeps a `left` figure for
+static_assert(kHStageCellLater <= kHCellLater && 2 + kHStageCellLater <= kHStageMax, "control block layout");
+
+// The stage boundaries (in pairs) from the candidate's full count B: the arithmetic of mcv_h_stage_plan, which
+// the kernel runs on the device and h_stage_plan_host (mcvHostHStagePlan) on the host. The first pruning boundary p1 is the first
+// point count at which a slot can fall below the bound (N - B) plus the slack, rounded up to a trip and not
+// before the prefix pa; the later stages split the rest evenly. Pruning switches itself off (reason != 0: p1 and
+// every later boundary are nPairs, so the stage behind boundary 1 runs every slot to the end and the others are
+// empty) without a candidate, with a sampler failure in the chunk and when p1 lies beyond latest/256 of the pairs.
+// subset: stage 1 starts at point 0 (boundary 1 is 0), since the counts buffer holds no stage-0 partials.
+// half: one more boundary in the middle of stage 1's range [boundary 1, p1), rounded down to a trip so that
+// every stage still starts trip-aligned; with one trip or none in the range it collapses onto the range's start
+// and the first half is empty. Boundaries are non-decreasing; all but the last are multiples of trip.
+struct HStagePlan {
+    int reason, stages;
+    int bound[kHStageMax + 1];
+};
+__host__ __device__ inline HStagePlan h_stage_plan(int N, int trip, int later, int slackPts, int latest256,
+                                                   bool subset, bool half, bool candidate, bool failure, int B,
+                                                   int pa) {
+    HStagePlan pl;
+    const int nPairs = (N + 1) / 2;
+    pl.reason = 0;
+    int p1 = nPairs;
+    if (!candidate) pl.reason = kHStageNoCandidate;
+    else if (failure) pl.reason = kHStageSamplerFailure;
+    else {
+        const int64_t pts = (int64_t)N - B + slackPts;
+        const int64_t pr = ((pts + 1) / 2 + trip - 1) / trip * trip;
+        p1 = pr < pa ? pa : (pr > nPairs ? nPairs : (int)pr);
+        if ((int64_t)p1 * 256 > (int64_t)nPairs * latest256) pl.reason = kHStageLate;
+    }
+    if (pl.reason) p1 = nPairs;
+    int n = 0;
+    pl.bound[n++] = 0;
+    const int start = subset ? 0 : pa;
+    pl.bound[n++] = start;
+    if (half) pl.bound[n++] = pl.reason ? nPairs : start + (p1 - start) / trip / 2 * trip;
+    pl.bound[n++] = p1;
+    const int trips = (nPairs - p1) / trip;   // whole trips left after the first pruning boundary
+    for (int s = 1; s <= later; ++s)
+        pl.bound[n++] = s == later ? nPairs : p1 + (int)((int64_t)trips * s / later) * trip;
+    pl.stages = n - 1;
+    for (; n <= kHStageMax; ++n) pl.bound[n] = 0;
+    return pl;
+}
+// The plan of a staged evaluate of N correspondences on the host, with the constants launch_h_verify_staged
+// gives the planner kernel (ransac_h_stage.hip holds both). cellBound: the per-cell bound runs (a shorter stage 0);
+// half: its second pass runs too (the half boundary); subset: stage 0 swept a leading subset. pa: stage 0's pairs.
+HStagePlan h_stage_plan_host(int N, bool candidate, bool failure, int B, bool cellBound, bool half, bool subset,
+                             int* pa);
 // what the two bound passes read beside the cell table: the record list of the non-empty cells (h_cell_pre.h:
 // h_cell_rec_ints(cells) ints, written by launch_h_cell_pre; always needed), the switch of the box test's fp32
 // prefilter (0: fp64 runs alone) and two counters, the (model, cell) tests of the passes and the undecided of

@@ -8,7 +8,8 @@
 // Mirrors cv::findHomography(..., RANSAC, thr, mask, maxIters, conf) of OpenCV 4.x
 // [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
 // Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHCellRel,
-// mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma, mcvTestHGenRow, mcvTestHGenerate, mcvHostHGenRow).
+// mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma, mcvTestHGenRow, mcvTestHGenerate, mcvHostHGenRow,
+// mcvHostHStagePlan, mcvTestHCellSecondPass).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -36,6 +37,8 @@ static thread_local Plan* t_hstage_plan = nullptr;
 // its two grids
 static int g_hcell_mode = 0;
 static int g_hcell_G = kHCellG, g_hcell_Gs = kHCellGs;
+// mcvTestHCellSecondPass: the bound's second pass: 0 the rule (and mcvTestHCellMode's mode 1), 2 never
+static int g_hcell_rel_mode = 0;
 // mcvTestHCellPre: the box test's fp32 prefilter (h_cell_pre.h): 0 automatic (on), 1 off; and where the calling
 // thread's last bound passes left their counters: a plan's device counters, or a hook call's own figures
 static int g_hcell_pre_mode = 0;
@@ -198,10 +201,10 @@ void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int
     // chunk's first failure; the plan takes the earlier of the two, and any failure switches pruning off
     // (kHStageSamplerFailure) with stage 1 running every slot from 0 to the end: full counts for the host's
     // fallback. No candidate among the subset (key 0), and the late-boundary rule: the same, every slot from 0 to
-    // the end. Recount marks: kStatusRedo marks of slots outside the subset first appear in stage 1; the first
-    // compaction reads them (count < 0: not listed) before the recount overwrites them, as it does for the marks
-    // stage 1 always could set; a mark stage 0 left in the scratch buffer is set again by stage 1, which tests the
-    // same model against the same extents.
+    // the end. Recount marks: kStatusRedo marks of slots outside the subset first appear in stage 1; every
+    // compaction reads them (count < 0: not listed) and the recount runs once, behind the last stage, as for the
+    // marks stage 1 always could set; a mark stage 0 left in the scratch buffer is set again by stage 1, which
+    // tests the same model against the same extents.
     // With the bound the later compactions read points-left per slot: left = the correspondences not yet
     // processed that lie in cells the bound did not certify for the slot's model. The unprocessed points of
     // certified cells are outliers of that model, so only `left` of the N - processed points can still add to
@@ -211,6 +214,18 @@ void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int
     // left >= full count >= B at every boundary and are never dropped (inclusive test, so ties stay).
     // Everything else above stands as written. Engaged where the size rule itself stages the call and
     // N >= kHCellMinN (kernels.h: the measured rows); forced staging of a small call keeps the plain stages.
+    // The half boundary (where the bound's second pass runs: one more boundary in the middle of stage 1's range,
+    // kernels.h) is one more place where the same test runs, on the same terms: a slot dropped there on
+    // count-so-far + left < B has a full count below B, with `left` its own third row of the per-slot figures,
+    // built for that boundary exactly as the other two. The sentence above covers "every boundary", so the
+    // candidate and the winners pass this one too. Without the second pass `left` is N - processed, with which
+    // nothing can be dropped before the first pruning boundary: there the plan keeps its four stages.
+    // An empty stage (boundaries that coincide: B near N puts the first pruning boundary on the prefix, a range
+    // of one trip puts the half boundary on its start) adds nothing to any count; the compaction behind it
+    // applies the test to the unchanged counts and hands the list on. With pruning off on the device
+    // (reason != 0) the stage behind boundary 1 runs every slot to the end and every later list stays empty.
+    // The test stays in mcv_h_stage_compact: run in the tail of the stage kernel's own waves (one atomic per
+    // wave of 6 slots in place of one per 64) it was measured slower ("The half boundary").
     const bool stageable = !fused && keyOnly;
     const bool sized = N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals;
     const bool staged = stageable && g_hstage_mode != 2 && (g_hstage_mode == 1 || sized);
@@ -218,7 +233,7 @@ void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int
     t_hstage_plan = &P;
     const bool cellBound = staged && g_hcell_mode != 2 && (g_hcell_mode == 1 || (sized && N >= kHCellMinN));
     // the bound's second pass costs a slot the same whatever N and saves in proportion to N (kernels.h)
-    const bool cellRel = cellBound && (g_hcell_mode == 1 || N >= kHCellRelMinN);
+    const bool cellRel = cellBound && g_hcell_rel_mode != 2 && (g_hcell_mode == 1 || N >= kHCellRelMinN);
     // stage 0 on a leading subset of the slots, where the bound runs and the chunk is large (or the hook says so)
     int stage0Slots = 0;
     if (cellBound) {
@@ -237,8 +252,8 @@ void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int
             P.hcellPreStats.ensure(2);
             if (cellRel) {
                 P.hcellId.ensure((size_t)N);
-                P.hcellPref.ensure(cells * kHStageLater);
-                P.hcellLeft.ensure((size_t)hypCount * kHStageLater);
+                P.hcellPref.ensure(cells * kHStageCellLater);
+                P.hcellLeft.ensure((size_t)hypCount * kHStageCellLater);
             }
         }
     }
@@ -569,6 +584,33 @@ extern "C" MCV_API int mcvTestHStage0Slots(int slots) {
         const int prev = g_hstage0_slots;
         if (slots >= 0) g_hstage0_slots = slots;
         return prev;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the switch of the per-cell bound's second pass.
+extern "C" MCV_API int mcvTestHCellSecondPass(int mode) {
+    MCV_GUARD(-1, {
+        const int prev = g_hcell_rel_mode;
+        if (mode == 0 || mode == 2) g_hcell_rel_mode = mode;
+        return prev;
+    })
+}
+
+// Host hook (declared in minicv_native.h): the stage plan the staged sweep's planner kernel computes, by the same
+// function and with the same constants (h_stage_plan_host, ransac_h_stage.hip). No device is touched.
+extern "C" MCV_API int mcvHostHStagePlan(int N, int candidate, int failure, int B, int cellBound, int subset,
+                                         int* out) {
+    MCV_GUARD(-1, {
+        if (N < 4 || B < 0 || B > N || cellBound < 0 || cellBound > 2 || !out)
+            fail("mcvHostHStagePlan: bad arguments");
+        int pa = 0;
+        const HStagePlan pl = h_stage_plan_host(N, candidate != 0, failure != 0, B, cellBound != 0, cellBound == 2,
+                                                subset != 0, &pa);
+        out[0] = pl.reason;
+        out[1] = pl.stages;
+        out[2] = pa;
+        for (int i = 0; i <= kHStageMax; ++i) out[3 + i] = pl.bound[i];
+        return pl.stages;
     })
 }
 

@@ -117,6 +117,29 @@ __global__ __launch_bounds__(1024) void mcv_h_stage_count(const float4* __restri
     }
 }
 
+// What the planner gets beside B, for the kernel and its host twin alike: the trip, the stages behind the first
+// pruning boundary, the slack, the late-boundary rule and stage 0's range in pairs: ~N / kHStagePrefixDiv points
+// (N / kHCellPrefixDiv with the per-cell bound: stage 0 is then the one full-width stage left), a whole number of
+// trips (at least one where N has one).
+struct HStagePlanArgs {
+    int trip, later, slackPts, latest256, pa;
+};
+static HStagePlanArgs h_stage_plan_args(int N, bool cellBound) {
+    const int trip = 64 * kCertNP, nFull = N / 2 / trip * trip;
+    int pa = (N / (cellBound ? kHCellPrefixDiv : kHStagePrefixDiv) / 2 + trip / 2) / trip * trip;
+    if (pa < trip) pa = trip;
+    if (pa > nFull) pa = nFull;
+    return HStagePlanArgs{trip, kHStageLater, N / kHStageSlackDiv, kHStageLatest256, pa};
+}
+
+HStagePlan h_stage_plan_host(int N, bool candidate, bool failure, int B, bool cellBound, bool half, bool subset,
+                             int* pa) {
+    const HStagePlanArgs a = h_stage_plan_args(N, cellBound);
+    if (pa) *pa = a.pa;
+    return h_stage_plan(N, a.trip, a.later, a.slackPts, a.latest256, cellBound && subset, cellBound && half,
+                        candidate, failure, B, a.pa);
+}
+
 // One thread: the stage boundaries from B. The first boundary is the first point count at which a
 // slot can fall below the bound (N - B) plus the slack, rounded up to a trip; the later stages split
 // the rest evenly. Pruning switches itself off (stage 1 runs every slot to the end) without a
@@ -126,10 +149,11 @@ __global__ __launch_bounds__(1024) void mcv_h_stage_count(const float4* __restri
 // subset's; the chunk's first sampler failure is the earlier of the subset's and the one a pass over every slot's
 // status left in ctl[kCtlFailAll]; and stage 1 starts at point 0 (boundary 1 is reset), since the counts buffer
 // holds no stage-0 partials.
+// half: the half boundary in the middle of stage 1's range (with the per-cell bound's second pass). The
+// arithmetic is h_stage_plan (kernels.h), shared with the host twin above.
 __global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int later, int slackPts, int latest256,
-                                 int subset) {
+                                 int subset, int half) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int nPairs = (N + 1) / 2;
     const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
     int64_t fail = *(const int64_t*)(ctl + kCtlKey + 2);
     if (subset) {
@@ -137,27 +161,36 @@ __global__ void mcv_h_stage_plan(int* __restrict__ ctl, int N, int trip, int lat
         fail = all < fail ? all : fail;
         *(int64_t*)(ctl + kCtlKey + 2) = fail;
     }
-    const int pa = ctl[kCtlBound + 1];
-    int reason = 0;
-    int p1 = nPairs;
-    if (key == 0) reason = kHStageNoCandidate;
-    else if (fail != INT64_MAX) reason = kHStageSamplerFailure;
-    else {
-        const int64_t pts = (int64_t)N - ctl[kCtlB] + slackPts;
-        const int64_t pr = ((pts + 1) / 2 + trip - 1) / trip * trip;
-        p1 = pr < pa ? pa : (pr > nPairs ? nPairs : (int)pr);
-        if ((int64_t)p1 * 256 > (int64_t)nPairs * latest256) reason = kHStageLate;
-    }
-    if (reason) p1 = nPairs;
-    ctl[kCtlReason] = reason;
-    ctl[kCtlStages] = 2 + later;
-    ctl[kCtlBound + 2] = p1;
-    const int trips = (nPairs - p1) / trip;   // whole trips left after the first boundary
-    for (int s = 1; s <= later; ++s) {
-        int b = s == later ? nPairs : p1 + (int)((int64_t)trips * s / later) * trip;
-        ctl[kCtlBound + 2 + s] = b;
-    }
-    if (subset) ctl[kCtlBound + 1] = 0;
+    const HStagePlan pl = h_stage_plan(N, trip, later, slackPts, latest256, subset != 0, half != 0, key != 0,
+                                       fail != INT64_MAX, ctl[kCtlB], ctl[kCtlBound + 1]);
+    ctl[kCtlReason] = pl.reason;
+    ctl[kCtlStages] = pl.stages;
+#pragma unroll
+    for (int i = 1; i <= kHStageMax; ++i)
+        if (i <= pl.stages) ctl[kCtlBound + i] = pl.bound[i];
+}
+
+// Who goes on past a boundary: a slot with a count (a status, count < 0, never enters a list) that can still
+// reach B. Inclusive, so ties survive.
+__device__ __forceinline__ bool h_stage_keeps(int count, int left, int B) { return count >= 0 && count + left >= B; }
+
+// `left` of a slot at a boundary: its own figure where the per-cell bound's second pass wrote one (row: the
+// boundary's row of slotLeft), else the points not yet processed at the boundary (given in pairs).
+__device__ __forceinline__ int h_stage_left(const int* __restrict__ row, int slot, int N, int boundPairs) {
+    if (row) return row[slot];
+    const int done2 = 2 * boundPairs;
+    return N - (done2 < N ? done2 : N);
+}
+
+// Appends the lanes with `keep` to a survivor list (ballot, one atomic per wave, any order).
+__device__ __forceinline__ void h_list_push(bool keep, int slot, int* total, int* __restrict__ dst) {
+    const uint64_t b = __ballot(keep);
+    if (b == 0) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(total, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
 }
 
 // Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
@@ -174,34 +207,14 @@ __global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict
     if (ctl[kCtlReason] != 0) return;
     const int n = src ? ctl[kCtlAlive + stage - 1] : hypCount;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const int done2 = 2 * ctl[kCtlBound + stage];
-    const int rest = N - (done2 < N ? done2 : N);
+    const int* row = slotLeft ? slotLeft + (size_t)(stage - 2) * hypCount : nullptr;
     bool keep = false;
     int slot = 0;
     if (i < n) {
         slot = src ? src[i] : i;
-        const int c = counts[slot];
-        const int left = slotLeft ? slotLeft[(size_t)(stage - 2) * hypCount + slot] : rest;
-        keep = c >= 0 && c + left >= ctl[kCtlB];
+        keep = h_stage_keeps(counts[slot], h_stage_left(row, slot, N, ctl[kCtlBound + stage]), ctl[kCtlB]);
     }
-    const uint64_t b = __ballot(keep);
-    if (b == 0) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(ctl + kCtlAlive + stage, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
-}
-
-// Appends the lanes with `keep` to a survivor list (ballot, one atomic per wave, any order).
-__device__ __forceinline__ void h_list_push(bool keep, int slot, int* total, int* __restrict__ dst) {
-    const uint64_t b = __ballot(keep);
-    if (b == 0) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(total, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
+    h_list_push(keep, slot, ctl + kCtlAlive + stage, dst);
 }
 
 // The second pass's buffers as the box pass sees them (pre == nullptr: no second pass, the test hook).
@@ -712,14 +725,14 @@ void h_cell_rel_host(const float* pts4, int N, const float* cand8, const float* 
 // the candidate's count, mcv_h_cell_bound drops the slots whose upper bound is below B before stage 1, and
 // stage 1 runs through its list. d_cell (with d_cells; id == nullptr: the box pass alone, the compactions
 // on N - processed): every point's cell id (N ints), the prefix table
-// (kHStageLater x cells ints) and the per-slot `left` figures (kHStageLater x hypCount ints) that the later
-// compactions use in place of N - processed (why that is exact: the caller's staging decision).
+// (kHStageCellLater x cells ints) and the per-slot `left` figures (kHStageCellLater x hypCount ints) that the
+// later boundaries' tests use in place of N - processed (why that is exact: the caller's staging decision).
+// With the second pass (d_cell.id) the plan has the half boundary: 5 stages (0, 1a, 1b, 2, 3), else 4.
 void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, const void* d_models, int* d_counts,
                             int hypCount, int64_t hypBegin, float thr2, const double* d_bb, int* d_ctl, int* d_list,
                             uint64_t* d_pkey, int64_t* d_pfail, hipStream_t s, const void* d_rec,
                             unsigned long long* d_stats, int form, int* d_cells, int G, int Gs, HCellBufs d_cell,
                             HCellPreBufs d_pre, int* d_s0, int s0Slots) {
-    constexpr int TRIP = 64 * kCertNP;
     // stage 0 on the first s0 slots only, into d_s0 (0: on every slot, into d_counts); only with the bound, whose
     // list stage 1 then runs from point 0
     const int s0 = d_cells && d_s0 && s0Slots > 0 && s0Slots < hypCount ? s0Slots : 0;
@@ -729,14 +742,14 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
     const bool mfma0 = s0 ? d_rec && d_stats && h_mfma_engages(N, s0, form, true) : mfma;
     // stages that run a list keep the VALU kernel; kHFormMfma is the A/B partner
     const bool mfmaList = mfma && form == kHFormMfma;
-    const int nFull = N / 2 / TRIP * TRIP;
-    // stage 0: ~N / kHStagePrefixDiv points (N / kHCellPrefixDiv with the per-cell bound: stage 0 is then the
-    // one full-width stage left), a whole number of trips (at least one where N has one)
-    int pa = (N / (d_cells ? kHCellPrefixDiv : kHStagePrefixDiv) / 2 + TRIP / 2) / TRIP * TRIP;
-    if (pa < TRIP) pa = TRIP;
-    if (pa > nFull) pa = nFull;
+    const HStagePlanArgs pa = h_stage_plan_args(N, d_cells != nullptr);
     const HCertSlopes slopes = h_cert_slopes_host(thr2);
-    auto stage = [&](int st, const int* list) {
+    const bool rel = d_cells && d_cell.id;   // the bound's second pass and the per-slot `left`
+    // with the second pass the half boundary splits stage 1 (kernels.h): one stage and one `left` row more
+    const int rows = rel ? kHStageCellLater : kHStageLater;   // the boundaries behind a list stage
+    const int nStages = 2 + rows;
+    int* lists[2] = {d_list, d_list + hypCount};
+    auto stage = [&](int st, const int* list) {   // the list of stage st is lists[st & 1]
         const HStageArgs sa{d_ctl, list, st};
         int* cnt = st == 0 && s0 ? d_s0 : d_counts;
         const int width = st == 0 && s0 ? s0 : hypCount;
@@ -745,11 +758,7 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
         else
             launch_h_cert_sweep(d_pairs, N, d_models, cnt, width, thr2, slopes, d_bb, sa, s);
     };
-    auto recount = [&]() {   // the slots marked kStatusRedo, over all N, by the exact scalar sweep
-        launch_h_recount(d_pts4, N, d_models, d_counts, hypCount, thr2, false, nullptr, s);
-    };
-    int* lists[2] = {d_list, d_list + hypCount};
-    hipLaunchKernelGGL(mcv_h_stage_init, dim3(1), dim3(64), 0, s, d_ctl, pa, hypCount,
+    hipLaunchKernelGGL(mcv_h_stage_init, dim3(1), dim3(64), 0, s, d_ctl, pa.pa, hypCount,
                        d_cells ? h_cell_count(G, Gs) : 0, s0 ? s0 : hypCount);
     if (s0) {
         // the subset's statuses as the generate wrote them, and the chunk's first sampler failure from one pass
@@ -760,11 +769,10 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
     stage(0, nullptr);
     // candidate: the best partial count before any sampler failure (minimum count 0: any model will do)
     launch_best(s0 ? d_s0 : d_counts, s0 ? s0 : hypCount, hypBegin, 0, d_pkey, d_pfail, (uint64_t*)(d_ctl + kCtlKey), s);
-    const bool rel = d_cells && d_cell.id;   // the bound's second pass and the per-slot `left`
     launch_h_stage_count(d_pts4, N, d_models, hypBegin, thr2, d_ctl, d_bb, d_cells, G, Gs, rel ? d_cell.id : nullptr, s);
-    hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, TRIP, kHStageLater,
-                       N / kHStageSlackDiv, kHStageLatest256, s0 ? 1 : 0);
-    // the list of stage 1 is lists[1 & 1], the source of the first count-based compaction: the box pass writes
+    hipLaunchKernelGGL(mcv_h_stage_plan, dim3(1), dim3(64), 0, s, d_ctl, N, pa.trip, pa.later, pa.slackPts,
+                       pa.latest256, s0 ? 1 : 0, rel ? 1 : 0);
+    // the list of stage 1 is lists[1 & 1], the source of the first count-based test: the box pass writes
     // lists[1] (the slots the relative test cannot drop) and lists[0] (the others), the second pass (box +
     // candidate-relative test, the per-slot `left`) appends what it keeps of lists[0] to lists[1]
     if (d_cells && d_pre.stats) (void)hipMemsetAsync(d_pre.stats, 0, 2 * sizeof(unsigned long long), s);
@@ -773,23 +781,30 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
         launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
                             s, nullptr, nullptr, 0, 0, d_pre);
     if (rel) {
-        launch_h_cell_prefix(d_cell.id, N, d_ctl, kHStageLater, G, Gs, d_cell.pref, s);
+        launch_h_cell_prefix(d_cell.id, N, d_ctl, rows, G, Gs, d_cell.pref, s);
         launch_h_cell_bound(d_models, d_counts, hypCount, thr2, d_bb, d_cells, G, Gs, d_ctl, lists[1], nullptr, nullptr,
-                            s, lists[0], d_cell.left, kHStageLater, N, d_pre);
-        launch_h_cell_rel(d_models, d_models, hypBegin, hypCount, thr2, d_bb, d_cells, G, Gs, d_cell.pref,
-                          kHStageLater, d_ctl, lists[0], lists[1], d_cell.left, nullptr, nullptr, s, d_pre);
+                            s, lists[0], d_cell.left, rows, N, d_pre);
+        launch_h_cell_rel(d_models, d_models, hypBegin, hypCount, thr2, d_bb, d_cells, G, Gs, d_cell.pref, rows,
+                          d_ctl, lists[0], lists[1], d_cell.left, nullptr, nullptr, s, d_pre);
     }
+    // With the bound's second pass: stage 1a, compaction, stage 1b, compaction, stage 2, compaction, stage 3;
+    // without it the plan has no half boundary (and without the bound stage 1 runs full width). Behind an empty stage (boundaries that coincide) the
+    // compaction hands the list on, with the same test on the unchanged counts.
     stage(1, d_cells ? lists[1] : nullptr);
-    for (int st = 2; st < 2 + kHStageLater; ++st) {
-        // the first compaction sees the recount marks (count < 0) before the recount overwrites them
+    for (int st = 2; st < nStages; ++st) {
         hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_counts, hypCount, N,
                            d_ctl, st, st == 2 && !d_cells ? (const int*)nullptr : (const int*)lists[(st - 1) & 1],
                            lists[st & 1], rel ? (const int*)d_cell.left : (const int*)nullptr);
-        if (st == 2) recount();
         stage(st, lists[st & 1]);
     }
-    // a wave of a later stage that left the fast path (event overflow in the tail) marked its slots too
-    recount();
+    // One recount, behind the last stage. A wave that leaves the fast path (a model outside the certificate's
+    // domain; event overflow in the tail of the last stage) marks its slots kStatusRedo. A marked slot enters no
+    // later list: every compaction reads the mark (count < 0), which only this recount overwrites. So no stage
+    // adds to a marked slot, and the recount over all N gives it its full count whenever it runs. The recount that
+    // used to sit behind the first compaction changed nothing that a stage or a compaction reads, and cost a
+    // launch over every slot (0.04 ms at 2^20 hypotheses): it pays for the half boundary's two launches where
+    // pruning is off on the device and they do nothing.
+    launch_h_recount(d_pts4, N, d_models, d_counts, hypCount, thr2, false, nullptr, s);
 }
 
 }  // namespace mcv

@@ -343,6 +343,8 @@ SIGNATURES = {
     "mcvTestHGenerate": (_I, [_P, _I, _U64, _P, _I64, _I, _I, _P, _P, _P]),
     "mcvHostHGenRow": (_I, [_P, _I, _U64, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mcvTestHStage0Slots": (_I, [_I]),
+    "mcvHostHStagePlan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "mcvTestHCellSecondPass": (_I, [_I]),
     "mcvTestHCellPreVerdicts": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
