@@ -660,6 +660,32 @@ MCV_API int cvBundleAdjust(const mcvCamera* cameras, int nCameras, const uint8_t
                            const mcvV3d* points, const mcvBaConfig* cfg /*nullable = defaults*/,
                            mcvCamera* outCameras, mcvV3d* outPoints, mcvBaSummary* summary /*nullable*/);
 
+/* Bundle adjustment that also refines the focal lengths: cvBundleAdjust's cost, used set,
+ * loss, damping, termination codes and arguments, minimised over the focal lengths as well.
+ *   focalMode 0: the focal lengths stay; the call runs cvBundleAdjust's kernels and returns its bits;
+ *             1: one scale s per group, focal <- focal (1 + s): the aspect fy / fx stays;
+ *             2: fx and fy on their own, focal <- focal + (dfx, dfy).
+ *   focalGroup[nCameras] (nullable: every camera is its own group): cameras with the same value, any value
+ *     in [0, nCameras), share one focal length and must enter with bit-equal focal;
+ *   fixedFocal[nCameras] (nullable): a non-zero byte keeps the whole group of that camera constant. It is
+ *     independent of fixedCameras, which fixes rotation and location only: the focal length of a
+ *     pose-fixed camera is refined unless fixedFocal says otherwise.
+ * A group that is fixed or has no used observation is constant: its cameras' focal comes back bit for bit.
+ * outCameras[j].focal carries the same bits for every camera of a group. A trial whose focal length is
+ * not finite and positive is rejected like one that puts a point behind a camera.
+ * summary->freeFocalGroups counts the groups that were refined (0 with focalMode 0). The outputs equal
+ * mcvHostBundleAdjustFocal's bit for bit. Returns as cvBundleAdjust does; refused in addition, on the
+ * host before the device is touched and with no output written: an unknown focalMode, a focalGroup
+ * value outside [0, nCameras), unequal focal lengths within a group, and (focalMode 1, 2) a focal length
+ * of a group not marked fixed that is not finite and positive. cfg == NULL: the defaults with focalMode 1. */
+typedef struct { mcvBaConfig base; int focalMode; int pad; } mcvBaFocalConfig;
+typedef struct { mcvBaSummary base; int freeFocalGroups; int pad; } mcvBaFocalSummary;
+MCV_API int cvBundleAdjustFocal(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras /*nullable*/,
+                                const int* focalGroup /*nullable*/, const uint8_t* fixedFocal /*nullable*/,
+                                const int* cameraIdx, const mcvV2d* observations, const int* offsets, int T,
+                                const mcvV3d* points, const mcvBaFocalConfig* cfg /*nullable*/,
+                                mcvCamera* outCameras, mcvV3d* outPoints, mcvBaFocalSummary* summary /*nullable*/);
+
 /* Batched CameraPose.findScaled: P independent cvFindScaledPose problems in one call, each bit-identical
  * to its own single call; the launches, copies and the one synchronisation do not grow with P (DESIGN
  * §7j). The observation sets are a CSR: offsets[S + 1] ints, offsets[0] == 0, non-decreasing, over the
@@ -1227,6 +1253,23 @@ MCV_API int mcvHostBaStep(const mcvCamera* cameras, int nCameras, const uint8_t*
  * launches, stream synchronisations, host<->device copies, memsets, linearisations, trials (LM
  * iterations), chunks of 8 PCG iterations, segments of the camera lists}. Returns 0. */
 MCV_API int mcvTestBundleAdjustStats(long long* stats8);
+/* Host twin of cvBundleAdjustFocal: the same arguments, checks, outputs, summary and return value. No GPU. */
+MCV_API int mcvHostBundleAdjustFocal(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                                     const int* focalGroup, const uint8_t* fixedFocal, const int* cameraIdx,
+                                     const mcvV2d* observations, const int* offsets, int T, const mcvV3d* points,
+                                     const mcvBaFocalConfig* cfg, mcvCamera* outCameras, mcvV3d* outPoints,
+                                     mcvBaFocalSummary* summary);
+/* The twin's first step at damping lambda with focalMode 1 or 2: focalBlocks[2 n] (per observation the
+ * focal block scaled by sqrt(w): the column (u0, u1) of s for mode 1, diag(u0, u1) for mode 2; zero for an
+ * unused observation or a constant group), dCameras[6 nCameras], dFocal[2 nCameras] (each camera's group
+ * step: (s, 0) or (dfx, dfy)) and dPoints[3 T]. Returns the PCG iterations, -1 on failure. */
+MCV_API int mcvHostBaFocalStep(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                               const int* focalGroup, const uint8_t* fixedFocal, const int* cameraIdx,
+                               const mcvV2d* observations, const int* offsets, int T, const mcvV3d* points,
+                               const mcvBaFocalConfig* cfg, double lambda, double* focalBlocks, double* dCameras,
+                               double* dFocal, double* dPoints);
+/* mcvTestBundleAdjustStats for the calling thread's last cvBundleAdjustFocal call that reached the device. */
+MCV_API int mcvTestBundleAdjustFocalStats(long long* stats8);
 
 #ifdef __cplusplus
 }

@@ -380,3 +380,51 @@ def bundleAdjust(cameras, cameraIdx, obs, offsets, points, fixed=None, cfg=None)
     (optional: true keeps that camera constant); cfg: a native.BaConfig (None = the library's defaults).
     -> (cameras[n, 14], points[T, 3], summary dict of mcvBaSummary's fields)."""
     return _bundle_adjust("cvBundleAdjust", cameras, cameraIdx, obs, offsets, points, fixed, cfg)
+
+
+def _bundle_adjust_focal(export: str, cameras, cameraIdx, obs, offsets, points, fixed=None, focalGroup=None,
+                         fixedFocal=None, cfg=None):
+    cams = cameras_array(cameras)
+    idx = np.ascontiguousarray(cameraIdx, np.int32).reshape(-1)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+    off = _offsets(offsets)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    T = off.size - 1
+    if idx.shape[0] != obs.shape[0]:
+        raise ValueError("cameraIdx and obs differ in length")
+    if pts.shape[0] != T:
+        raise ValueError("points needs one row per track")
+
+    def per_camera(a, what, dtype):
+        if a is None:
+            return None
+        a = np.asarray(a).reshape(-1)
+        a = (a != 0).astype(np.uint8) if dtype is np.uint8 else np.ascontiguousarray(a, dtype)
+        if a.shape[0] != cams.shape[0]:
+            raise ValueError(f"{what} needs one entry per camera")
+        return a
+
+    fixed = per_camera(fixed, "fixed", np.uint8)
+    fixedFocal = per_camera(fixedFocal, "fixedFocal", np.uint8)
+    focalGroup = per_camera(focalGroup, "focalGroup", np.int32)
+    ptr = lambda a: None if a is None else _nonnull(a, 1).ctypes.data
+    outC, outP, sm = np.empty_like(cams), np.empty_like(pts), N.BaFocalSummary()
+    k = getattr(N.lib(), export)(_nonnull(cams, (1, 14)).ctypes.data, cams.shape[0], ptr(fixed), ptr(focalGroup),
+                                 ptr(fixedFocal), _nonnull(idx, 1).ctypes.data, _nonnull(obs, (1, 2)).ctypes.data,
+                                 off.ctypes.data, T, _nonnull(pts, (1, 3)).ctypes.data,
+                                 None if cfg is None else C.addressof(cfg), _nonnull(outC, (1, 14)).ctypes.data,
+                                 _nonnull(outP, (1, 3)).ctypes.data, C.addressof(sm))
+    N.check(k >= 0, export)
+    return outC, outP, sm.as_dict()
+
+
+def bundleAdjustFocal(cameras, cameraIdx, obs, offsets, points, fixed=None, focalGroup=None, fixedFocal=None,
+                      cfg=None):
+    """cvBundleAdjustFocal: bundleAdjust that also refines the focal lengths. focalGroup[nCameras] (optional:
+    cameras with the same value share one focal length; None = one group per camera); fixedFocal[nCameras]
+    (optional: true keeps that camera's group constant; independent of fixed, which holds rotation and
+    location); cfg: a native.BaFocalConfig (None = the defaults with focalMode 1: one scale per group;
+    2 refines fx and fy on their own, 0 is bundleAdjust).
+    -> (cameras[n, 14] with the refined focal, points[T, 3], summary dict of mcvBaFocalSummary's fields)."""
+    return _bundle_adjust_focal("cvBundleAdjustFocal", cameras, cameraIdx, obs, offsets, points, fixed, focalGroup,
+                                fixedFocal, cfg)

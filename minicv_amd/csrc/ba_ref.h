@@ -1,4 +1,4 @@
-// ba_ref.h — the host side of bundle adjustment that needs no HIP: the argument checks,
+// ba_ref.h — the host side of bundle adjustment that needs no HIP (focal groups §7p): the argument checks,
 // the camera-side CSR and its segments, the Levenberg-Marquardt driver shared by the device export and
 // the twin, and the twin itself: ba_terms.h arithmetic summed sequentially in the orders the kernels
 // use. Plain C++ over plain arrays, so a stand-alone program can run it under a sanitizer
@@ -90,6 +90,61 @@ inline long long ba_build_csr(const int* cameraIdx, const int* offsets, int T, i
         c.camSegPtr[(size_t)j + 1] = (int)c.segCam.size();
     }
     return -1;
+}
+
+// ---- focal groups ----
+struct BaFocalConfig {
+    BaConfig base;
+    int focalMode, pad;
+};
+struct BaFocalSummary {
+    BaSummary base;
+    int freeFocalGroups, pad;
+};
+
+// The groups of a call, numbered by their first camera: group g holds the cameras
+// grpCam[grpPtr[g] .. grpPtr[g + 1]) in ascending index.
+struct BaGroups {
+    int nG = 0;
+    std::vector<int> camGrp, grpPtr, grpCam;
+    std::vector<uint8_t> grpFixed;
+};
+
+// Builds the groups and checks them: 0, or 1 unknown focalMode, 2 group value outside [0, nCameras),
+// 3 unequal focal lengths within a group, 4 a free group's focal length is not finite and positive
+// (fm != 0 only); *where is the camera at fault.
+inline int ba_build_groups(int fm, const int* focalGroup, const uint8_t* fixedFocal, const double* cameras,
+                           int nCameras, BaGroups& G, int* where) {
+    *where = 0;
+    if (fm < 0 || fm > 2) return 1;
+    std::vector<int> idOf((size_t)nCameras, -1);
+    G.camGrp.assign((size_t)nCameras, 0);
+    G.nG = 0;
+    for (int j = 0; j < nCameras; ++j) {
+        const int v = focalGroup ? focalGroup[j] : j;
+        *where = j;
+        if (v < 0 || v >= nCameras) return 2;
+        if (idOf[v] < 0) idOf[v] = G.nG++;
+        G.camGrp[j] = idOf[v];
+    }
+    G.grpPtr.assign((size_t)G.nG + 1, 0);
+    for (int j = 0; j < nCameras; ++j) G.grpPtr[(size_t)G.camGrp[j] + 1] += 1;
+    for (int g = 0; g < G.nG; ++g) G.grpPtr[(size_t)g + 1] += G.grpPtr[g];
+    std::vector<int> fill(G.grpPtr.begin(), G.grpPtr.end() - 1);
+    G.grpCam.assign((size_t)nCameras, 0);
+    for (int j = 0; j < nCameras; ++j) G.grpCam[(size_t)fill[G.camGrp[j]]++] = j;
+    G.grpFixed.assign((size_t)G.nG, 0);
+    for (int j = 0; j < nCameras; ++j)
+        if (fixedFocal && fixedFocal[j]) G.grpFixed[G.camGrp[j]] = 1;
+    for (int j = 0; j < nCameras; ++j) {
+        const double* f = cameras + 14 * (size_t)j + 12;
+        const double* f0 = cameras + 14 * (size_t)G.grpCam[G.grpPtr[G.camGrp[j]]] + 12;
+        *where = j;
+        if (std::memcmp(f, f0, 2 * sizeof(double)) != 0) return 3;
+        if (fm != 0 && !G.grpFixed[G.camGrp[j]] && !(ba_finite(f[0]) && ba_finite(f[1]) && f[0] > 0.0 && f[1] > 0.0))
+            return 4;
+    }
+    return 0;
 }
 
 // ---- the summation orders, sequentially ----
@@ -212,6 +267,24 @@ struct BaHost {
     std::vector<double> U, g, V, h, Vinv, t, L, b;  // per camera 21 / 6, per point 6 / 3 / 6 / 3, per camera 21 / 6
     std::vector<double> x, r, z, p, q, y;
     bool solveFailed = false;
+    // focal lengths (§7p); fm == 0 leaves every line below idle
+    int fm = 0, freeGroups = 0;
+    BaGroups grp;
+    std::vector<uint8_t> camHas, grpFree;
+    std::vector<double> Ef;                                   // 2 per observation: the focal block
+    std::vector<double> Gd, gf, Lf, bf, xf, rf, zf, pf, qf;   // per group 2, 2, 3, 2 ...
+    bool focalBad = false;                                    // the last trial's focal lengths
+
+    // The chain over a group's cameras, in ascending index from +0.0, of their per-camera sums.
+    template <int NQ, class F>
+    void group_sum(int g, F f, double* out) {
+        for (int q_ = 0; q_ < NQ; ++q_) out[q_] = 0.0;
+        for (int i = grp.grpPtr[g]; i < grp.grpPtr[g + 1]; ++i) {
+            double part[NQ];
+            ba_host_cam_sum<NQ>(csr, grp.grpCam[i], [&](int k, double* a) { f(k, a); }, part);
+            for (int q_ = 0; q_ < NQ; ++q_) out[q_] = out[q_] + part[q_];
+        }
+    }
 
     void init(const double* cameras, int nCameras_, const uint8_t* fixed_, const int* cameraIdx_, const double* obs_,
               const int* offsets_, int T_, const double* points, const BaConfig& cfg_) {
@@ -254,6 +327,21 @@ struct BaHost {
             for (int k = offsets[tr]; k < offsets[tr + 1]; ++k)
                 if (used[k]) active[cameraIdx[k]] = 1;
         }
+        if (fm) {
+            camHas = active;
+            grpFree.assign((size_t)grp.nG, 0);
+            freeGroups = 0;
+            for (int g = 0; g < grp.nG; ++g) {
+                bool has = false;
+                for (int i = grp.grpPtr[g]; i < grp.grpPtr[g + 1]; ++i) has = has || camHas[grp.grpCam[i]];
+                grpFree[g] = has && !grp.grpFixed[g];
+                freeGroups += grpFree[g];
+            }
+            Ef.assign(2 * (size_t)n, 0.0);
+            Gd.assign(2 * (size_t)grp.nG, 0.0);
+            gf = bf = xf = rf = zf = pf = qf = Gd;
+            Lf.assign(3 * (size_t)grp.nG, 0.0);
+        }
         for (int j = 0; j < nCameras; ++j) active[j] = active[j] && !(fixed && fixed[j]);
         E.assign((size_t)kBaEntry * n, 0.0);
         W.assign((size_t)n, 0.0);
@@ -294,6 +382,10 @@ struct BaHost {
                 W[k] = ba_linearize(cams.data() + 14 * (size_t)cameraIdx[k], pts.data() + 3 * (size_t)t_,
                                     obs[2 * (size_t)k], obs[2 * (size_t)k + 1], cfg.huberDelta,
                                     active[cameraIdx[k]] != 0, e);
+                if (fm)
+                    ba_linearize_focal(fm, cams.data() + 14 * (size_t)cameraIdx[k], pts.data() + 3 * (size_t)t_,
+                                       obs[2 * (size_t)k], obs[2 * (size_t)k + 1], cfg.huberDelta,
+                                       grpFree[grp.camGrp[cameraIdx[k]]] != 0, Ef.data() + 2 * (size_t)k);
                 ba_acc_point_lin(e, a);
             }, acc);
             for (int q_ = 0; q_ < 6; ++q_) V[6 * (size_t)t_ + q_] = acc[q_];
@@ -307,15 +399,31 @@ struct BaHost {
             for (int q_ = 0; q_ < 21; ++q_) U[21 * (size_t)j + q_] = acc[q_];
             for (int q_ = 0; q_ < 6; ++q_) g[6 * (size_t)j + q_] = -acc[21 + q_];
         }
+        for (int g_ = 0; fm && g_ < grp.nG; ++g_) {
+            double acc[4];
+            group_sum<4>(g_, [&](int k, double* a) {
+                if (used[k]) ba_acc_focal_lin(fm, Ef.data() + 2 * (size_t)k, E.data() + (size_t)kBaEntry * k, a);
+            }, acc);
+            const int nd = fm == 1 ? 1 : 2;
+            for (int a = 0; a < 2; ++a) {
+                Gd[2 * (size_t)g_ + a] = a < nd ? acc[a] : 0.0;
+                gf[2 * (size_t)g_ + a] = a < nd ? -acc[nd + a] : 0.0;
+            }
+        }
     }
 
     // y_i = Vinv_i sum W_k^T v_j over the used tracks
-    void point_pass(const std::vector<double>& v) {
+    void point_pass(const std::vector<double>& v, const std::vector<double>& vf) {
         for (int t_ = 0; t_ < T; ++t_) {
             if (!trackUsed[t_]) continue;
             double acc[3];
             ba_host_point_sum<3>(offsets[t_], offsets[t_ + 1] - offsets[t_], [&](int k, double* a) {
-                if (used[k]) ba_acc_point_wtp(E.data() + (size_t)kBaEntry * k, v.data() + 6 * (size_t)cameraIdx[k], a);
+                if (!used[k]) return;
+                if (fm)
+                    ba_acc_point_wtp_focal(fm, E.data() + (size_t)kBaEntry * k, Ef.data() + 2 * (size_t)k,
+                                           v.data() + 6 * (size_t)cameraIdx[k],
+                                           vf.data() + 2 * (size_t)grp.camGrp[cameraIdx[k]], a);
+                else ba_acc_point_wtp(E.data() + (size_t)kBaEntry * k, v.data() + 6 * (size_t)cameraIdx[k], a);
             }, acc);
             ba_symv3(Vinv.data() + 6 * (size_t)t_, acc, y.data() + 3 * (size_t)t_);
         }
@@ -326,10 +434,13 @@ struct BaHost {
         for (int a = 0; a < 6; ++a) Ul[ba_u6(a, a)] = ba_damp(Ul[ba_u6(a, a)], lambda);
     }
 
-    double cam_dot(const std::vector<double>& a, const std::vector<double>& c) {
+    // over the cameras and, after them, the groups (af . cf)
+    double cam_dot(const std::vector<double>& a, const std::vector<double>& c, const std::vector<double>& af,
+                   const std::vector<double>& cf) {
         double s;
-        ba_host_lane_sum<1>(nCameras, [&](int j, double* acc) {
-            acc[0] = acc[0] + ba_dot6(a.data() + 6 * (size_t)j, c.data() + 6 * (size_t)j);
+        ba_host_lane_sum<1>(nCameras + (fm ? grp.nG : 0), [&](int j, double* acc) {
+            if (j < nCameras) acc[0] = acc[0] + ba_dot6(a.data() + 6 * (size_t)j, c.data() + 6 * (size_t)j);
+            else acc[0] = acc[0] + ba_focal_dot(fm, af.data() + 2 * (size_t)(j - nCameras), cf.data() + 2 * (size_t)(j - nCameras));
         }, &s);
         return s;
     }
@@ -355,6 +466,18 @@ struct BaHost {
             for (int q_ = 0; q_ < 6; ++q_) b[6 * (size_t)j + q_] = g[6 * (size_t)j + q_] - acc[21 + q_];
             if (!ba_chol6(S, L.data() + 21 * (size_t)j)) fail = true;
         }
+        for (int g_ = 0; fm && g_ < grp.nG; ++g_) {
+            double acc[kBaFocalPart];
+            group_sum<kBaFocalPart>(g_, [&](int k, double* a) {
+                if (!used[k]) return;
+                const int i = csr.obsTrack[k];
+                ba_acc_focal_schur(fm, Ef.data() + 2 * (size_t)k, E.data() + (size_t)kBaEntry * k,
+                                   Vinv.data() + 6 * (size_t)i, t.data() + 3 * (size_t)i, a);
+            }, acc);
+            if (!ba_focal_block(fm, Gd.data() + 2 * (size_t)g_, gf.data() + 2 * (size_t)g_, acc, lambda,
+                                Lf.data() + 3 * (size_t)g_, bf.data() + 2 * (size_t)g_))
+                fail = true;
+        }
         if (fail) return false;
         // PCG
         for (int j = 0; j < nCameras; ++j) {
@@ -365,14 +488,30 @@ struct BaHost {
             ba_chol6_solve(L.data() + 21 * (size_t)j, r.data() + 6 * (size_t)j, z.data() + 6 * (size_t)j);
             for (int a = 0; a < 6; ++a) p[6 * (size_t)j + a] = z[6 * (size_t)j + a];
         }
-        double rz = cam_dot(r, z);
+        for (int g_ = 0; fm && g_ < grp.nG; ++g_) {
+            for (int a = 0; a < 2; ++a) {
+                xf[2 * (size_t)g_ + a] = 0.0;
+                rf[2 * (size_t)g_ + a] = bf[2 * (size_t)g_ + a];
+            }
+            ba_focal_solve(fm, Lf.data() + 3 * (size_t)g_, rf.data() + 2 * (size_t)g_, zf.data() + 2 * (size_t)g_);
+            for (int a = 0; a < 2; ++a) pf[2 * (size_t)g_ + a] = zf[2 * (size_t)g_ + a];
+        }
+        double rz = cam_dot(r, z, rf, zf);
         const double rz0 = rz, tol2 = cfg.cgTolerance * cfg.cgTolerance;
         if (!ba_finite(rz)) return false;
         bool done = rz <= tol2 * rz0;
         while (!done && cgIters < cfg.maxCgIterations) {
-            point_pass(p);
+            point_pass(p, pf);
             for (int j = 0; j < nCameras; ++j) {
-                double acc[6], Ul[21], up[6];
+                double acc[8], Ul[21], up[6];
+                if (fm)
+                    ba_host_cam_sum<8>(csr, j, [&](int k, double* a) {
+                        if (used[k])
+                            ba_acc_cam_wy_focal(fm, E.data() + (size_t)kBaEntry * k, Ef.data() + 2 * (size_t)k,
+                                                y.data() + 3 * (size_t)csr.obsTrack[k], p.data() + 6 * (size_t)j,
+                                                pf.data() + 2 * (size_t)grp.camGrp[j], a);
+                    }, acc);
+                else
                 ba_host_cam_sum<6>(csr, j, [&](int k, double* a) {
                     if (used[k]) ba_acc_cam_wy(E.data() + (size_t)kBaEntry * k, y.data() + 3 * (size_t)csr.obsTrack[k], a);
                 }, acc);
@@ -380,7 +519,18 @@ struct BaHost {
                 ba_symv6(Ul, p.data() + 6 * (size_t)j, up);
                 for (int a = 0; a < 6; ++a) q[6 * (size_t)j + a] = up[a] - acc[a];
             }
-            const double pq = cam_dot(p, q);
+            for (int g_ = 0; fm && g_ < grp.nG; ++g_) {
+                double acc[8];
+                group_sum<8>(g_, [&](int k, double* a) {
+                    if (used[k])
+                        ba_acc_cam_wy_focal(fm, E.data() + (size_t)kBaEntry * k, Ef.data() + 2 * (size_t)k,
+                                            y.data() + 3 * (size_t)csr.obsTrack[k], p.data() + 6 * (size_t)cameraIdx[k],
+                                            pf.data() + 2 * (size_t)g_, a);
+                }, acc);
+                ba_focal_q(fm, Gd.data() + 2 * (size_t)g_, lambda, pf.data() + 2 * (size_t)g_, acc + 6,
+                           qf.data() + 2 * (size_t)g_);
+            }
+            const double pq = cam_dot(p, q, pf, qf);
             const double alpha = rz / pq;
             if (!(pq > 0.0) || !ba_finite(alpha)) return false;
             for (int j = 0; j < nCameras; ++j) {
@@ -390,10 +540,18 @@ struct BaHost {
                 }
                 ba_chol6_solve(L.data() + 21 * (size_t)j, r.data() + 6 * (size_t)j, z.data() + 6 * (size_t)j);
             }
-            const double rzn = cam_dot(r, z);
+            for (int g_ = 0; fm && g_ < grp.nG; ++g_) {
+                for (int a = 0; a < 2; ++a) {
+                    xf[2 * (size_t)g_ + a] = xf[2 * (size_t)g_ + a] + alpha * pf[2 * (size_t)g_ + a];
+                    rf[2 * (size_t)g_ + a] = rf[2 * (size_t)g_ + a] - alpha * qf[2 * (size_t)g_ + a];
+                }
+                ba_focal_solve(fm, Lf.data() + 3 * (size_t)g_, rf.data() + 2 * (size_t)g_, zf.data() + 2 * (size_t)g_);
+            }
+            const double rzn = cam_dot(r, z, rf, zf);
             if (!ba_finite(rzn)) return false;
             const double beta = rzn / rz;
             for (size_t a = 0; a < 6 * (size_t)nCameras; ++a) p[a] = z[a] + beta * p[a];
+            for (size_t a = 0; fm && a < 2 * (size_t)grp.nG; ++a) pf[a] = zf[a] + beta * pf[a];
             rz = rzn;
             cgIters += 1;
             done = rz <= tol2 * rz0;
@@ -404,7 +562,7 @@ struct BaHost {
     // The step of the last solve: x for the cameras, dX_i = t_i - y_i(x) for the points, applied
     // into the trial copy. dPts (nullable) receives the point steps.
     void apply_step(double* dPts) {
-        point_pass(x);
+        point_pass(x, xf);
         pts2 = pts;
         for (int t_ = 0; t_ < T; ++t_) {
             for (int a = 0; a < 3; ++a) {
@@ -416,10 +574,17 @@ struct BaHost {
         cams2 = cams;
         for (int j = 0; j < nCameras; ++j)
             if (active[j]) ba_retract(cams.data() + 14 * (size_t)j, x.data() + 6 * (size_t)j, cams2.data() + 14 * (size_t)j);
+        focalBad = false;
+        for (int j = 0; fm && j < nCameras; ++j)
+            if (grpFree[grp.camGrp[j]] &&
+                !ba_focal_update(fm, cams.data() + 14 * (size_t)j + 12, xf.data() + 2 * (size_t)grp.camGrp[j],
+                                 cams2.data() + 14 * (size_t)j + 12))
+                focalBad = true;
     }
     void trial(double& c, bool& zok) {
         apply_step(nullptr);
         cost_of(cams2, pts2, c, zok);
+        zok = zok && !focalBad;
     }
     void accept() {
         cams.swap(cams2);
@@ -436,6 +601,24 @@ inline int ba_host_bundle_adjust(const double* cameras, int nCameras, const uint
     H.init(cameras, nCameras, fixed, cameraIdx, obs, offsets, T, points, cfg);
     H.csr.swap(csr);   // the CSR the caller's checks built
     const int it = ba_run(H, cfg, sm);
+    if (nCameras > 0) std::memcpy(outCameras, H.cams.data(), 14 * (size_t)nCameras * sizeof(double));
+    if (T > 0) std::memcpy(outPoints, H.pts.data(), 3 * (size_t)T * sizeof(double));
+    return it;
+}
+
+// The twin of cvBundleAdjustFocal over checked arguments, their CSR and their groups (both taken over).
+inline int ba_host_bundle_adjust_focal(const double* cameras, int nCameras, const uint8_t* fixed, const int* cameraIdx,
+                                       const double* obs, const int* offsets, int T, const double* points,
+                                       const BaFocalConfig& cfg, BaCsr& csr, BaGroups& grp, double* outCameras,
+                                       double* outPoints, BaFocalSummary& sm) {
+    BaHost H;
+    H.init(cameras, nCameras, fixed, cameraIdx, obs, offsets, T, points, cfg.base);
+    H.csr.swap(csr);
+    H.fm = cfg.focalMode;
+    std::swap(H.grp, grp);
+    const int it = ba_run(H, cfg.base, sm.base);
+    sm.freeFocalGroups = H.fm ? H.freeGroups : 0;
+    sm.pad = 0;
     if (nCameras > 0) std::memcpy(outCameras, H.cams.data(), 14 * (size_t)nCameras * sizeof(double));
     if (T > 0) std::memcpy(outPoints, H.pts.data(), 3 * (size_t)T * sizeof(double));
     return it;

@@ -313,4 +313,164 @@ MCV_HD void ba_retract(const double* __restrict__ cam, const double* __restrict_
     out[13] = cam[13];
 }
 
+// ---- focal lengths ----
+// fm = 1: one scale s per group, focal <- focal (1 + s), linearised at s = 0; fm = 2: (dfx, dfy),
+// focal <- focal + (dfx, dfy). An observation's focal block is the two doubles u, scaled by sqrt(w):
+// the column (u0, u1)^T for fm = 1, diag(u0, u1) for fm = 2; zero for a group that stays constant.
+// A group's vectors are kept two doubles wide and its packed symmetric block three (fm = 1 uses the first).
+// fm is a constant at every call, so the branches fold.
+
+static const int kBaFocalPart = 5;   // sums of the widest focal pass: the reduced system's, fm = 2
+
+MCV_HD void ba_linearize_focal(int fm, const double* __restrict__ cam, const double* __restrict__ X, double ox,
+                               double oy, double delta, bool ffree, double* __restrict__ u) {
+    double pc[3], r[2], w, rho;
+    ba_project(cam, X, ox, oy, pc, r);
+    ba_loss(r, delta, w, rho);
+    const double sw = sqrt(w);
+    const double a0 = fm == 1 ? cam[12] * pc[0] / pc[2] : pc[0] / pc[2];
+    const double a1 = fm == 1 ? cam[13] * pc[1] / pc[2] : pc[1] / pc[2];
+    u[0] = ffree ? a0 * sw : 0.0;
+    u[1] = ffree ? a1 * sw : 0.0;
+}
+
+// linearise: the diagonal of F^T F, then F^T r (fm = 1: 1 + 1 sums, fm = 2: 2 + 2)
+MCV_HD void ba_acc_focal_lin(int fm, const double* __restrict__ u, const double* __restrict__ e, double* __restrict__ acc) {
+    if (fm == 1) {
+        acc[0] = acc[0] + (u[0] * u[0] + u[1] * u[1]);
+        acc[1] = acc[1] + (u[0] * e[18] + u[1] * e[19]);
+    } else {
+        acc[0] = acc[0] + u[0] * u[0];
+        acc[1] = acc[1] + u[1] * u[1];
+        acc[2] = acc[2] + u[0] * e[18];
+        acc[3] = acc[3] + u[1] * e[19];
+    }
+}
+MCV_HD int ba_focal_lin_sums(int fm) { return fm == 1 ? 2 : 4; }
+
+// reduced system: with C = B Vinv B^T, F^T C F packed (1 or 3 sums), then F^T (B t) (1 or 2)
+MCV_HD void ba_acc_focal_schur(int fm, const double* __restrict__ u, const double* __restrict__ e,
+                               const double* __restrict__ Vinv, const double* __restrict__ t, double* __restrict__ acc) {
+    const double* B = e + 12;
+    double BV[6];
+    MCV_BA_UNROLL
+    for (int r = 0; r < 2; ++r)
+        MCV_BA_UNROLL
+        for (int c = 0; c < 3; ++c)
+            BV[3 * r + c] = B[3 * r] * Vinv[ba_s3(0, c)] + B[3 * r + 1] * Vinv[ba_s3(1, c)] + B[3 * r + 2] * Vinv[ba_s3(2, c)];
+    const double c00 = BV[0] * B[0] + BV[1] * B[1] + BV[2] * B[2];
+    const double c01 = BV[0] * B[3] + BV[1] * B[4] + BV[2] * B[5];
+    const double c11 = BV[3] * B[3] + BV[4] * B[4] + BV[5] * B[5];
+    const double bt0 = B[0] * t[0] + B[1] * t[1] + B[2] * t[2];
+    const double bt1 = B[3] * t[0] + B[4] * t[1] + B[5] * t[2];
+    if (fm == 1) {
+        acc[0] = acc[0] + (u[0] * (c00 * u[0] + c01 * u[1]) + u[1] * (c01 * u[0] + c11 * u[1]));
+        acc[1] = acc[1] + (u[0] * bt0 + u[1] * bt1);
+    } else {
+        acc[0] = acc[0] + u[0] * c00 * u[0];
+        acc[1] = acc[1] + u[0] * c01 * u[1];
+        acc[2] = acc[2] + u[1] * c11 * u[1];
+        acc[3] = acc[3] + u[0] * bt0;
+        acc[4] = acc[4] + u[1] * bt1;
+    }
+}
+MCV_HD int ba_focal_schur_sums(int fm) { return fm == 1 ? 2 : 5; }
+
+// points, PCG: += B^T (A p + F pf) (3)
+MCV_HD void ba_acc_point_wtp_focal(int fm, const double* __restrict__ e, const double* __restrict__ u,
+                                   const double* __restrict__ p, const double* __restrict__ pf, double* __restrict__ acc) {
+    const double ap0 = e[0] * p[0] + e[1] * p[1] + e[2] * p[2] + e[3] * p[3] + e[4] * p[4] + e[5] * p[5] + u[0] * pf[0];
+    const double ap1 = e[6] * p[0] + e[7] * p[1] + e[8] * p[2] + e[9] * p[3] + e[10] * p[4] + e[11] * p[5] +
+                       u[1] * pf[fm == 1 ? 0 : 1];
+    MCV_BA_UNROLL
+    for (int a = 0; a < 3; ++a) acc[a] = acc[a] + (e[12 + a] * ap0 + e[15 + a] * ap1);
+}
+
+// cameras and groups, PCG: += A^T (B y - F pf) (6), then += F^T (B y - A p) (1 or 2): W y together with
+// the coupling of the camera's block and its group's, which no stored matrix holds
+MCV_HD void ba_acc_cam_wy_focal(int fm, const double* __restrict__ e, const double* __restrict__ u,
+                                const double* __restrict__ y, const double* __restrict__ p,
+                                const double* __restrict__ pf, double* __restrict__ acc) {
+    const double by0 = e[12] * y[0] + e[13] * y[1] + e[14] * y[2];
+    const double by1 = e[15] * y[0] + e[16] * y[1] + e[17] * y[2];
+    const double v0 = by0 - u[0] * pf[0], v1 = by1 - u[1] * pf[fm == 1 ? 0 : 1];
+    MCV_BA_UNROLL
+    for (int a = 0; a < 6; ++a) acc[a] = acc[a] + (e[a] * v0 + e[6 + a] * v1);
+    const double ap0 = e[0] * p[0] + e[1] * p[1] + e[2] * p[2] + e[3] * p[3] + e[4] * p[4] + e[5] * p[5];
+    const double ap1 = e[6] * p[0] + e[7] * p[1] + e[8] * p[2] + e[9] * p[3] + e[10] * p[4] + e[11] * p[5];
+    const double w0 = by0 - ap0, w1 = by1 - ap1;
+    if (fm == 1) {
+        acc[6] = acc[6] + (u[0] * w0 + u[1] * w1);
+    } else {
+        acc[6] = acc[6] + u[0] * w0;
+        acc[7] = acc[7] + u[1] * w1;
+    }
+}
+MCV_HD int ba_focal_wy_sums(int fm) { return fm == 1 ? 1 : 2; }
+
+// A group's block of the reduced system from its chained sums: S = damped diagonal - F^T C F, its
+// Cholesky factor L (packed lower: l00, l10, l11) and b = gf - F^T B t. False when a pivot is not
+// positive and finite.
+MCV_HD bool ba_focal_block(int fm, const double* __restrict__ Gd, const double* __restrict__ gf,
+                           const double* __restrict__ sums, double lambda, double* __restrict__ L,
+                           double* __restrict__ b) {
+    const double s00 = ba_damp(Gd[0], lambda) - sums[0];
+    bool ok = s00 > 0.0 && ba_finite(s00);
+    L[0] = sqrt(s00);
+    if (fm == 1) {
+        L[1] = 0.0;
+        L[2] = 0.0;
+        b[0] = gf[0] - sums[1];
+        b[1] = 0.0;
+        return ok;
+    }
+    const double s01 = -sums[1];
+    const double s11 = ba_damp(Gd[1], lambda) - sums[2];
+    L[1] = s01 / L[0];
+    const double d = s11 - L[1] * L[1];
+    ok = ok && d > 0.0 && ba_finite(d);
+    L[2] = sqrt(d);
+    b[0] = gf[0] - sums[3];
+    b[1] = gf[1] - sums[4];
+    return ok;
+}
+
+// z = (L L^T)^-1 r of a group
+MCV_HD void ba_focal_solve(int fm, const double* __restrict__ L, const double* __restrict__ r, double* __restrict__ z) {
+    const double y0 = r[0] / L[0];
+    if (fm == 1) {
+        z[0] = y0 / L[0];
+        z[1] = 0.0;
+        return;
+    }
+    const double y1 = (r[1] - L[1] * y0) / L[2];
+    z[1] = y1 / L[2];
+    z[0] = (y0 - L[1] * z[1]) / L[0];
+}
+
+MCV_HD double ba_focal_dot(int fm, const double* __restrict__ a, const double* __restrict__ b) {
+    return fm == 1 ? a[0] * b[0] : a[0] * b[0] + a[1] * b[1];
+}
+
+// q = G_lambda pf - sums of a group, sums being the chained F^T (B y - A p)
+MCV_HD void ba_focal_q(int fm, const double* __restrict__ Gd, double lambda, const double* __restrict__ pf,
+                       const double* __restrict__ sums, double* __restrict__ q) {
+    q[0] = ba_damp(Gd[0], lambda) * pf[0] - sums[0];
+    q[1] = fm == 1 ? 0.0 : ba_damp(Gd[1], lambda) * pf[1] - sums[1];
+}
+
+// The trial focal length of a free group's camera. False when it is not finite and positive.
+MCV_HD bool ba_focal_update(int fm, const double* __restrict__ focal, const double* __restrict__ xf,
+                            double* __restrict__ out) {
+    if (fm == 1) {
+        const double s = 1.0 + xf[0];
+        out[0] = focal[0] * s;
+        out[1] = focal[1] * s;
+    } else {
+        out[0] = focal[0] + xf[0];
+        out[1] = focal[1] + xf[1];
+    }
+    return ba_finite(out[0]) && ba_finite(out[1]) && out[0] > 0.0 && out[1] > 0.0;
+}
+
 }  // namespace mcv

@@ -531,4 +531,425 @@ void launch_ba_trial(const BaDevice& D, hipStream_t s) {
     launch_ba_cost(D, D.cams2, D.pts2, s);
 }
 
+// ================= focal groups =================
+// cvBundleAdjustFocal with focalMode 1 or 2 (FM). Every kernel above that the focal lengths do not
+// change is launched as it is; the kernels here are the per-observation passes with the focal
+// accumulators beside the cameras' (instantiated per mode, so the kernels above carry none of it), and
+// one lane per group for what a group sums: the chain, from +0.0 over the group's cameras in ascending
+// index, of those cameras' per-camera sums (each the chain of the camera's segments, as above).
+
+// One segment with NC camera sums and NF focal sums: the first go to D.part, the others to F.partF.
+template <int NC, int NF, class Fn>
+__device__ __forceinline__ void baf_seg_sum(const BaDevice& D, const BaFocal& F, int seg, Fn f, double* lds) {
+    double acc[NC + NF];
+#pragma unroll
+    for (int q = 0; q < NC + NF; ++q) acc[q] = 0.0;
+    const int end = D.segEnd[seg];
+    for (int i = D.segStart[seg] + (int)threadIdx.x; i < end; i += kBaSegLanes) f(D.camObs[i], acc);
+    ba_block_tree<NC + NF>(acc, lds);
+    if (threadIdx.x < NC) D.part[27 * (size_t)seg + threadIdx.x] = lds[threadIdx.x * kBaSegLanes];
+    else if (threadIdx.x < NC + NF) F.partF[kBaFocalPart * (size_t)seg + (threadIdx.x - NC)] = lds[threadIdx.x * kBaSegLanes];
+}
+
+template <int NF>
+__device__ __forceinline__ void baf_group_total(const BaDevice& D, const BaFocal& F, int g, double (&out)[NF]) {
+#pragma unroll
+    for (int q = 0; q < NF; ++q) out[q] = 0.0;
+    for (int i = F.grpPtr[g]; i < F.grpPtr[g + 1]; ++i) {
+        const int j = F.grpCam[i];
+        double c[NF];
+#pragma unroll
+        for (int q = 0; q < NF; ++q) c[q] = 0.0;
+        for (int s = D.camSegPtr[j]; s < D.camSegPtr[j + 1]; ++s) {
+#pragma unroll
+            for (int q = 0; q < NF; ++q) c[q] = c[q] + F.partF[kBaFocalPart * (size_t)s + q];
+        }
+#pragma unroll
+        for (int q = 0; q < NF; ++q) out[q] = out[q] + c[q];
+    }
+}
+
+// The first group of thread tid in the chain over cameras, then groups, at stride kBaSegLanes.
+__device__ __forceinline__ int baf_first_group(const BaDevice& D) {
+    return (int)(((unsigned)threadIdx.x + kBaSegLanes - (unsigned)(D.nCameras % kBaSegLanes)) % kBaSegLanes);
+}
+
+__global__ __launch_bounds__(256) void mcv_baf_free(BaDevice D, BaFocal F, const int* __restrict__ camHas) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= F.nG) return;
+    bool has = false;
+    for (int i = F.grpPtr[g]; i < F.grpPtr[g + 1]; ++i) has = has || camHas[F.grpCam[i]] != 0;
+    const bool fr = has && !F.grpFixed[g];
+    F.grpFree[g] = fr ? 1 : 0;
+    if (fr) atomicAdd(&D.ctr[5], 1u);
+}
+
+template <int FM>
+__global__ __launch_bounds__(256) void mcv_baf_u(BaDevice D, BaFocal F) {
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < D.n; k += gridDim.x * 256) {
+        if (!D.used[k]) continue;
+        const int j = D.cameraIdx[k];
+        double u[2];
+        ba_linearize_focal(FM, D.cams + 14 * (size_t)j, D.pts + 3 * (size_t)D.obsTrack[k], D.obs[2 * (size_t)k],
+                           D.obs[2 * (size_t)k + 1], D.delta, F.grpFree[F.camGrp[j]] != 0, u);
+        F.Ef[2 * (size_t)k] = u[0];
+        F.Ef[2 * (size_t)k + 1] = u[1];
+    }
+}
+
+template <int FM>
+__global__ __launch_bounds__(kBaSegLanes) void mcv_baf_lin_cam_seg(BaDevice D, BaFocal F) {
+    constexpr int NF = FM == 1 ? 2 : 4;
+    __shared__ double lds[(27 + NF) * kBaSegLanes];
+    baf_seg_sum<27, NF>(D, F, blockIdx.x, [&](int k, double (&acc)[27 + NF]) {
+        if (!D.used[k]) return;
+        double e[kBaEntry], u[2];
+#pragma unroll
+        for (int q = 0; q < kBaEntry; ++q) e[q] = D.E[(size_t)kBaEntry * k + q];
+        u[0] = F.Ef[2 * (size_t)k];
+        u[1] = F.Ef[2 * (size_t)k + 1];
+        ba_acc_cam_lin(e, acc);
+        ba_acc_focal_lin(FM, u, e, acc + 27);
+    }, lds);
+}
+
+template <int FM>
+__global__ __launch_bounds__(256) void mcv_baf_grp_lin(BaDevice D, BaFocal F) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= F.nG) return;
+    constexpr int NF = FM == 1 ? 2 : 4, ND = FM == 1 ? 1 : 2;
+    double acc[NF];
+    baf_group_total<NF>(D, F, g, acc);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        F.Gd[2 * (size_t)g + a] = a < ND ? acc[a % ND] : 0.0;
+        F.gf[2 * (size_t)g + a] = a < ND ? -acc[ND + a % ND] : 0.0;
+    }
+}
+
+template <int FM>
+__global__ __launch_bounds__(kBaSegLanes) void mcv_baf_schur_seg(BaDevice D, BaFocal F) {
+    constexpr int NF = FM == 1 ? 2 : 5;
+    __shared__ double lds[(27 + NF) * kBaSegLanes];
+    baf_seg_sum<27, NF>(D, F, blockIdx.x, [&](int k, double (&acc)[27 + NF]) {
+        if (!D.used[k]) return;
+        const int i = D.obsTrack[k];
+        double e[kBaEntry], inv[6], tt[3], u[2];
+#pragma unroll
+        for (int q = 0; q < kBaEntry; ++q) e[q] = D.E[(size_t)kBaEntry * k + q];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) inv[q] = D.Vinv[6 * (size_t)i + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) tt[q] = D.t[3 * (size_t)i + q];
+        u[0] = F.Ef[2 * (size_t)k];
+        u[1] = F.Ef[2 * (size_t)k + 1];
+        ba_acc_cam_schur(e, inv, tt, acc);
+        ba_acc_focal_schur(FM, u, e, inv, tt, acc + 27);
+    }, lds);
+}
+
+template <int FM>
+__global__ __launch_bounds__(256) void mcv_baf_grp_schur(BaDevice D, BaFocal F) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= F.nG) return;
+    constexpr int NF = FM == 1 ? 2 : 5;
+    double acc[NF], sums[kBaFocalPart] = {0.0, 0.0, 0.0, 0.0, 0.0}, L[3], b[2];
+    baf_group_total<NF>(D, F, g, acc);
+#pragma unroll
+    for (int q = 0; q < NF; ++q) sums[q] = acc[q];
+    const double Gd[2] = {F.Gd[2 * (size_t)g], F.Gd[2 * (size_t)g + 1]};
+    const double gf[2] = {F.gf[2 * (size_t)g], F.gf[2 * (size_t)g + 1]};
+    if (!ba_focal_block(FM, Gd, gf, sums, D.lambda, L, b)) atomicOr(&D.ctr[3], 1u);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) F.Lf[3 * (size_t)g + q] = L[q];
+    F.bf[2 * (size_t)g] = b[0];
+    F.bf[2 * (size_t)g + 1] = b[1];
+}
+
+template <int FM>
+__device__ __forceinline__ void baf_precondition(const BaFocal& F, int g, const double (&r)[2], double (&z)[2]) {
+    const double L[3] = {F.Lf[3 * (size_t)g], F.Lf[3 * (size_t)g + 1], F.Lf[3 * (size_t)g + 2]};
+    ba_focal_solve(FM, L, r, z);
+}
+
+template <int FM>
+__global__ __launch_bounds__(kBaSegLanes) void mcv_baf_pcg_init(BaDevice D, BaFocal F) {
+    __shared__ double lds[kBaSegLanes];
+    const bool failed = D.ctr[3] != 0;
+    double acc = 0.0;
+    if (!failed) {
+        for (int j = threadIdx.x; j < D.nCameras; j += kBaSegLanes) {
+            double r[6], z[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) r[a] = D.b[6 * (size_t)j + a];
+            ba_precondition(D, j, r, z);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                D.x[6 * (size_t)j + a] = 0.0;
+                D.r[6 * (size_t)j + a] = r[a];
+                D.z[6 * (size_t)j + a] = z[a];
+                D.p[6 * (size_t)j + a] = z[a];
+            }
+            acc = acc + ba_dot6(r, z);
+        }
+        for (int g = baf_first_group(D); g < F.nG; g += kBaSegLanes) {
+            double r[2], z[2];
+#pragma unroll
+            for (int a = 0; a < 2; ++a) r[a] = F.bf[2 * (size_t)g + a];
+            baf_precondition<FM>(F, g, r, z);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                F.xf[2 * (size_t)g + a] = 0.0;
+                F.rf[2 * (size_t)g + a] = r[a];
+                F.zf[2 * (size_t)g + a] = z[a];
+                F.pf[2 * (size_t)g + a] = z[a];
+            }
+            acc = acc + ba_focal_dot(FM, r, z);
+        }
+    }
+    const double rz = ba_block_total(acc, lds);
+    if (threadIdx.x == 0) {
+        const bool bad = failed || !ba_finite(rz);
+        D.cg->rz = rz;
+        D.cg->rz0 = rz;
+        D.cg->iter = 0;
+        D.cg->failed = bad ? 1 : 0;
+        D.cg->done = bad || rz <= D.tol2 * rz || D.maxCg <= 0 ? 1 : 0;
+    }
+}
+
+template <int MODE, int FM>
+__device__ __forceinline__ void baf_point_entry(const BaDevice& D, const BaFocal& F, int k, double* acc) {
+    if (!D.used[k]) return;
+    double e[18], v[6], u[2], vf[2];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) e[q] = D.E[(size_t)kBaEntry * k + q];
+    const int j = D.cameraIdx[k];
+    const double* src = (MODE == 0 ? D.p : D.x) + 6 * (size_t)j;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) v[q] = src[q];
+    const double* srcf = (MODE == 0 ? F.pf : F.xf) + 2 * (size_t)F.camGrp[j];
+    vf[0] = srcf[0];
+    vf[1] = srcf[1];
+    u[0] = F.Ef[2 * (size_t)k];
+    u[1] = F.Ef[2 * (size_t)k + 1];
+    ba_acc_point_wtp_focal(FM, e, u, v, vf, acc);
+}
+
+template <int MODE, int FM>
+__global__ __launch_bounds__(256) void mcv_baf_point_short(BaDevice D, BaFocal F) {
+    if (MODE == 0 && D.cg->done) return;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= D.T) return;
+    if (!D.trackUsed[t]) {
+        if (MODE == 1) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) D.pts2[3 * (size_t)t + q] = D.pts[3 * (size_t)t + q];
+        }
+        return;
+    }
+    const int o0 = D.offsets[t], R = D.offsets[t + 1] - o0;
+    if (R > kBaShortMax) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < R; ++i) baf_point_entry<MODE, FM>(D, F, o0 + i, acc);
+    ba_point_store<MODE>(D, t, acc);
+}
+
+template <int MODE, int FM>
+__global__ __launch_bounds__(256) void mcv_baf_point_long(BaDevice D, BaFocal F) {
+    if (MODE == 0 && D.cg->done) return;
+    const int lane = threadIdx.x & 63, nLong = (int)D.ctr[0];
+    for (int w = blockIdx.x * 4 + (threadIdx.x >> 6); w < nLong; w += gridDim.x * 4) {
+        const int t = D.longList[w], o0 = D.offsets[t];
+        double acc[3];
+        ba_wave_sum<3>(o0, D.offsets[t + 1] - o0, lane, [&](int k, double (&a)[3]) { baf_point_entry<MODE, FM>(D, F, k, a); }, acc);
+        if (lane == 0) ba_point_store<MODE>(D, t, acc);
+    }
+}
+
+template <int FM>
+__global__ __launch_bounds__(kBaSegLanes) void mcv_baf_wy_seg(BaDevice D, BaFocal F) {
+    constexpr int NF = FM == 1 ? 1 : 2;
+    __shared__ double lds[(6 + NF) * kBaSegLanes];
+    if (D.cg->done) return;
+    const int j = D.segCam[blockIdx.x];
+    double p[6], pf[2];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) p[q] = D.p[6 * (size_t)j + q];
+    pf[0] = F.pf[2 * (size_t)F.camGrp[j]];
+    pf[1] = F.pf[2 * (size_t)F.camGrp[j] + 1];
+    baf_seg_sum<6, NF>(D, F, blockIdx.x, [&](int k, double (&acc)[6 + NF]) {
+        if (!D.used[k]) return;
+        double e[18], y[3], u[2];
+#pragma unroll
+        for (int q = 0; q < 18; ++q) e[q] = D.E[(size_t)kBaEntry * k + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) y[q] = D.y[3 * (size_t)D.obsTrack[k] + q];
+        u[0] = F.Ef[2 * (size_t)k];
+        u[1] = F.Ef[2 * (size_t)k + 1];
+        ba_acc_cam_wy_focal(FM, e, u, y, p, pf, acc);
+    }, lds);
+}
+
+// q of a group and its share of p.q
+template <int FM>
+__global__ __launch_bounds__(256) void mcv_baf_grp_q(BaDevice D, BaFocal F) {
+    if (D.cg->done) return;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= F.nG) return;
+    constexpr int NF = FM == 1 ? 1 : 2;
+    double acc[NF], sums[2] = {0.0, 0.0}, q[2];
+    baf_group_total<NF>(D, F, g, acc);
+#pragma unroll
+    for (int a = 0; a < NF; ++a) sums[a] = acc[a];
+    const double Gd[2] = {F.Gd[2 * (size_t)g], F.Gd[2 * (size_t)g + 1]};
+    const double pf[2] = {F.pf[2 * (size_t)g], F.pf[2 * (size_t)g + 1]};
+    ba_focal_q(FM, Gd, D.lambda, pf, sums, q);
+    F.qf[2 * (size_t)g] = q[0];
+    F.qf[2 * (size_t)g + 1] = q[1];
+    F.pqf[g] = ba_focal_dot(FM, pf, q);
+}
+
+template <int FM>
+__global__ __launch_bounds__(kBaSegLanes) void mcv_baf_pcg_update(BaDevice D, BaFocal F) {
+    __shared__ double lds[kBaSegLanes];
+    const BaCgState st = *D.cg;   // read by every thread before thread 0 writes it below (barriers between)
+    if (st.done) return;
+    const int g0 = baf_first_group(D);
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < D.nCameras; j += kBaSegLanes) acc = acc + D.pq[j];
+    for (int g = g0; g < F.nG; g += kBaSegLanes) acc = acc + F.pqf[g];
+    const double pq = ba_block_total(acc, lds);
+    const double alpha = st.rz / pq;
+    if (!(pq > 0.0) || !ba_finite(alpha)) {
+        if (threadIdx.x == 0) {
+            D.cg->failed = 1;
+            D.cg->done = 1;
+        }
+        return;
+    }
+    acc = 0.0;
+    for (int j = threadIdx.x; j < D.nCameras; j += kBaSegLanes) {
+        double r[6], z[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            D.x[6 * (size_t)j + a] = D.x[6 * (size_t)j + a] + alpha * D.p[6 * (size_t)j + a];
+            r[a] = D.r[6 * (size_t)j + a] - alpha * D.q[6 * (size_t)j + a];
+            D.r[6 * (size_t)j + a] = r[a];
+        }
+        ba_precondition(D, j, r, z);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) D.z[6 * (size_t)j + a] = z[a];
+        acc = acc + ba_dot6(r, z);
+    }
+    for (int g = g0; g < F.nG; g += kBaSegLanes) {
+        double r[2], z[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            F.xf[2 * (size_t)g + a] = F.xf[2 * (size_t)g + a] + alpha * F.pf[2 * (size_t)g + a];
+            r[a] = F.rf[2 * (size_t)g + a] - alpha * F.qf[2 * (size_t)g + a];
+            F.rf[2 * (size_t)g + a] = r[a];
+        }
+        baf_precondition<FM>(F, g, r, z);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) F.zf[2 * (size_t)g + a] = z[a];
+        acc = acc + ba_focal_dot(FM, r, z);
+    }
+    const double rzn = ba_block_total(acc, lds);
+    if (!ba_finite(rzn)) {
+        if (threadIdx.x == 0) {
+            D.cg->failed = 1;
+            D.cg->done = 1;
+        }
+        return;
+    }
+    const double beta = rzn / st.rz;
+    for (int j = threadIdx.x; j < D.nCameras; j += kBaSegLanes) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) D.p[6 * (size_t)j + a] = D.z[6 * (size_t)j + a] + beta * D.p[6 * (size_t)j + a];
+    }
+    for (int g = g0; g < F.nG; g += kBaSegLanes) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) F.pf[2 * (size_t)g + a] = F.zf[2 * (size_t)g + a] + beta * F.pf[2 * (size_t)g + a];
+    }
+    if (threadIdx.x == 0) {
+        D.cg->rz = rzn;
+        D.cg->iter = st.iter + 1;
+        D.cg->done = rzn <= D.tol2 * st.rz0 || st.iter + 1 >= D.maxCg ? 1 : 0;
+    }
+}
+
+// The trial focal lengths, over mcv_ba_retract's copies; a value that is not finite and positive
+// raises the flag that rejects the trial.
+template <int FM>
+__global__ __launch_bounds__(256) void mcv_baf_focal(BaDevice D, BaFocal F) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= D.nCameras) return;
+    const int g = F.camGrp[j];
+    if (!F.grpFree[g]) return;
+    const double f[2] = {D.cams[14 * (size_t)j + 12], D.cams[14 * (size_t)j + 13]};
+    const double xf[2] = {F.xf[2 * (size_t)g], F.xf[2 * (size_t)g + 1]};
+    double out[2];
+    if (!ba_focal_update(FM, f, xf, out)) atomicOr(&D.ctr[4], 1u);
+    D.cams2[14 * (size_t)j + 12] = out[0];
+    D.cams2[14 * (size_t)j + 13] = out[1];
+}
+
+#define MCV_BAF_LAUNCH(kernel, grid, block, ...)                                               \
+    do {                                                                                       \
+        if (F.fm == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<1>), grid, block, 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2>), grid, block, 0, s, __VA_ARGS__);   \
+    } while (0)
+#define MCV_BAF_LAUNCH_M(kernel, M, grid, block, ...)                                          \
+    do {                                                                                       \
+        if (F.fm == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<M, 1>), grid, block, 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<M, 2>), grid, block, 0, s, __VA_ARGS__); \
+    } while (0)
+
+void launch_baf_setup(const BaDevice& D, const BaFocal& F, hipStream_t s) {
+    launch_ba_setup(D, s);
+    ProfScope ps("baf_setup", s);
+    hipLaunchKernelGGL(mcv_baf_free, dim3(ba_blocks(F.nG)), dim3(256), 0, s, D, F, reinterpret_cast<const int*>(D.pq));
+}
+
+void launch_baf_linearize(const BaDevice& D, const BaFocal& F, hipStream_t s) {
+    ProfScope ps("baf_linearize", s);
+    hipLaunchKernelGGL(mcv_ba_lin_short, dim3(ba_blocks(D.T)), dim3(256), 0, s, D);
+    hipLaunchKernelGGL(mcv_ba_lin_long, dim3(ba_long_blocks(D)), dim3(256), 0, s, D);
+    MCV_BAF_LAUNCH(mcv_baf_u, dim3(kBaGrid), dim3(256), D, F);
+    MCV_BAF_LAUNCH(mcv_baf_lin_cam_seg, dim3(ba_seg_blocks(D)), dim3(kBaSegLanes), D, F);
+    hipLaunchKernelGGL(mcv_ba_lin_cam_final, dim3(ba_blocks(D.nCameras)), dim3(256), 0, s, D);
+    MCV_BAF_LAUNCH(mcv_baf_grp_lin, dim3(ba_blocks(F.nG)), dim3(256), D, F);
+}
+
+void launch_baf_system(const BaDevice& D, const BaFocal& F, hipStream_t s) {
+    ProfScope ps("baf_system", s);
+    hipLaunchKernelGGL(mcv_ba_point_solve, dim3(ba_blocks(D.T)), dim3(256), 0, s, D);
+    MCV_BAF_LAUNCH(mcv_baf_schur_seg, dim3(ba_seg_blocks(D)), dim3(kBaSegLanes), D, F);
+    hipLaunchKernelGGL(mcv_ba_schur_final, dim3(ba_blocks(D.nCameras)), dim3(256), 0, s, D);
+    MCV_BAF_LAUNCH(mcv_baf_grp_schur, dim3(ba_blocks(F.nG)), dim3(256), D, F);
+    MCV_BAF_LAUNCH(mcv_baf_pcg_init, dim3(1), dim3(kBaSegLanes), D, F);
+}
+
+void launch_baf_cg_iteration(const BaDevice& D, const BaFocal& F, hipStream_t s) {
+    ProfScope ps("baf_cg_iteration", s);
+    MCV_BAF_LAUNCH_M(mcv_baf_point_short, 0, dim3(ba_blocks(D.T)), dim3(256), D, F);
+    MCV_BAF_LAUNCH_M(mcv_baf_point_long, 0, dim3(ba_long_blocks(D)), dim3(256), D, F);
+    MCV_BAF_LAUNCH(mcv_baf_wy_seg, dim3(ba_seg_blocks(D)), dim3(kBaSegLanes), D, F);
+    hipLaunchKernelGGL(mcv_ba_q_final, dim3(ba_blocks(D.nCameras)), dim3(256), 0, s, D);
+    MCV_BAF_LAUNCH(mcv_baf_grp_q, dim3(ba_blocks(F.nG)), dim3(256), D, F);
+    MCV_BAF_LAUNCH(mcv_baf_pcg_update, dim3(1), dim3(kBaSegLanes), D, F);
+}
+
+void launch_baf_trial(const BaDevice& D, const BaFocal& F, hipStream_t s) {
+    {
+        ProfScope ps("baf_trial_update", s);
+        MCV_BAF_LAUNCH_M(mcv_baf_point_short, 1, dim3(ba_blocks(D.T)), dim3(256), D, F);
+        MCV_BAF_LAUNCH_M(mcv_baf_point_long, 1, dim3(ba_long_blocks(D)), dim3(256), D, F);
+        hipLaunchKernelGGL(mcv_ba_retract, dim3(ba_blocks(D.nCameras)), dim3(256), 0, s, D);
+        MCV_BAF_LAUNCH(mcv_baf_focal, dim3(ba_blocks(D.nCameras)), dim3(256), D, F);
+    }
+    launch_ba_cost(D, D.cams2, D.pts2, s);
+}
+
 }  // namespace mcv

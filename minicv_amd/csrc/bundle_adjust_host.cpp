@@ -2,6 +2,7 @@
 // staging and the launches of bundle_adjust.hip under the Levenberg-Marquardt driver of ba_ref.h, and
 // the host hooks (the twin mcvHostBundleAdjust, mcvHostBaLinearize, mcvHostBaStep). Launches, copies
 // and synchronisations per LM iteration and per chunk of PCG iterations never depend on the sizes.
+// cvBundleAdjustFocal and its hooks follow at the end: the same driver with the focal kernels.
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "ba_ref.h"
@@ -14,12 +15,15 @@ namespace {
 
 static_assert(sizeof(mcvBaConfig) == sizeof(BaConfig) && sizeof(mcvBaSummary) == sizeof(BaSummary),
               "the public records are read as ba_ref.h's");
+static_assert(sizeof(mcvBaFocalConfig) == sizeof(BaFocalConfig) && sizeof(mcvBaFocalSummary) == sizeof(BaFocalSummary),
+              "the public records are read as ba_ref.h's");
 static_assert(sizeof(mcvCamera) == 112 && sizeof(mcvV3d) == 24 && sizeof(mcvV2d) == 16, "read as plain doubles");
 
 struct BaStats : CallStats {
     long long linearizations = 0, trials = 0, cgChunks = 0, segments = 0;
 };
 thread_local BaStats t_stats;   // the calling thread's last call (mcvTestBundleAdjustStats)
+thread_local BaStats t_focal_stats;   // the same of cvBundleAdjustFocal (mcvTestBundleAdjustFocalStats)
 
 struct BaWork : DeviceWs {
     DevBuf<int> ints;          // offsets, cameraIdx, obsTrack, camObs, segCam, segStart, segEnd, camSegPtr, longList
@@ -28,6 +32,9 @@ struct BaWork : DeviceWs {
     DevBuf<unsigned int> ctr;
     DevBuf<BaCgState> cg;
     DevBuf<BaCostRecord> rec;
+    DevBuf<int> focalInts;        // camGrp, grpPtr, grpCam
+    DevBuf<double> focalDoubles;  // Ef, partF and the groups' vectors
+    DevBuf<uint8_t> focalBytes;   // grpFixed, grpFree
 };
 
 // The checks every form shares; everything here runs before the device is touched. Fills the CSR.
@@ -71,9 +78,14 @@ void write_summary(mcvBaSummary* out, const BaSummary& sm) {
 }
 
 // The device backend of ba_run.
+// fm != 0: the focal kernels (§7p) stand in for their stages; fm == 0 is cvBundleAdjust's sequence.
 struct BaGpu {
     BaDevice D;
     hipStream_t s;
+    BaStats& t_stats;   // the calling export's counters
+    int fm = 0;
+    BaFocal F{};
+    int freeGroups = 0;
 
     void launched(int k) {
         MCV_HIP(hipGetLastError());
@@ -92,13 +104,15 @@ struct BaGpu {
     }
 
     void setup(int& usedObs, int& usedTracks) {
-        launch_ba_setup(D, s);
-        launched(kBaLaunchesSetup);
+        if (fm) launch_baf_setup(D, F, s);
+        else launch_ba_setup(D, s);
+        launched(fm ? kBafLaunchesSetup : kBaLaunchesSetup);
         unsigned int ctr[kBaCtrs];
         copy(ctr, D.ctr, sizeof(ctr), hipMemcpyDeviceToHost);
         sync();
         usedObs = (int)ctr[1];
         usedTracks = (int)ctr[2];
+        freeGroups = (int)ctr[5];
     }
     void cost(double& c, bool& zok) {
         launch_ba_cost(D, D.cams, D.pts, s);
@@ -106,19 +120,24 @@ struct BaGpu {
         read_cost(c, zok);
     }
     void linearize() {
-        launch_ba_linearize(D, s);
-        launched(kBaLaunchesLinearize);
+        if (fm) launch_baf_linearize(D, F, s);
+        else launch_ba_linearize(D, s);
+        launched(fm ? kBafLaunchesLinearize : kBaLaunchesLinearize);
         t_stats.linearizations += 1;
     }
     bool solve(double lambda, int& cgIters) {
         D.lambda = lambda;
         counted_zero(t_stats, D.ctr + 3, sizeof(unsigned int), s);
-        launch_ba_system(D, s);
-        launched(kBaLaunchesSystem);
+        if (fm) launch_baf_system(D, F, s);
+        else launch_ba_system(D, s);
+        launched(fm ? kBafLaunchesSystem : kBaLaunchesSystem);
         BaCgState st;
         do {   // a chunk of iterations, then one small record; the kernels of a finished solve leave at once
-            for (int i = 0; i < kBaCgChunk; ++i) launch_ba_cg_iteration(D, s);
-            launched(kBaCgChunk * kBaLaunchesCgIter);
+            for (int i = 0; i < kBaCgChunk; ++i) {
+                if (fm) launch_baf_cg_iteration(D, F, s);
+                else launch_ba_cg_iteration(D, s);
+            }
+            launched(kBaCgChunk * (fm ? kBafLaunchesCgIter : kBaLaunchesCgIter));
             copy(&st, D.cg, sizeof(st), hipMemcpyDeviceToHost);
             sync();
             t_stats.cgChunks += 1;
@@ -127,8 +146,9 @@ struct BaGpu {
         return !st.failed;
     }
     void trial(double& c, bool& zok) {
-        launch_ba_trial(D, s);
-        launched(kBaLaunchesTrial);
+        if (fm) launch_baf_trial(D, F, s);
+        else launch_ba_trial(D, s);
+        launched(fm ? kBafLaunchesTrial : kBaLaunchesTrial);
         t_stats.trials += 1;
         read_cost(c, zok);
     }
@@ -147,7 +167,8 @@ T* carve(T*& cursor, size_t count) {
 
 int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras, const int* cameraIdx,
                const mcvV2d* observations, const int* offsets, int T, const mcvV3d* points, const BaConfig& cfg,
-               const BaCsr& csr, mcvCamera* outCameras, mcvV3d* outPoints, BaSummary& sm) {
+               const BaCsr& csr, mcvCamera* outCameras, mcvV3d* outPoints, BaSummary& sm, BaStats& t_stats = ::t_stats,
+               int fm = 0, const BaGroups* grp = nullptr, int* freeGroups = nullptr) {
     require_device();
     BaWork& w = thread_device_ws<BaWork>();
     t_stats = BaStats();
@@ -225,7 +246,38 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
     D.tol2 = cfg.cgTolerance * cfg.cgTolerance;
     D.maxCg = cfg.maxCgIterations;
 
-    BaGpu be{D, s};
+    BaGpu be{D, s, t_stats};
+    const size_t nG = fm ? (size_t)grp->nG : 0, nGp = nG ? nG : 1;
+    int *d_camGrp = nullptr, *d_grpPtr = nullptr, *d_grpCam = nullptr;
+    uint8_t* d_grpFixed = nullptr;
+    if (fm) {
+        w.focalInts.ensure(2 * nC + nG + 1);
+        w.focalDoubles.ensure(2 * n + (size_t)kBaFocalPart * (nSeg ? nSeg : 1) + (2 + 2 + 3 + 2 + 2 * 5 + 1) * nGp);
+        w.focalBytes.ensure(2 * nGp);
+        BaFocal& F = be.F;
+        be.fm = F.fm = fm;
+        F.nG = (int)nG;
+        int* fi = w.focalInts.p;
+        F.camGrp = d_camGrp = carve(fi, nC);
+        F.grpPtr = d_grpPtr = carve(fi, nG + 1);
+        F.grpCam = d_grpCam = carve(fi, nC);
+        double* fd = w.focalDoubles.p;
+        F.Ef = carve(fd, 2 * n);
+        F.partF = carve(fd, (size_t)kBaFocalPart * (nSeg ? nSeg : 1));
+        F.Gd = carve(fd, 2 * nGp);
+        F.gf = carve(fd, 2 * nGp);
+        F.Lf = carve(fd, 3 * nGp);
+        F.bf = carve(fd, 2 * nGp);
+        F.xf = carve(fd, 2 * nGp);
+        F.rf = carve(fd, 2 * nGp);
+        F.zf = carve(fd, 2 * nGp);
+        F.pf = carve(fd, 2 * nGp);
+        F.qf = carve(fd, 2 * nGp);
+        F.pqf = carve(fd, nGp);
+        uint8_t* fb = w.focalBytes.p;
+        F.grpFixed = d_grpFixed = carve(fb, nGp);
+        F.grpFree = carve(fb, nGp);
+    }
     const hipMemcpyKind up = hipMemcpyHostToDevice;
     {
         ProfScope ps("ba_upload", s);
@@ -244,6 +296,12 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
         else counted_zero(t_stats, d_fixed, nC, s);
         counted_zero(t_stats, D.ctr, kBaCtrs * sizeof(unsigned int), s);
         counted_zero(t_stats, D.pq, nCp * sizeof(double), s);   // the setup's per-camera marks
+        if (fm) {
+            be.copy(d_camGrp, grp->camGrp.data(), nC * sizeof(int), up);
+            be.copy(d_grpPtr, grp->grpPtr.data(), (nG + 1) * sizeof(int), up);
+            be.copy(d_grpCam, grp->grpCam.data(), nC * sizeof(int), up);
+            be.copy(d_grpFixed, grp->grpFixed.data(), nG, up);
+        }
     }
 
     const int it = ba_run(be, cfg, sm);
@@ -254,6 +312,7 @@ int run_device(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCamer
         be.copy(hp.data(), be.D.pts, nT * sizeof(mcvV3d), hipMemcpyDeviceToHost);
     }
     be.sync();
+    if (freeGroups) *freeGroups = fm ? be.freeGroups : 0;
     copy_out(hc.data(), outCameras, nC * sizeof(mcvCamera));
     copy_out(hp.data(), outPoints, nT * sizeof(mcvV3d));
     return it;
@@ -365,6 +424,134 @@ extern "C" MCV_API int mcvTestBundleAdjustStats(long long* stats8) {
     MCV_GUARD(-1, {
         const BaStats& st = t_stats;
         return stats8_out("mcvTestBundleAdjustStats", stats8, st,
+                          {st.linearizations, st.trials, st.cgChunks, st.segments});
+    })
+}
+
+// ---- focal groups ----
+namespace {
+
+BaFocalConfig focal_config_of(const mcvBaFocalConfig* cfg) {
+    if (!cfg) return BaFocalConfig{ba_default_config(), 1, 0};
+    return BaFocalConfig{config_of(&cfg->base), cfg->focalMode, 0};
+}
+
+// cvBundleAdjust's checks, then the groups'. Everything here runs before the device is touched.
+void check_focal_arguments(const char* name, const mcvCamera* cameras, int nCameras, const int* focalGroup,
+                           const uint8_t* fixedFocal, const int* cameraIdx, const mcvV2d* observations,
+                           const int* offsets, int T, const mcvV3d* points, const BaFocalConfig& cfg, BaCsr& csr,
+                           BaGroups& grp) {
+    if (cfg.focalMode < 0 || cfg.focalMode > 2) fail("%s: unknown focalMode %d", name, cfg.focalMode);
+    check_arguments(name, cameras, nCameras, cameraIdx, observations, offsets, T, points, cfg.base, csr);
+    int j = 0;
+    switch (ba_build_groups(cfg.focalMode, focalGroup, fixedFocal, (const double*)cameras, nCameras, grp, &j)) {
+        case 1: fail("%s: unknown focalMode %d", name, cfg.focalMode);
+        case 2: fail("%s: focalGroup[%d] = %d outside [0, %d)", name, j, focalGroup[j], nCameras);
+        case 3: fail("%s: camera %d's focal length differs from its group's", name, j);
+        case 4: fail("%s: camera %d's focal length is free and not finite and positive", name, j);
+        default: break;
+    }
+}
+
+void write_focal_summary(mcvBaFocalSummary* out, const BaFocalSummary& sm) {
+    if (out) std::memcpy(out, &sm, sizeof(sm));
+}
+
+}  // namespace
+
+extern "C" MCV_API int cvBundleAdjustFocal(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                                           const int* focalGroup, const uint8_t* fixedFocal, const int* cameraIdx,
+                                           const mcvV2d* observations, const int* offsets, int T,
+                                           const mcvV3d* points, const mcvBaFocalConfig* cfg, mcvCamera* outCameras,
+                                           mcvV3d* outPoints, mcvBaFocalSummary* summary) {
+    MCV_GUARD(-1, {
+        const char* name = "cvBundleAdjustFocal";
+        const BaFocalConfig c = focal_config_of(cfg);
+        BaCsr csr;
+        BaGroups grp;
+        check_focal_arguments(name, cameras, nCameras, focalGroup, fixedFocal, cameraIdx, observations, offsets, T,
+                              points, c, csr, grp);
+        if ((nCameras > 0 && !outCameras) || (T > 0 && !outPoints)) fail("%s: null outCameras or outPoints", name);
+        BaFocalSummary sm;
+        std::memset(&sm, 0, sizeof(sm));
+        int it = 0;
+        if (T == 0 || offsets[T] == 0) {   // nothing to adjust: the inputs, without touching the device
+            sm.base.termination = kBaTermNothing;
+            copy_out(cameras, outCameras, (size_t)nCameras * sizeof(mcvCamera));
+            copy_out(points, outPoints, (size_t)T * sizeof(mcvV3d));
+        } else {
+            it = run_device(cameras, nCameras, fixedCameras, cameraIdx, observations, offsets, T, points, c.base, csr,
+                            outCameras, outPoints, sm.base, t_focal_stats, c.focalMode, &grp, &sm.freeFocalGroups);
+        }
+        write_focal_summary(summary, sm);
+        return it;
+    })
+}
+
+extern "C" MCV_API int mcvHostBundleAdjustFocal(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                                                const int* focalGroup, const uint8_t* fixedFocal,
+                                                const int* cameraIdx, const mcvV2d* observations, const int* offsets,
+                                                int T, const mcvV3d* points, const mcvBaFocalConfig* cfg,
+                                                mcvCamera* outCameras, mcvV3d* outPoints, mcvBaFocalSummary* summary) {
+    MCV_GUARD(-1, {
+        const char* name = "mcvHostBundleAdjustFocal";
+        const BaFocalConfig c = focal_config_of(cfg);
+        BaCsr csr;
+        BaGroups grp;
+        check_focal_arguments(name, cameras, nCameras, focalGroup, fixedFocal, cameraIdx, observations, offsets, T,
+                              points, c, csr, grp);
+        if ((nCameras > 0 && !outCameras) || (T > 0 && !outPoints)) fail("%s: null outCameras or outPoints", name);
+        BaFocalSummary sm;
+        std::memset(&sm, 0, sizeof(sm));
+        std::vector<double> hc(14 * (size_t)nCameras), hp(3 * (size_t)T);
+        const int it = ba_host_bundle_adjust_focal((const double*)cameras, nCameras, fixedCameras, cameraIdx,
+                                                   (const double*)observations, offsets, T, (const double*)points, c,
+                                                   csr, grp, hc.data(), hp.data(), sm);
+        copy_out(hc.data(), outCameras, hc.size() * sizeof(double));
+        copy_out(hp.data(), outPoints, hp.size() * sizeof(double));
+        write_focal_summary(summary, sm);
+        return it;
+    })
+}
+
+extern "C" MCV_API int mcvHostBaFocalStep(const mcvCamera* cameras, int nCameras, const uint8_t* fixedCameras,
+                                          const int* focalGroup, const uint8_t* fixedFocal, const int* cameraIdx,
+                                          const mcvV2d* observations, const int* offsets, int T, const mcvV3d* points,
+                                          const mcvBaFocalConfig* cfg, double lambda, double* focalBlocks,
+                                          double* dCameras, double* dFocal, double* dPoints) {
+    MCV_GUARD(-1, {
+        const char* name = "mcvHostBaFocalStep";
+        const BaFocalConfig c = focal_config_of(cfg);
+        BaHost H;
+        check_focal_arguments(name, cameras, nCameras, focalGroup, fixedFocal, cameraIdx, observations, offsets, T,
+                              points, c, H.csr, H.grp);
+        if (c.focalMode == 0) fail("%s: focalMode 0 has no focal step", name);
+        if (!(lambda > 0.0) || !ba_finite(lambda)) fail("%s: lambda is not positive and finite", name);
+        const int n = offsets[T];
+        if ((nCameras > 0 && (!dCameras || !dFocal)) || (T > 0 && !dPoints) || (n > 0 && !focalBlocks))
+            fail("%s: null output", name);
+        H.init((const double*)cameras, nCameras, fixedCameras, cameraIdx, (const double*)observations, offsets, T,
+               (const double*)points, c.base);
+        H.fm = c.focalMode;
+        int usedObs = 0, usedTracks = 0, cg = 0;
+        H.setup(usedObs, usedTracks);
+        H.linearize();
+        if (!H.solve(lambda, cg)) fail("%s: the solve failed", name);
+        H.apply_step(dPoints);
+        copy_out(H.Ef.data(), focalBlocks, 2 * (size_t)n * sizeof(double));
+        copy_out(H.x.data(), dCameras, 6 * (size_t)nCameras * sizeof(double));
+        for (int j = 0; j < nCameras; ++j) {
+            dFocal[2 * (size_t)j] = H.xf[2 * (size_t)H.grp.camGrp[j]];
+            dFocal[2 * (size_t)j + 1] = H.xf[2 * (size_t)H.grp.camGrp[j] + 1];
+        }
+        return cg;
+    })
+}
+
+extern "C" MCV_API int mcvTestBundleAdjustFocalStats(long long* stats8) {
+    MCV_GUARD(-1, {
+        const BaStats& st = t_focal_stats;
+        return stats8_out("mcvTestBundleAdjustFocalStats", stats8, st,
                           {st.linearizations, st.trials, st.cgChunks, st.segments});
     })
 }

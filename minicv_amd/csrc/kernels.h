@@ -743,6 +743,26 @@ void launch_ba_system(const BaDevice& D, hipStream_t s);      // Vinv, t, L, b a
 void launch_ba_cg_iteration(const BaDevice& D, hipStream_t s);
 void launch_ba_trial(const BaDevice& D, hipStream_t s);       // cams2 / pts2 from x, and their cost -> D.rec
 
+// ---- bundle adjustment with focal groups (bundle_adjust.hip): what cvBundleAdjustFocal
+// keeps beside a BaDevice. d_ctr[5] counts the free groups.
+struct BaFocal {
+    int fm, nG;                 // focalMode 1 or 2, groups
+    const int *camGrp, *grpPtr, *grpCam;   // nCameras, nG + 1, nCameras: a group's cameras in ascending index
+    const uint8_t* grpFixed;    // nG
+    uint8_t* grpFree;           // nG: not fixed, and a camera of the group has a used observation
+    double* Ef;                 // 2 n: the focal block of every used observation
+    double* partF;              // kBaFocalPart per segment: the focal sums of the pass in flight
+    double *Gd, *gf, *Lf, *bf;  // per group: 2, 2, 3, 2
+    double *xf, *rf, *zf, *pf, *qf, *pqf;   // per group: 2 each, pqf 1
+};
+static const int kBafLaunchesSetup = kBaLaunchesSetup + 1, kBafLaunchesLinearize = 6, kBafLaunchesSystem = 5,
+                 kBafLaunchesCgIter = 6, kBafLaunchesTrial = 4 + kBaLaunchesCost;
+void launch_baf_setup(const BaDevice& D, const BaFocal& F, hipStream_t s);
+void launch_baf_linearize(const BaDevice& D, const BaFocal& F, hipStream_t s);
+void launch_baf_system(const BaDevice& D, const BaFocal& F, hipStream_t s);
+void launch_baf_cg_iteration(const BaDevice& D, const BaFocal& F, hipStream_t s);
+void launch_baf_trial(const BaDevice& D, const BaFocal& F, hipStream_t s);
+
 // ---- SIFT detection (sift.hip; the records are sift_math.h's)
 struct SiftParams;
 struct SiftKp;

@@ -63,6 +63,23 @@ class BaSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BaFocalConfig(C.Structure):
+    """mcvBaFocalConfig: mcvBaConfig and focalMode (0 constant, 1 one scale per group, 2 fx and fy)."""
+    _fields_ = [("base", BaConfig), ("focalMode", C.c_int), ("pad", C.c_int)]
+
+    @classmethod
+    def default(cls, focalMode: int = 1, **kw) -> "BaFocalConfig":
+        return cls(BaConfig.default(**kw), focalMode, 0)
+
+
+class BaFocalSummary(C.Structure):
+    """mcvBaFocalSummary."""
+    _fields_ = [("base", BaSummary), ("freeFocalGroups", C.c_int), ("pad", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return dict(self.base.as_dict(), freeFocalGroups=self.freeFocalGroups)
+
+
 class RecoverPoseConfig(C.Structure):
     """MiniCVNative.cpp:39-46 / OpenCV.fs:16-36."""
     _fields_ = [("FocalLength", C.c_double), ("PrincipalPoint", V2d), ("Probability", C.c_double),
@@ -163,6 +180,8 @@ BA_CG_CHUNK = 8                 # PCG iterations between two reads of the solve'
 # kernel launches of cvBundleAdjust's stages (kernels.h kBaLaunches*): the call's total is
 # SETUP + COST + LINEARIZE x linearisations + (SYSTEM + TRIAL) x trials + CG_ITER x BA_CG_CHUNK x chunks
 BA_LAUNCHES = {"setup": 3, "cost": 2, "linearize": 4, "system": 4, "cg_iter": 5, "trial": 5}
+# the same of cvBundleAdjustFocal with focalMode 1 or 2 (kernels.h kBafLaunches*); focalMode 0 has BA_LAUNCHES
+BA_FOCAL_LAUNCHES = {"setup": 4, "cost": 2, "linearize": 6, "system": 5, "cg_iter": 6, "trial": 6}
 FEATURE_AKAZE, FEATURE_ORB, FEATURE_BRISK, FEATURE_SIFT = 1, 2, 3, 4   # the reference's DetectorMode
 SIFT_MAX_SIDE = 8192            # width and height cap of cvDetectFeatures (sift_math.h kSiftMaxSide)
 SIFT_MAX_LAYERS = 6             # OctaveLayers 1 .. 6 (sift_math.h kSiftMaxLayers)
@@ -270,6 +289,7 @@ SIGNATURES = {
     "cvIntersectRays": (_I, [_P, _P, _I, _P, _P]),
     "cvTriangulateTracks": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "cvBuildTracks": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P]),
+    "cvBundleAdjustFocal": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "cvBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "cvFindScaledPoseBatch": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "cvFindScaledPoseBatchCosts": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
@@ -365,6 +385,9 @@ SIGNATURES = {
     "cvFreeFeaturesBatch": (None, [_P, _I]),
     "mcvTestSiftBatchStats": (_I, [_P]),
     "mcvTestSiftBatchPlan": (_I, [_P, _I, _I, _P, _P]),
+    "mcvHostBundleAdjustFocal": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "mcvHostBaFocalStep": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P, _P, _P]),
+    "mcvTestBundleAdjustFocalStats": (_I, [_P]),
     "mcvHostBundleAdjust": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mcvHostBaLinearize": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mcvHostBaStep": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _D, _P, _P]),
