@@ -992,6 +992,17 @@ MCV_API int mcvTestHStage0Slots(int slots);
  * alone otherwise runs only under the automatic rule, from 2^31 (hypothesis, correspondence) evaluations, which no
  * test can afford to check against the oracle. Not thread-safe: tests only. */
 MCV_API int mcvTestHCellSecondPass(int mode);
+/* The survivor lists of the staged homography sweep as its kernels push them (one atomic per block), on given data:
+ * the per-cell bound's box pass with the second pass behind it, the second pass, and two compactions. models8:
+ * nModels x 8 floats; cand8: the candidate's model; B: its count; counts (nModels ints): each slot's count so far
+ * (negative: a status, never listed); boundPairs: the boundary the compactions test at, in pairs of correspondences.
+ * lists (4 x nModels ints) and lens (4 ints): [0] the slots the box pass hands to the second pass, [1] the list of
+ * stage 1 (what the box pass keeps outright, then what the second pass keeps), [2] the compaction of [1] with the
+ * per-slot points-left, [3] a compaction over every slot with the points not yet processed. Lists are in any order;
+ * entries beyond a list's length read -1. Returns 1, 0 on error. Tests only. */
+MCV_API int mcvTestHListPush(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                             float thr2, int B, int G, int Gs, int boundPairs, const int* counts, int* lists,
+                             int* lens);
 /* The stage plan of the staged homography sweep for N correspondences, computed on the host by the function the
  * planner kernel runs (no device is touched). candidate: stage 0 named one (its full count is B); failure: the
  * chunk holds a sampler failure; cellBound 0: no per-cell bound, 1: its box pass alone (a shorter stage 0), 2: with

@@ -208,6 +208,10 @@ void launch_h_cell_bound(const void* d_models, const int* d_counts, int hypCount
                          const int* d_cells, int G, int Gs, int* d_ctl, int* d_list, int* d_ub, uint32_t* d_bits,
                          hipStream_t s, int* d_listPre, int* d_left, int nLater, int N, HCellPreBufs pre);
 void launch_h_cell_pre(const int* d_cells, int G, int Gs, float thr2, int* d_rec, hipStream_t s);
+// One compaction of the staged sweep: the survivors entering `stage` (>= 2) go from d_src (nullptr: every slot) to
+// d_dst, their number to ctl[kCtlAlive + stage]; d_left: the per-slot `left` rows (nullptr: N - processed).
+void launch_h_stage_compact(const int* d_counts, int hypCount, int N, int* d_ctl, int stage, const int* d_src,
+                            int* d_dst, const int* d_left, hipStream_t s);
 // the prefilter's verdict (h_cell_pre.h kHCellPre*) per (model, cell): nModels x cells bytes
 void launch_h_cell_pre_verdicts(const void* d_models, int nModels, float thr2, const double* d_bb, const int* d_cells,
                                 const int* d_rec, int G, int Gs, uint8_t* d_out, hipStream_t s);

@@ -9,7 +9,7 @@
 // [ext: calib3d/src/fundam.cpp, ptsetreg.cpp, levmarq.cpp — absent here, SURVEY.md §8c].
 // Also here: the homography test hooks (mcvTestHStaging, mcvTestHCellMode, mcvTestHCellBound, mcvTestHCellRel,
 // mcvTestHCellPre, mcvTestHCellPreVerdicts, mcvTestHMfma, mcvTestHGenRow, mcvTestHGenerate, mcvHostHGenRow,
-// mcvHostHStagePlan, mcvTestHCellSecondPass).
+// mcvHostHStagePlan, mcvTestHCellSecondPass, mcvTestHListPush).
 #include "minicv_native.h"
 #include "mcv_runtime.h"
 #include "kernels.h"
@@ -225,7 +225,8 @@ void h_evaluate(Plan& P, const void* d_ptsv, int N, const RansacConfig& cfg, int
     // applies the test to the unchanged counts and hands the list on. With pruning off on the device
     // (reason != 0) the stage behind boundary 1 runs every slot to the end and every later list stays empty.
     // The test stays in mcv_h_stage_compact: run in the tail of the stage kernel's own waves (one atomic per
-    // wave of 6 slots in place of one per 64) it was measured slower ("The half boundary").
+    // wave of 6 slots, where the compaction then took one per 64 and now takes one per block of 1024) it was
+    // measured slower ("The half boundary").
     const bool stageable = !fused && keyOnly;
     const bool sized = N >= kHStageMinN && (int64_t)N * hypCount >= kHStageMinEvals;
     const bool staged = stageable && g_hstage_mode != 2 && (g_hstage_mode == 1 || sized);
@@ -574,6 +575,73 @@ extern "C" MCV_API int mcvTestHCellRel(const float* pts4, int N, const float* ca
         MCV_HIP(hipMemcpy(left, dleft.p, (size_t)nModels * nBounds * sizeof(int), hipMemcpyDeviceToHost));
         MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
         *alive = hctl[kCtlAlive + 1];
+        return 1;
+    })
+}
+
+// Test hook (declared in minicv_native.h): the survivor lists themselves, as the staged sweep's kernels push them.
+// The box pass with the second pass behind it (two lists), the second pass over the first pass's list, then two
+// compactions on the given counts: one through the stage-1 list with the per-slot `left`, one over every slot with
+// the points not yet processed. Every list comes back with its length; entries no kernel wrote read -1.
+extern "C" MCV_API int mcvTestHListPush(const float* pts4, int N, const float* cand8, const float* models8, int nModels,
+                                        float thr2, int B, int G, int Gs, int boundPairs, const int* counts,
+                                        int* lists, int* lens) {
+    MCV_GUARD(0, {
+        if (!pts4 || !cand8 || !models8 || !counts || !lists || !lens) fail("mcvTestHListPush: null argument");
+        if (N <= 0 || nModels <= 0 || G < 1 || G > kHCellMaxG || Gs < 1 || Gs > kHCellMaxGs || boundPairs < 0 ||
+            boundPairs > (N + 1) / 2)
+            fail("mcvTestHListPush: bad sizes");
+        require_device();
+        const int cells = h_cell_count(G, Gs);
+        DevBuf<float> p, m, cand;
+        DevBuf<double> bb;
+        DevBuf<int> ctl, tab, cnt, out, did, rec, pref, dleft;
+        rec.ensure(h_cell_rec_ints(cells));
+        p.ensure((size_t)N * 4);
+        m.ensure((size_t)nModels * 8);
+        cand.ensure(8);
+        bb.ensure(4);
+        ctl.ensure(kHStageCtlInts);
+        tab.ensure((size_t)cells * kHCellInts);
+        cnt.ensure(nModels);
+        out.ensure(4 * (size_t)nModels);
+        did.ensure(N);
+        pref.ensure(cells);
+        dleft.ensure(nModels);
+        int *dPre = out.p, *dStage1 = out.p + nModels, *dNext = out.p + 2 * (size_t)nModels,
+            *dAll = out.p + 3 * (size_t)nModels;
+        MCV_HIP(hipMemcpy(p.p, pts4, (size_t)N * 16, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(m.p, models8, (size_t)nModels * 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cand.p, cand8, 32, hipMemcpyHostToDevice));
+        MCV_HIP(hipMemcpy(cnt.p, counts, (size_t)nModels * sizeof(int), hipMemcpyHostToDevice));
+        MCV_HIP(hipMemset(out.p, 0xFF, 4 * (size_t)nModels * sizeof(int)));
+        // a control block that names slot 0 of `cand` as the candidate; stages 2 and 3 both start at the boundary
+        int hctl[kHStageCtlInts] = {0};
+        const uint64_t key = (1ull << 32) | 0xFFFFFFFFull;
+        memcpy(hctl + kCtlKey, &key, sizeof(key));
+        hctl[kCtlBound + 2] = hctl[kCtlBound + 3] = boundPairs;
+        MCV_HIP(hipMemcpy(ctl.p, hctl, sizeof(hctl), hipMemcpyHostToDevice));
+        launch_abs_bound4(p.p, false, N, bb.p, nullptr, 0);
+        launch_h_stage_count(p.p, N, cand.p, 0, thr2, ctl.p, bb.p, tab.p, G, Gs, did.p, 0);
+        MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(ctl.p + kCtlB, &B, sizeof(int), hipMemcpyHostToDevice));
+        const HCellPreBufs pre{rec.p, g_hcell_pre_mode == 0, nullptr};
+        launch_h_cell_prefix(did.p, N, ctl.p, 1, G, Gs, pref.p, 0);
+        launch_h_cell_pre(tab.p, G, Gs, thr2, rec.p, 0);
+        launch_h_cell_bound(m.p, cnt.p, nModels, thr2, bb.p, tab.p, G, Gs, ctl.p, dStage1, nullptr, nullptr, 0, dPre,
+                            dleft.p, 1, N, pre);
+        launch_h_cell_rel(m.p, cand.p, 0, nModels, thr2, bb.p, tab.p, G, Gs, pref.p, 1, ctl.p, dPre, dStage1, dleft.p,
+                          nullptr, nullptr, 0, pre);
+        launch_h_stage_compact(cnt.p, nModels, N, ctl.p, 2, dStage1, dNext, dleft.p, 0);
+        launch_h_stage_compact(cnt.p, nModels, N, ctl.p, 3, nullptr, dAll, nullptr, 0);
+        MCV_HIP(hipGetLastError());
+        MCV_HIP(hipDeviceSynchronize());
+        MCV_HIP(hipMemcpy(lists, out.p, 4 * (size_t)nModels * sizeof(int), hipMemcpyDeviceToHost));
+        MCV_HIP(hipMemcpy(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost));
+        lens[0] = hctl[kCtlPre];
+        lens[1] = hctl[kCtlAlive + 1];
+        lens[2] = hctl[kCtlAlive + 2];
+        lens[3] = hctl[kCtlAlive + 3];
         return 1;
     })
 }

@@ -182,31 +182,50 @@ __device__ __forceinline__ int h_stage_left(const int* __restrict__ row, int slo
     return N - (done2 < N ? done2 : N);
 }
 
-// Appends the lanes with `keep` to a survivor list (ballot, one atomic per wave, any order).
-__device__ __forceinline__ void h_list_push(bool keep, int slot, int* total, int* __restrict__ dst) {
+// Appends the threads with `keep` to a survivor list, any order: a ballot per wave and one atomic per block.
+// The waves' ballot counts go to LDS (sh: WAVES + 1 ints of the caller's, one set per push of a kernel), one
+// returning atomic per block goes to the list's counter, and a lane writes at the block's base + its wave's
+// offset + its rank in the ballot. The counter serialises the pushes (a returning atomic on one address
+// costs about 12.5 ns when the waves arrive together), so a block of WAVES waves takes 1 / WAVES of
+// the time. Every thread of the block must call it (two barriers); a block that keeps nothing takes no atomic.
+template <int WAVES>
+__device__ __forceinline__ void h_list_push_block(bool keep, int slot, int* total, int* __restrict__ dst, int* sh) {
     const uint64_t b = __ballot(keep);
-    if (b == 0) return;
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(total, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (keep) dst[base + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) sh[wave] = (int)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const int c = sh[w];
+            sh[w] = sum;
+            sum += c;
+        }
+        sh[WAVES] = sum ? atomicAdd(total, sum) : 0;
+    }
+    __syncthreads();
+    if (keep) dst[sh[WAVES] + sh[wave] + (int)__popcll(b & ((1ull << lane) - 1))] = slot;
 }
 
 // Survivors entering `stage` (>= 2): the slots of the previous stage (src; nullptr: all of them)
 // whose count can still reach B, count + left >= B. Inclusive, so ties survive; a status
 // (count < 0: no model, no sample, the exact-recount mark) never enters a list. Any order: ballot
-// and one atomic per wave. left: without the per-cell bound (slotLeft == nullptr) the points not yet
+// and one atomic per block of 16 waves. left: without the per-cell bound (slotLeft == nullptr) the points not yet
 // processed, N - processed; with it the slot's own figure, the unprocessed points of the cells the bound
 // did not certify for the slot's model (slotLeft[(stage - 2) * hypCount + slot], written by mcv_h_cell_rel,
 // or by mcv_h_cell_bound for the slots it keeps out of the second pass).
-__global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict__ counts, int hypCount, int N,
-                                                           int* __restrict__ ctl, int stage,
-                                                           const int* __restrict__ src, int* __restrict__ dst,
-                                                           const int* __restrict__ slotLeft) {
+static constexpr int kHCompactThreads = 1024;
+__global__ __launch_bounds__(kHCompactThreads) void mcv_h_stage_compact(const int* __restrict__ counts, int hypCount,
+                                                                        int N, int* __restrict__ ctl, int stage,
+                                                                        const int* __restrict__ src,
+                                                                        int* __restrict__ dst,
+                                                                        const int* __restrict__ slotLeft) {
+    __shared__ int push[kHCompactThreads / 64 + 1];
     if (ctl[kCtlReason] != 0) return;
     const int n = src ? ctl[kCtlAlive + stage - 1] : hypCount;
-    const int i = blockIdx.x * 256 + threadIdx.x;
+    if ((int)(blockIdx.x * kHCompactThreads) >= n) return;   // block-uniform, as the return above
+    const int i = blockIdx.x * kHCompactThreads + threadIdx.x;
     const int* row = slotLeft ? slotLeft + (size_t)(stage - 2) * hypCount : nullptr;
     bool keep = false;
     int slot = 0;
@@ -214,7 +233,15 @@ __global__ __launch_bounds__(256) void mcv_h_stage_compact(const int* __restrict
         slot = src ? src[i] : i;
         keep = h_stage_keeps(counts[slot], h_stage_left(row, slot, N, ctl[kCtlBound + stage]), ctl[kCtlB]);
     }
-    h_list_push(keep, slot, ctl + kCtlAlive + stage, dst);
+    h_list_push_block<kHCompactThreads / 64>(keep, slot, ctl + kCtlAlive + stage, dst, push);
+}
+
+// d_src: the previous stage's list (its length in ctl[kCtlAlive + stage - 1]; nullptr: every slot below hypCount);
+// d_left: the per-slot `left` rows (nullptr: the points not yet processed). The grid covers every slot.
+void launch_h_stage_compact(const int* d_counts, int hypCount, int N, int* d_ctl, int stage, const int* d_src,
+                            int* d_dst, const int* d_left, hipStream_t s) {
+    hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + kHCompactThreads - 1) / kHCompactThreads),
+                       dim3(kHCompactThreads), 0, s, d_counts, hypCount, N, d_ctl, stage, d_src, d_dst, d_left);
 }
 
 // The second pass's buffers as the box pass sees them (pre == nullptr: no second pass, the test hook).
@@ -305,7 +332,7 @@ __device__ __forceinline__ void h_cell_pre_stats(unsigned long long* stats, int 
 // The per-cell bound (h_cell_bound.h), lane = slot: UB = the sizes of the cells the model does not certify
 // as all-outlier, an upper bound of the slot's full count. Slots with a model and UB >= B (inclusive: ties
 // survive) enter the survivor list of stage 1 as mcv_h_stage_compact writes its lists (ballot, one
-// atomic per wave, any order); their number goes to ctl[kCtlAlive + 1]. A status (count < 0: no model, no
+// atomic per block, any order); their number goes to ctl[kCtlAlive + 1]. A status (count < 0: no model, no
 // sample, stage 0's exact-recount mark) never enters the list. Where pruning is off on the device
 // (ctl[kCtlReason] != 0) every slot with a model is kept. The cells are wave-uniform (scalar loads); all
 // stores are per lane. ubOut / bitsOut (test hook): every slot's UB and its certified-cell bitmap
@@ -323,10 +350,11 @@ __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restric
                                                         int* __restrict__ dst, HCellPre hp,
                                                         int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
                                                         int bitWords, HCellPreBufs pa) {
+    __shared__ int push[2][256 / 64 + 1];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool have = i < hypCount && counts[i] >= 0;
     bool keep = have, second = false;
-    if (ctl[kCtlReason] == 0 && __ballot(have) != 0) {
+    if (ctl[kCtlReason] == 0 && __ballot(have) != 0) {   // per wave: the block-level pushes stay outside
         const HModelF m = models[i < hypCount ? i : hypCount - 1];
         double b4[4];
 #pragma unroll
@@ -359,10 +387,11 @@ __global__ __launch_bounds__(256) void mcv_h_cell_bound(const HModelF* __restric
                     hp.slotLeft[(size_t)j * hypCount + i] = hp.N - (d2 < hp.N ? d2 : hp.N);
                 }
             }
-            h_list_push(second, i, ctl + kCtlPre, hp.pre);
         }
     }
-    h_list_push(keep, i, ctl + kCtlAlive + 1, dst);
+    // `second` is false in a wave that skipped the bound (pruning off, or no lane with a model)
+    if (hp.pre) h_list_push_block<256 / 64>(second, i, ctl + kCtlPre, hp.pre, push[0]);
+    h_list_push_block<256 / 64>(keep, i, ctl + kCtlAlive + 1, dst, push[1]);
 }
 
 // The prefix table of the per-slot `left` figures: pref[j * nCells + c] = the points of cell c with index
@@ -416,6 +445,7 @@ __global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict_
                                                       int* __restrict__ dst, int* __restrict__ slotLeft,
                                                       int* __restrict__ ubOut, uint32_t* __restrict__ bitsOut,
                                                       int bitWords, HCellPreBufs pa) {
+    __shared__ int push[256 / 64 + 1];
     if (ctl[kCtlReason] != 0) return;
     const uint64_t key = *(const uint64_t*)(ctl + kCtlKey);
     if (key == 0) return;   // never with pruning on
@@ -466,7 +496,7 @@ __global__ __launch_bounds__(256) void mcv_h_cell_rel(const HModelF* __restrict_
         for (int j = 0; j < kHCellLater; ++j)
             if (j < nLater) slotLeft[(size_t)j * hypCount + slot] = left[j];
     }
-    h_list_push(keep, slot, ctl + kCtlAlive + 1, dst);
+    h_list_push_block<256 / 64>(keep, slot, ctl + kCtlAlive + 1, dst, push);   // the returns above are block-uniform
 }
 
 // The certified sweep in stages that prune themselves (the caller consumes only the best key): stage 0
@@ -792,9 +822,8 @@ void launch_h_verify_staged(const float* d_pts4, const void* d_pairs, int N, con
     // compaction hands the list on, with the same test on the unchanged counts.
     stage(1, d_cells ? lists[1] : nullptr);
     for (int st = 2; st < nStages; ++st) {
-        hipLaunchKernelGGL(mcv_h_stage_compact, dim3((hypCount + 255) / 256), dim3(256), 0, s, d_counts, hypCount, N,
-                           d_ctl, st, st == 2 && !d_cells ? (const int*)nullptr : (const int*)lists[(st - 1) & 1],
-                           lists[st & 1], rel ? (const int*)d_cell.left : (const int*)nullptr);
+        launch_h_stage_compact(d_counts, hypCount, N, d_ctl, st, st == 2 && !d_cells ? nullptr : lists[(st - 1) & 1],
+                               lists[st & 1], rel ? d_cell.left : nullptr, s);
         stage(st, lists[st & 1]);
     }
     // One recount, behind the last stage. A wave that leaves the fast path (a model outside the certificate's

@@ -365,6 +365,7 @@ SIGNATURES = {
     "mcvTestHStage0Slots": (_I, [_I]),
     "mcvHostHStagePlan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "mcvTestHCellSecondPass": (_I, [_I]),
+    "mcvTestHListPush": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P]),
     "mcvTestHCellPreVerdicts": (_I, [_P, _I, _P, _P, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mcvTestErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
     "mcvHostErrorRank": (_I, [_I, _P, _I, _P, _I, _I, _I, _P]),
